@@ -10,8 +10,15 @@
 One step = forward + BCE loss + backward (+ RCCL gradient all-reduce for N>1)
 + global-norm clip + Adam + LR schedule, dropout ON (p=0.1), synthetic inputs
 resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+everything else the line can carry: per-family kernel timings and their floors
+(roofline), the native-fp32 and bf16 legs of the same step, the optimizer alone,
+the CPU baseline.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below); the same arguments give the same inputs on every run.
 """
 import argparse
+import gc
 import json
 import os
 import subprocess
@@ -307,6 +314,39 @@ def pmc_traffic(args, M, cfgd, build_info):
     return out
 
 
+DUMP_SAMPLE = 1 << 22          # parameter elements (and Adam moments) --dump-outputs keeps: 16 MB per array
+DUMP_LIMIT = 64 << 20
+
+
+def param_sample_index(store, n=DUMP_SAMPLE, seed=0):
+    """Flat-buffer offsets of a fixed, seeded sample of n parameter elements of a ParamStore, in buffer order (the padding
+    between tensors is never drawn)."""
+    import numpy as np
+    sizes = np.array([store.params[k].numel() for k in store.names], dtype=np.int64)
+    starts = np.array([store.offsets[k] for k in store.names], dtype=np.int64)
+    cum = np.concatenate([[0], np.cumsum(sizes)])
+    pos = np.sort(np.random.default_rng(seed).choice(int(cum[-1]), size=min(n, int(cum[-1])), replace=False))
+    k = np.searchsorted(cum, pos, side='right') - 1
+    return starts[k] + (pos - cum[k])
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: each array as path/<name>.npy, float64 kept, everything else as float32; refuses more than `limit`
+    bytes in all.  Returns the bytes written."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > limit:
+        raise ValueError('--dump-outputs: %d bytes, more than the %d allowed' % (total, limit))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return total
+
+
 def parse_rccl_log(path):
     """What RCCL says it built, from rank 0's NCCL_DEBUG=INFO log (INIT,GRAPH,TUNING): channel count, ring / tree graphs,
     and the algorithm / protocol of the collectives where the TUNING lines name them.  Every field is None when the log has no
@@ -404,7 +444,17 @@ def parse_args(argv=None):
     ap.add_argument('--prewarm_s', type=float, default=1.0, help='seconds of untimed steps before the W warm-up steps (clock ramp)')
     ap.add_argument('--no_adam_overlap', action='store_true',
                     help='run the optimizer step as one launch on the main stream instead of block by block beside the next forward')
-    ap.add_argument('--prof_kind', type=int, default=-1, help='UNITER_K_* kind timed with HIP events inside the timed region (-1 = every kind, 0 = none)')
+    ap.add_argument('--prof_kind', type=int, default=None,
+                    help='UNITER_K_* kind timed with HIP events inside the timed region (-1 = every kind, 0 = none; default: -1 with '
+                         '--full, else 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-family kernel timings, floors and roofline, the native-fp32 and bf16 legs, '
+                         'the optimizer alone and the CPU baseline (each still subject to its own --no_* switch)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy: loss, per-sample '
+                         'probabilities (finetune), and a fixed seeded sample of the updated parameters and Adam moments. '
+                         'The clock warm-up runs on a throwaway copy of the model, so the same arguments give the same '
+                         'inputs on every run (N > 1: the CU-reserve pick takes untimed steps of its own; add --no_reserve_pick)')
     ap.add_argument('--reserve_ab', action='store_true',
                     help='with a gradient exchange attached: time the step once more with no CUs reserved for its kernels '
                          '(comm.no_reserve; `value` is the default reserve, comm.cu_reserve)')
@@ -420,7 +470,12 @@ def parse_args(argv=None):
     ap.add_argument('--dp_sparse_embeddings', action='store_true',
                     help='N > 1: exchange the touched word-embedding gradient rows (all-gather of ids + rows) instead of '
                          'all-reducing the whole 28996 x 768 table')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.prof_kind is None:
+        args.prof_kind = -1 if args.full else 0
+    return args
 
 
 def rank_host_threads(world):
@@ -564,7 +619,6 @@ def _run_rank(args, real_stdout, state):
     import ctypes as C
 
     cfgd = BASE if args.model == 'base' else LARGE
-    torch.manual_seed(0)                                   # identical init on every rank
     cfg = UniterConfig.from_dict(cfgd)
     B, T, R = args.batch, args.txt_len, args.num_bb
     lens = {}
@@ -576,51 +630,59 @@ def _run_rank(args, real_stdout, state):
     config = dict(optimizer='adam', lr=3e-5, beta1=0.9, beta2=0.999, weight_decay=1e-3,
                   gradient_accumulation=1, max_grad_norm=5, pos_wt=1.8, loss_func='bce_logits',
                   scheduler='warmup_cosine', warmup_steps=500, max_epoch=30)
+    tasks = ('itm', 'mlm', 'mrfr')
     if args.workload == 'finetune':
-        model = MemeUniter(UniterModel(cfg, img_dim=2048), cfg.hidden_size, 1).to(dev).train()
-        encoder = model.uniter_model
         batch = make_synthetic_batch(B, T, R, seed=1234 + rank, device=dev, **lens)
     else:
         from meme_challenge_amd.pretrain import UniterForPretraining
-        model = UniterForPretraining(cfg, img_dim=2048, img_label_dim=1601).to(dev).train()
-        encoder = model.uniter
-        tasks = ('itm', 'mlm', 'mrfr')
         batches = {t: make_synthetic_pretrain_batch(t, B, T, R, seed=1234 + rank, device=dev, **lens) for t in tasks}
+
+    def setup(exchange):
+        """The timed path from its seeds -- parameters, dropout stream, task sequence: every call starts from the same state.
+        Returns (model, encoder, optimizer, gradient exchange or None, TrainStep or None, one_step, task rng or None, last)."""
         import random
-        task_rng = random.Random(99)                       # same task sequence on every rank
-    encoder.use_side_stream = not args.no_side_stream
-    encoder.precision = args.precision
-    encoder.pack_padded = args.packed
-    encoder.set_dropout_seed(1234 + rank, 0)
-    opt = FusedAdam(model, lr=config['lr'], weight_decay=config['weight_decay'])
-    if not args.no_adam_overlap:
-        opt.overlap_encoder = encoder
-    sched = get_scheduler(opt, config, steps_per_epoch=1000)
-    sync = None
-    if use_dist:
-        dp.broadcast_parameters(model)
-        sync = dp.attach(model, sparse_embeddings=args.dp_sparse_embeddings, accum=config['gradient_accumulation'], token_capacity=B * T)
-        sync.timing = True
-    if args.workload == 'finetune':
-        step = TrainStep(model, opt, sched, config, grad_sync=sync)
+        torch.manual_seed(0)                                   # identical init on every rank
+        if args.workload == 'finetune':
+            model = MemeUniter(UniterModel(cfg, img_dim=2048), cfg.hidden_size, 1).to(dev).train()
+            encoder = model.uniter_model
+        else:
+            model = UniterForPretraining(cfg, img_dim=2048, img_label_dim=1601).to(dev).train()
+            encoder = model.uniter
+        task_rng = random.Random(99) if args.workload != 'finetune' else None       # same task sequence on every rank
+        encoder.use_side_stream = not args.no_side_stream
+        encoder.precision = args.precision
+        encoder.pack_padded = args.packed
+        encoder.set_dropout_seed(1234 + rank, 0)
+        opt = FusedAdam(model, lr=config['lr'], weight_decay=config['weight_decay'])
+        if not args.no_adam_overlap:
+            opt.overlap_encoder = encoder
+        sched = get_scheduler(opt, config, steps_per_epoch=1000)
+        sync = None
+        if exchange:
+            dp.broadcast_parameters(model)
+            sync = dp.attach(model, sparse_embeddings=args.dp_sparse_embeddings, accum=config['gradient_accumulation'], token_capacity=B * T)
+            sync.timing = True
+        last, step = {}, None
+        if args.workload == 'finetune':
+            step = TrainStep(model, opt, sched, config, grad_sync=sync)
 
-        def one_step():
-            step.train_iter(batch, iters=0)
-    else:
-        last = {}
-        if sync is None:
-            opt.attach_norm_hooks(encoder)
-        opt.lazy_zero_encoder = encoder
+            def one_step():
+                step.train_iter(batch, iters=0)
+        else:
+            if sync is None:
+                opt.attach_norm_hooks(encoder)
+            opt.lazy_zero_encoder = encoder
 
-        def one_step():
-            task = task_rng.choice(tasks)
-            if sync is not None:     # the MLM task's tied decoder makes the word-embedding gradient dense
-                sync.prepare(True, token_ids=None if task == 'mlm' else batches[task]['input_ids'])
-            loss = model(batches[task], task, compute_loss=True).mean()
-            loss.backward()
-            sync_step(opt, sync, 1, config['max_grad_norm'])
-            sched.step()
-            last['loss'] = loss.detach()
+            def one_step():
+                task = task_rng.choice(tasks)
+                if sync is not None:     # the MLM task's tied decoder makes the word-embedding gradient dense
+                    sync.prepare(True, token_ids=None if task == 'mlm' else batches[task]['input_ids'])
+                loss = model(batches[task], task, compute_loss=True).mean()
+                loss.backward()
+                sync_step(opt, sync, 1, config['max_grad_norm'])
+                sched.step()
+                last['loss'] = loss.detach()
+        return model, encoder, opt, sync, step, one_step, task_rng, last
 
     def barrier():
         if use_dist:
@@ -628,12 +690,18 @@ def _run_rank(args, real_stdout, state):
         torch.cuda.synchronize()
 
     # clock warm-up (untimed, not part of W): a GPU that idled through the imports starts at its lowest clocks; about a
-    # second of steps before the W warm-up steps keeps the ramp out of the timed region
-    t_pre = time.perf_counter()
-    while args.prewarm_s > 0 and time.perf_counter() - t_pre < args.prewarm_s:
-        for _ in range(5):
-            one_step()
-        torch.cuda.synchronize()
+    # second of steps before the W warm-up steps keeps the ramp out of the timed region.  How many steps that is depends on
+    # the clock, so they run on a throwaway copy of the path (no gradient exchange) and the timed path starts from its seeds
+    if args.prewarm_s > 0:
+        pre_step = setup(False)[5]
+        t_pre = time.perf_counter()
+        while time.perf_counter() - t_pre < args.prewarm_s:
+            for _ in range(5):
+                pre_step()
+            torch.cuda.synchronize()
+        del pre_step
+        gc.collect()              # the copy's library handle is released here, not at some collection inside the timed region
+    model, encoder, opt, sync, step, one_step, task_rng, last = setup(use_dist)
     # N > 1: how many CUs the persistent matrix kernels should leave to RCCL is a property of the node (channels RCCL opens on its
     # links, how long its kernels run beside the backward pass): time a few untimed steps with a reserve of 16, 0 and 48 CUs,
     # keep the fastest on every rank (dp.pick_cu_reserve; UNITER_DP_CU_RESERVE or --no_reserve_pick fix it instead)
@@ -659,6 +727,18 @@ def _run_rank(args, real_stdout, state):
         one_step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed one (before any --full leg moves the parameters on)
+        st = model.param_store()
+        idx = torch.from_numpy(param_sample_index(st)).to(dev)
+        outs = {'loss': (step.last_loss if args.workload == 'finetune' else last['loss']).reshape(1)}
+        if args.workload == 'finetune':
+            outs['probs'] = step.last_probs
+        outs.update(params_sample=st.flat_params[idx], adam_exp_avg_sample=opt.exp_avg[idx],
+                    adam_exp_avg_sq_sample=opt.exp_avg_sq[idx])
+        nb = dump_outputs(args.dump_outputs, outs)
+        print('bench.py: %d arrays, %d bytes -> %s' % (len(outs), nb, args.dump_outputs), file=sys.stderr)
+        del idx, outs
     comm = None
     if sync is not None:
         comm = comm_block(sync, args.steps, rccl_log if rank == 0 else None)
@@ -765,7 +845,7 @@ def _run_rank(args, real_stdout, state):
                 k_n[k] = 0; e_n[k] = 0
     loss = float((step.last_loss if args.workload == 'finetune' else last['loss']).item())
     native = None
-    if args.precision == 'fp32x3' and world == 1 and not use_dist and not args.no_native_leg:
+    if args.full and args.precision == 'fp32x3' and world == 1 and not use_dist and not args.no_native_leg:
         # the same step on the native fp32 MFMA kernels, same process and box: what the six-product form is measured against
         try:
             st_ = model.param_store()
@@ -791,7 +871,7 @@ def _run_rank(args, real_stdout, state):
         except Exception as e:                               # noqa: BLE001
             native = {'error': repr(e)}
     bf16_leg = None
-    if args.precision == 'fp32x3' and world == 1 and not use_dist and not args.no_bf16_leg and args.workload == 'finetune':
+    if args.full and args.precision == 'fp32x3' and world == 1 and not use_dist and not args.no_bf16_leg and args.workload == 'finetune':
         # the same step in the bf16 mode (BASELINE configs[2] arithmetic on one GPU), same process and box, 20 timed steps: the
         # driver's line carries a bf16 figure too.  Auxiliary: a failure is reported in the block, the headline is untouched
         try:
@@ -879,11 +959,12 @@ def _run_rank(args, real_stdout, state):
             ns = fixed if fixed > 0 else (4 if (tiles <= 128 and nk >= 48) else 2 if (tiles <= 320 and nk >= 24) else 1)
             return (64 if (ns == 1 and tiles <= 160) else 128, 128, ns)
         floors = None
-        try:
-            floors = family_floors(args.precision, M_eff, H, I, B, L_eff, cfgd['num_attention_heads'],
-                                   plan={'fp32x3': _plan_x3, 'bf16': _plan_b16}.get(args.precision), sq=sq)
-        except Exception as e:                                   # noqa: BLE001 -- auxiliary: reported, never fatal
-            prof_error = (prof_error or '') + ' floors: ' + repr(e)
+        if args.full:
+            try:
+                floors = family_floors(args.precision, M_eff, H, I, B, L_eff, cfgd['num_attention_heads'],
+                                       plan={'fp32x3': _plan_x3, 'bf16': _plan_b16}.get(args.precision), sq=sq)
+            except Exception as e:                               # noqa: BLE001 -- auxiliary: reported, never fatal
+                prof_error = (prof_error or '') + ' floors: ' + repr(e)
         families = []
         for k, (name, bound, work) in fam.items():
             in_run = k_n[k] > 0
@@ -992,11 +1073,12 @@ def _run_rank(args, real_stdout, state):
                     out['roofline']['traffic_source'] = 'traffic_from_profile (counter passes of this command; not read inside the timed run)'
         # the optimizer step alone (HBM-bound: 32 B / parameter), measured after the timed region.  This and the CPU leg
         # below are auxiliary measurements: if one of them fails, the line of the timed region is still printed
-        try:
-            optimizer_alone(out, opt, model)
-        except Exception as e:                                   # noqa: BLE001 -- reported, never silent
-            out['optimizer_error'] = repr(e)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                optimizer_alone(out, opt, model)
+            except Exception as e:                               # noqa: BLE001 -- reported, never silent
+                out['optimizer_error'] = repr(e)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(all_cores=args.cpu_all_cores)
             except Exception as e:                               # noqa: BLE001

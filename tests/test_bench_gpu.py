@@ -1,10 +1,11 @@
-"""GPU: bench.py keeps its output contract (one JSON line with the driver's keys, the roofline and
-cpu_baseline objects) and __graft_entry__.smoke() runs."""
+"""GPU: bench.py keeps its output contract (one JSON line with the driver's keys; with --full also the roofline and
+cpu_baseline objects), a plain run's --dump-outputs does not depend on the clock warm-up, and __graft_entry__.smoke() runs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _bench(*flags):
 
 
 def test_bench_default_contract():
-    d = _bench()
+    d = _bench('--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
@@ -99,7 +100,7 @@ def test_bench_default_contract():
 
 
 def test_bench_native_fp32_mode_keeps_its_roofline():
-    d = _bench('--precision', 'fp32', '--no_cpu_baseline')
+    d = _bench('--full', '--precision', 'fp32', '--no_cpu_baseline')
     assert d['dtype'] == 'f32' and d['roofline']['peak'] == 157.3 and 'native fp32 MFMA' in d['config']['workload']
     assert 'native_fp32' not in d and d['peak_tflops']['dense_products'] == 157.3 and d['peak_tflops']['attention'] == 157.3
 
@@ -108,7 +109,7 @@ def test_bench_native_fp32_mode_keeps_its_roofline():
                                    ('--ragged', '--packed', '--no_cpu_baseline'),
                                    ('--workload', 'multitask', '--batch', '8', '--no_cpu_baseline')])
 def test_bench_variants_run(flags):
-    d = _bench(*flags)
+    d = _bench('--full', *flags)
     assert d['value'] > 0 and 'cpu_baseline' not in d
 
 
@@ -119,7 +120,7 @@ def test_bench_starts_its_own_ranks(extra):
     per rank) -- the launcher, the rendezvous, the exchange and the line are the ones an 8-GPU run uses."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     env.update(UNITER_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1',
                           '--prewarm_s', '0', '--prof_kind', '0', '--no_cpu_baseline', *(extra or ()), *(('--no_reserve_pick',) if extra else ())],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -145,6 +146,34 @@ def test_bench_starts_its_own_ranks(extra):
         rp = c['reserve_pick']
         assert [k['cu_reserve'] for k in rp['candidates']] == [16, 0, 48] and all(k['ms_per_step'] > 0 for k in rp['candidates'])
         assert rp['picked'] in (16, 0, 48) and c['cu_reserve'] == rp['picked']
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run carries the headline only; --dump-outputs writes the last timed step's loss, probabilities and a sample of the
+    updated parameters and Adam moments.  The clock warm-up (a time, not a step count) runs on a throwaway copy of the model: with
+    and without it the timed steps start from the same state and compute the same outputs, up to the order of float atomics."""
+    runs = []
+    for tag, extra in (('warm', ()), ('cold', ('--prewarm_s', '0'))):
+        d = _bench('--dump-outputs', str(tmp_path / tag), *extra)
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in d, k
+        assert d['steps'] == 3 and d['dtype'] == 'f32' and d['higher_is_better'] is True and d['unit'] == 'samples/s'
+        assert abs(d['value'] - 16 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-3
+        for k in ('roofline', 'roofline_families', 'native_fp32', 'bf16', 'optimizer', 'cpu_baseline'):
+            assert k not in d, k
+        files = sorted(os.listdir(str(tmp_path / tag)))
+        assert files == ['adam_exp_avg_sample.npy', 'adam_exp_avg_sq_sample.npy', 'loss.npy', 'params_sample.npy', 'probs.npy']
+        arr = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arr.values())
+        assert sum(a.nbytes for a in arr.values()) <= 64 << 20
+        assert arr['probs'].shape == (16,) and arr['params_sample'].shape == (1 << 22,) and abs(arr['loss'][0] - d['final_loss']) < 1e-4
+        runs.append(arr)
+    a, b = runs
+    assert abs(a['loss'][0] - b['loss'][0]) <= 1e-5 * abs(a['loss'][0]) and np.abs(a['probs'] - b['probs']).max() <= 1e-5
+    # (a warm-up on the timed model itself would be ~100 more Adam steps: parameters 1e-4 .. 1e-3 away)
+    assert np.abs(a['params_sample'] - b['params_sample']).max() <= 1e-6
+    for k in ('adam_exp_avg_sample', 'adam_exp_avg_sq_sample'):
+        assert np.abs(a[k] - b[k]).max() <= 1e-3 * np.abs(a[k]).max()
 
 
 def test_graft_entry_smoke():

@@ -133,3 +133,42 @@ def test_rank_host_threads_and_floor_arithmetic():
     assert set(fam) >= {'gemm_ffn_up_fwd', 'gemm_dgrad', 'gemm_wgrad', 'attention_bwd', 'layernorm_fwd'}
     assert len(fam['gemm_dgrad']['launches']) == 4 and fam['gemm_dgrad']['floor_us'] >= fam['gemm_dgrad']['mfma_us']
     assert bench.family_floors('fp32', M, 768, 3072, 16, 164, 12)['gemm_ffn_up_fwd']['intake_us'] == 0.0      # no LDS-DMA staging there
+
+
+def test_plain_run_flags_and_output_dump(tmp_path):
+    """A plain run leaves the per-family timings (in-kernel stamps) to --full; --dump-outputs writes float32 / float64 arrays,
+    a parameter sample that never draws the padding between tensors and is the same on every call, and refuses more than 64 MB."""
+    import numpy as np
+    import pytest
+    import torch
+    from types import SimpleNamespace
+    import bench
+    a = bench.parse_args([])
+    assert not a.full and a.prof_kind == 0 and a.dump_outputs is None
+    assert bench.parse_args(['--full']).prof_kind == -1 and bench.parse_args(['--full', '--prof_kind', '0']).prof_kind == 0
+    assert bench.parse_args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+    # a flat store of three tensors, each on a 64-element boundary, the padding marked -1
+    sizes = {'a': 100, 'b': 7, 'c': 300}
+    offs, off = {}, 0
+    for k, n in sizes.items():
+        offs[k] = off
+        off += -(-n // 64) * 64
+    flat = torch.full((off,), -1.0)
+    for k, n in sizes.items():
+        flat[offs[k]:offs[k] + n] = torch.arange(n, dtype=torch.float32)
+    st = SimpleNamespace(names=list(sizes), offsets=offs, params={k: torch.empty(n) for k, n in sizes.items()})
+    idx = bench.param_sample_index(st, n=50)
+    assert len(idx) == 50 and np.all(np.diff(idx) > 0) and (flat[torch.from_numpy(idx)] >= 0).all()
+    assert np.array_equal(idx, bench.param_sample_index(st, n=50))
+    every = bench.param_sample_index(st, n=10 ** 6)
+    assert len(every) == sum(sizes.values()) and (flat[torch.from_numpy(every)] >= 0).all()
+    nb = bench.dump_outputs(str(tmp_path / 'out'), {'loss': torch.tensor([0.5]), 'probs': torch.rand(4, dtype=torch.float16),
+                                                    'x': np.arange(3, dtype=np.float64)})
+    got = {f[:-4]: np.load(str(tmp_path / 'out' / f)) for f in os.listdir(str(tmp_path / 'out'))}
+    assert sorted(got) == ['loss', 'probs', 'x'] and nb == 4 + 16 + 24
+    assert got['loss'].dtype == np.float32 and got['probs'].dtype == np.float32 and got['x'].dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'p': np.zeros(bench.DUMP_LIMIT // 4 + 1, dtype=np.float32)})
+    assert not os.path.exists(str(tmp_path / 'big'))
