@@ -283,7 +283,8 @@ __global__ __launch_bounds__(256) void gather_rows_ex_kernel(const float* __rest
   else row_store_bf16<NV>(v, outb + (size_t)row * H, H4, lane);
 }
 
-// source-indexed: dcat[b,s] = sum over j with gi[b,j]==s of dout[b,j]  (no atomics, deterministic)
+// source-indexed: dcat[b,s] = sum over j with clamp(gi[b,j]) == s of dout[b,j]  (no atomics, deterministic; the adjoint of the
+// clamped forward, so an out-of-range index sends its gradient to the row it read)
 __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __restrict__ dout,
                                                               const int64_t* __restrict__ gi,
                                                               float* __restrict__ dcat, int B, int S, int Lout, int H) {
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __res
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int j0 = 0; j0 < Lout; j0 += 64) {
       const int j = j0 + lane;
-      const bool hit = j < Lout && gi[(size_t)b * Lout + j] == (int64_t)s;
+      const bool hit = j < Lout && clampi(gi[(size_t)b * Lout + j], S) == s;     // the row the forward read (gather_rows_kernel)
       unsigned long long m = __ballot(hit);
       while (m) {
         const int jj = j0 + __builtin_ctzll(m);
@@ -321,8 +322,9 @@ __global__ void img_mask_add_kernel(const float* __restrict__ feat, const int64_
   if (idx >= (size_t)rows * D4) return;
   const int row = (int)(idx / D4), c = (int)(idx - (size_t)row * D4);
   f32x4 v = reinterpret_cast<const f32x4*>(feat)[idx];
-  const int64_t m = masks[row];
-  if (m != 0) v += reinterpret_cast<const f32x4*>(mask_emb + (size_t)(m > 1 ? 1 : m) * D4 * 4)[c];   // row 0 == 0
+  // any non-zero mask adds row 1 (row 0 is zero in the reference); the same test as masked_rowsum_kernel, its gradient -- a
+  // negative mask used to index before the table
+  if (masks[row] != 0) v += reinterpret_cast<const f32x4*>(mask_emb + (size_t)D4 * 4)[c];
   reinterpret_cast<f32x4*>(out)[idx] = v;
 }
 

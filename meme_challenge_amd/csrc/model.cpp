@@ -1313,10 +1313,13 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
   // text branch and the image branch share nothing but dcat: with an auxiliary stream the text branch (and, behind the image rows'
   // pass, the region projection's bias column sums) runs there, beside the image branch.  Same kernels, same results; the token-type
   // table's gradient is the one buffer both branches add to (row 0 / the text rows' types there, row 1 / the image rows' types here):
-  // with explicit type ids both scatter by float atomics, without them each finalizes into its own row -- no ordering between them
-  // is needed either way.  UNITER_EMBED_BWD_PAR=0 keeps one stream.
+  // with explicit type ids on both sides both scatter by float atomics, without them on either side each finalizes into its own row,
+  // and in those two cases no ordering between the branches is needed.  With mixed ids (one side explicit, the other implicit) one
+  // branch's atomics land on the row the other finalizes with a plain read-add-write, which could lose an update: those batches keep
+  // one stream, whose order serializes the two writers.  UNITER_EMBED_BWD_PAR=0 keeps one stream.
   static const bool par_env = [] { const char* e = getenv("UNITER_EMBED_BWD_PAR"); return !(e && e[0] == '0'); }();
-  hipStream_t ax = (par_env && m->aux && m->aux != st && m->aux != sd && pl.has_txt && pl.has_img) ? m->aux : nullptr;
+  const bool types_alike = (b.txt_type_ids == nullptr) == (b.img_type_ids == nullptr);
+  hipStream_t ax = (par_env && m->aux && m->aux != st && m->aux != sd && pl.has_txt && pl.has_img && types_alike) ? m->aux : nullptr;
   if (ax) {
     if (!m->ev_emb0) UCHECK_HIP(hipEventCreateWithFlags(&m->ev_emb0, hipEventDisableTiming));
     if (!m->ev_emb1) UCHECK_HIP(hipEventCreateWithFlags(&m->ev_emb1, hipEventDisableTiming));
