@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
+#include "switches.h"
 #include "philox.h"
 
 namespace {
@@ -586,8 +587,7 @@ int fill(Args& a, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t of
   a.B = B; a.L = L; a.nh = nh; a.H = nh * D; a.Lp4 = (L + 3) / 4;
   a.scale = 0.125f;        // 1/sqrt(64), model/layer.py:86
   a.drop = make_drop(p_drop, seed, offset, site);
-  static const int prio = [] { const char* e = getenv("UNITER_ATTN_PRIO"); return e ? atoi(e) : 2; }();
-  a.prio = prio;
+  a.prio = uniter_switches().attn_prio;
   return 0;
 }
 
@@ -644,8 +644,7 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
   const size_t red_dq = max3((size_t)(2 * Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4, 0);
   const size_t red_dkv = max3((size_t)(2 * D * TLD) * 2, (size_t)nblk * 64 * 64 * 4, 0);
   const size_t lds_dq = red_dq + 192 * 4, lds_dkv = red_dkv + 192 * 4;
-  static const bool fused = [] { const char* e = getenv("UNITER_ATTN_BWD_FUSED"); return !(e && e[0] == '0'); }();
-  if (fused) {
+  if (uniter_switches().attn_bwd_fused) {
     const size_t lds = lds_dq > lds_dkv ? lds_dq : lds_dkv;
     if (a.qb16) {
       UCHECK_RC(set_lds(attn_b16_bwd_fused_kernel<true>, lds));

@@ -25,6 +25,7 @@
 // lse/delta [B, nh, L].  head_dim == 64.
 #include <stdlib.h>
 #include "common.h"
+#include "switches.h"
 #include "philox.h"
 
 namespace {
@@ -1006,17 +1007,8 @@ int set_dyn_lds(K kernel, size_t bytes) {
   return 0;
 }
 
-// UNITER_ATTN_SPLIT=0 keeps the one-wave-per-block resident kernels (A/B measurements)
-bool split_enabled() {
-  static const bool on = [] { const char* e = getenv("UNITER_ATTN_SPLIT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// UNITER_ATTN_BWD_FUSED=0: the two passes of the L <= 192 backward as two launches (A/B measurements)
-bool bwd_fused() {
-  static const bool on = [] { const char* e = getenv("UNITER_ATTN_BWD_FUSED"); return !(e && e[0] == '0'); }();
-  return on;
-}
+bool split_enabled() { return uniter_switches().attn_split; }
+bool bwd_fused() { return uniter_switches().attn_bwd_fused; }
 
 int make_args(AttnArgs& a, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
               uint32_t site) {
@@ -1025,8 +1017,7 @@ int make_args(AttnArgs& a, int B, int L, int nh, float p_drop, uint64_t seed, ui
   a.B = B; a.L = L; a.nh = nh; a.H = nh * D; a.Lp4 = (L + 3) / 4;
   a.scale = 0.125f;   // 1/sqrt(64), model/layer.py:86
   a.drop = make_drop(p_drop, seed, offset, site);
-  static const int prio = [] { const char* e = getenv("UNITER_ATTN_PRIO"); return e ? atoi(e) : 2; }();
-  a.prio = prio;
+  a.prio = uniter_switches().attn_prio;
   return 0;
 }
 

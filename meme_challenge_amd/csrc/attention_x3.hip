@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "switches.h"
 
 namespace {
 
@@ -760,8 +761,7 @@ int fill(Args& a, int B, int L, int nh, float p_drop, const void* keep_bits, con
   a.scale = 0.125f;        // 1/sqrt(64), model/layer.py:86
   a.keep_bits = p_drop > 0.f ? static_cast<const u16*>(keep_bits) : nullptr;
   a.drop_scale = 1.0f / (1.0f - p_drop);
-  static const int prio = [] { const char* e = getenv("UNITER_ATTN_PRIO"); return e ? atoi(e) : 2; }();
-  a.prio = prio;
+  a.prio = uniter_switches().attn_prio;
   return 0;
 }
 
@@ -781,8 +781,7 @@ int launch_bwd(const Args& a, hipStream_t st) {
   const size_t lds = (size_t)2 * NP * IMG + (size_t)3 * Lr * 4 + 192 * 4 + (size_t)Lr * (Lr / 32) * 4;
 #ifdef UNITER_X3_LAB
   if constexpr (NP == 3 && !QB16) {
-    const char* e = getenv("UNITER_ATTN_X3_LAB");
-    const int lab = e ? atoi(e) : 0;
+    const int lab = uniter_switch_attn_x3_lab();
 #define X3A_LAB_CASE(N)                                                                                                  \
     if (lab == N) {                                                                                                      \
       UCHECK_RC(set_lds(attn_x3_bwd_kernel<3, false, N>, lds));                                                          \

@@ -17,6 +17,7 @@
 // identical for all three layouts and no transposed LDS read is needed.
 #include <stdlib.h>
 #include "common.h"
+#include "switches.h"
 
 namespace {
 
@@ -497,10 +498,8 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
 template <int BM, int BN, bool AKM, bool BKM, bool RES = false>
 int launch_b(GemmArgsB g, hipStream_t st, int slots) {
   if (BM == 64 && BN == 64) slots = 768;     // three 64x64 workgroups per CU (wgs_per_cu)
-  static const int sk_slots = [] { const char* e = getenv("UNITER_WGRAD_SLOTS"); return e ? atoi(e) : 0; }();   // A/B: stream-K pieces
-  // weight gradients run on the side stream BESIDE the input-gradient chain: 512 pieces (two per CU, ~96 KB of LDS)
-  // leave room for a 64-KB workgroup of the other stream on every CU, 768 (three per CU) fill the LDS and the two
-  // streams take turns instead (bf16 step 2898 -> 2944 samples/s; 384: 2913, 256: 2798)
+  // weight gradients: 512 stream-K pieces unless UNITER_WGRAD_SLOTS names another count (switches.h)
+  const int sk_slots = uniter_switches().wgrad_slots;
   if (g.beta == 1 && AKM && BKM && BM == 64 && BN == 64) slots = sk_slots > 0 ? sk_slots : 512;
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;

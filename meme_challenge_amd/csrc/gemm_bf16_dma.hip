@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "switches.h"
 #include "riders.h"
 
 namespace {
@@ -729,17 +730,11 @@ int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int 
 // dW_p[M_p, N_p] += A_p^T B_p for up to four products of one reduction length K (A_p [K, M_p], B_p [K, N_p] bf16,
 // dW_p fp32 with leading dimension N_p), one launch; cfg 1 = two LDS stages (two workgroups per CU), 4 = three.
 // workgroups of the grouped launch over `total` tiles: a multiple of 8, capped (max_wgs > 0: by the caller; else
-// UNITER_WGRAD_GROUP_WGS, default 256 = one workgroup per CU walking its tiles)
+// UNITER_WGRAD_GROUP_WGS, default 256 = one workgroup per CU walking its tiles: switches.h)
 int gemm_chip_cus();
 static int wgrad_group_grid(int total, int max_wgs) {
   int grid = (total + 7) / 8 * 8;
-  // UNITER_WGRAD_GROUP_WGS: cap of the grid (a multiple of 8; 0 = one workgroup per tile).  Default 256 = one workgroup of this
-  // launch per CU, walking its tiles: the launch alone takes what two co-resident workgroups take (a lone 4-wave tile runs
-  // its k-loop at 0.57 us per k-tile against 0.93 for two), and every CU keeps a slot for the other stream's kernels.
-  // Measured again once the attention backward took its CU in one launch (four same-box rounds): UNITER-base 4.75 -> 4.71 ms,
-  // UNITER-large 9.65 -> 9.49, config 5 at B = 32 8.19 -> 8.00 ms per step; 192 / 320 / 384 workgroups 4.77-4.80, 128 5.13
-  static const int cap_env = [] { const char* e = getenv("UNITER_WGRAD_GROUP_WGS"); return e ? atoi(e) / 8 * 8 : 256; }();
-  int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : cap_env;
+  int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : uniter_switches().wgrad_group_wgs;
   if (g_uniter_cu_reserve > 0 && cap >= 8) {              // CUs left to the data-parallel exchange's kernels (common.h)
     const int room = (gemm_chip_cus() - g_uniter_cu_reserve) / 8 * 8;      // (the device's CU count: gemm_split3.hip)
     if (room >= 8 && cap > room) cap = room;
@@ -849,15 +844,10 @@ int gemm_bf16v2_pick_split(int M, int N, int K) {
 }
 
 // Weight gradients dW[M, N] += dY^T X (both operands k-major, K = rows of the batch): pieces of the split-K slab form,
-// or 0 = keep the stream-K + float-atomics kernel of gemm_bf16.hip.  Measured at K = 2624
-// (profiles/r02_gemm_bf16_v2.txt): 768 x 3072 39.2 -> 30.9 us with two pieces, 2304 x 768 26.0 -> 24.7 (two),
-// 768 x 768 17.9 -> 16.8 (four); 3072 x 768 stays on stream-K (29.0 vs 31.2).
-// In the training step the gain does not survive (2870 -> 2855 samples/s: the weight gradients share the chip with the
-// input-gradient chain, whose idle slots the perfectly balanced stream-K pieces fill better), so the slab form is an
-// opt-in (UNITER_WGRAD_SLABS=1) and the default stays stream-K.
+// or 0 = keep the stream-K + float-atomics kernel of gemm_bf16.hip (the default: the slab form is the opt-in
+// UNITER_WGRAD_SLABS=1, switches.h)
 int gemm_bf16v2_wgrad_pieces(int M, int N, int K) {
-  static const bool on = [] { const char* e = getenv("UNITER_WGRAD_SLABS"); return e && e[0] == '1'; }();
-  if (!on || K < 1024 || M % 8 || N % 8) return 0;
+  if (!uniter_switches().wgrad_slabs || K < 1024 || M % 8 || N % 8) return 0;
   const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
   if (tiles <= 48) return 4;
   if (M <= N || tiles <= 128) return 2;

@@ -28,6 +28,7 @@
 //  * epilogues through buffer instructions with scalar row offsets; optional per-32-row column sums.
 #include <stdlib.h>
 #include "common.h"
+#include "switches.h"
 
 namespace {
 
@@ -54,11 +55,6 @@ __device__ __forceinline__ float buf_ld_f32(__amdgpu_buffer_rsrc_t r, int voff, 
 }
 __device__ __forceinline__ void buf_st_f32(float v, __amdgpu_buffer_rsrc_t r, int voff, int soff, int aux) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-}
-
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
 }
 
 constexpr int BK = 32;
@@ -750,7 +746,7 @@ int launch_v3(GemmArgs g, hipStream_t st, int slots, bool allow_sk = true) {
   }
   int grid = tiles < slots ? (tiles + 7) / 8 * 8 : slots;
   // stream-K when the tiles fill the slots unevenly (only legal for a plain accumulating GEMM)
-  static const int sk_mode = env_int("UNITER_GEMM_SK", 1);     // 0 never, 1 heuristic, 2 whenever legal
+  const int sk_mode = uniter_switches().gemm_sk;     // 0 never, 1 heuristic, 2 whenever legal
   if constexpr (TAG == 0) if (allow_sk && sk_mode && g.beta == 1 && g.epi == UNITER_EPI_NONE && !g.colsum_part && tiles >= 8) {
     const int rounds = (tiles + slots - 1) / slots;
     const bool uneven = (long)tiles * 100 < (long)rounds * slots * 88;
@@ -761,7 +757,7 @@ int launch_v3(GemmArgs g, hipStream_t st, int slots, bool allow_sk = true) {
     if (units < 8l * slots) sk_n = (int)(units / 8 / 256) * 256;
     if ((uneven || sk_mode == 2) && sk_n >= 256) {
       slots = sk_n;
-      static const int sk_slots = env_int("UNITER_WGRAD_SLOTS_F32", 0);      // A/B: pieces of the stream-K form
+      const int sk_slots = uniter_switches().wgrad_slots_f32;      // A/B: pieces of the stream-K form
       if (sk_slots > 0) slots = sk_slots;
       hipLaunchKernelGGL((gemm_f32_v3_kernel<BM, BN, AKM, BKM, 0, true>), dim3(slots), dim3(256), 0, st, g);
       UCHECK_LAUNCH();
@@ -831,7 +827,7 @@ int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float
   G.start[4] = total;
   for (int p = n; p < 4; ++p) G.start[p] = total;
   G.K = K; G.overwrite = overwrite; G.prio = take_launch_prio(); G.stamp = take_stamp_slot();
-  static const int slots_env = env_int("UNITER_WGRAD_GROUP_F32_SLOTS", 1024);
+  const int slots_env = uniter_switches().wgrad_group_f32_slots;
   const int slots = slots_env >= 8 ? slots_env / 8 * 8 : 1024;
   const int grid = total < slots ? (total + 7) / 8 * 8 : slots;
   hipLaunchKernelGGL(gemm_f32_wgrad_group_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, G);

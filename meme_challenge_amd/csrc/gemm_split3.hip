@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "switches.h"
 #include "riders.h"
 
 namespace {
@@ -1109,9 +1110,7 @@ void plan_tiles3(S3Args& g, int BN) {
   long bh = 1;
   while ((bh + 1) * (bh + 1) * (long)BM <= 32l * BN) ++bh;
   g.band_h = (int)(bh > 16 ? 16 : bh);
-  // UNITER_X3_BAND_H: tile rows per band of the walk (lab switch: how many row panels an XCD's chunk of the walk spans decides how
-  // often the eight L2s fetch the same operand panels -- VERDICT r04 item 7)
-  static const int band_env = [] { const char* e = getenv("UNITER_X3_BAND_H"); return e ? atoi(e) : 0; }();
+  const int band_env = uniter_switches().x3_band_h;      // (lab switch)
   if (band_env > 0) g.band_h = band_env;
   if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
 }
@@ -1422,8 +1421,7 @@ int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, i
 // only: more tiles than that fill the chip without them).  Written for `avail` < the chip's CUs too: while a data-parallel
 // exchange holds CUs (uniter_model_set_cu_reserve) the 252-item forms that exactly fit 256 CUs would run two rounds on 240.
 void x3_choose(int M, int N, int K, int avail, int nsplit_fixed, int* cfg_out, int* ns_out, bool allow192) {
-  static const bool wide_on = [] { const char* e = getenv("UNITER_X3_WIDE"); return !(e && e[0] == '0'); }();
-  static const bool on192 = [] { const char* e = getenv("UNITER_X3_192"); return !(e && e[0] == '0'); }();
+  const bool wide_on = uniter_switches().x3_wide, on192 = uniter_switches().x3_192;
   if (avail < 8) avail = 8;
   const long tm = (M + 127) / 128, t128 = tm * ((N + 127) / 128), t256 = tm * ((N + 255) / 256), t192 = tm * ((N + 191) / 192);
   const int nk = (K + 31) / 32;
@@ -1565,10 +1563,7 @@ static int wgrad_tiles(int cfg, int n, const int* Mo, const int* No) {
   return total;
 }
 // the default geometry of the grouped launch (UNITER_X3_WGRAD_CFG = 3 | 4 overrides)
-int gemm_x3_wgrad_default_cfg() {
-  static const int c = [] { const char* e = getenv("UNITER_X3_WGRAD_CFG"); const int v = e ? atoi(e) : 0; return (v == 3 || v == 4) ? v : 4; }();
-  return c;
-}
+int gemm_x3_wgrad_default_cfg() { return uniter_switches().x3_wgrad_cfg; }
 
 int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B,
                         float* const* dW, void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders,

@@ -10,6 +10,7 @@
 // per-workgroup partial rows in a workspace, then a finalize kernel.
 #include <stdlib.h>
 #include "common.h"
+#include "switches.h"
 #include "philox.h"
 #include "rowops.h"
 
@@ -285,8 +286,8 @@ __global__ void add_kernel(float* __restrict__ out, const float* __restrict__ a,
 }
 
 // waves per workgroup / rows per wave of the backward row pass (A/B switches: UNITER_LNB_WAVES = 4 | 8, UNITER_LNB_ROWS)
-inline int lnb_waves() { static const int w = [] { const char* e = getenv("UNITER_LNB_WAVES"); return (e && atoi(e) == 8) ? 8 : 4; }(); return w; }
-inline int lnb_rows() { static const int r = [] { const char* e = getenv("UNITER_LNB_ROWS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v; }(); return r; }
+inline int lnb_waves() { return uniter_switches().lnb_waves; }
+inline int lnb_rows() { return uniter_switches().lnb_rows; }
 inline int ln_bwd_blocks(int M) {
   const int per = lnb_waves() * lnb_rows();
   int b = (M + per - 1) / per;

@@ -16,6 +16,7 @@
 #include <vector>
 #include "common.h"
 #include "philox.h"
+#include "switches.h"
 
 // internal helpers implemented in other translation units
 int launch_add_f32(float* out, const float* a, const float* b, size_t n, hipStream_t st);
@@ -106,10 +107,23 @@ struct LayerBufs {   // saved activations + backward scratch of one layer
   unsigned short *ctxb, *y1b, *hactb, *y2b, *g2b, *dub, *g1b, *dqkvb;
 };
 
+// the attention kernel of a plan, by its forward entry point; the backward entry point follows from it (backward_layer)
+enum AttnKernel {
+  ATTN_F32,          // uniter_attn_fwd / uniter_attn_bwd: any length, reads the padded mask
+  ATTN_F32_PRE,      // uniter_attn_fwd_pre / uniter_attn_bwd_ex: the L <= 192 kernels (packed batches, saved plans)
+  ATTN_F32_PRE_X3,   // uniter_attn_fwd_pre_x3 / uniter_attn_bwd_ex_x3: the same with x3 pieces out (precision 3)
+  ATTN_X3,           // uniter_attn_x3_fwd / _bwd: precision 3, the attention's own products on the bf16 pipe
+  ATTN_BF16_PRE,     // uniter_attn_bf16_fwd_pre / uniter_attn_bf16_bwd: precision 2 (attention_bf16.hip)
+  ATTN_B16X          // uniter_attn_b16x_fwd / _bwd: precision 2 in attention_x3.hip's decomposition
+};
+inline bool attn_is_b16(AttnKernel k) { return k == ATTN_BF16_PRE || k == ATTN_B16X; }
+
 struct Plan {
   int B, T, R, L, S, T0, M, mode;
   bool has_txt, has_img;
   bool gelu_d;      // forward stored gelu'(u) in LayerBufs::u rather than u
+  // the attention kernels of this plan's forward and backward pass (attn_kernel(), decided once by uniter_model_forward)
+  AttnKernel attn_fwd, attn_bwd;
   float *feat_eff, *imgfc, *img_stats, *cat, *emb;
   std::vector<LayerBufs> layers;
   float *dcat, *d_imgfc, *d_posfc, *d_feat, *dsum, *dpk;
@@ -206,18 +220,11 @@ int check_cfg(const uniter_config_t* c) {
 }
 
 int x3_backward_cus(const uniter_model* m);
-// precision 2, round 6: which products run on the persistent kernels of gemm_bf16_p.hip (bit mask, see gemm_v2 / backward_layer)
-int b16_persist_mask() {
-  // default 0: built, parity-tested through the C ABI, faster isolated -- and the STEP is slower with every subset of them (same-box A/B,
-  // profiles/r06_b16_persist_ab.txt: 4.39 ms with none, 4.43-4.75 with bits 1 / 2 / 4 / 7 / 12 / 15): their 96-144 KB workgroups own a
-  // CU, where two 64-KB workgroups of gemm_dma_kernel let the two backward streams and the kernel boundaries of the forward pass overlap
-  static const int m = [] { const char* e = getenv("UNITER_B16_PERSIST"); return e ? atoi(e) : 0; }();
-  return m;
-}
 
 void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, int L, bool has_txt,
                bool has_img, bool has_masks, int mode, int Mrows = -1) {
   const uniter_config_t& c = m->cfg;
+  const Switches& sw = uniter_switches();
   const int H = c.hidden_size, I = c.intermediate_size, nl = c.num_hidden_layers, nh = c.num_attention_heads;
   pl.B = B; pl.T = T; pl.R = R; pl.L = L; pl.mode = mode; pl.has_txt = has_txt; pl.has_img = has_img;
   pl.T0 = has_txt ? T : 0;
@@ -239,7 +246,7 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   pl.embb = (pl.res || pl.x3) ? cv.h(pc * M * H) : nullptr;
   pl.ns_ki = pl.res ? gemm_bf16v2_pick_split(pl.M, H, I) : pl.x3 ? gemm_x3_pick_split(pl.M, H, I) : 1;
   pl.ns_k3h = pl.res ? gemm_bf16v2_pick_split(pl.M, H, 3 * H) : pl.x3 ? gemm_x3_pick_split(pl.M, H, 3 * H) : 1;
-  if (pl.res && (b16_persist_mask() & 2)) {
+  if (pl.res && (sw.b16_persist & 2)) {
     // round 6: the N = hidden products on the persistent kernels are planned by their own cost model (one workgroup per CU: two
     // k-pieces fill the chip where gemm_dma_kernel's two workgroups per CU wanted four -- two slabs less for the row pass behind)
     const int a = gemm_b1p_pick_split(pl.M, H, I, 0), b = gemm_b1p_pick_split(pl.M, H, 3 * H, 0);
@@ -293,15 +300,10 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
       if (l & 1) pl.layers[l].y2 = yB;
     }
   }
-  // UNITER_X3_BALANCED (default 0: off; bit 0 = the grouped weight gradients, bit 1 = the forward products with a bias epilogue): the
-  // balanced walk is built and parity-tested, and LOSES in the step -- 9.40 -> 9.81 ms (bit 0), 9.40 -> 9.52 (bit 1) at configs[1],
-  // +0.8 % only for UNITER-large's weight gradients (384 tiles: two rounds): the CUs a 216-tile launch leaves idle are not idle in the
-  // step (the other stream's input-gradient kernels take them), the hand-over costs ~4 k-tiles per workgroup, and a workgroup
-  // that waits for a partial sum holds its CU (profiles/r05_balanced_walk_ab.txt)
-  static const int sk_env = [] { const char* e = getenv("UNITER_X3_BALANCED"); return e ? atoi(e) : 0; }();
+  // the balanced walk's workspaces (UNITER_X3_BALANCED, default off: bit 0 = the grouped weight gradients, bit 1 = the forward products)
   pl.sk_bytes = gemm_x3_sk_ws_bytes();
-  pl.sk_main = (pl.x3 && (sk_env & 2)) ? cv.raw(pl.sk_bytes) : nullptr;
-  pl.sk_side = (pl.x3 && save && (sk_env & 1)) ? cv.raw(pl.sk_bytes) : nullptr;
+  pl.sk_main = (pl.x3 && (sw.x3_balanced & 2)) ? cv.raw(pl.sk_bytes) : nullptr;
+  pl.sk_side = (pl.x3 && save && (sw.x3_balanced & 1)) ? cv.raw(pl.sk_bytes) : nullptr;
   if (save) {
     pl.hid_stride = align_up(uniter_hidden_keep_bits_bytes(M * H), 256);
     pl.hid_keepb = (unsigned char*)cv.raw(pl.hid_stride * 2 * nl);
@@ -324,10 +326,7 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
     pl.attn_ws_bytes = uniter_attn_bwd_ws_bytes(B, L, c.num_attention_heads);
     pl.attn_ws = cv.raw(pl.attn_ws_bytes);
     pl.wg_slabs = pl.res ? cv.f((size_t)4 * 3 * H * (I > 3 * H ? I : 3 * H)) : nullptr;
-    // 1 (default): the four weight gradients of a layer as one launch of whole-K tiles (gemm_bf16_dma.hip); 0: four
-    // stream-K launches with float atomics; 2: as 1 with the three early products launched next to the attention
-    // backward (measured slower); 4: as 1 with three LDS stages (measured slower)
-    static const int wg_env = [] { const char* e = getenv("UNITER_WGRAD_GROUP"); return e ? atoi(e) : 1; }();
+    const int wg_env = sw.wgrad_group;      // (1, the default: one launch of whole-K tiles; 2 / 4: its measured-slower forms; 0: stream-K)
     pl.wg_group = (pl.res && H % 8 == 0 && I % 8 == 0 && (wg_env == 1 || wg_env == 2 || wg_env == 4)) ? wg_env : 0;
     // the grouped kernel addresses its operands with 31-bit buffer offsets: very long batches keep the stream-K launches
     if ((size_t)(M + 64) * (I > 3 * H ? I : 3 * H) * 2 >= (1ull << 31)) pl.wg_group = 0;
@@ -358,21 +357,15 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
          int lda, const float* B, int ldb, float* C, int ldc, int epi, const float* bias, const float* aux_in,
          float* aux_out, int ld_aux, int beta, float* colsum_part = nullptr) {
   ProfScope ps(m, kind, st);
-  // weight gradients: UNITER_WGRAD_CFG = 21 selects 128 x 128 stream-K tiles (measured slower: DESIGN.md section 9), 24 the 64 x 64 ones
-  static const int wg_cfg = [] { const char* e = getenv("UNITER_WGRAD_CFG"); return e ? atoi(e) : 0; }();
-  // UNITER_WGRAD_WHOLE: bit mask over a layer's weight gradients by output shape (1: [H, I] output.dense, 2: [I, H]
-  // intermediate.dense, 4: [H, H] attention output, 8: [3H, H] query|key|value): whole-K tiles (cfg 25) instead of stream-K.
-  // Default 15: measured 13.95 against 14.06 ms per step with every shape on whole tiles -- the k-synchronous tiles of a
-  // tile row share their operand panel in L2 (the LayerNorm backward beside them runs at 17 instead of 26 us) -- and
-  // without float atomics the fp32 weight gradients are bit-reproducible and a first backward pass may overwrite them.
-  static const int wg_whole = [] { const char* e = getenv("UNITER_WGRAD_WHOLE"); return e ? atoi(e) : 15; }();
+  const Switches& sw = uniter_switches();
   int cfg = 0;
   const bool wgrad = kind == UNITER_K_GEMM_WGRAD && akm && bkm && (beta == 1 || beta == -1);
   if (wgrad && (m->precision == 0 || m->precision == 3)) {
-    cfg = wg_cfg;
+    // a layer's weight gradients by output shape: whole-K tiles (cfg 25, UNITER_WGRAD_WHOLE's bit) or UNITER_WGRAD_CFG's stream-K tiles
+    cfg = sw.wgrad_cfg;
     const int H_ = m->cfg.hidden_size, I_ = m->cfg.intermediate_size;
     const int bit = (M == H_ && N == I_) ? 1 : (M == I_ && N == H_) ? 2 : (M == H_ && N == H_) ? 4 : (M == 3 * H_ && N == H_) ? 8 : 0;
-    if (wg_whole & bit) cfg = 25;
+    if (sw.wgrad_whole & bit) cfg = 25;
   }
   if (beta == -1) {
     // overwrite requested (uniter_model_set_wgrad_overwrite): whole-K tiles store their result; every form that adds
@@ -380,12 +373,8 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
     if (cfg == 25) beta = 0;
     else { UCHECK_HIP(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(float), st)); beta = 1; }
   }
-  // wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h).  fp32: measured WORSE
-  // (14.09 against 13.73 ms per step with level 2: the input-gradient GEMM then starves the weight-gradient launch it
-  // shares the matrix pipe with, and the chain waits for that launch at the layer's end), so the default is 0 here; the
-  // bf16-resident GEMMs below gain 0.6 % from level 2 (their bound is operand staging, not the pipe)
-  static const int main_prio = [] { const char* e = getenv("UNITER_MAIN_PRIO"); return e ? atoi(e) : 0; }();
-  g_uniter_launch_prio = kind == UNITER_K_GEMM_WGRAD ? 0 : main_prio;
+  // wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h; UNITER_MAIN_PRIO, default 0)
+  g_uniter_launch_prio = kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio;
   if (m->precision == 1 || m->precision == 2)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
     return gemm_bf16_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias, aux_in, aux_out, ld_aux, beta,
                          colsum_part, st);
@@ -400,16 +389,11 @@ int gemm_v2(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, in
             const float* bias, const void* aux_in, int aux_in_b16, void* aux_out, int aux_out_b16, int ld_aux,
             float* colpart = nullptr) {
   ProfScope ps(m, kind, st);
-  static const int main_prio = [] { const char* e = getenv("UNITER_MAIN_PRIO_BF16"); return e ? atoi(e) : 2; }();
-  g_uniter_launch_prio = main_prio;
-  // round 6: the persistent loader / compute kernels (csrc/gemm_bf16_p.hip) where they win isolated (profiles/r06_b1p_lab.txt):
-  // the query|key|value projection on 128 x 192 tiles (252 for 256 CUs: 15.4 against 16.9 us), the N = hidden products with k-pieces
-  // on persistent 128 x 128 tiles (FFN-down forward 20.4 against 22.6 us, FFN-up / QKV input gradients 22.1 / 19.1 against
-  // 24.1 / 20.5).  The N = intermediate products tie (128 x 256 tiles stage a quarter less per k-tile -- 0.75 against 0.93 us, the
-  // vendor library's slope -- and pay 2 us more fixed cost on a 12-k-tile loop): they keep gemm_dma_kernel.  UNITER_B16_PERSIST is a
-  // bit mask: 1 = QKV forward, 2 = N = hidden products, 8 = the wide products as well (4: the grouped weight gradients, below)
+  g_uniter_launch_prio = uniter_switches().main_prio_bf16;
+  // round 6: the persistent loader / compute kernels (csrc/gemm_bf16_p.hip) for the products UNITER_B16_PERSIST names (default: none):
+  // 1 = QKV forward, 2 = N = hidden products, 8 = the wide products as well (4: the grouped weight gradients, wgrad_group())
   int cfg = 0;
-  const int mask = b16_persist_mask();
+  const int mask = uniter_switches().b16_persist;
   const bool epi_ok = epi == UNITER_EPI_NONE || epi == UNITER_EPI_BIAS || epi == UNITER_EPI_ADD || epi == UNITER_EPI_BIAS_GELU_D || epi == UNITER_EPI_MUL;
   if (epi_ok && K % 64 == 0) {
     if ((mask & 1) && kind == UNITER_K_GEMM_QKV_FWD && !bkm && N % 192 == 0) cfg = 8;
@@ -424,17 +408,21 @@ int gemm_v2(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, in
   return gemm_bf16v2_run(cfg, nsplit, 0, bkm, M, N, K, A, lda, B, ldb, C, ldc, (long)M * ldc, Cb, ldcb, epi, bias, aux_in,
                          aux_in_b16, aux_out, aux_out_b16, ld_aux, 0, st);
 }
-// precision 3: the attention's products on the bf16 pipe too (csrc/attention_x3.hip) -- L <= 192 and, with dropout, keep flags drawn
-// ahead of the kernel.  UNITER_ATTN_X3=0 keeps the fp32-MFMA kernels of attention_f32.hip (A/B measurements).
-bool attn_x3_products(int L, float p_drop, bool keep_flags_ready) {
-  static const bool on = [] { const char* e = getenv("UNITER_ATTN_X3"); return !(e && e[0] == '0'); }();
-  return on && L <= uniter_attn_x3_max_len() && (p_drop == 0.f || keep_flags_ready);
-}
-// precision 2: the bf16 attention in attention_x3.hip's decomposition (no scratch hand-over).  UNITER_ATTN_B16X=0 keeps
-// attention_bf16.hip's kernels (A/B measurements).
-bool attn_b16x(int L, float p_drop, bool keep_flags_ready) {
-  static const bool on = [] { const char* e = getenv("UNITER_ATTN_B16X"); return !(e && e[0] == '0'); }();
-  return on && L <= uniter_attn_x3_max_len() && (p_drop == 0.f || keep_flags_ready);
+// The attention kernel of a plan's forward pass (`keep_pre`: the forward drew the dropout keep flags ahead of its kernels) or of its
+// backward pass (bwd).  The kernels of attention_x3.hip (ATTN_X3, ATTN_B16X) read the keep flags and draw none, so with dropout they
+// need them ready; the backward pass of a saved plan always finds them -- whichever forward kernel ran left them -- which is why a
+// forward pass without pre-drawn flags (UNITER_KEEP_PREGEN=0) pairs a *_PRE forward kernel with the ATTN_X3 / ATTN_B16X backward.
+AttnKernel attn_kernel(const Plan& pl, float p_drop, bool save, bool keep_pre, bool bwd) {
+  const Switches& sw = uniter_switches();
+  const bool fused = pl.L <= uniter_attn_varlen_max_len();      // the L <= 192 kernels (none with UNITER_ATTN_SPLIT=0)
+  const bool pieces = pl.L <= uniter_attn_x3_max_len() && (p_drop == 0.f || keep_pre || bwd);
+  // precision 2, L <= 192: attention on the bf16 pipe, which also writes the bf16 copies of its outputs
+  if (pl.res && fused) return (sw.attn_b16x && pieces) ? ATTN_B16X : ATTN_BF16_PRE;
+  // precision 3: the attention's own products on the bf16 pipe as well (its backward emits the fused query|key|value bias partials)
+  if (pl.x3 && sw.attn_x3 && pieces && (fused || !bwd)) return ATTN_X3;
+  if (pl.x3 && fused) return ATTN_F32_PRE_X3;
+  if (pl.packed || (save && fused)) return ATTN_F32_PRE;
+  return ATTN_F32;
 }
 // precision 3: A = x3 activations [M][3][K]; W = the piece-major x3 mirror of an encoder weight (row stride ldw, piece stride =
 // the flat parameter buffer's length); outputs fp32 (nsplit slabs) or x3 [M][3][N]; aux operands fp32 (csrc/gemm_split3.hip)
@@ -442,13 +430,9 @@ int gemm_x3(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, in
             int ldw, float* C, int nsplit, unsigned short* Cx, int epi, const float* bias, const float* aux_in, float* aux_out,
             float* colsum_part = nullptr) {
   ProfScope ps(m, kind, st);
-  static const int cfg_all = [] { const char* e = getenv("UNITER_X3_CFG"); return e ? atoi(e) : 0; }();
-  // (lab switch: the FFN-up forward product alone on another tile geometry -- 3 = 128 x 128, whose workgroups leave register room
-  // for a resident optimizer wave, which the 128 x 256 geometry's 504 of 512 registers per SIMD do not)
-  static const int cfg_ffn_up = [] { const char* e = getenv("UNITER_X3_CFG_FFN_UP_FWD"); return e ? atoi(e) : 0; }();
-  const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && cfg_ffn_up) ? cfg_ffn_up : cfg_all;
-  static const int main_prio = [] { const char* e = getenv("UNITER_MAIN_PRIO_X3"); return e ? atoi(e) : 0; }();
-  g_uniter_launch_prio = main_prio;
+  const Switches& sw = uniter_switches();
+  const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && sw.x3_cfg_ffn_up_fwd) ? sw.x3_cfg_ffn_up_fwd : sw.x3_cfg;
+  g_uniter_launch_prio = sw.main_prio_x3;
   // (every product of this helper runs on the main stream: the balanced walk's main-stream workspace)
   // (cfg | 64: the weight's pieces in the paired-row layout -- full 128-byte source lines for the loaders of the forward products)
   return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), nsplit, 0, bkm, M, N, K, A, 3 * K, K, W, ldw, (int)m->mirror_numel, C, N, (long)M * N, Cx, 3 * N, N, epi,
@@ -464,44 +448,43 @@ int x3_backward_cus(const uniter_model* m) {
   const int a = (cus - m->cu_reserve) / 8 * 8;
   return a >= 8 ? a : 8;
 }
-// precision 3: side work of a layer's backward rides on its grouped weight-gradient launch (default geometry only)
-bool x3_riders_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("UNITER_X3_RIDERS");
-    const char* c = getenv("UNITER_X3_CFG");
-    return !(e && e[0] == '0') && (!c || atoi(c) == 0 || atoi(c) == 3);
-  }();
-  return on;
-}
-// precision 3: dU's column sums (the bias gradient of intermediate.dense) as column partials of the product that writes dU + a
-// reduction job of the riders, instead of ones-MFMAs in the weight-gradient launch: whenever that launch runs on 128 x 256 tiles
-bool x3_colpart_on() {
-  static const bool cfg_ok = [] { const char* c = getenv("UNITER_X3_CFG"); return !c || atoi(c) == 0 || atoi(c) >= 3; }();
-  return x3_riders_enabled() && cfg_ok && gemm_x3_wgrad_default_cfg() == 4;
-}
-// precision 2: the same riders on the grouped bf16 weight-gradient launch -- built, parity-tested, and OFF by default
-// (UNITER_B16_RIDERS=1 switches them on): measured 4.42 -> 4.51 ms per step, two same-box pairs.  In this mode the two backward
-// streams really overlap (two 64-KB workgroups share a CU) and the weight-gradient stream idles half of every layer: the separate
-// column-sum / finalize / sum-of-squares launches cost the step nothing there, while the riders lengthen the launch the
-// input-gradient chain shares its CUs with (the fp32x3 mode is the opposite case: its streams serialise, every launch is step time)
-bool b16_riders_enabled() {
-  static const bool on = [] { const char* e = getenv("UNITER_B16_RIDERS"); return e && e[0] == '1'; }();
-  return on;
-}
-// round 6: with the grouped launch on the persistent 128 x 256-tile kernel (UNITER_B16_PERSIST bit 4) a workgroup of it owns its CU, the
-// two backward streams time-slice as in the fp32x3 mode, and every side launch is step time: there the riders are ON unless
-// UNITER_B16_RIDERS=0
-bool b16_p7() { return (b16_persist_mask() & 4) != 0; }
-bool b16_riders_on(const Plan& pl) {
-  static const bool off = [] { const char* e = getenv("UNITER_B16_RIDERS"); return e && e[0] == '0'; }();
+// The grouped weight-gradient launch of layer l's backward pass (precision 2 or 3: four products, Mo = {I, H, 3H, H}, No = {H, I, H, H}):
+// what rides on it, its geometry, its grid cap, and -- with riders -- the clip-norm slots it fills.  Read by backward_layer, which
+// launches it, and by uniter_model_norm_partials_per_layer, which announces its slots.
+struct WgradGroup {
+  bool riders = false;    // the layer's column reductions, intermediate.dense's bias gradient and its clip-norm share ride on the launch
+  bool colpart = false;   // ... and dU's column sums (that bias gradient) start as column partials of the product that writes dU
+  int cfg = 0, max_wgs = 0, slots = 0;
+};
+WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int precision, int l) {
+  const Switches& sw = uniter_switches();
+  const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size;
+  const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
+  WgradGroup g;
+  if (precision == 3) {
+    // UNITER_X3_RIDERS, and the default geometries only.  Column partials whenever the launch runs on 128 x 256 tiles
+    g.riders = sw.x3_riders && (sw.x3_cfg == 0 || sw.x3_cfg == 3);
+    g.colpart = g.riders && gemm_x3_wgrad_default_cfg() == 4;
+    g.cfg = g.riders ? (sw.x3_cfg == 3 ? 3 : 0) : sw.x3_cfg;
+    // UNITER_WGRAD_X3_WGS = n forces a grid for every layer (0 = one workgroup per CU); unset, layer 0 takes the smallest grid that
+    // needs no more rounds (switches.h) and every other layer one workgroup per CU
+    g.max_wgs = sw.wgrad_x3_wgs >= 0 ? sw.wgrad_x3_wgs : (l == 0 ? gemm_x3_wgrad_group_balanced_wgs(0, 4, Mo, No) : 0);
+    if (g.riders) g.slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, g.max_wgs, pl.M, pl.sk_side ? pl.sk_bytes : 0);
+    return g;
+  }
+  // precision 2: riders only on UNITER_B16_RIDERS=1 -- except with the launch on the persistent 128 x 256-tile kernel (UNITER_B16_PERSIST
+  // bit 4), where they are on unless UNITER_B16_RIDERS=0 (switches.h)
+  const bool p7 = (sw.b16_persist & 4) != 0;
   // (on the 128 x 256 geometry the bias gradient of intermediate.dense must come from column partials -- bit 8 and the gelu' form of the
   // forward epilogue: a separate pass over dU would write it outside the launch, and its squares would reach no clip-norm slot)
-  if (b16_p7()) return pl.res && pl.wg_group == 1 && !off && (b16_persist_mask() & 8) && pl.gelu_d;
-  return pl.res && pl.wg_group == 1 && b16_riders_enabled();
+  g.riders = pl.res && pl.wg_group == 1 && (p7 ? sw.b16_riders != '0' && (sw.b16_persist & 8) && pl.gelu_d : sw.b16_riders == '1');
+  // ... finished by a fourth reduction job of the riders
+  g.colpart = p7 && g.riders;
+  g.cfg = pl.wg_group == 4 ? 4 : (p7 ? 7 : 1);      // (4: three LDS stages; 7: 216 whole-K tiles of 128 x 256 on the persistent kernel)
+  g.max_wgs = 0;                                   // (the grid cap of UNITER_WGRAD_GROUP_WGS / its default)
+  if (g.riders) g.slots = p7 ? gemm_b1p_wgrad_group_slots(4, Mo, No, g.max_wgs) : gemm_bf16v2_wgrad_group_slots(4, Mo, No, g.max_wgs);
+  return g;
 }
-// ... and dU's column sums (the bias gradient of intermediate.dense) start in the epilogue of the product that writes dU when that product
-// runs on the persistent 128 x 256 kernel (bit 8), finished by a fourth reduction job of the riders
-bool b16_colpart_on(const Plan& pl) { return b16_p7() && b16_riders_on(pl); }
 // the side work of layer l's backward as riders of its grouped weight-gradient launch (product 0 must be dW1 = dU^T y1: its A
 // operand's column sums are intermediate.dense's bias gradient)
 void fill_layer_riders(uniter_x3_riders_t& x, const uniter_model* m, int l, const LayerBufs& lb, int M, int B, int H, bool fused_qb,
@@ -715,16 +698,14 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   const float pa = train == 1 ? c.attention_probs_dropout_prob : 0.f;
   const int B = b->B, T = b->T, R = b->R, L = b->L, S = pl.S, M = pl.M;
   const bool save = train != 0;
-  static const bool gelu_d_env = [] { const char* e = getenv("UNITER_GELU_D"); return !(e && e[0] == '0'); }();
-  const bool gelu_d = gelu_d_env || m->precision == 3;      // UNITER_GELU_D=0: A/B switch (store the pre-activation, libm erf twice)
+  const Switches& sw = uniter_switches();
+  const bool gelu_d = sw.gelu_d || m->precision == 3;      // UNITER_GELU_D=0: A/B switch (store the pre-activation, libm erf twice)
   pl.gelu_d = gelu_d;
   m->batch = *b; m->hidden_out = hidden_out; m->all_layers = all_layers; m->seed = seed; m->offset = offset;
   m->bwd_open = false;
   ++m->generation;
 
   const bool res = pl.res, x3 = pl.x3;
-  // L <= 192: attention on the bf16 pipe (attention_bf16.hip), which also writes the bf16 copies of its outputs
-  const bool attn_b16 = res && L <= uniter_attn_varlen_max_len();
 
   // the flag words of the balanced walk's two workspaces (16 KB each): zero before the first launch that uses them -- the launches
   // leave them zero, but the workspace is the caller's and may be a new one
@@ -734,9 +715,8 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   // dropout keep flags of the attention probabilities of ALL layers, drawn in one elementwise launch ahead of everything --
   // a function of (seed, offset) alone, so it runs while the optimizer still streams the word table the text branch waits for
   // (the L <= 192 kernels then read them; the backward pass reads the same words)
-  static const bool pregen_env = [] { const char* e = getenv("UNITER_KEEP_PREGEN"); return !e || e[0] != '0'; }();
   bool keep_on_aux = false;
-  bool keep_pre = pregen_env && save && pa > 0.f && L <= uniter_attn_varlen_max_len() && (attn_b16 || packed || save);
+  bool keep_pre = sw.keep_pregen && save && pa > 0.f && L <= uniter_attn_varlen_max_len();
   if (keep_pre) {
     const size_t stride = nl > 1 ? (size_t)((char*)pl.layers[1].keepb - (char*)pl.layers[0].keepb) : 0;
     for (int l = 1; l < nl && keep_pre; ++l)
@@ -758,14 +738,14 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
       if (ks != st) { UCHECK_HIP(hipEventRecord(m->ev_aux1, ks)); keep_on_aux = true; }
     }
   }
+  // the attention kernels of this plan, forward and backward: decided here, once, and only read from now on
+  pl.attn_fwd = attn_kernel(pl, pa, save, keep_pre, false);
+  pl.attn_bwd = attn_kernel(pl, pa, save, keep_pre, true);
+  const bool attn_b16 = attn_is_b16(pl.attn_fwd);
   // the hidden dropout's keep flags (the two dropout + residual + LayerNorm passes of every layer, forward AND backward) behind them
-  // on the same stream: built, bit-identical (tests/test_layernorm_gpu.py) and OFF by default (UNITER_HIDDEN_PREGEN=1 switches it on).
-  // Alone a row pass is 1.5 / 1.8 us faster without its ten Philox rounds per group; in the step it is not -- there the passes wait
-  // for memory, the Philox rounds run in that shadow, and the generator launch is one more kernel beside the forward's head:
-  // 9.87 / 9.87 ms without against 9.96 / 9.86 with (fp32x3), 4.58 / 4.60 against 4.60 / 4.61 (bf16), two same-box pairs each
-  static const bool hid_env = [] { const char* e = getenv("UNITER_HIDDEN_PREGEN"); return e && e[0] == '1'; }();
+  // on the same stream: OFF by default (UNITER_HIDDEN_PREGEN=1 switches it on)
   pl.hid_on = false;
-  if (hid_env && save && ph > 0.f && m->aux && m->aux != st && pl.hid_keepb) {
+  if (sw.hidden_pregen && save && ph > 0.f && m->aux && m->aux != st && pl.hid_keepb) {
     if (!m->ev_aux0) UCHECK_HIP(hipEventCreateWithFlags(&m->ev_aux0, hipEventDisableTiming));
     if (!m->ev_aux2) UCHECK_HIP(hipEventCreateWithFlags(&m->ev_aux2, hipEventDisableTiming));
     if (!keep_on_aux) {      // (no attention flags were drawn on the stream: order it behind the flags' last readers ourselves)
@@ -795,12 +775,8 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     // region-feature projection (model/model.py:267): 576 x 768 outputs are 108 tiles of 64 x 64 for 1024 workgroup slots
     // with K = 2048 -- as a stream-K accumulation on top of the bias rows it fills the chip (fp32: 58 -> 25 us)
     const long t64 = (long)((B * R + 63) / 64) * ((H + 63) / 64);
-    static const bool img_sk = [] { const char* e = getenv("UNITER_IMG_SK"); return !e || e[0] != '0'; }();
-    // (native fp32 only: the float atomics make the sum's order vary from run to run -- 1e-7 in fp32, but the bf16 mode amplifies any
-    // such difference through its rounding stages, DESIGN.md section 2, and the fp32x3 mode's forward and backward are bit-reproducible
-    // run to run, which tests/test_model_gpu.py::test_cu_reserve_for_a_gradient_exchange_changes_no_result relies on -- round 6 tried
-    // the stream-K form there and took it out again for that reason)
-    if (img_sk && m->precision == 0 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
+    // (UNITER_IMG_SK; native fp32 only: the float atomics make the sum's order vary from run to run, switches.h)
+    if (sw.img_sk && m->precision == 0 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
       UCHECK_RC(uniter_bias_rows(m->P(P_IMG_B), pl.imgfc, B * R, H, st));
       UCHECK_RC(gemm(m, 0, st, 0, 0, B * R, H, c.img_dim, feat, c.img_dim, m->P(P_IMG_W), c.img_dim, pl.imgfc, H,
                      UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 1));
@@ -823,8 +799,7 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   const bool joint = has_txt && has_img;
   // (round 6) the joint rows and their operand copy for layer 0's first product in ONE launch: this chain -- text embeddings, gather,
   // split -- is what the first encoder product waits for behind the optimizer's update of the word table
-  static const bool gather_ex = [] { const char* e = getenv("UNITER_GATHER_EX"); return !(e && e[0] == '0'); }();
-  const bool fuse_copy = gather_ex && !packed && (res || x3) && H <= 1024 && m->mirror != nullptr;
+  const bool fuse_copy = sw.gather_ex && !packed && (res || x3) && H <= 1024 && m->mirror != nullptr;
   if (packed) UCHECK_RC(uniter_row_gather(pl.cat, b->pack_src, pl.emb, M, H, B * S, st));
   else if (fuse_copy) UCHECK_RC(uniter_gather_rows_ex(pl.cat, joint ? b->gather_index : nullptr, pl.emb, pl.embb, x3 ? 1 : 2, B, S, L, H, st));
   else UCHECK_RC(uniter_gather_rows(pl.cat, joint ? b->gather_index : nullptr, pl.emb, B, S, L, H, st));
@@ -856,27 +831,35 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
                      UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, nullptr, 0, 0));
     {
       ProfScope ps(m, UNITER_K_ATTN_FWD, st);
-      if (attn_b16 && attn_b16x(L, pa, keep_pre))      // precision 2: the attention products run on the bf16 pipe as well
+      switch (pl.attn_fwd) {
+      case ATTN_B16X:      // precision 2: the attention products run on the bf16 pipe as well
         UCHECK_RC(uniter_attn_b16x_fwd(lb.qkv, 1, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr, lb.ctx,
                                        lb.ctxb, lb.lse, pa > 0.f ? lb.keepb : nullptr, B, L, nh, pa, st));
-      else if (attn_b16)
+        break;
+      case ATTN_BF16_PRE:
         UCHECK_RC(uniter_attn_bf16_fwd_pre(lb.qkv, 1, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
                                            lb.ctx, lb.ctxb, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
                                            seed, offset, SITE_ATTN_PROBS(l), st));
-      else if (x3 && attn_x3_products(L, pa, keep_pre))      // the attention's own products on the bf16 pipe as well
+        break;
+      case ATTN_X3:      // the attention's own products on the bf16 pipe as well
         UCHECK_RC(uniter_attn_x3_fwd(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr, lb.ctx,
                                      lb.ctxb, lb.lse, pa > 0.f ? lb.keepb : nullptr, B, L, nh, pa, st));
-      else if (x3 && L <= uniter_attn_varlen_max_len())      // the context leaves the kernel as x3 pieces too
+        break;
+      case ATTN_F32_PRE_X3:      // the context leaves the kernel as x3 pieces too
         UCHECK_RC(uniter_attn_fwd_pre_x3(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
                                          lb.ctx, lb.ctxb, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
                                          seed, offset, SITE_ATTN_PROBS(l), st));
-      else if (packed || (save && L <= uniter_attn_varlen_max_len()))
+        break;
+      case ATTN_F32_PRE:
         UCHECK_RC(uniter_attn_fwd_pre(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
                                       lb.ctx, nullptr, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
                                       seed, offset, SITE_ATTN_PROBS(l), st));
-      else
+        break;
+      case ATTN_F32:
         UCHECK_RC(uniter_attn_fwd(lb.qkv, b->attention_mask, lb.ctx, lb.lse, B, L, nh, pa, seed, offset,
                                   SITE_ATTN_PROBS(l), st));
+        break;
+      }
     }
     if (res) {
       if (!attn_b16) UCHECK_RC(cast_b(lb.ctx, lb.ctxb, (size_t)M * H, st));
@@ -1029,17 +1012,19 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // intermediate.dense): saves a 32 MB re-read of du
   const bool fuse_db1 = H % 64 == 0;
   const bool res = pl.res;
-  const bool attn_b16 = res && L <= uniter_attn_varlen_max_len();
-  // the L <= 192 attention backward kernels also emit the per-sample column sums of dqkv (the fused
+  const Switches& sw = uniter_switches();
+  const bool attn_b16 = attn_is_b16(pl.attn_bwd);
+  // the L <= 192 attention backward kernels (every one but uniter_attn_bwd) also emit the per-sample column sums of dqkv (the fused
   // query|key|value bias gradient before its sum over the batch): no 24 MB re-read of dqkv
-  const bool fused_qb = L <= uniter_attn_varlen_max_len();
+  const bool fused_qb = pl.attn_bwd != ATTN_F32;
   // precision 3 with the x3 attention backward: the attention-output input gradient leaves as k-pieces (the kernel sums them)
-  static const bool dctx_split = [] { const char* e = getenv("UNITER_DCTX_SPLIT"); return !(e && e[0] == '0'); }();      // A/B switch
-  const int ns_dctx = (x3 && fused_qb && dctx_split && attn_x3_products(L, pa, pa > 0.f)) ? pl.ns_kh_b : 1;
+  const int ns_dctx = (pl.attn_bwd == ATTN_X3 && sw.dctx_split) ? pl.ns_kh_b : 1;
   const int epi_du = pl.gelu_d ? UNITER_EPI_MUL : UNITER_EPI_DGELU;
+  // what rides on the layer's grouped weight-gradient launch (precisions 2 and 3), and that launch's geometry
+  const WgradGroup wg = (res || x3) ? wgrad_group(m, pl, res ? 2 : 3, l) : WgradGroup();
   if (res) {
     UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, lb.g2b, H, m->WB(l, L_W2), I, nullptr, I, 1, lb.dub, I,
-                      epi_du, nullptr, lb.u, 1, nullptr, 0, I, b16_colpart_on(pl) ? lb.du_csum : nullptr));
+                      epi_du, nullptr, lb.u, 1, nullptr, 0, I, wg.colpart ? lb.du_csum : nullptr));
     UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, lb.dub, I, m->WB(l, L_W1), H, lb.dy1, H, pl.ns_ki, nullptr, 0,
                       UNITER_EPI_ADD, nullptr, lb.dz2, 0, nullptr, 0, H));
   } else if (x3) {
@@ -1047,7 +1032,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     // (with riders on the 128 x 256 weight-gradient geometry the bias gradient of intermediate.dense -- dU's column sums -- starts
     // here: one row of partial sums per 64 rows of dU, finished by a reduction job of the riders)
     UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, lb.g2b, m->WB(l, L_W2), I, nullptr, 1, lb.dub, UNITER_EPI_MUL,
-                      nullptr, lb.u, nullptr, x3_colpart_on() ? lb.du_csum : nullptr));
+                      nullptr, lb.u, nullptr, wg.colpart ? lb.du_csum : nullptr));
     UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, lb.dub, m->WB(l, L_W1), H, lb.dy1, pl.ns_ki_b, nullptr, UNITER_EPI_ADD,
                       nullptr, lb.dz2, nullptr));
   } else {
@@ -1096,33 +1081,41 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   }
   {
     ProfScope ps(m, UNITER_K_ATTN_BWD, st);
-    if (attn_b16 && attn_b16x(L, pa, pa > 0.f))      // (the forward pass of a saved plan left the keep flags)
+    switch (pl.attn_bwd) {
+    case ATTN_B16X:      // (the forward pass of a saved plan left the keep flags)
       UCHECK_RC(uniter_attn_b16x_bwd(lb.qkv, 1, pl.packed ? nullptr : m->batch.attention_mask,
                                      pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
                                      lb.qb_part, pa > 0.f ? lb.keepb : nullptr, lb.delta, B, L, nh, pa, st));
-    else if (attn_b16)
+      break;
+    case ATTN_BF16_PRE:
       UCHECK_RC(uniter_attn_bf16_bwd(lb.qkv, 1, pl.packed ? nullptr : m->batch.attention_mask,
                                      pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx,
                                      nullptr /* fp32 dqkv has no reader in this mode: bias partials are fused */,
                                      lb.dqkvb, lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset,
                                      SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
-    else if (fused_qb && x3 && attn_x3_products(L, pa, pa > 0.f))      // (the forward pass of a saved plan left the keep flags)
+      break;
+    case ATTN_X3:      // (the forward pass of a saved plan left the keep flags)
       UCHECK_RC(uniter_attn_x3_bwd(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
                                    pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, ns_dctx, (size_t)M * H,
                                    nullptr, lb.dqkvb, lb.qb_part, pa > 0.f ? lb.keepb : nullptr, lb.delta, B, L, nh, pa, st));
-    else if (fused_qb && x3)      // dqkv leaves the kernel as x3 pieces only: nothing reads an fp32 copy in this mode
+      break;
+    case ATTN_F32_PRE_X3:      // dqkv leaves the kernel as x3 pieces only: nothing reads an fp32 copy in this mode
       UCHECK_RC(uniter_attn_bwd_ex_x3(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
                                       pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
                                       lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
                                       pl.attn_ws, pl.attn_ws_bytes, st));
-    else if (fused_qb)
+      break;
+    case ATTN_F32_PRE:
       UCHECK_RC(uniter_attn_bwd_ex(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
                                    pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr,
                                    lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
                                    pl.attn_ws, pl.attn_ws_bytes, st));
-    else
+      break;
+    case ATTN_F32:
       UCHECK_RC(uniter_attn_bwd(lb.qkv, m->batch.attention_mask, lb.ctx, lb.lse, lb.dctx, lb.dqkv, lb.delta, B, L,
                                 nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
+      break;
+    }
   }
   if (res) {
     if (!attn_b16) UCHECK_RC(cast_b(lb.dqkv, lb.dqkvb, (size_t)M * 3 * H, st));
@@ -1142,11 +1135,10 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     UCHECK_HIP(hipEventRecord(m->ev_main[l], st));
     UCHECK_HIP(hipStreamWaitEvent(sd, m->ev_main[l], 0));
   }
-  // precision 3 (round 5): the column reductions below, the bias gradient of intermediate.dense and the layer's share of the clip
-  // norm RIDE on the grouped weight-gradient launch (uniter_wgrad_x3_group_riders) -- no finalize / column-sum / sum-of-squares
-  // launches on this stream.  UNITER_X3_RIDERS=0 keeps the separate launches (A/B measurements)
-  const bool riders_b16 = b16_riders_on(pl);
-  const bool riders_on = (x3 && x3_riders_enabled()) || riders_b16;
+  // with riders (wgrad_group(): the default of precision 3) the column reductions below, the bias gradient of intermediate.dense and the
+  // layer's share of the clip norm RIDE on the grouped weight-gradient launch -- no finalize / column-sum / sum-of-squares launches
+  // on this stream
+  const bool riders_on = wg.riders;
   // LayerNorm / dense-bias gradients: the column reductions of the two row passes above, the attention backward's
   // per-sample query|key|value bias partials and (fp32 mode) the dU column partials -- ONE launch for all of them
   if (!riders_on) {
@@ -1178,26 +1170,21 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
       const void* const As[4] = {lb.dub, lb.g2b, lb.dqkvb, lb.g1b};
       const void* const Bs[4] = {lb.y1b, lb.hactb, xb, lb.ctxb};
       float* const dWs[4] = {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)};
-      const int b16_wgs = 0;      // (the grid cap of UNITER_WGRAD_GROUP_WGS / its default)
-      if (riders_b16) {
+      if (riders_on) {
         uniter_x3_riders_t x;
         memset(&x, 0, sizeof(x));
-        const bool p7 = b16_p7(), colpart = b16_colpart_on(pl);
-        const int slots = p7 ? gemm_b1p_wgrad_group_slots(4, Mo, No, b16_wgs) : gemm_bf16v2_wgrad_group_slots(4, Mo, No, b16_wgs);
         if (m->norm_parts) {
-          UCHECK_ARG((size_t)slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
-                     slots, m->norm_stride);
+          UCHECK_ARG((size_t)wg.slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
+                     wg.slots, m->norm_stride);
           x.ssq = m->norm_parts + (size_t)l * m->norm_stride;
         }
-        fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, colpart);
+        fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, wg.colpart);
         ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-        UCHECK_RC(gemm_bf16v2_wgrad_group(p7 ? 7 : 1, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, b16_wgs, &x));
+        UCHECK_RC(gemm_bf16v2_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, &x));
       } else {
         {
           ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-          // (round 6: 216 whole-K tiles of 128 x 256 on the persistent kernel -- 47 against 61 us alone, UNITER_B16_PERSIST bit 4)
-          const int wcfg = pl.wg_group == 4 ? 4 : ((b16_persist_mask() & 4) ? 7 : 1);
-          UCHECK_RC(gemm_bf16v2_wgrad_group(wcfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, b16_wgs, nullptr));
+          UCHECK_RC(gemm_bf16v2_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, nullptr));
         }
         UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
       }
@@ -1210,58 +1197,40 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     }
   } else if (x3) {
     // the layer's four weight gradients as ONE persistent launch of whole-K 128 x 128 tiles on x3 operands (432 tiles for
-    // UNITER-base), no atomics; UNITER_WGRAD_X3_WGS caps its grid (0 = one workgroup per CU)
+    // UNITER-base), no atomics; wg.max_wgs caps its grid (0 = one workgroup per CU; layer 0: the smallest grid of as many rounds)
     const unsigned short* xb = l == 0 ? pl.embb : pl.layers[l - 1].y2b;
     const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
     const void* const As[4] = {lb.dub, lb.g2b, lb.dqkvb, lb.g1b};
     const void* const Bs[4] = {lb.y1b, lb.hactb, xb, lb.ctxb};
     float* const dWs[4] = {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)};
-    static const int x3_cfg = [] { const char* e = getenv("UNITER_X3_CFG"); return e ? atoi(e) : 0; }();
-    static const int x3_wgs_env = [] { const char* e = getenv("UNITER_WGRAD_X3_WGS"); return e ? atoi(e) : -1; }();
-    // layer 0's launch runs BEHIND the input-gradient chain, beside the embedding backward's row passes on the main stream: the
-    // smallest grid that needs no more rounds (432 tiles: 216 workgroups walk two tiles each, as 256 would) leaves 40 CUs to
-    // those passes -- their 190-register waves find no room on a CU a persistent 144-KB workgroup holds (img_embed_bwd 112 us
-    // for 576 rows when it has to wait for one).  UNITER_WGRAD_X3_WGS = n forces a grid for every layer (0 = one per CU)
-    const int x3_wgs = x3_wgs_env >= 0 ? x3_wgs_env : (l == 0 ? gemm_x3_wgrad_group_balanced_wgs(0, 4, Mo, No) : 0);
     if (riders_on) {
       // product 0 is dW1 = dU^T y1: its A operand's column sums are intermediate.dense's bias gradient
       uniter_x3_riders_t x;
       memset(&x, 0, sizeof(x));
-      const int slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, x3_wgs, M, pl.sk_side ? pl.sk_bytes : 0);
       if (m->norm_parts) {
-        UCHECK_ARG((size_t)slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
-                   slots, m->norm_stride);
+        UCHECK_ARG((size_t)wg.slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
+                   wg.slots, m->norm_stride);
         x.ssq = m->norm_parts + (size_t)l * m->norm_stride;
       }
-      fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, x3_colpart_on());
+      fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, wg.colpart);
       ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      UCHECK_RC(gemm_x3_wgrad_group(x3_cfg == 3 ? 3 : 0, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, x3_wgs, &x,
+      UCHECK_RC(gemm_x3_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, &x,
                                     pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
     } else {
       {
         ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-        UCHECK_RC(gemm_x3_wgrad_group(x3_cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, x3_wgs, nullptr,
+        UCHECK_RC(gemm_x3_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, nullptr,
                                       pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
       }
       UCHECK_RC(uniter_colsum_x3_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
     }
   } else {
     const int wb = m->wg_overwrite ? -1 : 1;      // -1: overwrite (or clear, then accumulate) -- see gemm()
-    // UNITER_WGRAD_GROUP_F32=1: EVERY layer's four weight gradients as ONE persistent launch of whole-K tiles (1728 tiles for
-    // 1024 slots, uniter_wgrad_f32_group).  Measured (three same-box pairs): the launch itself runs at 0.47-0.49 of the fp32 peak
-    // in situ (four launches: 0.39), both gradient families together at 0.78 (0.67), the attention backward beside it at 97
-    // instead of 151 us -- and the STEP is 0.7-1.1 % slower (13.87-13.90 vs 13.72-13.75 ms): its 1024 resident workgroups
-    // hold every CU's LDS for 370 us, and each kernel of the input-gradient chain queues for slots before its first
-    // workgroup starts (a wait no per-launch figure shows).  So layers nl-1 .. 1 keep four launches.
-    // Layer 0 is the exception (UNITER_WGRAD_GROUP_F32 = 2, the default; 0 = never, 1 = every layer): its weight gradients run
-    // BEHIND the input-gradient chain, alone on the chip, where four launches of 576 / 576 / 144 / 432 tiles leave a quarter
-    // of the 1024 slots idle and one balanced launch does not: 13.69 -> 13.55 ms per step (three same-box pairs).
-    static const int group_mode = [] { const char* e = getenv("UNITER_WGRAD_GROUP_F32"); return e ? atoi(e) : 2; }();
-    const bool group_env = group_mode == 1 || (group_mode == 2 && l == 0);
-    static const bool whole_all = [] { const char* e = getenv("UNITER_WGRAD_WHOLE"); return !e || atoi(e) == 15; }();
-    static const bool cfg_default = [] { const char* e = getenv("UNITER_WGRAD_CFG"); return !e || atoi(e) == 0; }();
+    // the layer's four weight gradients as ONE persistent launch of whole-K tiles (uniter_wgrad_f32_group): layer 0 only by default
+    // (UNITER_WGRAD_GROUP_F32 = 2; 0 = never, 1 = every layer: measured slower, switches.h), and only when every shape is on whole tiles
+    const bool group_env = sw.wgrad_group_f32 == 1 || (sw.wgrad_group_f32 == 2 && l == 0);
     bool grouped = false;
-    if (group_env && whole_all && cfg_default && (m->precision == 0) && fuse_db1) {
+    if (group_env && sw.wgrad_whole == 15 && sw.wgrad_cfg == 0 && (m->precision == 0) && fuse_db1) {
       const int Mo[4] = {H, I, H, 3 * H}, No[4] = {I, H, H, H};
       const float* const As[4] = {g2, lb.du, g1, lb.dqkv};
       const float* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x};
@@ -1307,17 +1276,10 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
   } else {
     UCHECK_RC(uniter_gather_rows_bwd(demb, joint ? b.gather_index : nullptr, pl.dcat, B, S, L, H, st));
   }
-  // Round 6: the tail of the step is a chain of latency-bound launches behind the last input gradient (text-embedding backward 55 us,
-  // image-embedding backward 67, the 7-d projection's and the region projection's weight gradients 15 + 52, column sums: 220 us on one
-  // stream, profiles/r06_timeline_f32x3.txt), while layer 0's weight-gradient launch holds most of the chip on the side stream.  The
-  // text branch and the image branch share nothing but dcat: with an auxiliary stream the text branch (and, behind the image rows'
-  // pass, the region projection's bias column sums) runs there, beside the image branch.  Same kernels, same results; the token-type
-  // table's gradient is the one buffer both branches add to (row 0 / the text rows' types there, row 1 / the image rows' types here):
-  // with explicit type ids on both sides both scatter by float atomics, without them on either side each finalizes into its own row,
-  // and in those two cases no ordering between the branches is needed.  With mixed ids (one side explicit, the other implicit) one
-  // branch's atomics land on the row the other finalizes with a plain read-add-write, which could lose an update: those batches keep
-  // one stream, whose order serializes the two writers.  UNITER_EMBED_BWD_PAR=0 keeps one stream.
-  static const bool par_env = [] { const char* e = getenv("UNITER_EMBED_BWD_PAR"); return !(e && e[0] == '0'); }();
+  // Round 6: with an auxiliary stream the text branch (and, behind the image rows' pass, the region projection's bias column sums)
+  // runs there, beside the image branch; batches with mixed token-type ids (one side explicit, the other implicit) keep one stream,
+  // whose order serializes the two writers of the token-type table's gradient.  UNITER_EMBED_BWD_PAR=0 keeps one stream (switches.h)
+  const bool par_env = uniter_switches().embed_bwd_par;
   const bool types_alike = (b.txt_type_ids == nullptr) == (b.img_type_ids == nullptr);
   hipStream_t ax = (par_env && m->aux && m->aux != st && m->aux != sd && pl.has_txt && pl.has_img && types_alike) ? m->aux : nullptr;
   if (ax) {
@@ -1391,24 +1353,17 @@ extern "C" int uniter_model_set_norm_partials(uniter_model_t* m, double* parts, 
 
 extern "C" int uniter_model_norm_partials_per_layer(const uniter_model_t* m) {
   if (!m) return 0;
-  const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size;
-  const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
-  if (m->precision == 2) {
-    // (the grouped launch is the default form of this precision: UNITER_WGRAD_GROUP unset or 1; very long batches fall back)
-    // (answers for the plan of the LAST forward: the grouped launch is that plan's choice -- very long batches keep stream-K)
-    if (!(m->plan.mode != 0 && b16_riders_on(m->plan))) return 0;
-    // (as in the fp32x3 mode: a plan beyond the fused query|key|value bias partials announces no slots -- ADVICE r05)
-    if (m->plan.L > uniter_attn_varlen_max_len()) return 0;
-    return b16_p7() ? gemm_b1p_wgrad_group_slots(4, Mo, No, 0) : gemm_bf16v2_wgrad_group_slots(4, Mo, No, 0);
-  }
-  if (m->precision != 3 || !x3_riders_enabled()) return 0;
+  if (m->precision != 2 && m->precision != 3) return 0;
+  // (answers for the plan of the LAST forward: its grouped launch -- very long batches of precision 2 keep stream-K --, its row count
+  // as the reduction length, its workspace of the balanced walk.  An upper bound over layers: layer 1's grid, one workgroup per CU,
+  // where layer 0's balanced grid fills fewer slots)
+  const WgradGroup g = wgrad_group(m, m->plan, m->precision, 1);
+  if (!g.riders || (m->precision == 2 && m->plan.mode == 0)) return 0;
   //  a plan whose joint length is beyond the fused query|key|value bias partials (L > uniter_attn_varlen_max_len(), or
   // UNITER_ATTN_SPLIT=0) writes that bias gradient by a separate column-sum launch BEHIND the riders' launch: its squares would reach
   // no slot.  Such a plan announces no slots at all -- the caller reduces the layer's bucket itself, as in the other precisions
-  if (m->plan.mode != 0 && m->plan.L > uniter_attn_varlen_max_len()) return 0;
-  static const int x3_wgs = [] { const char* e = getenv("UNITER_WGRAD_X3_WGS"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-  // (the plan of the LAST forward: its row count is the reduction length, its workspace the balanced walk's)
-  return gemm_x3_wgrad_group_slots(0, 4, Mo, No, x3_wgs, m->plan.M, m->plan.sk_side ? m->plan.sk_bytes : 0);
+  if (m->plan.mode != 0 && m->plan.attn_bwd == ATTN_F32) return 0;
+  return g.slots;
 }
 
 extern "C" int uniter_model_set_wgrad_overwrite(uniter_model_t* m, int on) {
