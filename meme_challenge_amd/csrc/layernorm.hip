@@ -444,6 +444,7 @@ extern "C" int uniter_ln_fwd_slabs_x3(const float* x, int nslab, size_t slab_str
                                       const float* beta, float* z_out, float* y, void* y_x3, float* mean, float* rstd,
                                       int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
                                       void* stream) {
+  if (H % 8 != 0 || ((uintptr_t)y_x3 & 15) != 0) take_drop_bits();      // (a refused call consumes the hand-over, as in ln_fwd_run)
   UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)y_x3 & 15) == 0, "ln_fwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
   return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_x3, 3, mean, rstd, M, H, p_drop, seed, offset, site, stream);
 }
@@ -533,6 +534,7 @@ extern "C" int uniter_ln_bwd_rows_slabs_x3(const float* dy, int nslab, size_t sl
                                            const float* rstd, const float* gamma, float* dz, float* dx, void* dx_x3,
                                            int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
                                            uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  if (H % 8 != 0 || ((uintptr_t)dx_x3 & 15) != 0) take_drop_bits();
   UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)dx_x3 & 15) == 0, "ln_bwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
   return ln_bwd_rows_run(dy, nslab, slab_stride, z, mean, rstd, gamma, dz, dx, dx_x3, 3, want_dbias, M, H, p_drop, seed,
                          offset, site, ws, ws_bytes, stream);

@@ -140,7 +140,9 @@ def test_ln_x3_copies_are_the_exact_pieces_of_the_fp32_outputs(M, H, p, nslab):
     assert torch.equal(dxx2, dxx)
 
 
-@pytest.mark.parametrize('M,H,p', [(37, 768, 0.1), (2624, 768, 0.1), (50, 1024, 0.3), (9, 128, 0.1)])
+# H = 260, 1020: an odd number of 4-element groups per row, so every second row starts in the high nibble of a byte
+@pytest.mark.parametrize('M,H,p', [(37, 768, 0.1), (2624, 768, 0.1), (50, 1024, 0.3), (9, 128, 0.1), (5, 260, 0.1), (7, 1020, 0.3),
+                                   (37, 260, 0.5)])
 def test_keep_flags_drawn_ahead_are_the_row_passes_own(M, H, p):
     """uniter_hidden_keep_bits_gen + uniter_ln_set_next_keep_bits: the forward and backward row passes that READ the keep flags
     (one nibble per 4-element group, drawn ahead for several sites in one launch) give the outputs of the passes that draw them
