@@ -571,6 +571,8 @@ int uniter_dgelu_mul(const float* dy, const float* u, float* out, size_t n, void
  *   chunk_flags[i] for elements [64*i, 64*i+64): 0 = skip (no gradient this step),
  *   1 = no weight decay, 2 = weight decay; + 4 = zero_grads leaves this chunk's gradient alone (the next backward pass
  *   overwrites it: uniter_model_set_wgrad_overwrite) -- 28 instead of 32 bytes per parameter.
+ *   Valid bytes are 0, 1, 2, 5 and 6 (what trainer.FusedAdam writes).  4 (0 + 4) is NOT a skip: any non-zero byte puts the chunk on
+ *   the update path and into the norm, and 4 or 3 take no weight decay there -- a caller must not pass them.
  * ------------------------------------------------------------------------- */
 /* sumsq[0] = sum g^2 over flagged chunks (device scalar, double) */
 int uniter_grad_sumsq(const float* grads, const uint8_t* chunk_flags, size_t n,

@@ -14,6 +14,8 @@
 //   1 = no weight decay ('bias' / 'LayerNorm.*' names), 2 = weight decay;
 //   + 4 = leave the gradient as it is (zero_grads notwithstanding): the next backward pass OVERWRITES this chunk
 //         (the encoder's weight gradients, uniter_model_set_wgrad_overwrite) -- 28 instead of 32 bytes per parameter.
+// The kernels test the whole byte for "skip", so 4 alone is invalid (it would update and count the chunk): callers pass
+// 0, 1, 2, 5 or 6 (include/uniter_hip.h).
 #include "common.h"
 
 namespace {
