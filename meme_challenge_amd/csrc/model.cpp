@@ -107,6 +107,19 @@ struct LayerBufs {   // saved activations + backward scratch of one layer
   unsigned short *ctxb, *y1b, *hactb, *y2b, *g2b, *dub, *g1b, *dqkvb;
 };
 
+// How the encoder's dense products run (uniter_model_set_precision).  A forward pass copies the model's setting into its plan
+// (make_plan); the schedule of that pass and of its backward pass reads the plan's copy only.
+enum Precision {
+  PREC_F32 = 0,         // fp32 MFMA GEMMs
+  PREC_BF16_MFMA = 1,   // bf16 MFMA GEMMs on fp32 storage: scheduled like PREC_F32, gemm() picks the kernel
+  PREC_BF16 = 2,        // bf16-resident operands: activations are handed on as bf16 copies, weights come from the bf16 mirror
+  PREC_X3 = 3           // fp32 from three bf16 pieces per value: operand copies and mirror hold x3 pieces
+};
+
+// An activation as the dense products see it: its fp32 tensor and its operand copy (bf16 in PREC_BF16, x3 pieces [rows][3][cols] in
+// PREC_X3, none below).  As an output: a product that is given a place for the operand copy writes ONLY that.
+struct Act { float* f; unsigned short* b; };
+
 // the attention kernel of a plan, by its forward entry point; the backward entry point follows from it (backward_layer)
 enum AttnKernel {
   ATTN_F32,          // uniter_attn_fwd / uniter_attn_bwd: any length, reads the padded mask
@@ -128,8 +141,8 @@ struct Plan {
   std::vector<LayerBufs> layers;
   float *dcat, *d_imgfc, *d_posfc, *d_feat, *dsum, *dpk;
   unsigned short* embb;   // precision 2: bf16 copy of the embedding output
-  bool res;               // this plan was carved for precision 2
-  bool x3;                // this plan was carved for precision 3: the *b buffers hold x3 pieces [rows][3][cols], embb likewise
+  Precision prec = PREC_F32;   // what this plan was carved for: PREC_X3's *b buffers hold x3 pieces [rows][3][cols], embb likewise
+  bool copies() const { return prec >= PREC_BF16; }      // activations have operand copies (LayerBufs::*b, embb)
   int ns_kh;              // precision 3: k-pieces of the attention-output forward product (N = K = hidden)
   // precision 3: k-pieces of the BACKWARD pass's N = hidden products (FFN-up / attention-output / QKV input gradients), chosen for the
   // CUs the backward pass may use: all of them, or what a data-parallel exchange leaves (uniter_model_set_cu_reserve)
@@ -162,9 +175,9 @@ struct uniter_model {
   std::vector<float*> p, g;
   std::vector<std::string> names;
   std::vector<hipEvent_t> ev_main, ev_side, ev_mid;
-  int precision = 0;        // 0 = fp32 MFMA GEMMs, 1 = bf16 MFMA GEMMs (fp32 storage)
+  Precision precision = PREC_F32;   // the caller's setting, any of the four modes; the schedule reads the copy in the plan (Plan::prec)
   bool mirror_paired = false;               // precision 3: the encoder layers' weights sit in the mirror in the paired-row layout
-  const unsigned short* mirror = nullptr;   // bf16 copy of the flat parameter buffer (precision 2)
+  const unsigned short* mirror = nullptr;   // bf16 copy of the flat parameter buffer (precision 2; precision 3: its three pieces)
   const float* mirror_base = nullptr;
   size_t mirror_numel = 0;
   const unsigned short* WB(int l, int k) const { return mirror + (LP(l, k) - mirror_base); }
@@ -239,23 +252,23 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   pl.img_stats = cv.f(BR * 6);
   pl.cat = cv.f((size_t)B * pl.S * H);
   pl.emb = cv.f(M * H);
-  pl.res = m->precision == 2;
-  pl.x3 = m->precision == 3;
+  pl.prec = m->precision;
+  const bool res = pl.prec == PREC_BF16, x3 = pl.prec == PREC_X3;
   pl.hid_keepb = nullptr; pl.hid_stride = 0; pl.hid_on = false;
-  const size_t pc = pl.x3 ? 3 : 1;       // bf16 elements per value in the operand copies
-  pl.embb = (pl.res || pl.x3) ? cv.h(pc * M * H) : nullptr;
-  pl.ns_ki = pl.res ? gemm_bf16v2_pick_split(pl.M, H, I) : pl.x3 ? gemm_x3_pick_split(pl.M, H, I) : 1;
-  pl.ns_k3h = pl.res ? gemm_bf16v2_pick_split(pl.M, H, 3 * H) : pl.x3 ? gemm_x3_pick_split(pl.M, H, 3 * H) : 1;
-  if (pl.res && (sw.b16_persist & 2)) {
+  const size_t pc = x3 ? 3 : 1;       // bf16 elements per value in the operand copies
+  pl.embb = pl.copies() ? cv.h(pc * M * H) : nullptr;
+  pl.ns_ki = res ? gemm_bf16v2_pick_split(pl.M, H, I) : x3 ? gemm_x3_pick_split(pl.M, H, I) : 1;
+  pl.ns_k3h = res ? gemm_bf16v2_pick_split(pl.M, H, 3 * H) : x3 ? gemm_x3_pick_split(pl.M, H, 3 * H) : 1;
+  if (res && (sw.b16_persist & 2)) {
     // round 6: the N = hidden products on the persistent kernels are planned by their own cost model (one workgroup per CU: two
     // k-pieces fill the chip where gemm_dma_kernel's two workgroups per CU wanted four -- two slabs less for the row pass behind)
     const int a = gemm_b1p_pick_split(pl.M, H, I, 0), b = gemm_b1p_pick_split(pl.M, H, 3 * H, 0);
     if (a > 1) pl.ns_ki = a;
     if (b > 1) pl.ns_k3h = b;
   }
-  pl.ns_kh = pl.x3 ? gemm_x3_pick_split(pl.M, H, H) : 1;
+  pl.ns_kh = x3 ? gemm_x3_pick_split(pl.M, H, H) : 1;
   pl.ns_ki_b = pl.ns_ki; pl.ns_k3h_b = pl.ns_k3h; pl.ns_kh_b = pl.ns_kh;
-  if (pl.x3) {
+  if (x3) {
     // (the forward pass runs before any collective of its step: it keeps every CU; the backward pass's products are planned for the
     // CUs it will have)
     const int avail_b = x3_backward_cus(m);
@@ -273,7 +286,7 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
     b.z1 = save ? cv.f(M * H) : nullptr; b.mean1 = cv.f(M); b.rstd1 = cv.f(M); b.y1 = cv.f(M * H);
     b.u = save ? cv.f(M * I) : nullptr; b.hact = cv.f(M * I); b.t2 = cv.f(s_ki * M * H);
     b.z2 = save ? cv.f(M * H) : nullptr; b.mean2 = cv.f(M); b.rstd2 = cv.f(M); b.y2 = cv.f(M * H);
-    if (pl.res || pl.x3) { b.ctxb = cv.h(pc * M * H); b.y1b = cv.h(pc * M * H); b.hactb = cv.h(pc * M * I); b.y2b = cv.h(pc * M * H); }
+    if (pl.copies()) { b.ctxb = cv.h(pc * M * H); b.y1b = cv.h(pc * M * H); b.hactb = cv.h(pc * M * I); b.y2b = cv.h(pc * M * H); }
   };
   if (save) {
     for (int l = 0; l < nl; ++l) {
@@ -288,7 +301,7 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
       b.keepb = (unsigned short*)cv.raw(uniter_attn_keep_bits_bytes(B, L, nh));
       b.ln_ws1 = cv.raw(uniter_ln_bwd_ws_bytes(pl.M, H));
       b.ln_ws2 = cv.raw(uniter_ln_bwd_ws_bytes(pl.M, H));
-      if (pl.res || pl.x3) { b.g2b = cv.h(pc * M * H); b.dub = cv.h(pc * M * I); b.g1b = cv.h(pc * M * H); b.dqkvb = cv.h(pc * M * 3 * H); }
+      if (pl.copies()) { b.g2b = cv.h(pc * M * H); b.dub = cv.h(pc * M * I); b.g1b = cv.h(pc * M * H); b.dqkvb = cv.h(pc * M * 3 * H); }
     }
   } else {
     // inference: every layer reuses one set of buffers; the layer output ping-pongs
@@ -302,8 +315,8 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   }
   // the balanced walk's workspaces (UNITER_X3_BALANCED, default off: bit 0 = the grouped weight gradients, bit 1 = the forward products)
   pl.sk_bytes = gemm_x3_sk_ws_bytes();
-  pl.sk_main = (pl.x3 && (sw.x3_balanced & 2)) ? cv.raw(pl.sk_bytes) : nullptr;
-  pl.sk_side = (pl.x3 && save && (sw.x3_balanced & 1)) ? cv.raw(pl.sk_bytes) : nullptr;
+  pl.sk_main = (x3 && (sw.x3_balanced & 2)) ? cv.raw(pl.sk_bytes) : nullptr;
+  pl.sk_side = (x3 && save && (sw.x3_balanced & 1)) ? cv.raw(pl.sk_bytes) : nullptr;
   if (save) {
     pl.hid_stride = align_up(uniter_hidden_keep_bits_bytes(M * H), 256);
     pl.hid_keepb = (unsigned char*)cv.raw(pl.hid_stride * 2 * nl);
@@ -325,9 +338,9 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
     pl.emb_ws3 = cv.raw(pl.emb_ws_bytes);
     pl.attn_ws_bytes = uniter_attn_bwd_ws_bytes(B, L, c.num_attention_heads);
     pl.attn_ws = cv.raw(pl.attn_ws_bytes);
-    pl.wg_slabs = pl.res ? cv.f((size_t)4 * 3 * H * (I > 3 * H ? I : 3 * H)) : nullptr;
+    pl.wg_slabs = res ? cv.f((size_t)4 * 3 * H * (I > 3 * H ? I : 3 * H)) : nullptr;
     const int wg_env = sw.wgrad_group;      // (1, the default: one launch of whole-K tiles; 2 / 4: its measured-slower forms; 0: stream-K)
-    pl.wg_group = (pl.res && H % 8 == 0 && I % 8 == 0 && (wg_env == 1 || wg_env == 2 || wg_env == 4)) ? wg_env : 0;
+    pl.wg_group = (res && H % 8 == 0 && I % 8 == 0 && (wg_env == 1 || wg_env == 2 || wg_env == 4)) ? wg_env : 0;
     // the grouped kernel addresses its operands with 31-bit buffer offsets: very long batches keep the stream-K launches
     if ((size_t)(M + 64) * (I > 3 * H ? I : 3 * H) * 2 >= (1ull << 31)) pl.wg_group = 0;
   }
@@ -360,7 +373,8 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
   const Switches& sw = uniter_switches();
   int cfg = 0;
   const bool wgrad = kind == UNITER_K_GEMM_WGRAD && akm && bkm && (beta == 1 || beta == -1);
-  if (wgrad && (m->precision == 0 || m->precision == 3)) {
+  const Precision prec = m->plan.prec;
+  if (wgrad && (prec == PREC_F32 || prec == PREC_X3)) {
     // a layer's weight gradients by output shape: whole-K tiles (cfg 25, UNITER_WGRAD_WHOLE's bit) or UNITER_WGRAD_CFG's stream-K tiles
     cfg = sw.wgrad_cfg;
     const int H_ = m->cfg.hidden_size, I_ = m->cfg.intermediate_size;
@@ -375,37 +389,60 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
   }
   // wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h; UNITER_MAIN_PRIO, default 0)
   g_uniter_launch_prio = kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio;
-  if (m->precision == 1 || m->precision == 2)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
+  if (prec == PREC_BF16_MFMA || prec == PREC_BF16)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
     return gemm_bf16_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias, aux_in, aux_out, ld_aux, beta,
                          colsum_part, st);
   return gemm_f32_run(cfg, kind == UNITER_K_GEMM_FFN_UP_FWD, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias,
                       aux_in, aux_out, ld_aux, beta, colsum_part, st);
 }
 
-// precision 2: both operands already bf16 in memory.  Forward and input-gradient products run on the LDS-DMA kernel
-// (gemm_bf16_dma.hip); aux operands (gelu' in, gelu' out) are bf16 there, residual gradients fp32.
-int gemm_v2(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int K, const void* A, int lda,
-            const void* B, int ldb, float* C, int ldc, int nsplit, unsigned short* Cb, int ldcb, int epi,
-            const float* bias, const void* aux_in, int aux_in_b16, void* aux_out, int aux_out_b16, int ld_aux,
-            float* colpart = nullptr) {
+// One dense product of encoder layer l against weight w (L_QW, L_OW, L_W1, L_W2): c = epilogue(a . W^T), or with b_kmajor the input
+// gradient c = epilogue(a . W).  The site states the product; the plan's precision decides the operand format:
+//   PREC_F32 / PREC_BF16_MFMA: fp32 operands and the fp32 weight, through gemm().
+//   PREC_BF16: both operands already bf16 in memory (a's copy, the mirror's weight) on the LDS-DMA kernel (gemm_bf16_dma.hip); the
+//     gelu' operand of the GELU epilogues (aux_out forward, aux_in of dU) is bf16 there, residual gradients fp32.
+//   PREC_X3: a = x3 activations [M][3][K], W = the piece-major x3 mirror (piece stride = the flat parameter buffer's length), output
+//     fp32 or x3 [M][3][N], aux operands fp32 (gemm_split3.hip).
+// The fp32 output is `pieces` k-piece slabs [M][N], summed by the row pass or attention kernel that reads them.
+int linear(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int K, int l, int w, Act a, Act c, int pieces, int epi,
+           const float* bias, const float* aux_in, float* aux_out, float* colpart = nullptr) {
+  const Plan& pl = m->plan;
+  const Switches& sw = uniter_switches();
+  const int ldw = bkm ? N : K;                                                        // W is [N][K] forward, [K][N] for an input gradient
+  const int ld_aux = (epi == UNITER_EPI_NONE || epi == UNITER_EPI_BIAS) ? 0 : N;      // (the other epilogues read or write an [M][N] operand)
+  float* C = c.b ? nullptr : c.f;
+  if (!pl.copies()) {
+    UCHECK_ARG(pieces == 1, "linear: the fp32 kernels write one slab");
+    return gemm(m, kind, st, 0, bkm, M, N, K, a.f, K, m->LP(l, w), ldw, C, N, epi, bias, aux_in, aux_out, ld_aux, 0, colpart);
+  }
   ProfScope ps(m, kind, st);
-  g_uniter_launch_prio = uniter_switches().main_prio_bf16;
+  if (pl.prec == PREC_X3) {
+    const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && sw.x3_cfg_ffn_up_fwd) ? sw.x3_cfg_ffn_up_fwd : sw.x3_cfg;
+    g_uniter_launch_prio = sw.main_prio_x3;
+    // (every product of this helper runs on the main stream: the balanced walk's main-stream workspace)
+    // (cfg | 64: the weight's pieces in the paired-row layout -- full 128-byte source lines for the loaders of the forward products)
+    return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), pieces, 0, bkm, M, N, K, a.b, 3 * K, K, m->WB(l, w), ldw, (int)m->mirror_numel, C, N,
+                       (long)M * N, c.b, 3 * N, N, epi, bias, aux_in, aux_out, N, st, colpart, pl.sk_main, pl.sk_main ? pl.sk_bytes : 0);
+  }
+  g_uniter_launch_prio = sw.main_prio_bf16;
+  const int aux_in_b16 = epi == UNITER_EPI_MUL || epi == UNITER_EPI_DGELU, aux_out_b16 = epi == UNITER_EPI_BIAS_GELU || epi == UNITER_EPI_BIAS_GELU_D;
+  const int ldcb = c.b ? N : 0;
   // round 6: the persistent loader / compute kernels (csrc/gemm_bf16_p.hip) for the products UNITER_B16_PERSIST names (default: none):
   // 1 = QKV forward, 2 = N = hidden products, 8 = the wide products as well (4: the grouped weight gradients, wgrad_group())
   int cfg = 0;
-  const int mask = uniter_switches().b16_persist;
+  const int mask = sw.b16_persist;
   const bool epi_ok = epi == UNITER_EPI_NONE || epi == UNITER_EPI_BIAS || epi == UNITER_EPI_ADD || epi == UNITER_EPI_BIAS_GELU_D || epi == UNITER_EPI_MUL;
   if (epi_ok && K % 64 == 0) {
     if ((mask & 1) && kind == UNITER_K_GEMM_QKV_FWD && !bkm && N % 192 == 0) cfg = 8;
-    else if ((mask & 2) && nsplit > 1 && N <= 1024) cfg = 6;
-    else if ((mask & 8) && nsplit == 1 && N >= 2048) cfg = 7;
+    else if ((mask & 2) && pieces > 1 && N <= 1024) cfg = 6;
+    else if ((mask & 8) && pieces == 1 && N >= 2048) cfg = 7;
   }
   if (colpart) {      // (the product that writes dU also leaves its column partials: the persistent 128 x 256 kernel's epilogue)
-    UCHECK_ARG(epi_ok && K % 64 == 0 && nsplit == 1, "gemm_v2: column partials ride on the persistent kernels");
-    return gemm_b1p_run(7, 1, bkm, M, N, K, A, lda, B, ldb, C, ldc, (long)M * ldc, Cb, ldcb, epi, bias, aux_in, aux_in_b16, aux_out,
+    UCHECK_ARG(epi_ok && K % 64 == 0 && pieces == 1, "linear: column partials ride on the persistent kernels");
+    return gemm_b1p_run(7, 1, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in, aux_in_b16, aux_out,
                         aux_out_b16, ld_aux, colpart, st);
   }
-  return gemm_bf16v2_run(cfg, nsplit, 0, bkm, M, N, K, A, lda, B, ldb, C, ldc, (long)M * ldc, Cb, ldcb, epi, bias, aux_in,
+  return gemm_bf16v2_run(cfg, pieces, 0, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in,
                          aux_in_b16, aux_out, aux_out_b16, ld_aux, 0, st);
 }
 // The attention kernel of a plan's forward pass (`keep_pre`: the forward drew the dropout keep flags ahead of its kernels) or of its
@@ -417,26 +454,12 @@ AttnKernel attn_kernel(const Plan& pl, float p_drop, bool save, bool keep_pre, b
   const bool fused = pl.L <= uniter_attn_varlen_max_len();      // the L <= 192 kernels (none with UNITER_ATTN_SPLIT=0)
   const bool pieces = pl.L <= uniter_attn_x3_max_len() && (p_drop == 0.f || keep_pre || bwd);
   // precision 2, L <= 192: attention on the bf16 pipe, which also writes the bf16 copies of its outputs
-  if (pl.res && fused) return (sw.attn_b16x && pieces) ? ATTN_B16X : ATTN_BF16_PRE;
+  if (pl.prec == PREC_BF16 && fused) return (sw.attn_b16x && pieces) ? ATTN_B16X : ATTN_BF16_PRE;
   // precision 3: the attention's own products on the bf16 pipe as well (its backward emits the fused query|key|value bias partials)
-  if (pl.x3 && sw.attn_x3 && pieces && (fused || !bwd)) return ATTN_X3;
-  if (pl.x3 && fused) return ATTN_F32_PRE_X3;
+  if (pl.prec == PREC_X3 && sw.attn_x3 && pieces && (fused || !bwd)) return ATTN_X3;
+  if (pl.prec == PREC_X3 && fused) return ATTN_F32_PRE_X3;
   if (pl.packed || (save && fused)) return ATTN_F32_PRE;
   return ATTN_F32;
-}
-// precision 3: A = x3 activations [M][3][K]; W = the piece-major x3 mirror of an encoder weight (row stride ldw, piece stride =
-// the flat parameter buffer's length); outputs fp32 (nsplit slabs) or x3 [M][3][N]; aux operands fp32 (csrc/gemm_split3.hip)
-int gemm_x3(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int K, const void* A, const unsigned short* W,
-            int ldw, float* C, int nsplit, unsigned short* Cx, int epi, const float* bias, const float* aux_in, float* aux_out,
-            float* colsum_part = nullptr) {
-  ProfScope ps(m, kind, st);
-  const Switches& sw = uniter_switches();
-  const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && sw.x3_cfg_ffn_up_fwd) ? sw.x3_cfg_ffn_up_fwd : sw.x3_cfg;
-  g_uniter_launch_prio = sw.main_prio_x3;
-  // (every product of this helper runs on the main stream: the balanced walk's main-stream workspace)
-  // (cfg | 64: the weight's pieces in the paired-row layout -- full 128-byte source lines for the loaders of the forward products)
-  return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), nsplit, 0, bkm, M, N, K, A, 3 * K, K, W, ldw, (int)m->mirror_numel, C, N, (long)M * N, Cx, 3 * N, N, epi,
-                     bias, aux_in, aux_out, N, st, colsum_part, m->plan.sk_main, m->plan.sk_main ? m->plan.sk_bytes : 0);
 }
 // CUs the backward pass's persistent launches may use: the chip's minus what the caller reserved for a gradient exchange
 int x3_backward_cus(const uniter_model* m) {
@@ -456,12 +479,12 @@ struct WgradGroup {
   bool colpart = false;   // ... and dU's column sums (that bias gradient) start as column partials of the product that writes dU
   int cfg = 0, max_wgs = 0, slots = 0;
 };
-WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int precision, int l) {
+WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l) {
   const Switches& sw = uniter_switches();
   const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size;
   const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
   WgradGroup g;
-  if (precision == 3) {
+  if (pl.prec == PREC_X3) {
     // UNITER_X3_RIDERS, and the default geometries only.  Column partials whenever the launch runs on 128 x 256 tiles
     g.riders = sw.x3_riders && (sw.x3_cfg == 0 || sw.x3_cfg == 3);
     g.colpart = g.riders && gemm_x3_wgrad_default_cfg() == 4;
@@ -477,7 +500,7 @@ WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int precision, int
   const bool p7 = (sw.b16_persist & 4) != 0;
   // (on the 128 x 256 geometry the bias gradient of intermediate.dense must come from column partials -- bit 8 and the gelu' form of the
   // forward epilogue: a separate pass over dU would write it outside the launch, and its squares would reach no clip-norm slot)
-  g.riders = pl.res && pl.wg_group == 1 && (p7 ? sw.b16_riders != '0' && (sw.b16_persist & 8) && pl.gelu_d : sw.b16_riders == '1');
+  g.riders = pl.wg_group == 1 && (p7 ? sw.b16_riders != '0' && (sw.b16_persist & 8) && pl.gelu_d : sw.b16_riders == '1');
   // ... finished by a fourth reduction job of the riders
   g.colpart = p7 && g.riders;
   g.cfg = pl.wg_group == 4 ? 4 : (p7 ? 7 : 1);      // (4: three LDS stages; 7: 216 whole-K tiles of 128 x 256 on the persistent kernel)
@@ -509,32 +532,75 @@ void fill_layer_riders(uniter_x3_riders_t& x, const uniter_model* m, int l, cons
     x.out[j][0] = m->LG(l, L_B1); x.out[j][1] = x.out[j][2] = nullptr;
   }
 }
-int split_x3(const float* src, unsigned short* dst, int rows, int cols, hipStream_t st) {
-  return uniter_split3(src, rows, cols, cols, dst, (size_t)3 * cols, (size_t)cols, st);
+// the operand copy of an activation [rows][cols] that no kernel wrote along with the fp32 tensor: bf16, or x3 pieces in PREC_X3
+int operand_copy(const Plan& pl, Act a, int rows, int cols, hipStream_t st) {
+  if (pl.prec == PREC_X3) return uniter_split3(a.f, rows, cols, cols, a.b, (size_t)3 * cols, (size_t)cols, st);
+  return uniter_cast_bf16(a.f, a.b, (size_t)rows * cols, st);
 }
-// weight gradients (both operands k-major, stream-K, fp32 atomics into the gradient buffer): gemm_bf16.hip
-int gemm_r(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int N, int K, const void* A, int lda,
-           const void* B, int ldb, float* C, int ldc, unsigned short* Cb, int ldcb, int epi, const float* bias,
-           const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part = nullptr) {
-  ProfScope ps(m, kind, st);
-  return gemm_bf16res_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, Cb, ldcb, epi, bias, aux_in, aux_out, ld_aux,
-                          beta, colsum_part, st);
+// Dropout + residual + LayerNorm behind layer l's attention output (second = 0) or FFN output (second = 1): t is `pieces` k-piece slabs
+// of the product in front [M][H] each (one slab: stride 0, as uniter_ln_fwd_b16 passes it); y.b takes the operand copy of the result where the plan has one.  mean / rstd are kept
+// only by a pass that saves for a backward pass.
+int ln_fwd(uniter_model* m, hipStream_t st, int l, int second, const float* t, int pieces, const float* resid, float* z,
+           Act y, float* mean, float* rstd, float ph) {
+  const Plan& pl = m->plan;
+  const bool save = pl.mode != 0;
+  const int g = second ? L_LN2_G : L_LN1_G;      // (its bias follows it)
+  ProfScope ps(m, UNITER_K_LN, st);
+  g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;
+  return (pl.prec == PREC_X3 ? uniter_ln_fwd_slabs_x3 : uniter_ln_fwd_slabs)(
+      t, pieces, pieces > 1 ? (size_t)pl.M * m->cfg.hidden_size : 0, resid, m->LP(l, g), m->LP(l, g + 1), z, y.f, y.b, save ? mean : nullptr, save ? rstd : nullptr, pl.M,
+      m->cfg.hidden_size, ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), st);
 }
-// dW[Mo, No] += A^T B with A [K, Mo], B [K, No] bf16: split-K slabs + one reduce pass where that beats stream-K atomics
-int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, int Mo, int No, int K, const void* A, const void* B, float* dW) {
-  if (m->wg_overwrite) UCHECK_HIP(hipMemsetAsync(dW, 0, (size_t)Mo * No * sizeof(float), st));      // these forms accumulate
+// its backward row pass: dy is `pieces` slabs [M][H]; g takes the dropped gradient (fp32 and / or operand copy), ws the column partials
+int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, int pieces, const float* z, const float* mean,
+           const float* rstd, float* dz, Act g, void* ws, float ph) {
+  const Plan& pl = m->plan;
+  const int H = m->cfg.hidden_size;
+  ProfScope ps(m, UNITER_K_LN_BWD, st);
+  g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;      // (the forward pass's flags)
+  return (pl.prec == PREC_X3 ? uniter_ln_bwd_rows_slabs_x3 : uniter_ln_bwd_rows_slabs)(
+      dy, pieces, (size_t)pl.M * H, z, mean, rstd, m->LP(l, second ? L_LN2_G : L_LN1_G), dz, g.f, g.b, 1, pl.M, H, ph, m->seed, m->offset,
+      second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), ws, pl.ln_ws_bytes, st);
+}
+// The four weight gradients of a layer in PREC_BF16 / PREC_X3, dW[p] [Mo[p], No[p]] += A[p]^T B[p] over the plan's M rows, in the grouped
+// launch's order {W1, W2, QKV, attention output}.  Product 0 must be dW1 = dU^T y1: its A operand's column sums are intermediate.dense's
+// bias gradient
+struct WgradProducts { int Mo[4], No[4]; const void *A[4], *B[4]; float* dW[4]; };
+// product p alone in PREC_BF16 (both operands k-major): split-K slabs + one reduce pass where that beats stream-K atomics into the
+// gradient buffer (gemm_bf16.hip)
+int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, const WgradProducts& t, int p) {
+  const int Mo = t.Mo[p], No = t.No[p], K = pl.M;
+  if (m->wg_overwrite) UCHECK_HIP(hipMemsetAsync(t.dW[p], 0, (size_t)Mo * No * sizeof(float), st));      // these forms accumulate
   const int pieces = gemm_bf16v2_wgrad_pieces(Mo, No, K);
-  if (pieces == 0 || !pl.wg_slabs)
-    return gemm_r(m, UNITER_K_GEMM_WGRAD, st, 1, 1, Mo, No, K, A, Mo, B, No, dW, No, nullptr, 0, UNITER_EPI_NONE, nullptr,
-                  nullptr, nullptr, 0, 1);
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, st);
-    UCHECK_RC(gemm_bf16v2_run(0, pieces, 1, 1, Mo, No, K, A, Mo, B, No, pl.wg_slabs, No, (long)Mo * No, nullptr, 0,
+    if (pieces == 0 || !pl.wg_slabs)
+      return gemm_bf16res_run(0, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, t.dW[p], No, nullptr, 0, UNITER_EPI_NONE, nullptr, nullptr,
+                              nullptr, 0, 1, nullptr, st);
+    UCHECK_RC(gemm_bf16v2_run(0, pieces, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, pl.wg_slabs, No, (long)Mo * No, nullptr, 0,
                               UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0, st));
   }
-  return uniter_slab_reduce_add(pl.wg_slabs, pieces, (size_t)Mo * No, dW, (size_t)Mo * No, st);
+  return uniter_slab_reduce_add(pl.wg_slabs, pieces, (size_t)Mo * No, t.dW[p], (size_t)Mo * No, st);
 }
-int cast_b(const float* src, unsigned short* dst, size_t n, hipStream_t st) { return uniter_cast_bf16(src, dst, n, st); }
+// Products idx[0 .. n) as ONE launch of whole-K tiles on the weight-gradient stream (gemm_bf16v2_wgrad_group / gemm_x3_wgrad_group by
+// precision); colsum_after: followed by the column sums of dU (product 0's A operand), which nothing riding on the launch has taken
+int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t, const int* idx, int n, int cfg, int max_wgs,
+                 uniter_x3_riders_t* riders, bool colsum_after) {
+  const Plan& pl = m->plan;
+  const bool x3 = pl.prec == PREC_X3;
+  int Mo[4], No[4];
+  const void *A[4], *B[4];
+  float* dW[4];
+  for (int i = 0; i < n; ++i) { Mo[i] = t.Mo[idx[i]]; No[i] = t.No[idx[i]]; A[i] = t.A[idx[i]]; B[i] = t.B[idx[i]]; dW[i] = t.dW[idx[i]]; }
+  const int overwrite = m->wg_overwrite ? 1 : 0;
+  {
+    ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
+    if (x3) UCHECK_RC(gemm_x3_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
+    else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders));
+  }
+  if (!colsum_after) return 0;
+  return (x3 ? uniter_colsum_x3_add : uniter_colsum_bf16_add)(t.A[0], pl.M, t.Mo[0], t.Mo[0], m->LG(l, L_B1), sd);      // intermediate.dense bias gradient
+}
 
 int validate_batch(const uniter_model* m, const uniter_batch_t* b) {
   UCHECK_ARG(b, "batch is NULL");
@@ -699,13 +765,11 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   const int B = b->B, T = b->T, R = b->R, L = b->L, S = pl.S, M = pl.M;
   const bool save = train != 0;
   const Switches& sw = uniter_switches();
-  const bool gelu_d = sw.gelu_d || m->precision == 3;      // UNITER_GELU_D=0: A/B switch (store the pre-activation, libm erf twice)
+  const bool gelu_d = sw.gelu_d || pl.prec == PREC_X3;      // UNITER_GELU_D=0: A/B switch (store the pre-activation, libm erf twice)
   pl.gelu_d = gelu_d;
   m->batch = *b; m->hidden_out = hidden_out; m->all_layers = all_layers; m->seed = seed; m->offset = offset;
   m->bwd_open = false;
   ++m->generation;
-
-  const bool res = pl.res, x3 = pl.x3;
 
   // the flag words of the balanced walk's two workspaces (16 KB each): zero before the first launch that uses them -- the launches
   // leave them zero, but the workspace is the caller's and may be a new one
@@ -776,7 +840,7 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     // with K = 2048 -- as a stream-K accumulation on top of the bias rows it fills the chip (fp32: 58 -> 25 us)
     const long t64 = (long)((B * R + 63) / 64) * ((H + 63) / 64);
     // (UNITER_IMG_SK; native fp32 only: the float atomics make the sum's order vary from run to run, switches.h)
-    if (sw.img_sk && m->precision == 0 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
+    if (sw.img_sk && pl.prec == PREC_F32 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
       UCHECK_RC(uniter_bias_rows(m->P(P_IMG_B), pl.imgfc, B * R, H, st));
       UCHECK_RC(gemm(m, 0, st, 0, 0, B * R, H, c.img_dim, feat, c.img_dim, m->P(P_IMG_W), c.img_dim, pl.imgfc, H,
                      UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 1));
@@ -799,128 +863,77 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   const bool joint = has_txt && has_img;
   // (round 6) the joint rows and their operand copy for layer 0's first product in ONE launch: this chain -- text embeddings, gather,
   // split -- is what the first encoder product waits for behind the optimizer's update of the word table
-  const bool fuse_copy = sw.gather_ex && !packed && (res || x3) && H <= 1024 && m->mirror != nullptr;
+  const bool fuse_copy = sw.gather_ex && !packed && pl.copies() && H <= 1024 && m->mirror != nullptr;
   if (packed) UCHECK_RC(uniter_row_gather(pl.cat, b->pack_src, pl.emb, M, H, B * S, st));
-  else if (fuse_copy) UCHECK_RC(uniter_gather_rows_ex(pl.cat, joint ? b->gather_index : nullptr, pl.emb, pl.embb, x3 ? 1 : 2, B, S, L, H, st));
+  else if (fuse_copy) UCHECK_RC(uniter_gather_rows_ex(pl.cat, joint ? b->gather_index : nullptr, pl.emb, pl.embb, pl.prec == PREC_X3 ? 1 : 2, B, S, L, H, st));
   else UCHECK_RC(uniter_gather_rows(pl.cat, joint ? b->gather_index : nullptr, pl.emb, B, S, L, H, st));
   const size_t PH = (size_t)B * L * H;          // one layer of the padded output
-  if ((res || x3) && !fuse_copy) {
+  Act x = {pl.emb, pl.embb};
+  if (pl.copies() && !fuse_copy) {
     UCHECK_ARG(m->mirror != nullptr, "model_forward: precision 2 / 3 needs uniter_model_set_weight_mirror");
-    if (res) UCHECK_RC(cast_b(pl.emb, pl.embb, (size_t)M * H, st));
-    else UCHECK_RC(split_x3(pl.emb, pl.embb, M, H, st));
+    UCHECK_RC(operand_copy(pl, x, M, H, st));
   }
-  const unsigned short* xb = pl.embb;
   // ---- encoder (model/model.py:282-292; model/layer.py:166-170) ----
-  const float* x = pl.emb;
+  const float* mask = packed ? nullptr : b->attention_mask;
+  const int32_t* cu_seqlens = packed ? b->cu_seqlens : nullptr;
+  // the context's operand copy is made after the fact where the attention kernel left none: PREC_BF16 unless the kernel was a bf16 one;
+  // PREC_X3 beyond the L <= 192 kernels only
+  const bool ctx_copy = pl.prec == PREC_BF16 ? !attn_b16 : pl.prec == PREC_X3 && L > uniter_attn_varlen_max_len();
   for (int l = 0; l < nl; ++l) {
     LayerBufs& lb = pl.layers[l];
     if (gated) UCHECK_HIP(hipStreamWaitEvent(st, m->ready[1 + l], 0));
     if (l == 0 && keep_on_aux) UCHECK_HIP(hipStreamWaitEvent(st, m->ev_aux1, 0));      // the keep flags of every layer are drawn
     float* y2 = packed ? lb.y2 : (all_layers ? hidden_out + l * PH : (l == nl - 1 ? hidden_out : lb.y2));
-    if (attn_b16)      // the bf16 attention kernels read Q, K, V as bf16: write only that (in the qkv buffer's place)
-      UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_QKV_FWD, st, 0, M, 3 * H, H, xb, H, m->WB(l, L_QW), H, nullptr, 3 * H, 1,
-                        (unsigned short*)lb.qkv, 3 * H, UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, 0, nullptr, 0, 0));
-    else if (res)
-      UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_QKV_FWD, st, 0, M, 3 * H, H, xb, H, m->WB(l, L_QW), H, lb.qkv, 3 * H, 1,
-                        nullptr, 0, UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, 0, nullptr, 0, 0));
-    else if (x3)
-      UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_QKV_FWD, st, 0, M, 3 * H, H, xb, m->WB(l, L_QW), H, lb.qkv, 1, nullptr,
-                        UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, nullptr));
-    else
-      UCHECK_RC(gemm(m, UNITER_K_GEMM_QKV_FWD, st, 0, 0, M, 3 * H, H, x, H, m->LP(l, L_QW), H, lb.qkv, 3 * H,
-                     UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, nullptr, 0, 0));
+    // (the bf16 attention kernels read Q, K, V as bf16: the product writes only that, in the qkv buffer's place)
+    const Act qkv = attn_b16 ? Act{nullptr, (unsigned short*)lb.qkv} : Act{lb.qkv, nullptr};
+    UCHECK_RC(linear(m, UNITER_K_GEMM_QKV_FWD, st, 0, M, 3 * H, H, l, L_QW, x, qkv, 1, UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, nullptr));
     {
       ProfScope ps(m, UNITER_K_ATTN_FWD, st);
+      // the dropout keep flags: attention_x3.hip's kernels only read them; the others draw them (or read them: keep_pre) for the backward pass
+      unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;
+      unsigned short* keep_wr = save ? lb.keepb : nullptr;
       switch (pl.attn_fwd) {
       case ATTN_B16X:      // precision 2: the attention products run on the bf16 pipe as well
-        UCHECK_RC(uniter_attn_b16x_fwd(lb.qkv, 1, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr, lb.ctx,
-                                       lb.ctxb, lb.lse, pa > 0.f ? lb.keepb : nullptr, B, L, nh, pa, st));
+        UCHECK_RC(uniter_attn_b16x_fwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_rd, B, L, nh, pa, st));
         break;
       case ATTN_BF16_PRE:
-        UCHECK_RC(uniter_attn_bf16_fwd_pre(lb.qkv, 1, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
-                                           lb.ctx, lb.ctxb, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
+        UCHECK_RC(uniter_attn_bf16_fwd_pre(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
                                            seed, offset, SITE_ATTN_PROBS(l), st));
         break;
       case ATTN_X3:      // the attention's own products on the bf16 pipe as well
-        UCHECK_RC(uniter_attn_x3_fwd(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr, lb.ctx,
-                                     lb.ctxb, lb.lse, pa > 0.f ? lb.keepb : nullptr, B, L, nh, pa, st));
+        UCHECK_RC(uniter_attn_x3_fwd(lb.qkv, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_rd, B, L, nh, pa, st));
         break;
       case ATTN_F32_PRE_X3:      // the context leaves the kernel as x3 pieces too
-        UCHECK_RC(uniter_attn_fwd_pre_x3(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
-                                         lb.ctx, lb.ctxb, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
+        UCHECK_RC(uniter_attn_fwd_pre_x3(lb.qkv, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
                                          seed, offset, SITE_ATTN_PROBS(l), st));
         break;
       case ATTN_F32_PRE:
-        UCHECK_RC(uniter_attn_fwd_pre(lb.qkv, packed ? nullptr : b->attention_mask, packed ? b->cu_seqlens : nullptr,
-                                      lb.ctx, nullptr, lb.lse, save ? lb.keepb : nullptr, keep_pre ? 1 : 0, B, L, nh, pa,
+        UCHECK_RC(uniter_attn_fwd_pre(lb.qkv, mask, cu_seqlens, lb.ctx, nullptr, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
                                       seed, offset, SITE_ATTN_PROBS(l), st));
         break;
-      case ATTN_F32:
-        UCHECK_RC(uniter_attn_fwd(lb.qkv, b->attention_mask, lb.ctx, lb.lse, B, L, nh, pa, seed, offset,
-                                  SITE_ATTN_PROBS(l), st));
+      case ATTN_F32:      // (never packed)
+        UCHECK_RC(uniter_attn_fwd(lb.qkv, mask, lb.ctx, lb.lse, B, L, nh, pa, seed, offset, SITE_ATTN_PROBS(l), st));
         break;
       }
     }
-    if (res) {
-      if (!attn_b16) UCHECK_RC(cast_b(lb.ctx, lb.ctxb, (size_t)M * H, st));
-      UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, M, H, H, lb.ctxb, H, m->WB(l, L_OW), H, lb.t1, H, 1,
-                        nullptr, 0, UNITER_EPI_BIAS, m->LP(l, L_OB), nullptr, 0, nullptr, 0, 0));
-    } else if (x3) {
-      // the context as x3 pieces: operand of the projection below and of its weight gradient (L <= 192: the attention kernel wrote them)
-      if (L > uniter_attn_varlen_max_len()) UCHECK_RC(split_x3(lb.ctx, lb.ctxb, M, H, st));
-      UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, M, H, H, lb.ctxb, m->WB(l, L_OW), H, lb.t1, pl.ns_kh, nullptr,
-                        UNITER_EPI_BIAS, m->LP(l, L_OB), nullptr, nullptr));
-    } else {
-      UCHECK_RC(gemm(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, 0, M, H, H, lb.ctx, H, m->LP(l, L_OW), H, lb.t1, H,
-                     UNITER_EPI_BIAS, m->LP(l, L_OB), nullptr, nullptr, 0, 0));
-    }
+    // the context's operand copy: operand of the projection below and of its weight gradient
+    const Act ctx = {lb.ctx, lb.ctxb}, y1 = {lb.y1, lb.y1b}, hact = {lb.hact, lb.hactb};
+    if (ctx_copy) UCHECK_RC(operand_copy(pl, ctx, M, H, st));
+    UCHECK_RC(linear(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, M, H, H, l, L_OW, ctx, Act{lb.t1, nullptr}, pl.ns_kh, UNITER_EPI_BIAS,
+                     m->LP(l, L_OB), nullptr, nullptr));
     if (l == 0 && pl.hid_on) UCHECK_HIP(hipStreamWaitEvent(st, m->ev_aux2, 0));      // every layer's hidden keep flags are drawn
-    {
-      ProfScope ps(m, UNITER_K_LN, st);
-      g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l) * pl.hid_stride : nullptr;
-      if (x3)
-        UCHECK_RC(uniter_ln_fwd_slabs_x3(lb.t1, pl.ns_kh, (size_t)M * H, x, m->LP(l, L_LN1_G), m->LP(l, L_LN1_B), lb.z1, lb.y1,
-                                         lb.y1b, save ? lb.mean1 : nullptr, save ? lb.rstd1 : nullptr, M, H, ph, seed, offset,
-                                         SITE_ATTN_OUT(l), st));
-      else
-      UCHECK_RC(uniter_ln_fwd_b16(lb.t1, x, m->LP(l, L_LN1_G), m->LP(l, L_LN1_B), lb.z1, lb.y1, res ? lb.y1b : nullptr,
-                                  save ? lb.mean1 : nullptr, save ? lb.rstd1 : nullptr, M, H, ph, seed, offset,
-                                  SITE_ATTN_OUT(l), st));
-    }
-    if (res) {
-      // the activation and gelu'(u) (or u) only exist in bf16: operand of FFN-down / of its weight gradient, factor of dU
-      UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_FFN_UP_FWD, st, 0, M, I, H, lb.y1b, H, m->WB(l, L_W1), H, nullptr, I, 1,
-                        lb.hactb, I, gelu_d ? UNITER_EPI_BIAS_GELU_D : UNITER_EPI_BIAS_GELU, m->LP(l, L_B1), nullptr, 0,
-                        save ? (void*)lb.u : (void*)lb.hact, 1, I));
-      UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_FFN_DOWN_FWD, st, 0, M, H, I, lb.hactb, I, m->WB(l, L_W2), I, lb.t2, H, pl.ns_ki,
-                        nullptr, 0, UNITER_EPI_BIAS, m->LP(l, L_B2), nullptr, 0, nullptr, 0, 0));
-    } else if (x3) {
-      // the activation exists only as x3 pieces (operand of FFN-down and of its weight gradient); gelu'(u) stays fp32
-      UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_FFN_UP_FWD, st, 0, M, I, H, lb.y1b, m->WB(l, L_W1), H, nullptr, 1, lb.hactb,
-                        UNITER_EPI_BIAS_GELU_D, m->LP(l, L_B1), nullptr, save ? lb.u : lb.hact));
-      UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_FFN_DOWN_FWD, st, 0, M, H, I, lb.hactb, m->WB(l, L_W2), I, lb.t2, pl.ns_ki, nullptr,
-                        UNITER_EPI_BIAS, m->LP(l, L_B2), nullptr, nullptr));
-    } else {
-      UCHECK_RC(gemm(m, UNITER_K_GEMM_FFN_UP_FWD, st, 0, 0, M, I, H, lb.y1, H, m->LP(l, L_W1), H, lb.hact, I,
-                     gelu_d ? UNITER_EPI_BIAS_GELU_D : UNITER_EPI_BIAS_GELU, m->LP(l, L_B1), nullptr, lb.u, I, 0));
-      UCHECK_RC(gemm(m, UNITER_K_GEMM_FFN_DOWN_FWD, st, 0, 0, M, H, I, lb.hact, I, m->LP(l, L_W2), I, lb.t2, H,
-                     UNITER_EPI_BIAS, m->LP(l, L_B2), nullptr, nullptr, 0, 0));
-    }
-    {
-      ProfScope ps(m, UNITER_K_LN, st);
-      g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + 1) * pl.hid_stride : nullptr;
-      if (x3)
-        UCHECK_RC(uniter_ln_fwd_slabs_x3(lb.t2, pl.ns_ki, (size_t)M * H, lb.y1, m->LP(l, L_LN2_G), m->LP(l, L_LN2_B), lb.z2, y2,
-                                         lb.y2b, save ? lb.mean2 : nullptr, save ? lb.rstd2 : nullptr, M, H, ph, seed, offset,
-                                         SITE_FFN_OUT(l), st));
-      else
-      UCHECK_RC(uniter_ln_fwd_slabs(lb.t2, pl.ns_ki, (size_t)M * H, lb.y1, m->LP(l, L_LN2_G), m->LP(l, L_LN2_B), lb.z2, y2,
-                                    res ? lb.y2b : nullptr, save ? lb.mean2 : nullptr, save ? lb.rstd2 : nullptr, M, H,
-                                    ph, seed, offset, SITE_FFN_OUT(l), st));
-    }
+    UCHECK_RC(ln_fwd(m, st, l, 0, lb.t1, pl.ns_kh, x.f, lb.z1, y1, lb.mean1, lb.rstd1, ph));
+    // FFN-up writes gelu'(u) (or u: gelu_d) beside the activation, for the backward pass.  With operand copies the activation exists only
+    // as one (operand of FFN-down and of its weight gradient), and a pass that saves nothing parks gelu'(u) in the unused fp32 buffer;
+    // gelu'(u) is bf16 in PREC_BF16 and fp32 elsewhere (linear())
+    float* gelu_aux = save ? lb.u : (pl.copies() ? lb.hact : nullptr);
+    UCHECK_RC(linear(m, UNITER_K_GEMM_FFN_UP_FWD, st, 0, M, I, H, l, L_W1, y1, hact, 1, gelu_d ? UNITER_EPI_BIAS_GELU_D : UNITER_EPI_BIAS_GELU,
+                     m->LP(l, L_B1), nullptr, gelu_aux));
+    UCHECK_RC(linear(m, UNITER_K_GEMM_FFN_DOWN_FWD, st, 0, M, H, I, l, L_W2, hact, Act{lb.t2, nullptr}, pl.ns_ki, UNITER_EPI_BIAS,
+                     m->LP(l, L_B2), nullptr, nullptr));
+    UCHECK_RC(ln_fwd(m, st, l, 1, lb.t2, pl.ns_ki, lb.y1, lb.z2, Act{y2, lb.y2b}, lb.mean2, lb.rstd2, ph));
     lb.y2 = y2;
-    x = y2;
-    if (res || x3) xb = lb.y2b;
+    x = Act{y2, lb.y2b};
     if (packed && (all_layers || l == nl - 1)) {
       // padded [B, L, H] view for the caller: valid rows scattered, padded positions zero
       float* dst = all_layers ? hidden_out + l * PH : hidden_out;
@@ -965,7 +978,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   const float pa = pl.mode == 1 ? c.attention_probs_dropout_prob : 0.f;
   hipStream_t st = m->st, sd = m->side;
   LayerBufs& lb = pl.layers[l];
-  const float* x = l == 0 ? pl.emb : pl.layers[l - 1].y2;
+  const Act x = l == 0 ? Act{pl.emb, pl.embb} : Act{pl.layers[l - 1].y2, pl.layers[l - 1].y2b};      // the layer's input
   const size_t MH = (size_t)M * H;
 
   // upstream gradient w.r.t. this layer's output (packed mode: the caller's padded gradient gathered
@@ -989,29 +1002,18 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   }
   // the dropped gradient in fp32: the operand of the fp32 GEMMs; the bf16-resident GEMMs read its bf16 copy only, so
   // the fp32 store (8 MB per pass) is skipped there
-  const bool x3 = pl.x3;
-  float* g2 = ph > 0.f ? ((pl.res || x3) ? nullptr : lb.g2) : lb.dz2;
-  float* g1 = ph > 0.f ? ((pl.res || x3) ? nullptr : lb.g1) : lb.dz1;
+  const bool copies = pl.copies();
+  const Act g2 = {ph > 0.f ? (copies ? nullptr : lb.g2) : lb.dz2, lb.g2b};
+  const Act g1 = {ph > 0.f ? (copies ? nullptr : lb.g1) : lb.dz1, lb.g1b};
   // precision 2: the next layer's dx may be split-K slabs (summed here); never for the last layer (dy is the caller's
   // gradient), with all_layers (dy is dsum) or in layer 0 (the embedding backward reads a plain dx)
   const int ns_dy = (l == nl - 1 || m->all_layers) ? 1 : pl.ns_k3h;
   const int ns_dx = (l == 0 || m->all_layers) ? 1 : pl.ns_k3h;
-  {
-    ProfScope ps(m, UNITER_K_LN_BWD, st);
-    g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + 1) * pl.hid_stride : nullptr;      // (the forward pass's flags)
-    if (x3)
-      UCHECK_RC(uniter_ln_bwd_rows_slabs_x3(dy, ns_dy, MH, lb.z2, lb.mean2, lb.rstd2, m->LP(l, L_LN2_G), lb.dz2, g2, lb.g2b, 1, M, H,
-                                            ph, m->seed, m->offset, SITE_FFN_OUT(l), lb.ln_ws2, pl.ln_ws_bytes, st));
-    else
-    UCHECK_RC(uniter_ln_bwd_rows_slabs(dy, ns_dy, MH, lb.z2, lb.mean2, lb.rstd2, m->LP(l, L_LN2_G), lb.dz2, g2,
-                                       pl.res ? lb.g2b : nullptr, 1, M, H, ph, m->seed, m->offset, SITE_FFN_OUT(l),
-                                       lb.ln_ws2, pl.ln_ws_bytes, st));
-  }
+  UCHECK_RC(ln_bwd(m, st, l, 1, dy, ns_dy, lb.z2, lb.mean2, lb.rstd2, lb.dz2, g2, lb.ln_ws2, ph));
   // FFN down dgrad (+ GELU'), FFN up dgrad (+ residual grad)
   // the GEMM's epilogue also emits per-32-row column sums of du (= partial bias gradients of
   // intermediate.dense): saves a 32 MB re-read of du
   const bool fuse_db1 = H % 64 == 0;
-  const bool res = pl.res;
   const Switches& sw = uniter_switches();
   const bool attn_b16 = attn_is_b16(pl.attn_bwd);
   // the L <= 192 attention backward kernels (every one but uniter_attn_bwd) also emit the per-sample column sums of dqkv (the fused
@@ -1021,114 +1023,71 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   const int ns_dctx = (pl.attn_bwd == ATTN_X3 && sw.dctx_split) ? pl.ns_kh_b : 1;
   const int epi_du = pl.gelu_d ? UNITER_EPI_MUL : UNITER_EPI_DGELU;
   // what rides on the layer's grouped weight-gradient launch (precisions 2 and 3), and that launch's geometry
-  const WgradGroup wg = (res || x3) ? wgrad_group(m, pl, res ? 2 : 3, l) : WgradGroup();
-  if (res) {
-    UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, lb.g2b, H, m->WB(l, L_W2), I, nullptr, I, 1, lb.dub, I,
-                      epi_du, nullptr, lb.u, 1, nullptr, 0, I, wg.colpart ? lb.du_csum : nullptr));
-    UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, lb.dub, I, m->WB(l, L_W1), H, lb.dy1, H, pl.ns_ki, nullptr, 0,
-                      UNITER_EPI_ADD, nullptr, lb.dz2, 0, nullptr, 0, H));
-  } else if (x3) {
-    // dU = (g2 . W2) * gelu'(u) exists only as x3 pieces: operand of the next product and of intermediate.dense's weight gradient
-    // (with riders on the 128 x 256 weight-gradient geometry the bias gradient of intermediate.dense -- dU's column sums -- starts
-    // here: one row of partial sums per 64 rows of dU, finished by a reduction job of the riders)
-    UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, lb.g2b, m->WB(l, L_W2), I, nullptr, 1, lb.dub, UNITER_EPI_MUL,
-                      nullptr, lb.u, nullptr, wg.colpart ? lb.du_csum : nullptr));
-    UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, lb.dub, m->WB(l, L_W1), H, lb.dy1, pl.ns_ki_b, nullptr, UNITER_EPI_ADD,
-                      nullptr, lb.dz2, nullptr));
-  } else {
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_DGRAD, st, 0, 1, M, I, H, g2, H, m->LP(l, L_W2), I, lb.du, I, epi_du,
-                   nullptr, lb.u, nullptr, I, 0, fuse_db1 ? lb.du_csum : nullptr));
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_DGRAD, st, 0, 1, M, H, I, lb.du, I, m->LP(l, L_W1), H, lb.dy1, H, UNITER_EPI_ADD,
-                   nullptr, lb.dz2, nullptr, H, 0));
-  }
-  {
-    ProfScope ps(m, UNITER_K_LN_BWD, st);
-    g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l) * pl.hid_stride : nullptr;
-    if (x3)
-      UCHECK_RC(uniter_ln_bwd_rows_slabs_x3(lb.dy1, pl.ns_ki_b, MH, lb.z1, lb.mean1, lb.rstd1, m->LP(l, L_LN1_G), lb.dz1, g1, lb.g1b,
-                                            1, M, H, ph, m->seed, m->offset, SITE_ATTN_OUT(l), lb.ln_ws1, pl.ln_ws_bytes, st));
-    else
-    UCHECK_RC(uniter_ln_bwd_rows_slabs(lb.dy1, res ? pl.ns_ki : 1, MH, lb.z1, lb.mean1, lb.rstd1, m->LP(l, L_LN1_G), lb.dz1,
-                                       g1, res ? lb.g1b : nullptr, 1, M, H, ph, m->seed, m->offset, SITE_ATTN_OUT(l),
-                                       lb.ln_ws1, pl.ln_ws_bytes, st));
-  }
-  const bool wg_early = res && pl.wg_group >= 2 && sd != st;
+  const WgradGroup wg = copies ? wgrad_group(m, pl, l) : WgradGroup();
+  // dU = (g2 . W2) * gelu'(u): with operand copies it exists only as one (operand of the next product and of intermediate.dense's weight
+  // gradient).  Its column sums (that layer's bias gradient) start here as column partials: per 32 rows in the fp32 kernels; with operand
+  // copies only when riders of the 128 x 256 weight-gradient geometry finish them (one row of partial sums per 64 rows of dU)
+  const Act du = {lb.du, lb.dub}, dqkv = {lb.dqkv, lb.dqkvb};
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, l, L_W2, g2, du, 1, epi_du, nullptr, lb.u, nullptr,
+                   (copies ? wg.colpart : fuse_db1) ? lb.du_csum : nullptr));
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, l, L_W1, du, Act{lb.dy1, nullptr}, pl.ns_ki_b, UNITER_EPI_ADD, nullptr, lb.dz2,
+                   nullptr));
+  UCHECK_RC(ln_bwd(m, st, l, 0, lb.dy1, pl.ns_ki_b, lb.z1, lb.mean1, lb.rstd1, lb.dz1, g1, lb.ln_ws1, ph));
+  // the layer's weight gradients in precisions 2 and 3 (WgradProducts)
+  const WgradProducts wp = {{I, H, 3 * H, H}, {H, I, H, H}, {lb.dub, lb.g2b, lb.dqkvb, lb.g1b}, {lb.y1b, lb.hactb, x.b, lb.ctxb},
+                            {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)}};
+  const int wp_all[4] = {0, 1, 2, 3}, wp_early[3] = {0, 1, 3}, wp_late[1] = {2};
+  const bool wg_early = pl.prec == PREC_BF16 && pl.wg_group >= 2 && sd != st;
   if (wg_early) {
     // the three weight gradients whose operands exist now (FFN down / up, attention output: 324 whole-K tiles) start on
     // the side stream here, next to the attention backward (192 workgroups with large LDS: a quarter of the CUs idle)
     UCHECK_HIP(hipEventRecord(m->ev_mid[l], st));
     UCHECK_HIP(hipStreamWaitEvent(sd, m->ev_mid[l], 0));
-    const int Mo[3] = {I, H, H}, No[3] = {H, I, H};
-    const void* const As[3] = {lb.dub, lb.g2b, lb.g1b};
-    const void* const Bs[3] = {lb.y1b, lb.hactb, lb.ctxb};
-    float* const dWs[3] = {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_OW)};
-    {
-      ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      UCHECK_RC(gemm_bf16v2_wgrad_group(1, 3, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, 0, nullptr));
-    }
-    UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
+    UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_early, 3, 1, 0, nullptr, true));
   }
-  if (res) {
-    UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, H, lb.g1b, H, m->WB(l, L_OW), H, lb.dctx, H, 1, nullptr, 0,
-                      UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0));
-  } else if (x3) {
-    // (two k-pieces when the x3 attention backward follows: it sums the slabs while it reads them -- 126 tiles do not fill the chip)
-    UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, H, lb.g1b, m->WB(l, L_OW), H, lb.dctx, ns_dctx, nullptr, UNITER_EPI_NONE,
-                      nullptr, nullptr, nullptr));
-  } else {
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_DGRAD, st, 0, 1, M, H, H, g1, H, m->LP(l, L_OW), H, lb.dctx, H, UNITER_EPI_NONE,
-                   nullptr, nullptr, nullptr, 0, 0));
-  }
+  // (two k-pieces when the x3 attention backward follows: it sums the slabs while it reads them -- 126 tiles do not fill the chip)
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, H, l, L_OW, g1, Act{lb.dctx, nullptr}, ns_dctx, UNITER_EPI_NONE, nullptr, nullptr,
+                   nullptr));
   {
     ProfScope ps(m, UNITER_K_ATTN_BWD, st);
+    const float* mask = pl.packed ? nullptr : m->batch.attention_mask;
+    const int32_t* cu_seqlens = pl.packed ? m->batch.cu_seqlens : nullptr;
+    unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;      // attention_x3.hip's kernels (the forward pass of a saved plan left the flags)
     switch (pl.attn_bwd) {
-    case ATTN_B16X:      // (the forward pass of a saved plan left the keep flags)
-      UCHECK_RC(uniter_attn_b16x_bwd(lb.qkv, 1, pl.packed ? nullptr : m->batch.attention_mask,
-                                     pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
-                                     lb.qb_part, pa > 0.f ? lb.keepb : nullptr, lb.delta, B, L, nh, pa, st));
+    case ATTN_B16X:
+      UCHECK_RC(uniter_attn_b16x_bwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, lb.qb_part, keep_rd, lb.delta,
+                                     B, L, nh, pa, st));
       break;
     case ATTN_BF16_PRE:
-      UCHECK_RC(uniter_attn_bf16_bwd(lb.qkv, 1, pl.packed ? nullptr : m->batch.attention_mask,
-                                     pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx,
+      UCHECK_RC(uniter_attn_bf16_bwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx,
                                      nullptr /* fp32 dqkv has no reader in this mode: bias partials are fused */,
                                      lb.dqkvb, lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset,
                                      SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
       break;
-    case ATTN_X3:      // (the forward pass of a saved plan left the keep flags)
-      UCHECK_RC(uniter_attn_x3_bwd(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
-                                   pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, ns_dctx, (size_t)M * H,
-                                   nullptr, lb.dqkvb, lb.qb_part, pa > 0.f ? lb.keepb : nullptr, lb.delta, B, L, nh, pa, st));
+    case ATTN_X3:
+      UCHECK_RC(uniter_attn_x3_bwd(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, ns_dctx, MH, nullptr, lb.dqkvb, lb.qb_part, keep_rd,
+                                   lb.delta, B, L, nh, pa, st));
       break;
     case ATTN_F32_PRE_X3:      // dqkv leaves the kernel as x3 pieces only: nothing reads an fp32 copy in this mode
-      UCHECK_RC(uniter_attn_bwd_ex_x3(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
-                                      pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
+      UCHECK_RC(uniter_attn_bwd_ex_x3(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
                                       lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
                                       pl.attn_ws, pl.attn_ws_bytes, st));
       break;
     case ATTN_F32_PRE:
-      UCHECK_RC(uniter_attn_bwd_ex(lb.qkv, pl.packed ? nullptr : m->batch.attention_mask,
-                                   pl.packed ? m->batch.cu_seqlens : nullptr, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr,
+      UCHECK_RC(uniter_attn_bwd_ex(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr,
                                    lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
                                    pl.attn_ws, pl.attn_ws_bytes, st));
       break;
-    case ATTN_F32:
-      UCHECK_RC(uniter_attn_bwd(lb.qkv, m->batch.attention_mask, lb.ctx, lb.lse, lb.dctx, lb.dqkv, lb.delta, B, L,
+    case ATTN_F32:      // (never packed)
+      UCHECK_RC(uniter_attn_bwd(lb.qkv, mask, lb.ctx, lb.lse, lb.dctx, lb.dqkv, lb.delta, B, L,
                                 nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
       break;
     }
   }
-  if (res) {
-    if (!attn_b16) UCHECK_RC(cast_b(lb.dqkv, lb.dqkvb, (size_t)M * 3 * H, st));
-    UCHECK_RC(gemm_v2(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, 3 * H, lb.dqkvb, 3 * H, m->WB(l, L_QW), H, lb.dx, H, ns_dx,
-                      nullptr, 0, UNITER_EPI_ADD, nullptr, lb.dz1, 0, nullptr, 0, H));
-  } else if (x3) {
-    if (!fused_qb) UCHECK_RC(split_x3(lb.dqkv, lb.dqkvb, M, 3 * H, st));
-    UCHECK_RC(gemm_x3(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, 3 * H, lb.dqkvb, m->WB(l, L_QW), H, lb.dx, ns_dx, nullptr, UNITER_EPI_ADD,
-                      nullptr, lb.dz1, nullptr));
-  } else {
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_DGRAD, st, 0, 1, M, H, 3 * H, lb.dqkv, 3 * H, m->LP(l, L_QW), H, lb.dx, H,
-                   UNITER_EPI_ADD, nullptr, lb.dz1, nullptr, H, 0));
-  }
+  // dqkv's operand copy where the attention kernel left none: PREC_BF16 unless the kernel was a bf16 one; PREC_X3 behind uniter_attn_bwd only
+  if (pl.prec == PREC_BF16 ? !attn_b16 : pl.prec == PREC_X3 && !fused_qb) UCHECK_RC(operand_copy(pl, dqkv, M, 3 * H, st));
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, 3 * H, l, L_QW, dqkv, Act{lb.dx, nullptr}, ns_dx, UNITER_EPI_ADD, nullptr, lb.dz1,
+                   nullptr));
 
   // weight / bias gradients on the side stream (accumulate into the bound grad buffers)
   if (sd != st) {
@@ -1138,13 +1097,12 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // with riders (wgrad_group(): the default of precision 3) the column reductions below, the bias gradient of intermediate.dense and the
   // layer's share of the clip norm RIDE on the grouped weight-gradient launch -- no finalize / column-sum / sum-of-squares launches
   // on this stream
-  const bool riders_on = wg.riders;
   // LayerNorm / dense-bias gradients: the column reductions of the two row passes above, the attention backward's
   // per-sample query|key|value bias partials and (fp32 mode) the dU column partials -- ONE launch for all of them
-  if (!riders_on) {
+  if (!wg.riders) {
     const int lnp = ln_bwd_partial_rows(M);
     const float* parts[4] = {(const float*)lb.ln_ws2, (const float*)lb.ln_ws1, fused_qb ? lb.qb_part : nullptr,
-                             (!res && !x3 && fuse_db1) ? lb.du_csum : nullptr};
+                             (!copies && fuse_db1) ? lb.du_csum : nullptr};
     const int nparts[4] = {lnp, lnp, B, (M + 31) / 32};
     const size_t strides[4] = {(size_t)3 * H, (size_t)3 * H, (size_t)3 * H, (size_t)I};
     float* const outs[4][3] = {{m->LG(l, L_LN2_G), m->LG(l, L_LN2_B), m->LG(l, L_B2)},
@@ -1155,85 +1113,39 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     const int seg[4] = {H, H, 3 * H, I};
     UCHECK_RC(finalize_partials_jobs(4, parts, nparts, strides, outs, nout, seg, sd));
   }
-  if (res) {
-    const unsigned short* xb = l == 0 ? pl.embb : pl.layers[l - 1].y2b;
-    if (wg_early) {
-      const int Mo[1] = {3 * H}, No[1] = {H};
-      const void* const As[1] = {lb.dqkvb};
-      const void* const Bs[1] = {xb};
-      float* const dWs[1] = {m->LG(l, L_QW)};
-      ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      UCHECK_RC(gemm_bf16v2_wgrad_group(1, 1, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, 0, nullptr));
-    } else if (pl.wg_group) {
-      // all four weight gradients of the layer as one launch: 432 whole-K tiles for 512 workgroup slots (UNITER-base)
-      const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
-      const void* const As[4] = {lb.dub, lb.g2b, lb.dqkvb, lb.g1b};
-      const void* const Bs[4] = {lb.y1b, lb.hactb, xb, lb.ctxb};
-      float* const dWs[4] = {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)};
-      if (riders_on) {
-        uniter_x3_riders_t x;
-        memset(&x, 0, sizeof(x));
-        if (m->norm_parts) {
-          UCHECK_ARG((size_t)wg.slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
-                     wg.slots, m->norm_stride);
-          x.ssq = m->norm_parts + (size_t)l * m->norm_stride;
-        }
-        fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, wg.colpart);
-        ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-        UCHECK_RC(gemm_bf16v2_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, &x));
-      } else {
-        {
-          ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-          UCHECK_RC(gemm_bf16v2_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, nullptr));
-        }
-        UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
-      }
-    } else {
-      UCHECK_RC(wgrad_b16(m, pl, sd, H, I, M, lb.g2b, lb.hactb, m->LG(l, L_W2)));
-      UCHECK_RC(wgrad_b16(m, pl, sd, I, H, M, lb.dub, lb.y1b, m->LG(l, L_W1)));
-      UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
-      UCHECK_RC(wgrad_b16(m, pl, sd, H, H, M, lb.g1b, lb.ctxb, m->LG(l, L_OW)));
-      UCHECK_RC(wgrad_b16(m, pl, sd, 3 * H, H, M, lb.dqkvb, xb, m->LG(l, L_QW)));
-    }
-  } else if (x3) {
-    // the layer's four weight gradients as ONE persistent launch of whole-K 128 x 128 tiles on x3 operands (432 tiles for
-    // UNITER-base), no atomics; wg.max_wgs caps its grid (0 = one workgroup per CU; layer 0: the smallest grid of as many rounds)
-    const unsigned short* xb = l == 0 ? pl.embb : pl.layers[l - 1].y2b;
-    const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
-    const void* const As[4] = {lb.dub, lb.g2b, lb.dqkvb, lb.g1b};
-    const void* const Bs[4] = {lb.y1b, lb.hactb, xb, lb.ctxb};
-    float* const dWs[4] = {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)};
-    if (riders_on) {
-      // product 0 is dW1 = dU^T y1: its A operand's column sums are intermediate.dense's bias gradient
-      uniter_x3_riders_t x;
-      memset(&x, 0, sizeof(x));
+  if (wg_early) {
+    UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_late, 1, 1, 0, nullptr, false));
+  } else if (pl.prec == PREC_X3 || pl.wg_group) {
+    // all four weight gradients of the layer as ONE launch of whole-K tiles, no atomics (432 tiles for UNITER-base: for 512 workgroup
+    // slots in PREC_BF16; PREC_X3: persistent, wg.max_wgs caps its grid -- 0 = one workgroup per CU; layer 0: the smallest grid of as
+    // many rounds)
+    uniter_x3_riders_t riders;
+    memset(&riders, 0, sizeof(riders));
+    if (wg.riders) {
       if (m->norm_parts) {
         UCHECK_ARG((size_t)wg.slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
                    wg.slots, m->norm_stride);
-        x.ssq = m->norm_parts + (size_t)l * m->norm_stride;
+        riders.ssq = m->norm_parts + (size_t)l * m->norm_stride;
       }
-      fill_layer_riders(x, m, l, lb, M, B, H, fused_qb, wg.colpart);
-      ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      UCHECK_RC(gemm_x3_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, &x,
-                                    pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
-    } else {
-      {
-        ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-        UCHECK_RC(gemm_x3_wgrad_group(wg.cfg, 4, Mo, No, M, As, Bs, dWs, sd, m->wg_overwrite ? 1 : 0, wg.max_wgs, nullptr,
-                                      pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
-      }
-      UCHECK_RC(uniter_colsum_x3_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
+      fill_layer_riders(riders, m, l, lb, M, B, H, fused_qb, wg.colpart);
     }
+    UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_all, 4, wg.cfg, wg.max_wgs, wg.riders ? &riders : nullptr, !wg.riders));
+  } else if (pl.prec == PREC_BF16) {
+    UCHECK_RC(wgrad_b16(m, pl, sd, wp, 1));
+    UCHECK_RC(wgrad_b16(m, pl, sd, wp, 0));
+    UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
+    UCHECK_RC(wgrad_b16(m, pl, sd, wp, 3));
+    UCHECK_RC(wgrad_b16(m, pl, sd, wp, 2));
   } else {
     const int wb = m->wg_overwrite ? -1 : 1;      // -1: overwrite (or clear, then accumulate) -- see gemm()
     // the layer's four weight gradients as ONE persistent launch of whole-K tiles (uniter_wgrad_f32_group): layer 0 only by default
     // (UNITER_WGRAD_GROUP_F32 = 2; 0 = never, 1 = every layer: measured slower, switches.h), and only when every shape is on whole tiles
     const bool group_env = sw.wgrad_group_f32 == 1 || (sw.wgrad_group_f32 == 2 && l == 0);
     bool grouped = false;
-    if (group_env && sw.wgrad_whole == 15 && sw.wgrad_cfg == 0 && (m->precision == 0) && fuse_db1) {
+    if (group_env && sw.wgrad_whole == 15 && sw.wgrad_cfg == 0 && pl.prec == PREC_F32 && fuse_db1) {
       const int Mo[4] = {H, I, H, 3 * H}, No[4] = {I, H, H, H};
-      const float* const As[4] = {g2, lb.du, g1, lb.dqkv};
-      const float* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x};
+      const float* const As[4] = {g2.f, lb.du, g1.f, lb.dqkv};
+      const float* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x.f};
       float* const dWs[4] = {m->LG(l, L_W2), m->LG(l, L_W1), m->LG(l, L_OW), m->LG(l, L_QW)};
       ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
       const int rc = gemm_f32_wgrad_group(4, Mo, No, M, As, Bs, dWs, m->wg_overwrite ? 1 : 0, sd);
@@ -1241,14 +1153,14 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
       else if (rc != UNITER_E_SHAPE) return rc;
     }
     if (!grouped) {
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, H, I, M, g2, H, lb.hact, I, m->LG(l, L_W2), I, UNITER_EPI_NONE,
+    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, H, I, M, g2.f, H, lb.hact, I, m->LG(l, L_W2), I, UNITER_EPI_NONE,
                    nullptr, nullptr, nullptr, 0, wb));
     UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, I, H, M, lb.du, I, lb.y1, H, m->LG(l, L_W1), H, UNITER_EPI_NONE,
                    nullptr, nullptr, nullptr, 0, wb));
     if (!fuse_db1) UCHECK_RC(uniter_colsum_f32(lb.du, M, I, I, m->LG(l, L_B1), 1, pl.col_ws, pl.col_ws_bytes, sd));
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, H, H, M, g1, H, lb.ctx, H, m->LG(l, L_OW), H, UNITER_EPI_NONE,
+    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, H, H, M, g1.f, H, lb.ctx, H, m->LG(l, L_OW), H, UNITER_EPI_NONE,
                    nullptr, nullptr, nullptr, 0, wb));
-    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, 3 * H, H, M, lb.dqkv, 3 * H, x, H, m->LG(l, L_QW), H,
+    UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, sd, 1, 1, 3 * H, H, M, lb.dqkv, 3 * H, x.f, H, m->LG(l, L_QW), H,
                    UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, wb));
     }
   }
@@ -1353,12 +1265,12 @@ extern "C" int uniter_model_set_norm_partials(uniter_model_t* m, double* parts, 
 
 extern "C" int uniter_model_norm_partials_per_layer(const uniter_model_t* m) {
   if (!m) return 0;
-  if (m->precision != 2 && m->precision != 3) return 0;
+  if (!m->plan.copies()) return 0;
   // (answers for the plan of the LAST forward: its grouped launch -- very long batches of precision 2 keep stream-K --, its row count
   // as the reduction length, its workspace of the balanced walk.  An upper bound over layers: layer 1's grid, one workgroup per CU,
   // where layer 0's balanced grid fills fewer slots)
-  const WgradGroup g = wgrad_group(m, m->plan, m->precision, 1);
-  if (!g.riders || (m->precision == 2 && m->plan.mode == 0)) return 0;
+  const WgradGroup g = wgrad_group(m, m->plan, 1);
+  if (!g.riders || (m->plan.prec == PREC_BF16 && m->plan.mode == 0)) return 0;
   //  a plan whose joint length is beyond the fused query|key|value bias partials (L > uniter_attn_varlen_max_len(), or
   // UNITER_ATTN_SPLIT=0) writes that bias gradient by a separate column-sum launch BEHIND the riders' launch: its squares would reach
   // no slot.  Such a plan announces no slots at all -- the caller reduces the layer's bucket itself, as in the other precisions
@@ -1430,7 +1342,7 @@ extern "C" int uniter_model_set_precision(uniter_model_t* m, int precision) {
   UCHECK_SHAPE(precision != 2 || (m->cfg.intermediate_size % 64 == 0 && m->cfg.hidden_size % 64 == 0),
                "set_precision: the bf16-resident mode needs hidden_size and intermediate_size %% 64 == 0 (got %d, %d): every "
                "forward and input-gradient product runs on 64-deep k-tiles", m->cfg.hidden_size, m->cfg.intermediate_size);
-  m->precision = precision;
+  m->precision = (Precision)precision;
   return 0;
 }
 
