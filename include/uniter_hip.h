@@ -654,6 +654,28 @@ int uniter_adam_step_x3p(float* params, float* grads, const void* grads_bf16, fl
                          float lr, float beta1, float beta2, float eps, float weight_decay, int step, int adamw,
                          int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element,
                          int max_workgroups, void* stream);
+/* The optimizer FAMILY behind one entry point: uniter_adam_step_x3p's launch -- the same walk (pair_src / first_element), chunk flags
+ * (0 = skip, 1 / 2 = without / with weight decay, + 4 = leave the gradient), bf16 gradient payload, mirror writes (one bf16 copy or the
+ * three exact pieces at mirror_piece_stride), zero_grads and max_workgroups -- with the update rule chosen by `kind`.  Replaces, for every
+ * `--optimizer` of the reference's get_optimizer (utils/optim_utils.py:32-45), average_gradients + clip_grad_norm_ + optimizer.step +
+ * zero_grad (train_template.py:89-92,103-107).  With coef = grad_scale * min(1, max_norm / (sqrt(sumsq) * grad_scale + 1e-6)) and
+ * wd = weight_decay where the chunk's flag & 3 is 2, else 0:
+ *   kind 0  torch.optim.Adam  (utils/optim_utils.py:33-35)  = uniter_adam_step_x3p with adamw = 0   } the `adamw` argument is
+ *   kind 1  torch.optim.AdamW (utils/optim_utils.py:38-40)  = uniter_adam_step_x3p with adamw = 1   } ignored: kind decides
+ *   kind 2  torch.optim.Adamax (utils/optim_utils.py:36-37; coupled L2):
+ *             g' = g coef + wd p;  m' = beta1 m + (1 - beta1) g';  u' = max(beta2 u, |g'| + eps);
+ *             p' = p - (lr / (1 - beta1^step)) m' / u'             m = exp_avg, u = exp_avg_sq (the infinity norm lives in the second buffer)
+ *   kind 3  torch.optim.SGD with momentum, dampening 0, no Nesterov (utils/optim_utils.py:41-43; coupled L2):
+ *             g' = g coef + wd p;  b' = beta1 b + g';  p' = p - lr b'      b = exp_avg, beta1 = the momentum (0 = plain SGD)
+ *           a zero buffer gives torch's first step (buf = g') exactly.  There is NO second state: exp_avg_sq may be NULL and is neither
+ *           read nor written (24 instead of 32 bytes per parameter and step); beta2 and eps are ignored.
+ * lr / (1 - beta1^step) is formed in double on the host.  `step` counts the launches' optimizer steps (>= 1): ONE counter for every
+ * parameter, where torch keeps one per tensor.  Any other kind returns UNITER_E_ARG with a message and launches nothing. */
+int uniter_optim_step(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                      const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, int adamw,
+                      int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element,
+                      int max_workgroups, void* stream);
 int uniter_mirror_refresh_x3(const float* params_base, size_t first, size_t n, void* mirror, size_t piece_stride,
                              const int* pair_dst, void* stream);
 int uniter_adam_step_rows(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,

@@ -102,19 +102,38 @@ struct AdamArgs {
 };
 
 #define NT_LOAD(base, idx) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base) + (idx))
+// The update rule is a compile-time parameter of the step kernel: the walk, the chunk flags, the gradient widening, the non-temporal
+// accesses and the mirror writes are one skeleton (adam_kernel<RULE>), the arithmetic per element is the rule's (include/uniter_hip.h,
+// uniter_optim_step).  RULE_ADAM is torch.optim.Adam / AdamW as before (the adamw flag stays a launch argument).
+enum { RULE_ADAM = 0, RULE_ADAMAX = 1, RULE_SGD = 2 };
+template <int RULE>
 __device__ __forceinline__ void adam_update4(const AdamArgs& a, float coef, float wd, f32x4& p, const f32x4& g, f32x4& m, f32x4& v) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float gg = g[e] * coef;
     float pp = p[e];
-    if (a.adamw) pp *= 1.0f - a.lr * wd;
-    else gg += wd * pp;
-    m[e] = a.b1 * m[e] + (1.0f - a.b1) * gg;
-    v[e] = a.b2 * v[e] + (1.0f - a.b2) * gg * gg;
-    const float denom = sqrtf(v[e]) * a.inv_sqrt_bc2 + a.eps;
-    p[e] = pp - a.step_size * (m[e] / denom);
+    if constexpr (RULE == RULE_ADAM) {
+      if (a.adamw) pp *= 1.0f - a.lr * wd;
+      else gg += wd * pp;
+      m[e] = a.b1 * m[e] + (1.0f - a.b1) * gg;
+      v[e] = a.b2 * v[e] + (1.0f - a.b2) * gg * gg;
+      const float denom = sqrtf(v[e]) * a.inv_sqrt_bc2 + a.eps;
+      p[e] = pp - a.step_size * (m[e] / denom);
+    } else if constexpr (RULE == RULE_ADAMAX) {
+      // torch.optim.Adamax: v is the infinity norm u; eps inside the max, bias correction of the first moment only
+      gg += wd * pp;
+      m[e] = a.b1 * m[e] + (1.0f - a.b1) * gg;
+      v[e] = fmaxf(a.b2 * v[e], fabsf(gg) + a.eps);
+      p[e] = pp - a.step_size * (m[e] / v[e]);
+    } else {
+      // torch.optim.SGD, dampening 0, no Nesterov: m is the momentum buffer (b1 = the momentum); no second state
+      gg += wd * pp;
+      m[e] = a.b1 * m[e] + gg;
+      p[e] = pp - a.lr * m[e];
+    }
   }
 }
+template <int RULE>
 __device__ __forceinline__ void adam_store4(const AdamArgs& a, size_t i, size_t si, const f32x4& p, const f32x4& m, const f32x4& v, bool clear) {
   // the update streams 34 bytes per parameter once: non-temporal accesses, so that it does not evict the operand panels of
   // the forward kernels that share the chip with it from the L2s.  si: the item's place in the parameter buffers, i: in the mirror
@@ -133,7 +152,7 @@ __device__ __forceinline__ void adam_store4(const AdamArgs& a, size_t i, size_t 
     }
   }
   __builtin_nontemporal_store(m, reinterpret_cast<f32x4*>(a.m) + si);
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.v) + si);
+  if constexpr (RULE != RULE_SGD) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.v) + si);
   // zero_grad: only where something was written -- four of five rows of the embeddings' block (the word table away from
   // the batch's tokens) hold zeros already
   if (clear) __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f32x4*>(a.g) + si);
@@ -142,7 +161,8 @@ __device__ __forceinline__ bool any_nonzero(const f32x4& g) { return g[0] != 0.f
 
 // Two 16-byte elements per thread and iteration, all eight loads issued before the arithmetic: a grid of one or two
 // workgroups per CU (the launch that shares the chip with the next forward, see trainer.FusedAdam) still keeps
-// 32-64 KB per CU in flight.
+// 32-64 KB per CU in flight.  (RULE_SGD: six loads, a.v is never touched and may be NULL.)
+template <int RULE>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
   float coef = a.gscale;
   if (a.max_norm > 0.f && a.sumsq) {
@@ -174,19 +194,21 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     const bool no_g = a.rowmask && a.rows_want == 0;      // rows without a gradient this step: g == 0, unread
     f32x4 p0, g0 = {0.f, 0.f, 0.f, 0.f}, m0, v0, p1, g1 = g0, m1, v1;
     if (f0) {
-      p0 = NT_LOAD(a.p, si); if (!no_g) g0 = a.g16 ? widen4(a.g16, si) : NT_LOAD(a.g, si); m0 = NT_LOAD(a.m, si); v0 = NT_LOAD(a.v, si);
+      p0 = NT_LOAD(a.p, si); if (!no_g) g0 = a.g16 ? widen4(a.g16, si) : NT_LOAD(a.g, si); m0 = NT_LOAD(a.m, si);
+      if constexpr (RULE != RULE_SGD) v0 = NT_LOAD(a.v, si);
     }
     if (f1) {
-      p1 = NT_LOAD(a.p, sj); if (!no_g) g1 = a.g16 ? widen4(a.g16, sj) : NT_LOAD(a.g, sj); m1 = NT_LOAD(a.m, sj); v1 = NT_LOAD(a.v, sj);
+      p1 = NT_LOAD(a.p, sj); if (!no_g) g1 = a.g16 ? widen4(a.g16, sj) : NT_LOAD(a.g, sj); m1 = NT_LOAD(a.m, sj);
+      if constexpr (RULE != RULE_SGD) v1 = NT_LOAD(a.v, sj);
     }
     // (gradients read from the bf16 payload: the fp32 buffer holds this rank's own sums, cleared whatever the payload says)
     if (f0) {
       const bool c0 = !no_g && a.zero_grads && !(f0 & 4) && (a.g16 != nullptr || any_nonzero(g0));
-      adam_update4(a, coef, (f0 & 3) == 2 ? a.wd : 0.f, p0, g0, m0, v0); adam_store4(a, i, si, p0, m0, v0, c0);
+      adam_update4<RULE>(a, coef, (f0 & 3) == 2 ? a.wd : 0.f, p0, g0, m0, v0); adam_store4<RULE>(a, i, si, p0, m0, v0, c0);
     }
     if (f1) {
       const bool c1 = !no_g && a.zero_grads && !(f1 & 4) && (a.g16 != nullptr || any_nonzero(g1));
-      adam_update4(a, coef, (f1 & 3) == 2 ? a.wd : 0.f, p1, g1, m1, v1); adam_store4(a, j, sj, p1, m1, v1, c1);
+      adam_update4<RULE>(a, coef, (f1 & 3) == 2 ? a.wd : 0.f, p1, g1, m1, v1); adam_store4<RULE>(a, j, sj, p1, m1, v1, c1);
     }
   }
 }
@@ -284,7 +306,7 @@ extern "C" int uniter_adam_step_g16(float* params, float* grads, const void* gra
                              beta1, beta2, eps, weight_decay, step, adamw, zero_grads, mirror_bf16, 0, max_workgroups, stream);
 }
 
-static int adam_step_impl(float* params, float* grads, const void* grads_bf16, float* exp_avg,
+static int adam_step_impl(int rule, float* params, float* grads, const void* grads_bf16, float* exp_avg,
                           float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
@@ -296,7 +318,7 @@ extern "C" int uniter_adam_step_x3(float* params, float* grads, const void* grad
                                    float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                                    size_t mirror_piece_stride, int max_workgroups, void* stream) {
-  return adam_step_impl(params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
+  return adam_step_impl(RULE_ADAM, params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
                         eps, weight_decay, step, adamw, zero_grads, mirror_bf16, mirror_piece_stride, max_workgroups, nullptr, 0, 0, nullptr, 0, stream);
 }
 
@@ -311,7 +333,7 @@ extern "C" int uniter_adam_step_x3p(float* params, float* grads, const void* gra
                                     size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream) {
   UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
              "adam_step_x3p: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
-  return adam_step_impl(params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
+  return adam_step_impl(RULE_ADAM, params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
                         eps, weight_decay, step, adamw, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src,
                         (long)first_element, stream);
 }
@@ -329,19 +351,19 @@ extern "C" int uniter_adam_step_rows(float* params, float* grads, float* exp_avg
                                      float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
                                      const uint8_t* row_mask, int row_len, int rows_touched, int max_workgroups, void* stream) {
   UCHECK_ARG(row_mask && row_len > 0 && row_len % CHUNK == 0 && n % (size_t)row_len == 0, "adam_step_rows: row_len must be a multiple of 64 dividing n");
-  return adam_step_impl(params, grads, nullptr, exp_avg, exp_avg_sq, chunk_flags, n, rows_touched ? sumsq : nullptr, grad_scale,
+  return adam_step_impl(RULE_ADAM, params, grads, nullptr, exp_avg, exp_avg_sq, chunk_flags, n, rows_touched ? sumsq : nullptr, grad_scale,
                         rows_touched ? max_norm : 0.f, lr, beta1, beta2, eps, weight_decay, step, adamw, zero_grads, nullptr, 0,
                         max_workgroups, row_mask, row_len / CHUNK, rows_touched ? 1 : 0, nullptr, 0, stream);
 }
 
-static int adam_step_impl(float* params, float* grads, const void* grads_bf16, float* exp_avg,
+static int adam_step_impl(int rule, float* params, float* grads, const void* grads_bf16, float* exp_avg,
                           float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                           size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
                           const void* vsrc, long vsrc_base, void* stream) {
   UCHECK_SHAPE(mirror_piece_stride % 4 == 0 && (mirror_piece_stride == 0 || mirror_bf16), "adam_step: bad mirror piece stride");
-  UCHECK_ARG(params && grads && exp_avg && exp_avg_sq && chunk_flags, "adam_step: null pointer");
+  UCHECK_ARG(params && grads && exp_avg && (exp_avg_sq || rule == RULE_SGD) && chunk_flags, "adam_step: null pointer");
   UCHECK_SHAPE(((uintptr_t)grads_bf16 & 7) == 0, "adam_step: bf16 gradients must be 8-byte aligned");
   UCHECK_SHAPE(n % CHUNK == 0, "adam_step: n must be a multiple of 64");
   UCHECK_ARG(step >= 1, "adam_step: step must be >= 1");
@@ -366,7 +388,28 @@ static int adam_step_impl(float* params, float* grads, const void* grads_bf16, f
     const size_t full = (a.n4 + 511) / 512;
     nb = (int)(full < (size_t)max_workgroups ? (full < 1 ? 1 : full) : (size_t)max_workgroups);
   }
-  hipLaunchKernelGGL(adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  if (rule == RULE_ADAMAX) hipLaunchKernelGGL(adam_kernel<RULE_ADAMAX>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  else if (rule == RULE_SGD) hipLaunchKernelGGL(adam_kernel<RULE_SGD>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(adam_kernel<RULE_ADAM>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
+}
+
+// The optimizer family behind one entry point (include/uniter_hip.h): kind 0 / 1 = uniter_adam_step_x3p with adamw = 0 / 1, kind 2 =
+// torch.optim.Adamax, kind 3 = torch.optim.SGD with momentum beta1 (exp_avg_sq may be NULL and is neither read nor written).
+extern "C" int uniter_optim_step(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
+                                 float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
+                                 float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int step, int adamw, int zero_grads, void* mirror,
+                                 size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream) {
+  UCHECK_ARG(kind >= 0 && kind <= 3, "optim_step: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)");
+  if (kind <= 1)
+    return uniter_adam_step_x3p(params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1,
+                                beta2, eps, weight_decay, step, kind, zero_grads, mirror, mirror_piece_stride, pair_src, first_element,
+                                max_workgroups, stream);
+  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
+             "optim_step: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
+  return adam_step_impl(kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg, kind == 3 ? nullptr : exp_avg_sq,
+                        chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, step, 0, zero_grads, mirror,
+                        mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element, stream);
 }

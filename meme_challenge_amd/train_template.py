@@ -22,8 +22,9 @@ The loop itself is this package's own:
     together (barrier) before anything downstream reads those files;
   * `loss_func`: 'bce_logits' (one logit, pos_weight) is one fused kernel; 'bce' and 'ce'
     (train_template.py:66-69) are formed by torch on the model's output and backpropagate into the
-    same HIP backward; `--optimizer adamax | sgd` use torch's update on the flat buffers
-    (trainer.TorchOptimizerStep) -- the fused step is built for the recipe the reference trains with.
+    same HIP backward; every `--optimizer` of the reference (adam | adamw | adamax | sgd) runs as the fused step
+    (trainer.FusedAdam / FusedAdamax / FusedSGD: one kernel family, uniter_optim_step) with the overlap, the clip norm
+    taken during the backward pass and the weight mirror written by the update itself.
 """
 import datetime
 import json

@@ -97,22 +97,30 @@ class FusedAdam(torch.optim.Optimizer):
     one kernel launch.  ``step()`` also performs ``average_gradients`` (``grad_scale``)
     and ``clip_grad_norm_`` (``max_grad_norm``) when asked to, and zeroes the
     gradients (the reference calls ``zero_grad`` right after ``step``).
+
+    FusedAdamax and FusedSGD below are this class with another update rule (``KIND``, uniter_optim_step): everything around the
+    arithmetic -- the clip norm, the block-wise overlap with the next forward pass, lazy zeroing, the bf16 gradient payload, the
+    weight mirror -- is inherited.
     """
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False):
+    KIND = None             # None: torch.optim.Adam / AdamW through uniter_adam_step_x3p; 2 / 3: uniter_optim_step's Adamax / SGD
+    SECOND_STATE = True     # the rule keeps exp_avg_sq (Adam's second moment, Adamax's infinity norm)
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False, defaults=None):
         self.model = model
         self.store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
         named = list(model.named_parameters())
         decay = [p for n, p in named if not no_decay(n)]
         nodecay = [p for n, p in named if no_decay(n)]
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if defaults is None:
+            defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__([{'params': decay, 'weight_decay': weight_decay},
                           {'params': nodecay, 'weight_decay': 0.0}], defaults)
         self.adamw = bool(adamw)
         self.step_count = 0
         st = self.store
         self.exp_avg = torch.zeros_like(st.flat_params)
-        self.exp_avg_sq = torch.zeros_like(st.flat_params)
+        self.exp_avg_sq = torch.zeros_like(st.flat_params) if self.SECOND_STATE else None
         self._sumsq = torch.zeros(1, dtype=torch.float64, device=st.device)
         self._parts = None          # per-slice partial sums of the clip norm (data parallel: one per collective)
         # the clip norm taken during the backward pass (attach_norm_hooks): unreduced partial sums per bucket
@@ -147,7 +155,8 @@ class FusedAdam(torch.optim.Optimizer):
         # (built, bit-identical, and OFF by default: same-box A/B 9.53 ms with and without in fp32x3, 4.39 -> 4.44 ms in bf16 --
         # profiles/r06_word_rows_ab.txt: the 100 us the head of the next forward pass no longer waits for are CU-time the ahead-of-time
         # launch takes from the forward pass it runs beside, and behind the table the next forward's own first kernels bound the head)
-        self.split_word_rows = os.environ.get('UNITER_ADAM_WORD_ROWS', '0') == '1'
+        # (Adam / AdamW only: uniter_adam_step_rows knows no other rule, FusedAdamax / FusedSGD never split)
+        self.split_word_rows = self.KIND is None and os.environ.get('UNITER_ADAM_WORD_ROWS', '0') == '1'
         self._rowmask = None        # one byte per row of the table: 1 = a token of the micro-batches since the last step looks it up
         self._rows_noted = False    # every micro-batch since the last step announced its ids (none had a dense table gradient)
         self._early = None          # the rows without a gradient were updated ahead: (step_count, lr, betas, eps, wd, adamw, event)
@@ -315,6 +324,9 @@ class FusedAdam(torch.optim.Optimizer):
         forward pass, whose text branch used to wait for all of it, and streams beside this step's own forward / backward instead.
         `step()` then updates the looked-up rows only (with their gradients, clipped).  Parameters bit-identical to the one-launch
         update.  Returns True when the ahead-of-time launch was issued."""
+        if self.KIND is not None:
+            raise UniterHipError('%s: the row-split update of the word-embedding table is built for Adam / AdamW only'
+                                 % type(self).__name__)
         wt = self._word_table()
         if wt is None or self._rows_noted is not True or self._early is not None:
             return False
@@ -357,6 +369,11 @@ class FusedAdam(torch.optim.Optimizer):
             f = torch.full((n // CHUNK,), 1 if nodecay else 2, dtype=torch.uint8, device=self.store.device)
             self._flags_cache[key] = f
         return f
+
+    def _rule_args(self, group):
+        """(beta1, beta2, eps) of the launch, from a parameter group"""
+        b1, b2 = group['betas']
+        return float(b1), float(b2), float(group['eps'])
 
     def join(self):
         """Make the current stream wait for an overlapped update still running on the side stream."""
@@ -453,7 +470,7 @@ class FusedAdam(torch.optim.Optimizer):
         else:
             self._np_blocks = 0
         self.step_count += 1
-        b1, b2 = g0['betas']
+        b1, b2, eps = self._rule_args(g0)
 
         mirror = getattr(st, 'mirror', None)
         enc = self.overlap_encoder
@@ -471,25 +488,28 @@ class FusedAdam(torch.optim.Optimizer):
             # (precision 'fp32x3': its three bf16 pieces, piece p at mirror + p * numel)
             x3 = mirror is not None and getattr(st, 'mirror_pieces', 1) == 3
             dst = st.pair_src() if x3 else None       # fp32x3: the layers' weights go to the mirror in the paired-row layout (the launch walks the mirror's order)
-            check(lib.uniter_adam_step_x3p(st.flat_params.data_ptr() + off, st.flat_grads.data_ptr() + off,
-                                           (grad_bf16.data_ptr() + lo * 2) if grad_bf16 is not None else None,
-                                           self.exp_avg.data_ptr() + off, self.exp_avg_sq.data_ptr() + off,
-                                           flags.data_ptr() + lo // CHUNK, hi - lo, ptr(self._sumsq),
-                                           float(grad_scale), float(max_grad_norm or 0.0), lr, float(b1), float(b2),
-                                           float(g0['eps']), float(g0['weight_decay']), self.step_count,
-                                           int(self.adamw), int(bool(zero_grads)),
-                                           (mirror.data_ptr() + lo * 2) if mirror is not None else None,
-                                           st.numel if x3 else 0,
-                                           (dst.data_ptr() + 8 * (lo // CHUNK)) if dst is not None else None,
-                                           lo if dst is not None else 0,
-                                           max_wgs, stream_ptr),
-                  'uniter_adam_step')
+            args = (st.flat_params.data_ptr() + off, st.flat_grads.data_ptr() + off,
+                    (grad_bf16.data_ptr() + lo * 2) if grad_bf16 is not None else None,
+                    self.exp_avg.data_ptr() + off, (self.exp_avg_sq.data_ptr() + off) if self.exp_avg_sq is not None else None,
+                    flags.data_ptr() + lo // CHUNK, hi - lo, ptr(self._sumsq),
+                    float(grad_scale), float(max_grad_norm or 0.0), lr, b1, b2,
+                    eps, float(g0['weight_decay']), self.step_count,
+                    int(self.adamw), int(bool(zero_grads)),
+                    (mirror.data_ptr() + lo * 2) if mirror is not None else None,
+                    st.numel if x3 else 0,
+                    (dst.data_ptr() + 8 * (lo // CHUNK)) if dst is not None else None,
+                    lo if dst is not None else 0,
+                    max_wgs, stream_ptr)
+            if self.KIND is None:
+                check(lib.uniter_adam_step_x3p(*args), 'uniter_adam_step')
+            else:
+                check(lib.uniter_optim_step(self.KIND, *args), 'uniter_optim_step')
 
         # the word-embedding table's rows without a gradient were updated ahead (early_word_update): its launch takes the looked-up rows
         early, self._early = self._early, None
         wt = self._word_table() if early is not None else None
         if early is not None:
-            ok = (wt is not None and early[:6] == (self.step_count, lr, (float(b1), float(b2)), float(g0['eps']), float(g0['weight_decay']),
+            ok = (wt is not None and early[:6] == (self.step_count, lr, (b1, b2), eps, float(g0['weight_decay']),
                                                   bool(self.adamw)) and grad_bf16 is None)
             if not ok:
                 raise UniterHipError('FusedAdam.step: the word-embedding rows without a gradient were updated ahead (early_word_update) '
@@ -501,8 +521,8 @@ class FusedAdam(torch.optim.Optimizer):
             rf = self._row_flags(off, V * H, no_decay(name))
             check(lib.uniter_adam_step_rows(st.flat_params.data_ptr() + 4 * off, st.flat_grads.data_ptr() + 4 * off,
                                             self.exp_avg.data_ptr() + 4 * off, self.exp_avg_sq.data_ptr() + 4 * off, rf.data_ptr(),
-                                            V * H, ptr(self._sumsq), float(grad_scale), float(max_grad_norm or 0.0), lr, float(b1),
-                                            float(b2), float(g0['eps']), float(g0['weight_decay']), self.step_count, int(self.adamw),
+                                            V * H, ptr(self._sumsq), float(grad_scale), float(max_grad_norm or 0.0), lr, b1,
+                                            b2, eps, float(g0['weight_decay']), self.step_count, int(self.adamw),
                                             int(bool(zero_grads)), self._rowmask.data_ptr(), H, 1, max_wgs, stream_ptr),
                   'uniter_adam_step_rows')
 
@@ -607,10 +627,46 @@ class FusedAdam(torch.optim.Optimizer):
         self._flags_key = None
 
 
+class FusedAdamax(FusedAdam):
+    """torch.optim.Adamax (coupled L2; utils/optim_utils.py:36-37) over the flat buffers: FusedAdam's launch with the Adamax rule
+    (uniter_optim_step, kind 2).  ``exp_avg_sq`` holds the infinity norm (torch's ``exp_inf``).
+
+    The step counter is the OPTIMIZER's (``step_count``), as in FusedAdam; torch keeps one per parameter.  The two agree as long
+    as every parameter receives a gradient from the first step on; a parameter whose first gradient arrives late (a head that
+    joins multitask training at step k) gets the GLOBAL bias correction 1 - beta1^step here, torch's starts it at 1 - beta1.
+
+    No row-split update of the word-embedding table (``split_word_rows`` is False whatever UNITER_ADAM_WORD_ROWS says)."""
+
+    KIND = 2
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(model, lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=False)
+
+
+class FusedSGD(FusedAdam):
+    """torch.optim.SGD with momentum, dampening 0, no Nesterov (coupled L2; utils/optim_utils.py:41-43) over the flat buffers:
+    FusedAdam's launch with the SGD rule (uniter_optim_step, kind 3).  ``exp_avg`` is the momentum buffer -- zeros before the first
+    step, which reproduces torch's ``buf = grad`` exactly -- and there is NO second state: ``exp_avg_sq`` is None, 8 bytes per
+    parameter less than Adam in memory and in the step's traffic.  ``momentum = 0`` is plain SGD.
+
+    A parameter without a gradient in a step is skipped, momentum included, as torch skips ``grad is None``.  The rule has no step
+    counter of its own; ``step_count`` counts as in FusedAdam.  No row-split update of the word-embedding table."""
+
+    KIND = 3
+    SECOND_STATE = False
+
+    def __init__(self, model, lr, momentum=0.0, weight_decay=0.0):
+        super().__init__(model, lr, weight_decay=weight_decay, adamw=False,
+                         defaults=dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+
+    def _rule_args(self, group):
+        return float(group['momentum']), 0.0, 0.0
+
+
 class TorchOptimizerStep(object):
-    """`--optimizer adamax | sgd` (utils/optim_utils.py:36-43): the update itself is torch.optim's, on the views
-    into the flat buffers; averaging, global-norm clipping and zero_grad around it follow FusedAdam.step's
-    contract so the trainer drives both alike.  Not a fused kernel: the reference's recipe trains with Adam."""
+    """`--optimizer adamax | sgd` (utils/optim_utils.py:36-43) with torch.optim's own update on the views into the flat buffers
+    (get_optimizer(.., fused=False)); averaging, global-norm clipping and zero_grad around it follow FusedAdam.step's
+    contract so the trainer drives both alike.  Not a fused kernel: the comparison partner of FusedAdamax / FusedSGD."""
 
     def __init__(self, model, inner):
         self.store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
@@ -644,9 +700,10 @@ class TorchOptimizerStep(object):
         self.store.zero_grads()
 
 
-def get_optimizer(model, config, group_param_func=None):
+def get_optimizer(model, config, group_param_func=None, fused=True):
     """utils/optim_utils.py:9-46: two parameter groups (weight decay off for biases and LayerNorm), then the
-    optimizer by name.  adam / adamw run as the fused HIP step."""
+    optimizer by name.  All four run as the fused HIP step; fused=False runs adamax / sgd as torch.optim's own update
+    (TorchOptimizerStep)."""
     if group_param_func is not None:
         raise UniterHipError('custom parameter grouping is not supported (INTEGRATION.md: out of scope)')
     name = config['optimizer']
@@ -663,7 +720,13 @@ def get_optimizer(model, config, group_param_func=None):
         inner = torch.optim.Adamax(groups, lr=config['lr'])
     else:                            # :41-43: momentum = beta1
         inner = torch.optim.SGD(groups, lr=config['lr'], momentum=config['beta1'])
-    return TorchOptimizerStep(model, inner)
+    if not fused:
+        return TorchOptimizerStep(model, inner)
+    # the torch optimizer carries the reference's hyper-parameters (its defaults where the reference passes none)
+    g0 = inner.param_groups[0]
+    if name == 'adamax':
+        return FusedAdamax(model, lr=g0['lr'], betas=tuple(g0['betas']), eps=g0['eps'], weight_decay=g0['weight_decay'])
+    return FusedSGD(model, lr=g0['lr'], momentum=g0['momentum'], weight_decay=g0['weight_decay'])
 
 
 # --------------------------------------------------------------------------- #
@@ -769,7 +832,7 @@ class TrainStep(object):
         accum = cfg['gradient_accumulation']
         stepping = self.iters % accum == 0
         opt = self.optimizer
-        if self.grad_sync is None and isinstance(opt, FusedAdam):
+        if self.grad_sync is None and isinstance(opt, FusedAdam) and opt.split_word_rows:
             # single process: the rows of the word-embedding table this step cannot touch are updated AHEAD, beside this forward pass
             # (FusedAdam.early_word_update); with a gradient exchange the other ranks' tokens are not known here
             opt.note_tokens(batch.get('input_ids'))
