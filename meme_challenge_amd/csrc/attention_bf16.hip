@@ -22,13 +22,12 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
+#include "bf16_tile.h"
 #include "switches.h"
 #include "philox.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
 
 constexpr int D = 64;
@@ -67,12 +66,6 @@ __device__ __forceinline__ Span span_of(const Args& a, int b) {
   return s;
 }
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-
 // One [L, 64] operand on its way into LDS: the 16-byte pieces of this thread (blockDim.x = 4 Lr: four pieces of an fp32
 // source, two of a bf16 source) are ALL loaded before anything else happens -- the kernels issue the loads of every
 // operand and of their row fragments first and write LDS afterwards (piece by piece, each write waited for its own
@@ -89,11 +82,10 @@ struct StageF {       // fp32 source, rounded to bf16 on the way
     }
   }
   __device__ __forceinline__ void store_rm(u16* s, int Lr, int tid, int nthr) const {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int idx = tid + it * nthr, r = idx >> 4, c4 = idx & 15;
-      if (idx < Lr * 16) *reinterpret_cast<u32x2*>(s + r * KLD + c4 * 4) = u32x2{pack2(v[it][0], v[it][1]), pack2(v[it][2], v[it][3])};
+      if (idx < Lr * 16) *reinterpret_cast<u32x2_t*>(s + r * KLD + c4 * 4) = u32x2_t{pack2(v[it][0], v[it][1]), pack2(v[it][2], v[it][3])};
     }
   }
   __device__ __forceinline__ void store_tr(u16* s, int Lr, int tid, int nthr) const {

@@ -25,6 +25,7 @@
 // lse/delta [B, nh, L].  head_dim == 64.
 #include <stdlib.h>
 #include "common.h"
+#include "bf16_tile.h"
 #include "switches.h"
 #include "philox.h"
 
@@ -120,30 +121,28 @@ __device__ __forceinline__ void store_rowT(float* __restrict__ row, const f32x16
 
 __device__ __forceinline__ void store_rowT_bf16(unsigned short* __restrict__ row, const f32x16& a0, const f32x16& a1,
                                                 float mul, int h) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
-    bf16x4_t v0 = {(__bf16)(a0[4 * g] * mul), (__bf16)(a0[4 * g + 1] * mul), (__bf16)(a0[4 * g + 2] * mul), (__bf16)(a0[4 * g + 3] * mul)};
-    bf16x4_t v1 = {(__bf16)(a1[4 * g] * mul), (__bf16)(a1[4 * g + 1] * mul), (__bf16)(a1[4 * g + 2] * mul), (__bf16)(a1[4 * g + 3] * mul)};
-    *reinterpret_cast<bf16x4_t*>(row + 8 * g + 4 * h) = v0;
-    *reinterpret_cast<bf16x4_t*>(row + 32 + 8 * g + 4 * h) = v1;
+    bf16x4 v0 = {(__bf16)(a0[4 * g] * mul), (__bf16)(a0[4 * g + 1] * mul), (__bf16)(a0[4 * g + 2] * mul), (__bf16)(a0[4 * g + 3] * mul)};
+    bf16x4 v1 = {(__bf16)(a1[4 * g] * mul), (__bf16)(a1[4 * g + 1] * mul), (__bf16)(a1[4 * g + 2] * mul), (__bf16)(a1[4 * g + 3] * mul)};
+    *reinterpret_cast<bf16x4*>(row + 8 * g + 4 * h) = v0;
+    *reinterpret_cast<bf16x4*>(row + 32 + 8 * g + 4 * h) = v1;
   }
 }
 
 // the three bf16 pieces of the row (x = x1 + x2 + x3 exactly, round-to-nearest residuals) at row, row + ps, row + 2 ps
 __device__ __forceinline__ void store_rowT_x3(unsigned short* __restrict__ row, int ps, const f32x16& a0, const f32x16& a1,
                                               float mul, int h) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     f32x4 r0 = {a0[4 * g] * mul, a0[4 * g + 1] * mul, a0[4 * g + 2] * mul, a0[4 * g + 3] * mul};
     f32x4 r1 = {a1[4 * g] * mul, a1[4 * g + 1] * mul, a1[4 * g + 2] * mul, a1[4 * g + 3] * mul};
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-      const bf16x4_t v0 = {(__bf16)r0[0], (__bf16)r0[1], (__bf16)r0[2], (__bf16)r0[3]};
-      const bf16x4_t v1 = {(__bf16)r1[0], (__bf16)r1[1], (__bf16)r1[2], (__bf16)r1[3]};
-      *reinterpret_cast<bf16x4_t*>(row + p * ps + 8 * g + 4 * h) = v0;
-      *reinterpret_cast<bf16x4_t*>(row + p * ps + 32 + 8 * g + 4 * h) = v1;
+      const bf16x4 v0 = {(__bf16)r0[0], (__bf16)r0[1], (__bf16)r0[2], (__bf16)r0[3]};
+      const bf16x4 v1 = {(__bf16)r1[0], (__bf16)r1[1], (__bf16)r1[2], (__bf16)r1[3]};
+      *reinterpret_cast<bf16x4*>(row + p * ps + 8 * g + 4 * h) = v0;
+      *reinterpret_cast<bf16x4*>(row + p * ps + 32 + 8 * g + 4 * h) = v1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) { r0[e] -= (float)v0[e]; r1[e] -= (float)v1[e]; }
     }

@@ -29,15 +29,13 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "bf16_tile.h"
 #include "switches.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
 typedef unsigned char u8;
 
@@ -73,35 +71,20 @@ __device__ __forceinline__ Span span_of(const Args& a, int b) {
   return s;
 }
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};      // v_cvt_pk_bf16_f32: round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bflo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bfhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-// the three bf16 pieces of two fp32 values (exact: every residual is representable)
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& w1, unsigned& w2, unsigned& w3) {
-  w1 = pack2(x0, x1);
-  float r0 = x0 - bflo(w1), r1 = x1 - bfhi(w1);
-  w2 = pack2(r0, r1);
-  r0 -= bflo(w2); r1 -= bfhi(w2);
-  w3 = pack2(r0, r1);
-}
 // pieces of 8 values as MFMA fragments (NP = 3: the exact split; NP = 1: rounded to bf16, the bf16 mode's operands)
 template <int NP>
 __device__ __forceinline__ void split8(const f32x4& x, const f32x4& y, bf16x8 (&f)[NP]) {
   if constexpr (NP == 1) {
-    f[0] = __builtin_bit_cast(bf16x8, u32x4{pack2(x[0], x[1]), pack2(x[2], x[3]), pack2(y[0], y[1]), pack2(y[2], y[3])});
+    f[0] = __builtin_bit_cast(bf16x8, u32x4_t{pack2(x[0], x[1]), pack2(x[2], x[3]), pack2(y[0], y[1]), pack2(y[2], y[3])});
     return;
   }
   unsigned w[3][4];
-  split2(x[0], x[1], w[0][0], w[1][0], w[2][0]);
-  split2(x[2], x[3], w[0][1], w[1][1], w[2][1]);
-  split2(y[0], y[1], w[0][2], w[1][2], w[2][2]);
-  split2(y[2], y[3], w[0][3], w[1][3], w[2][3]);
+  split3_pair(x[0], x[1], w[0][0], w[1][0], w[2][0]);
+  split3_pair(x[2], x[3], w[0][1], w[1][1], w[2][1]);
+  split3_pair(y[0], y[1], w[0][2], w[1][2], w[2][2]);
+  split3_pair(y[2], y[3], w[0][3], w[1][3], w[2][3]);
 #pragma unroll
-  for (int p = 0; p < NP; ++p) f[p] = __builtin_bit_cast(bf16x8, u32x4{w[p][0], w[p][1], w[p][2], w[p][3]});
+  for (int p = 0; p < NP; ++p) f[p] = __builtin_bit_cast(bf16x8, u32x4_t{w[p][0], w[p][1], w[p][2], w[p][3]});
 }
 
 // chunk swizzle of the images (header)
@@ -146,14 +129,14 @@ struct Stage {
         if (idx < Lr * 16) {
           u8* p = img + r * ROWB + 16 * ((c4 >> 1) ^ swz(r)) + 8 * (c4 & 1);
           if constexpr (NP == 1) {
-            *reinterpret_cast<u32x2*>(p) = u32x2{pack2(v[it][0], v[it][1]), pack2(v[it][2], v[it][3])};
+            *reinterpret_cast<u32x2_t*>(p) = u32x2_t{pack2(v[it][0], v[it][1]), pack2(v[it][2], v[it][3])};
           } else {
             unsigned a1, a2, a3, b1, b2, b3;
-            split2(v[it][0], v[it][1], a1, a2, a3);
-            split2(v[it][2], v[it][3], b1, b2, b3);
-            *reinterpret_cast<u32x2*>(p) = u32x2{a1, b1};
-            *reinterpret_cast<u32x2*>(p + IMG) = u32x2{a2, b2};
-            *reinterpret_cast<u32x2*>(p + 2 * IMG) = u32x2{a3, b3};
+            split3_pair(v[it][0], v[it][1], a1, a2, a3);
+            split3_pair(v[it][2], v[it][3], b1, b2, b3);
+            *reinterpret_cast<u32x2_t*>(p) = u32x2_t{a1, b1};
+            *reinterpret_cast<u32x2_t*>(p + IMG) = u32x2_t{a2, b2};
+            *reinterpret_cast<u32x2_t*>(p + 2 * IMG) = u32x2_t{a3, b3};
           }
         }
       }
@@ -166,15 +149,15 @@ struct Stage {
 // words per four values, no vector work on the way into the images.  Run over a buffer 1.5 x the fp32 one (tests/tools/attn_x3_lab.py);
 // the values are meaningless, the instruction and byte counts are those of the real thing.
 struct StagePieces {
-  u32x2 w[4][3];
+  u32x2_t w[4][3];
   __device__ __forceinline__ void load(const u16* __restrict__ base, int ld, int L, int Lr, int tid, int nthr) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int idx = tid + it * nthr, r = idx >> 4, c4 = idx & 15;
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
-        w[it][p] = u32x2{0u, 0u};
-        if (idx < Lr * 16 && r < L) w[it][p] = *reinterpret_cast<const u32x2*>(base + ((size_t)r * 3 + p) * ld + c4 * 4);
+        w[it][p] = u32x2_t{0u, 0u};
+        if (idx < Lr * 16 && r < L) w[it][p] = *reinterpret_cast<const u32x2_t*>(base + ((size_t)r * 3 + p) * ld + c4 * 4);
       }
     }
   }
@@ -185,7 +168,7 @@ struct StagePieces {
       if (idx < Lr * 16) {
         u8* q = img + r * ROWB + 16 * ((c4 >> 1) ^ swz(r)) + 8 * (c4 & 1);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2*>(q + p * IMG) = w[it][p];
+        for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(q + p * IMG) = w[it][p];
       }
     }
   }
@@ -313,17 +296,17 @@ __device__ __forceinline__ void store_row(bool valid, float* __restrict__ row, u
         wa[0][0] = pack2(v[db][0], v[db][1]); wa[0][1] = pack2(v[db][2], v[db][3]);
         wb[0][0] = pack2(v[db + 1][0], v[db + 1][1]); wb[0][1] = pack2(v[db + 1][2], v[db + 1][3]);
       } else {
-        split2(v[db][0], v[db][1], wa[0][0], wa[1][0], wa[2][0]);
-        split2(v[db][2], v[db][3], wa[0][1], wa[1][1], wa[2][1]);
-        split2(v[db + 1][0], v[db + 1][1], wb[0][0], wb[1][0], wb[2][0]);
-        split2(v[db + 1][2], v[db + 1][3], wb[0][1], wb[1][1], wb[2][1]);
+        split3_pair(v[db][0], v[db][1], wa[0][0], wa[1][0], wa[2][0]);
+        split3_pair(v[db][2], v[db][3], wa[0][1], wa[1][1], wa[2][1]);
+        split3_pair(v[db + 1][0], v[db + 1][1], wb[0][0], wb[1][0], wb[2][0]);
+        split3_pair(v[db + 1][2], v[db + 1][3], wb[0][1], wb[1][1], wb[2][1]);
       }
       u16* dst = row_x3 + (db + (g & 1)) * 16 + 8 * (g >> 1);
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const auto r0 = __builtin_amdgcn_permlane16_swap(wa[p][0], wb[p][0], false, false);
         const auto r1 = __builtin_amdgcn_permlane16_swap(wa[p][1], wb[p][1], false, false);
-        if (valid) *reinterpret_cast<u32x4*>(dst + p * ps) = u32x4{r0[0], r1[0], r0[1], r1[1]};
+        if (valid) *reinterpret_cast<u32x4_t*>(dst + p * ps) = u32x4_t{r0[0], r1[0], r0[1], r1[1]};
       }
     }
   }

@@ -14,6 +14,7 @@
 // fast shape, MI355X_MICROARCH.md "Global float atomics"); affine / type grads use
 // deterministic two-stage column reductions.
 #include "common.h"
+#include "gemm_internal.h"
 #include "philox.h"
 #include "rowops.h"
 

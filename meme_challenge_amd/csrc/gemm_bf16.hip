@@ -17,13 +17,11 @@
 // identical for all three layouts and no transposed LDS read is needed.
 #include <stdlib.h>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 
 struct GemmArgsB {
   int M, N, K;
@@ -51,21 +49,6 @@ __device__ __forceinline__ void buf_st_f32(float v, __amdgpu_buffer_rsrc_t r, in
 
 constexpr int BKB = 64;            // k-tile depth
 constexpr int LDB16 = 72;          // LDS row stride in bf16 elements (144 B)
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-
-__device__ __forceinline__ void tile_coords_b(int t, int tiles_m, int tiles_n, int band_h, int& tm, int& tn) {
-  const int full = band_h * tiles_n;
-  const int band = t / full;
-  const int rem = t - band * full;
-  const int bh = min(band_h, tiles_m - band * band_h);
-  tn = rem / bh;
-  tm = band * band_h + (rem - tn * bh);
-}
 
 // per-thread byte offsets of the float4 loads of one tile (k0 = 0)
 template <int R, bool KM>
@@ -101,7 +84,7 @@ __device__ __forceinline__ void tile_store_b(const f32x4 (&reg)[R / 16], unsigne
     const int c4 = tid & 15, rr = tid >> 4;
 #pragma unroll
     for (int p = 0; p < R / 16; ++p) {
-      u32x2_t v = {pack_bf16(reg[p][0], reg[p][1]), pack_bf16(reg[p][2], reg[p][3])};
+      u32x2_t v = {pack2(reg[p][0], reg[p][1]), pack2(reg[p][2], reg[p][3])};
       *reinterpret_cast<u32x2_t*>(s + (rr + 16 * p) * LDB16 + c4 * 4) = v;
     }
   } else {
@@ -111,7 +94,7 @@ __device__ __forceinline__ void tile_store_b(const f32x4 (&reg)[R / 16], unsigne
       const int c4 = ((id >> 7) << 2) | (id & 3), kp = (id >> 2) & 31;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        *reinterpret_cast<unsigned*>(s + (c4 * 4 + e) * LDB16 + 2 * kp) = pack_bf16(reg[2 * p][e], reg[2 * p + 1][e]);
+        *reinterpret_cast<unsigned*>(s + (c4 * 4 + e) * LDB16 + 2 * kp) = pack2(reg[2 * p][e], reg[2 * p + 1][e]);
     }
   }
 }
@@ -277,7 +260,7 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
   StB sb;
   {
     int tmi, tni;
-    tile_coords_b(chunk0 + lt, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
+    tile_coords(chunk0 + lt, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
     sa.offsets(g.lda, tmi * BM, tid);
     sb.offsets(g.ldb, tni * BN, tid);
   }
@@ -292,7 +275,7 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
         lk = 0; lt += t_step;                                                            \
         if (loaded < total_units) {                                                      \
           int tmi_, tni_;                                                                \
-          tile_coords_b(chunk0 + lt, g.tiles_m, g.tiles_n, g.band_h, tmi_, tni_);        \
+          tile_coords(chunk0 + lt, g.tiles_m, g.tiles_n, g.band_h, tmi_, tni_);        \
           sa.offsets(g.lda, tmi_ * BM, tid);                                             \
           sb.offsets(g.ldb, tni_ * BN, tid);                                             \
         }                                                                                \
@@ -314,7 +297,7 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
 
   int ct = t_first, ck = k_first;
   int tmi0, tni0;
-  tile_coords_b(chunk0 + ct, g.tiles_m, g.tiles_n, g.band_h, tmi0, tni0);
+  tile_coords(chunk0 + ct, g.tiles_m, g.tiles_n, g.band_h, tmi0, tni0);
   int m0 = tmi0 * BM, n0 = tni0 * BN;
 
   f32x16 acc[TM][TN];
@@ -341,7 +324,6 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
 #define AUXV(rr) (AUXPF ? auxv[rr] : buf_ld_f32(rsI, voX, (((rr) & 3) + 8 * ((rr) >> 2)) * stX))
 #define EPILOGUE_B()                                                                                    \
   {                                                                                                     \
-    constexpr int OOB = 0x7ffffff0;                                                                     \
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, g.C ? g.M * g.ldc * 4 : 0, 0x00020000); \
     const __amdgpu_buffer_rsrc_t rsCb = __builtin_amdgcn_make_buffer_rsrc(g.Cb, 0, g.Cb ? g.M * g.ldcb * 2 : 0, 0x00020000); \
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(                                \
@@ -474,7 +456,7 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
       EPILOGUE_B();                                                                                     \
       ck = 0; ct += t_step;                                                                             \
       if (more) {                                                                                       \
-        tile_coords_b(chunk0 + ct, g.tiles_m, g.tiles_n, g.band_h, tmi0, tni0);                         \
+        tile_coords(chunk0 + ct, g.tiles_m, g.tiles_n, g.band_h, tmi0, tni0);                         \
         m0 = tmi0 * BM; n0 = tni0 * BN;                                                                 \
       }                                                                                                 \
     }                                                                                                   \
@@ -548,7 +530,7 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
                                                         size_t n4) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
-    u32x2_t o = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+    u32x2_t o = {pack2(v[0], v[1]), pack2(v[2], v[3])};
     reinterpret_cast<u32x2_t*>(dst)[i] = o;
   }
 }
@@ -616,10 +598,6 @@ extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* str
   UCHECK_LAUNCH();
   return 0;
 }
-
-int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
-                 const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                 const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
 
 // Same contract as gemm_f32_run, contraction on the bf16 matrix pipe.  Shapes the bf16 kernel does
 // not cover (K % 64 != 0, offsets beyond 31 bits) run on the exact fp32 kernel instead.

@@ -9,14 +9,7 @@
 // Replaces cuBLAS behind nn.Linear forward and input-gradient products of model/layer.py:76-78 (query / key /
 // value), :112 (attention output), :140 (intermediate) and :153 (output) in the bf16 mode.
 //
-// LDS images (per operand and stage, R = rows of the tile, 64 k per k-tile, no padding: LDS-DMA writes
-// 1 KiB = 64 lanes x 16 B contiguously, so the swizzle sits on the per-lane SOURCE address and on the read):
-//   k-contiguous operand ([rows][K] in memory): [R][64] bf16, 128-B rows, 16-B chunk c of row r stored at
-//     chunk c ^ ((r >> 1) & 7): 16 consecutive rows x one k-chunk cover all 64 banks (ds_read_b128).
-//   k-major operand ([K][cols] in memory: the weight of an input-gradient product): [64 k][R] bf16 as
-//     256-B segments, chunk c (0..15) of k-row k stored at c ^ (((k & 3) << 2) | ((k >> 2) & 3)); the
-//     MFMA operand is gathered by ds_read_b64_tr_b16 (4 k-rows x 16 columns per 16-lane group), whose 32
-//     lanes per half then touch 32 distinct 8-byte units.
+// LDS images (per operand and stage, 64 k per k-tile): bf16_tile.h, Dma.
 //
 // Split-K: a tile's k-range may be cut into `nsplit` pieces computed by different workgroups; piece s
 // stores its fp32 partial tile to C + s * c_split_stride (piece 0 applies the epilogue); the CONSUMER
@@ -24,17 +17,15 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 #include "riders.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef short short8v __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct GArgsD {
   int M, N, K;
@@ -55,66 +46,12 @@ struct GArgsD {
 };
 
 constexpr int KT = 64;                 // k-tile depth
-constexpr int OOB = 0x7ffffff0;        // buffer offset beyond every descriptor: load returns 0, store is dropped
-
-__device__ __forceinline__ void tile_coords_d(int t, int tiles_m, int tiles_n, int band_h, int& tm, int& tn) {
-  const int full = band_h * tiles_n;
-  const int band = t / full;
-  const int rem = t - band * full;
-  const int bh = min(band_h, tiles_m - band * band_h);
-  tn = rem / bh;
-  tm = band * band_h + (rem - tn * bh);
-}
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-// ---- LDS-DMA fill of one operand image --------------------------------------------------------------
-template <int R, bool KM, int NW>
-struct Dma {
-  static constexpr int NI = R / 8 / NW;          // 1-KiB wave-instructions per wave and k-tile
-  static_assert(NI >= 1 && NI * 8 * NW == R, "tile rows must be a multiple of 8 x waves");
-  static_assert(!KM || R == 128 || R == 256, "k-major tiles are 128 or 256 wide");
-  int voff[NI];
-  static __device__ __forceinline__ int kstep(int ld) { return (KM ? KT * ld : KT) * 2; }
-  __device__ __forceinline__ void offsets(int ld, int rc0, int wave, int lane) {
-#pragma unroll
-    for (int t = 0; t < NI; ++t) {
-      const int j = wave + NW * t;
-      if constexpr (!KM) {
-        const int row = 8 * j + (lane >> 3);
-        const int c = (lane & 7) ^ ((4 * (j & 1) + (lane >> 4)) & 7);
-        voff[t] = (rc0 + row) * ld * 2 + c * 16;
-      } else if constexpr (R == 128) {
-        const int k = 4 * j + (lane >> 4);
-        const int c = (lane & 15) ^ (((lane >> 4) << 2) | (j & 3));
-        voff[t] = (k * ld + rc0) * 2 + c * 16;
-      } else {
-        const int k = 2 * j + (lane >> 5);
-        const int sw = (((2 * (j & 1) + (lane >> 5)) & 3) << 2) | ((j >> 1) & 3);
-        const int c = (lane & 15) ^ sw;
-        voff[t] = (k * ld + rc0) * 2 + ((lane >> 4) & 1) * 256 + c * 16;
-      }
-    }
-  }
-  __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rs, unsigned char* img, int soff, int wave) const {
-#pragma unroll
-    for (int t = 0; t < NI; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(img + (wave + NW * t) * 1024), 16, voff[t], soff, 0, 0);
-  }
-};
 
 // ---- MFMA operand fragments ---------------------------------------------------------------------------
 // 8 consecutive k (k16-step ks, lane half h) of row / column 32 blk + i5 of the operand image.
 // k-contiguous images are read by plain 16-byte LDS loads (the compiler schedules and counts them).
-// k-major images are read by ds_read_b64_tr_b16 issued as INLINE ASSEMBLY with hand-counted lgkmcnt waits:
-// behind the builtin form of that read hipcc (ROCm 7.2) waits s_waitcnt vmcnt(0) whenever an LDS-DMA is in
-// flight, which would drain the two-tile prefetch every k-tile (checked in the .s).
+// k-major images are read by ds_read_b64_tr_b16 as inline assembly with hand-counted lgkmcnt waits (bf16_tile.h says why).
+// Differs from Frag3 / Frag16 / FragP: 32-row blocks of a 64-deep image, four k16-steps, two blocks per wave.
 template <int R, bool KM>
 struct Frag {
   int o0, o1;         // k-contiguous: row byte offset, swizzle key
@@ -147,26 +84,17 @@ struct Frag {
   // asm form of read() for the kernels whose other operand is k-major: one kind of LDS read per loop, all counted by hand
   template <int KS, int T>
   __device__ __forceinline__ void read_asm(unsigned img_addr, u32x4_t& out) const {
-#if defined(__HIP_DEVICE_COMPILE__)      // the host pass parses this body too and knows no "v" constraint
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(out) : "v"(img_addr + ka[KS]), "n"(T * 32 * 128) : "memory");
-#endif
+    lds_read_b128<T * 32 * 128>(out, img_addr + ka[KS]);
   }
   // raw halves of the fragment of block t, k16-step KS; complete only after the caller's lgkmcnt wait
   template <int KS>
   __device__ __forceinline__ void read_tr(unsigned img_addr, int t, u32x2_t& lo, u32x2_t& hi) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(img_addr + tr[t][0]), "n"(KS * 16 * R * 2) : "memory");
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(img_addr + tr[t][1]), "n"(KS * 16 * R * 2) : "memory");
-#endif
+    lds_read_tr<KS * 16 * R * 2>(lo, img_addr + tr[t][0]);
+    lds_read_tr<KS * 16 * R * 2>(hi, img_addr + tr[t][1]);
   }
 };
 
-__device__ __forceinline__ bf16x8 join_halves(u32x2_t lo, u32x2_t hi) {
-  const u32x4_t v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// differs from bf16_tile.h's lgkm_wait + tie: the wait names its destinations itself
 template <int N>
 __device__ __forceinline__ void wait_lgkm(u32x2_t& a, u32x2_t& b, u32x2_t& c, u32x2_t& d, u32x4_t& e, u32x4_t& f) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -183,17 +111,6 @@ __device__ __forceinline__ void wait_lgkm8(u32x2_t& a, u32x2_t& b, u32x2_t& c, u
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N) : "memory");
 #endif
-}
-
-// work item of this workgroup, XCD-chunked (blocks b and b + 8 share an XCD's L2: consecutive items go to one XCD);
-// -1 for the padding blocks of the grid.  round > 0: the items a workgroup of a grid SMALLER than the work takes after
-// its first one (the grouped weight-gradient launch on a capped grid), still inside its XCD's chunk
-__device__ __forceinline__ int xcd_work_item(int nwork, int round = 0) {
-  const int xcd = blockIdx.x & 7, idx = (blockIdx.x >> 3) + round * (int)(gridDim.x >> 3);
-  const int q8 = nwork >> 3, r8 = nwork & 7;
-  const int chunk0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int chunk_n = q8 + (xcd < r8 ? 1 : 0);
-  return idx < chunk_n ? chunk0 + idx : -1;
 }
 
 // one work item w = (tile, k-piece) of the product g
@@ -217,7 +134,7 @@ __device__ __forceinline__ void gemm_dma_tile(const GArgsD& g, const int w, unsi
 
   const int tile = w / g.nsplit, piece = w - tile * g.nsplit;
   int tmi, tni;
-  tile_coords_d(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
+  tile_coords(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
   const int m0 = tmi * BM, n0 = tni * BN;
   const int nk = (g.K + KT - 1) / KT;
   const int kb = (int)((long)nk * piece / g.nsplit), ke = (g.dbg & 2) ? kb : (int)((long)nk * (piece + 1) / g.nsplit);
@@ -226,12 +143,12 @@ __device__ __forceinline__ void gemm_dma_tile(const GArgsD& g, const int w, unsi
       const_cast<void*>(g.A), 0, (AKM ? g.K : g.M) * g.lda * 2, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(g.B), 0, (BKM ? g.K : g.N) * g.ldb * 2, 0x00020000);
-  Dma<BM, AKM, NW> da;
-  Dma<BN, BKM, NW> db;
+  Dma<BM, AKM, NW, KT> da;
+  Dma<BN, BKM, NW, KT> db;
   da.offsets(g.lda, m0, wave, lane);
   db.offsets(g.ldb, n0, wave, lane);
-  const int kstepA = Dma<BM, AKM, NW>::kstep(g.lda), kstepB = Dma<BN, BKM, NW>::kstep(g.ldb);
-  constexpr int NDMA = Dma<BM, AKM, NW>::NI + Dma<BN, BKM, NW>::NI;
+  const int kstepA = Dma<BM, AKM, NW, KT>::kstep(g.lda), kstepB = Dma<BN, BKM, NW, KT>::kstep(g.ldb);
+  constexpr int NDMA = Dma<BM, AKM, NW, KT>::NI + Dma<BN, BKM, NW, KT>::NI;
 
   Frag<BM, AKM> fa;
   Frag<BN, BKM> fb;
@@ -670,14 +587,6 @@ int dispatch_epi(int cfg, const GArgsD& g, hipStream_t st) {
 
 }  // namespace
 
-// the persistent loader / compute kernels (gemm_bf16_p.hip, round 6): cfg 6 = 128 x 128 tiles, 7 = 128 x 256, 8 = 128 x 192
-int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                 float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue, const float* bias,
-                 const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16, int ld_aux, float* colpart, void* stream);
-int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B, float* const* dW,
-                         void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders);
-int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs);
-
 // cfg: 1 = 128x128 (2 stages), 2 = 128x256, 3 = 256x128, 4 = 128x128 (3 stages), 5 = 64x128 (2 waves); 0 = choose;
 // 6 / 7 / 8 = the persistent loader / compute kernels of gemm_bf16_p.hip (128 x 128 / 128 x 256 / 128 x 192 tiles).
 // beta = 1: C += A.B through fp32 atomics (lane = column orientation; no epilogue, no bf16 output).
@@ -730,13 +639,13 @@ int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int 
 // dW_p[M_p, N_p] += A_p^T B_p for up to four products of one reduction length K (A_p [K, M_p], B_p [K, N_p] bf16,
 // dW_p fp32 with leading dimension N_p), one launch; cfg 1 = two LDS stages (two workgroups per CU), 4 = three.
 // workgroups of the grouped launch over `total` tiles: a multiple of 8, capped (max_wgs > 0: by the caller; else
-// UNITER_WGRAD_GROUP_WGS, default 256 = one workgroup per CU walking its tiles: switches.h)
-int gemm_chip_cus();
+// UNITER_WGRAD_GROUP_WGS, default 256 = one workgroup per CU walking its tiles: switches.h).  Not persistent_grid
+// (gemm_internal.h): the default cap is the switch, not the chip's CUs, and a cap below 8 leaves the grid uncapped
 static int wgrad_group_grid(int total, int max_wgs) {
   int grid = (total + 7) / 8 * 8;
   int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : uniter_switches().wgrad_group_wgs;
   if (g_uniter_cu_reserve > 0 && cap >= 8) {              // CUs left to the data-parallel exchange's kernels (common.h)
-    const int room = (gemm_chip_cus() - g_uniter_cu_reserve) / 8 * 8;      // (the device's CU count: gemm_split3.hip)
+    const int room = (gemm_chip_cus() - g_uniter_cu_reserve) / 8 * 8;
     if (room >= 8 && cap > room) cap = room;
   }
   if (cap >= 8 && grid > cap) grid = cap;

@@ -17,30 +17,23 @@
 // Replaces cuBLAS behind nn.Linear forward, input-gradient and (grouped per layer) weight-gradient products of
 // model/layer.py:76-78 (query / key / value), :112 (attention output), :140 (intermediate) and :153 (output) in the bf16 mode.
 //
-// LDS images per operand and stage (64-deep k-tiles, as gemm_bf16_dma.hip):
-//   k-contiguous ([rows][K]): [R][64] bf16, 128-B rows, 16-B chunk c of row r at c ^ ((r >> 1) & 7) -- conflict-free for the
-//     16x16x32 fragment read (lane = row l & 15, k-octet 4 s + (l >> 4) of step s) as well: every ds_read_b128 lane group holds
-//     8 rows of one k-octet and the 8 complementary rows of the next, whose chunk numbers cover 0..7 in each row parity.
-//   k-major ([K][cols]): 256-B segments, chunk c of k-row k at c ^ (((k & 3) << 2) | ((k >> 2) & 3)), gathered by
-//     ds_read_b64_tr_b16; the 64-deep image is two 32-deep images of gemm_split3.hip behind each other.
+// LDS images per operand and stage (64-deep k-tiles): bf16_tile.h, Dma.
+//   k-contiguous: the chunk swizzle c ^ ((r >> 1) & 7) is conflict-free for the 16x16x32 fragment read (lane = row l & 15, k-octet
+//     4 s + (l >> 4) of step s) as well: every ds_read_b128 lane group holds 8 rows of one k-octet and the 8 complementary rows of
+//     the next, whose chunk numbers cover 0..7 in each row parity.
+//   k-major: the 64-deep image is two 32-deep images of gemm_split3.hip behind each other.
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "riders.h"
-
-int gemm_chip_cus();      // gemm_split3.hip: CUs of the current device, a multiple of 8
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int KT = 64;                 // k-tile depth: two 32-deep MFMA steps
-#define OOB 0x7ffffff0                 /* buffer offset beyond every descriptor: load returns 0, store is dropped */
 
 struct P1Args {
   int M, N, K;
@@ -67,105 +60,8 @@ struct P1Group {
 
 enum { P1_NONE = 0, P1_BIAS = 1, P1_ADD = 4, P1_BIAS_GELU_D = 5, P1_MUL = 6 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-__device__ __forceinline__ void tile_coords_p(int t, int tiles_m, int tiles_n, int band_h, int& tm, int& tn) {
-  const int full = band_h * tiles_n;
-  const int band = t / full;
-  const int rem = t - band * full;
-  const int bh = min(band_h, tiles_m - band * band_h);
-  tn = rem / bh;
-  tm = band * band_h + (rem - tn * bh);
-}
-
-__device__ __forceinline__ unsigned pack2p(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};      // v_cvt_pk_bf16_f32: round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf_lo_p(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf_hi_p(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-// work item of this workgroup, XCD-chunked (blocks b and b + 8 share an XCD's L2)
-__device__ __forceinline__ int xcd_work_item_p(int nwork, int round) {
-  const int xcd = blockIdx.x & 7, idx = (blockIdx.x >> 3) + round * (int)(gridDim.x >> 3);
-  const int q8 = nwork >> 3, r8 = nwork & 7;
-  const int chunk0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int chunk_n = q8 + (xcd < r8 ? 1 : 0);
-  return idx < chunk_n ? chunk0 + idx : -1;
-}
-
-// ---- LDS-DMA fill of one operand image (the layouts of gemm_bf16_dma.hip) ---------------------------------------------
-template <int R, bool KM, int NW>
-struct DmaP {
-  static constexpr int NI = R / 8 / NW;          // 1-KiB wave-instructions per loader wave and k-tile
-  static_assert(NI >= 1 && NI * 8 * NW == R, "tile rows must be a multiple of 8 x loader waves");
-  static_assert(!KM || R == 128 || R == 256, "k-major tiles are 128 or 256 wide");
-  int voff[NI];
-  static __device__ __forceinline__ int kstep(int ld) { return (KM ? KT * ld : KT) * 2; }
-  __device__ __forceinline__ void offsets(int ld, int rc0, int wave, int lane) {
-#pragma unroll
-    for (int t = 0; t < NI; ++t) {
-      const int j = wave + NW * t;
-      if constexpr (!KM) {
-        // eight rows x one 128-byte line per instruction: the eight lanes of a row fetch the whole line
-        const int row = 8 * j + (lane >> 3);
-        const int c = (lane & 7) ^ ((4 * (j & 1) + (lane >> 4)) & 7);
-        voff[t] = (rc0 + row) * ld * 2 + c * 16;
-      } else if constexpr (R == 128) {
-        const int k = 4 * j + (lane >> 4);
-        const int c = (lane & 15) ^ (((lane >> 4) << 2) | (j & 3));
-        voff[t] = (k * ld + rc0) * 2 + c * 16;
-      } else {
-        const int k = 2 * j + (lane >> 5);
-        const int sw = (((2 * (j & 1) + (lane >> 5)) & 3) << 2) | ((j >> 1) & 3);
-        const int c = (lane & 15) ^ sw;
-        voff[t] = (k * ld + rc0) * 2 + ((lane >> 4) & 1) * 256 + c * 16;
-      }
-    }
-  }
-  template <int T>
-  __device__ __forceinline__ void issue1(__amdgpu_buffer_rsrc_t rs, unsigned char* img, int soff, int wave) const {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(img + (wave + NW * T) * 1024), 16, voff[T], soff, 0, 0);
-  }
-};
-
-template <int OFF>
-__device__ __forceinline__ void lds_read_b128_p(u32x4_t& out, unsigned addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(out) : "v"(addr), "n"(OFF) : "memory");
-#endif
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read_tr_p(u32x2_t& out, unsigned addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(addr), "n"(OFF) : "memory");
-#endif
-}
-__device__ __forceinline__ void tie_p(u32x4_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v)::"memory");
-#endif
-}
-__device__ __forceinline__ void tie2_p(u32x2_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v)::"memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void lgkm_wait_p() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void wait_vm_p() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // ---- fragments of v_mfma_f32_16x16x32_bf16: lane l holds row l & 15 of a 16-row block, k = 8 (l >> 4) .. + 7 of a 32-deep step ----
+// differs from Frag16 (gemm_split3.hip): 128-byte rows of a 64-deep image with two steps, one piece, the swizzle of bf16_tile.h
 template <int R, bool KM, int NB>
 struct FragP {
   unsigned ka[2];           // k-contiguous: offset of step s in the wave's first 16-row block (block t: + t * 2048 B)
@@ -199,12 +95,12 @@ struct RegsP<R, false, NB> {
   __device__ __forceinline__ void read(const FragP<R, false, NB>& f, unsigned img_addr) {
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_b128_p<T * 2048>(v[T], img_addr + f.ka[S]);
+      lds_read_b128<T * 2048>(v[T], img_addr + f.ka[S]);
     });
   }
   __device__ __forceinline__ void tie_all() {
 #pragma unroll
-    for (int t = 0; t < NB; ++t) tie_p(v[t]);
+    for (int t = 0; t < NB; ++t) tie(v[t]);
   }
   template <int T> __device__ __forceinline__ bf16x8 get() const { return __builtin_bit_cast(bf16x8, v[T]); }
 };
@@ -216,16 +112,16 @@ struct RegsP<R, true, NB> {
   __device__ __forceinline__ void read(const FragP<R, true, NB>& f, unsigned img_addr) {
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_tr_p<S * 32 * R * 2>(lo[T], img_addr + f.tr[T][0]);
-      lds_read_tr_p<S * 32 * R * 2>(hi[T], img_addr + f.tr[T][1]);
+      lds_read_tr<S * 32 * R * 2>(lo[T], img_addr + f.tr[T][0]);
+      lds_read_tr<S * 32 * R * 2>(hi[T], img_addr + f.tr[T][1]);
     });
   }
   __device__ __forceinline__ void tie_all() {
 #pragma unroll
-    for (int t = 0; t < NB; ++t) { tie2_p(lo[t]); tie2_p(hi[t]); }
+    for (int t = 0; t < NB; ++t) { tie2(lo[t]); tie2(hi[t]); }
   }
   template <int T> __device__ __forceinline__ bf16x8 get() const {
-    return __builtin_bit_cast(bf16x8, u32x4_t{lo[T][0], lo[T][1], hi[T][0], hi[T][1]});
+    return join_halves(lo[T], hi[T]);
   }
 };
 
@@ -277,7 +173,7 @@ __device__ __forceinline__ float p1_epilogue(const P1Args& g, int piece, int m0,
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
           const u32x2_t t = raw[a][b];
-          ax[a][b] = f32x4{bf_lo_p(t[0]), bf_hi_p(t[0]), bf_lo_p(t[1]), bf_hi_p(t[1])};
+          ax[a][b] = f32x4{bf_lo(t[0]), bf_hi(t[0]), bf_lo(t[1]), bf_hi(t[1])};
         }
     } else {
 #pragma unroll
@@ -322,11 +218,11 @@ __device__ __forceinline__ float p1_epilogue(const P1Args& g, int piece, int m0,
       }
       if (TWO && !g.aux_out_bf16)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, x2[b]), rsX, n < g.N ? (m * g.ld_aux + n) * 4 : OOB, 0, 0);
-      pk[b][0] = pack2p(v[0], v[1]); pk[b][1] = pack2p(v[2], v[3]);
-      if constexpr (TWO) { pk2[b][0] = pack2p(x2[b][0], x2[b][1]); pk2[b][1] = pack2p(x2[b][2], x2[b][3]); }
+      pk[b][0] = pack2(v[0], v[1]); pk[b][1] = pack2(v[2], v[3]);
+      if constexpr (TWO) { pk2[b][0] = pack2(x2[b][0], x2[b][1]); pk2[b][1] = pack2(x2[b][2], x2[b][3]); }
       if constexpr (EPI == P1_MUL) {
         // the bias gradient that belongs to this dY sums the STORED (rounded) values, as a pass over the bf16 tensor would
-        if (g.colpart && first) csum[b] += f32x4{bf_lo_p(pk[b][0]), bf_hi_p(pk[b][0]), bf_lo_p(pk[b][1]), bf_hi_p(pk[b][1])};
+        if (g.colpart && first) csum[b] += f32x4{bf_lo(pk[b][0]), bf_hi(pk[b][0]), bf_lo(pk[b][1]), bf_hi(pk[b][1])};
       }
     }
     // bf16 outputs: two column blocks at a time -- v_permlane16_swap hands the odd 16-lane rows of block b to the even rows and the
@@ -396,7 +292,7 @@ void gemm_b1p_kernel(const P1Group G) {
   constexpr int IMG_A = BM * KT * 2, IMG_B = BN * KT * 2, STAGE = IMG_A + IMG_B;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[ST * STAGE];
   const int nwork = G.start[4];
-  if (!XTR && xcd_work_item_p(nwork, 0) < 0) return;        // (with riders every workgroup stays: it owns sum-of-squares slots)
+  if (!XTR && xcd_work_item(nwork, 0) < 0) return;        // (with riders every workgroup stays: it owns sum-of-squares slots)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   stamp_begin(G.p[0].stamp);
@@ -404,7 +300,7 @@ void gemm_b1p_kernel(const P1Group G) {
   struct Item { int p, piece, m0, n0, kb, ke; bool valid; };
   auto item = [&](int round) -> Item {
     Item it;
-    const int w = xcd_work_item_p(nwork, round);
+    const int w = xcd_work_item(nwork, round);
     it.valid = w >= 0;
     if (!it.valid) { it.p = 0; it.piece = it.m0 = it.n0 = it.kb = it.ke = 0; return it; }
     it.p = (w >= G.start[1]) + (w >= G.start[2]) + (w >= G.start[3]);
@@ -413,7 +309,7 @@ void gemm_b1p_kernel(const P1Group G) {
     const int tile = local / g.nsplit;
     it.piece = local - tile * g.nsplit;
     int tmi, tni;
-    tile_coords_p(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
+    tile_coords(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
     it.m0 = tmi * BM; it.n0 = tni * BN;
     const int nk = (g.K + KT - 1) / KT;
     it.kb = (int)((long)nk * it.piece / g.nsplit);
@@ -424,8 +320,8 @@ void gemm_b1p_kernel(const P1Group G) {
   if (wave >= NWC) {
     // ------------------------------------------------------------------ loader waves ----
     set_wave_prio(2);
-    typedef DmaP<BM, AKM, NWL> DA;
-    typedef DmaP<BN, BKM, NWL> DB;
+    typedef Dma<BM, AKM, NWL, KT> DA;
+    typedef Dma<BN, BKM, NWL, KT> DB;
     constexpr int NDL = DA::NI + DB::NI;        // LDS-DMA instructions per loader wave and k-tile
     static_assert((ST - 2) * NDL <= 63, "vmcnt is six bits");
     const int lw = wave - NWC;
@@ -466,7 +362,7 @@ void gemm_b1p_kernel(const P1Group G) {
       if (!c.valid) break;
       for (int kt = c.kb; kt < c.ke; ++kt) {
         // k-tile `consumed` has landed once at most the k-tiles issued after it are outstanding
-        if (issued - consumed - 1 >= ST - 2) wait_vm_p<(ST - 2) * NDL>(); else wait_vm_p<0>();
+        if (issued - consumed - 1 >= ST - 2) wait_vm<(ST - 2) * NDL>(); else wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         issue_next();
         ++consumed;
@@ -520,11 +416,11 @@ void gemm_b1p_kernel(const P1Group G) {
         RB_ b0, b1;
         a0.template read<0>(fa, sA); b0.template read<0>(fb, sB);
         a1.template read<1>(fa, sA); b1.template read<1>(fb, sB);
-        lgkm_wait_p<(RS > 15 ? 15 : RS)>();
+        lgkm_wait<(RS > 15 ? 15 : RS)>();
         a0.tie_all(); b0.tie_all();
         mma(a0, b0);
         __builtin_amdgcn_sched_barrier(0);
-        lgkm_wait_p<0>();          // every read of the stage is complete in front of the next barrier (the loaders overwrite it behind it)
+        lgkm_wait<0>();          // every read of the stage is complete in front of the next barrier (the loaders overwrite it behind it)
         a1.tie_all(); b1.tie_all();
         mma(a1, b1);
         __builtin_amdgcn_sched_barrier(0);
@@ -539,31 +435,16 @@ void gemm_b1p_kernel(const P1Group G) {
 #endif
 }
 
-// band of the tile walk: an XCD's ~32 concurrent tiles as a sqrt(32 BN / BM)-row rectangle (gemm_split3.hip, plan_tiles3)
 void plan_tiles_p(P1Args& g, int BM, int BN) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
-  long bh = 1;
-  while ((bh + 1) * (bh + 1) * (long)BM <= 32l * BN) ++bh;
-  g.band_h = (int)(bh > 16 ? 16 : bh);
+  g.band_h = tile_band_height(BM, BN);
   if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
-}
-
-// workgroups of a persistent launch over `nwork` items: a multiple of 8 (one chunk of the work per XCD), one per CU at most
-int p1_grid(int nwork, int max_wgs) {
-  int grid = (nwork + 7) / 8 * 8;
-  const int cus = gemm_chip_cus();
-  int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : cus;
-  if (g_uniter_cu_reserve > 0) {                          // CUs left to the data-parallel exchange's kernels
-    const int room = (cus - g_uniter_cu_reserve) / 8 * 8;
-    if (room >= 8 && cap > room) cap = room;
-  }
-  return grid > cap ? cap : grid;
 }
 
 template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int ST, int EPI, bool XTR = false>
 int launch_p1(const P1Group& G, int max_wgs, hipStream_t st) {
-  const int grid = p1_grid(G.start[4], max_wgs);
+  const int grid = persistent_grid(G.start[4], max_wgs);
   hipLaunchKernelGGL((gemm_b1p_kernel<BM, BN, WM, WN, AKM, BKM, ST, 4, EPI, XTR>), dim3(grid), dim3(64 * ((BM / WM) * (BN / WN) + 4)), 0, st, G);
   UCHECK_LAUNCH();
   return 0;
@@ -612,13 +493,13 @@ void b1p_choose(int M, int N, int K, int avail, int nsplit_fixed, bool b_kmajor,
 // product of the bf16 mode on `avail_cus` CUs (0 = the chip's): geometry 6 / 7 / 8 and k-pieces.  Host arithmetic, no launch.
 extern "C" int uniter_gemm_bf16p_plan(int M, int N, int K, int avail_cus, int nsplit_fixed, int b_kmajor, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_bf16p_plan: bad argument");
-  b1p_choose(M, N, K, avail_cus > 0 ? avail_cus : p1_grid(1 << 20, 0), nsplit_fixed, b_kmajor != 0, cfg, nsplit);
+  b1p_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, b_kmajor != 0, cfg, nsplit);
   return 0;
 }
 
 int gemm_b1p_pick_split(int M, int N, int K, int avail) {
   int c, n;
-  b1p_choose(M, N, K, avail > 0 ? avail : p1_grid(1 << 20, 0), 0, false, &c, &n);
+  b1p_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0), 0, false, &c, &n);
   return n;
 }
 
@@ -645,7 +526,7 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
                "gemm_bf16p: operand beyond 31-bit offsets");
   if (cfg == 0) {
     int ns_;
-    b1p_choose(M, N, K, p1_grid(1 << 20, 0), nsplit, b_kmajor != 0, &cfg, &ns_);
+    b1p_choose(M, N, K, persistent_grid(1 << 20, 0), nsplit, b_kmajor != 0, &cfg, &ns_);
   }
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
@@ -687,7 +568,7 @@ static int b1p_wgrad_tiles(int n, const int* Mo, const int* No) {
 }
 int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
-  return 8 * p1_grid(b1p_wgrad_tiles(n, Mo, No), max_wgs);
+  return 8 * persistent_grid(b1p_wgrad_tiles(n, Mo, No), max_wgs);
 }
 int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B, float* const* dW,
                          void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders) {
@@ -718,7 +599,7 @@ int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void*
   if (riders) {
     UCHECK_ARG(!riders->colsum_out, "wgrad_bf16p_group: colsum_out does not ride on the 128 x 256 geometry (take the bias gradient from the "
                "producing product's column partials as a reduction job)");
-    riders->grid = p1_grid(total, max_wgs);
+    riders->grid = persistent_grid(total, max_wgs);
     UCHECK_RC(riders_prepare(*riders, "wgrad_bf16p_group"));
     G.x = *riders;
     return overwrite ? launch_p1<128, 256, 64, 64, true, true, 3, P1_NONE, true>(G, max_wgs, st)

@@ -28,6 +28,8 @@
 //  * epilogues through buffer instructions with scalar row offsets; optional per-32-row column sums.
 #include <stdlib.h>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 
 namespace {
@@ -97,8 +99,6 @@ __device__ __forceinline__ void tile_load(f32x4 (&reg)[R / 32], const float* __r
 // a k-contiguous operand and out-of-range k-rows of a k-major operand read as 0).  Needs
 // K % 32 == 0 for k-contiguous operands (no in-row k tail).  voff[] holds the per-pass byte
 // offsets for k0 = 0; the k advance goes in the scalar offset.
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
 template <int R, bool KM>
 __device__ __forceinline__ void tile_offsets(int (&voff)[R / 32], int ld, int row0, int tid) {
   if constexpr (!KM) {
@@ -281,21 +281,6 @@ int launch(GemmArgs g, hipStream_t st) {
 //     ds_writes complete under kb2's MFMAs, and the first MFMA after the barrier
 //     never waits for LDS.
 // ---------------------------------------------------------------------------
-// L2-aware tile order.  The workgroups of one XCD run ~128 consecutive tiles of the linear
-// order at once (32 CUs x 4 resident workgroups).  Row-major order makes that window 2-3 tile
-// rows x all tile columns: the whole B operand streams through the 4 MiB L2 again for every few
-// rows (measured on FFN-up: 68 % L2 hit rate, ~250 MB fetched beyond L2 for 17 MB of operands).
-// Banded order: bands of `band_h` tile rows whose A panel stays L2-resident, tile columns swept
-// inside a band with the row index fastest, so the window is band_h x ~(128/band_h) tiles.
-__device__ __forceinline__ void tile_coords(int t, int tiles_m, int tiles_n, int band_h, int& tm, int& tn) {
-  const int full = band_h * tiles_n;
-  const int band = t / full;
-  const int rem = t - band * full;
-  const int bh = min(band_h, tiles_m - band * band_h);
-  tn = rem / bh;
-  tm = band * band_h + (rem - tn * bh);
-}
-
 // ---------------------------------------------------------------------------
 // v3: the schedule above with a full-iteration prefetch distance.  The k-tiles a workgroup will consume
 // (across all of its output tiles) form one flat sequence of "units"; in the middle of iteration u
@@ -487,7 +472,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_v3_kernel(const GemmArgs g) {
 // address arithmetic, compares or exec-mask branches per element.
 #define EPILOGUE()                                                                                      \
   {                                                                                                     \
-    constexpr int OOB = 0x7ffffff0;                                                                     \
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, g.M * g.ldc * 4, 0x00020000); \
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(                                \
         g.aux_out, 0, g.aux_out ? g.M * g.ld_aux * 4 : 0, 0x00020000);                                  \
@@ -670,7 +654,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_wgrad_group_kernel(const Gemm
   FB[0] = frag_read<BN, BKM>(SBp, wn * WN, KB, i, h);
 #define GROUP_EPILOGUE()                                                                 \
   {                                                                                      \
-    constexpr int OOB = 0x7ffffff0;                                                      \
     const int Mp = G.M[cp], Np = G.N[cp];                                                \
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(G.C[cp], 0, Mp * Np * 4, 0x00020000); \
     const int col = n0 + wn * WN + i;                                                    \

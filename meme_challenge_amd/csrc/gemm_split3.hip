@@ -24,22 +24,19 @@
 // LDS images per piece and stage:
 //   k-contiguous operand ([rows][K]): [R][32] bf16, 64-B rows, 16-B chunk c of row r at c ^ ((r >> 2) & 3): the 16 lanes
 //     of a ds_read_b128 group cover all 64 banks.
-//   k-major operand ([K][cols]): the image of gemm_bf16_dma.hip cut to 32 k-rows: 256-B segments, chunk c of k-row k at
+//   k-major operand ([K][cols]): the k-major image of bf16_tile.h (Dma) cut to 32 k-rows: 256-B segments, chunk c of k-row k at
 //     c ^ (((k & 3) << 2) | ((k >> 2) & 3)), gathered by ds_read_b64_tr_b16.
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 #include "riders.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct S3Args {
   int M, N, K;
@@ -62,56 +59,12 @@ struct S3Args {
                       // floats per 64 output rows (row 2 (m0 / 128) + wm): the bias gradient that belongs to a dY this product writes
 };
 
-#define OOB 0x7ffffff0        /* buffer offset beyond every descriptor: load returns 0, store is dropped */
 // cache policy of the 16x16x32 epilogue's output stores (lab switch, -DX3_ST_AUX=2: nt, =16: sc1 write-through, =18: both).  A
 // one-round launch of 252 workgroups ends in one store burst (80 MB for FFN-up forward) and the kernel boundary behind it writes the
 // L2s' dirty lines back: round 6 measured whether stores that leave the L2 as they are issued shorten that
 #ifndef X3_ST_AUX
 #define X3_ST_AUX 0
 #endif
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-__device__ __forceinline__ void tile_coords3(int t, int tiles_m, int tiles_n, int band_h, int& tm, int& tn) {
-  const int full = band_h * tiles_n;
-  const int band = t / full;
-  const int rem = t - band * full;
-  const int bh = min(band_h, tiles_m - band * band_h);
-  tn = rem / bh;
-  tm = band * band_h + (rem - tn * bh);
-}
-
-__device__ __forceinline__ unsigned pack2r(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};      // v_cvt_pk_bf16_f32: round to nearest even
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bflo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bfhi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-// the three bf16 pieces of two fp32 values (exact: every residual is representable)
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& w1, unsigned& w2, unsigned& w3) {
-  w1 = pack2r(x0, x1);
-  float r0 = x0 - bflo(w1), r1 = x1 - bfhi(w1);
-  w2 = pack2r(r0, r1);
-  r0 -= bflo(w2); r1 -= bfhi(w2);
-  w3 = pack2r(r0, r1);
-}
-
-// work item of this workgroup, XCD-chunked (blocks b and b + 8 share an XCD's L2)
-__device__ __forceinline__ int xcd_work_item3(int nwork, int round = 0) {
-  const int xcd = blockIdx.x & 7, idx = (blockIdx.x >> 3) + round * (int)(gridDim.x >> 3);
-  const int q8 = nwork >> 3, r8 = nwork & 7;
-  const int chunk0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int chunk_n = q8 + (xcd < r8 ? 1 : 0);
-  return idx < chunk_n ? chunk0 + idx : -1;
-}
 
 // ---- LDS-DMA fill of the three piece images of one operand ---------------------------------------------------------
 // chunk swizzle of the k-contiguous image by row group (row >> 2) & 3: the identity for the 32x32x16 fragments (lane = row i5,
@@ -120,6 +73,7 @@ __device__ __forceinline__ int xcd_work_item3(int nwork, int round = 0) {
 template <bool M16>
 __device__ __forceinline__ int chunk_swz(int rowgroup) { return M16 ? ((0x1320 >> (4 * rowgroup)) & 3) : rowgroup; }
 
+// differs from Dma (bf16_tile.h): three piece images per k-tile, 32-deep k-tiles (64-byte rows), the paired-row source layout
 template <int R, bool KM, int NW, int KT, bool M16 = false>
 struct Dma3 {
   static constexpr int NP = R * KT / 512;          // 1-KiB wave-instructions per piece image and k-tile
@@ -164,6 +118,7 @@ struct Dma3 {
 };
 
 // ---- MFMA operand fragments: per-lane LDS byte offsets inside one piece image -------------------------------------------
+// differs from Frag (gemm_bf16_dma.hip): 64-byte rows of a 32-deep image, two k16-steps, NB blocks per wave
 template <int R, bool KM, int NB, int KT>
 struct Frag3 {
   unsigned ka[KT / 16];     // k-contiguous: offset of k16-step ks in the wave's first block (block t: + t * 32 rows)
@@ -189,36 +144,6 @@ struct Frag3 {
   }
 };
 
-template <int OFF>
-__device__ __forceinline__ void lds_read_b128_o(u32x4_t& out, unsigned addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(out) : "v"(addr), "n"(OFF) : "memory");
-#endif
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read_tr_o(u32x2_t& out, unsigned addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(addr), "n"(OFF) : "memory");
-#endif
-}
-// ties a fragment's first use to the statements above it (the wait): an empty volatile asm that "rewrites" the register
-__device__ __forceinline__ void tie(u32x4_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v)::"memory");
-#endif
-}
-__device__ __forceinline__ void tie2(u32x2_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v)::"memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void lgkm_wait() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-template <int N> __device__ __forceinline__ void wait_vm3() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // One k-contiguous operand's fragments of one k16-step: [piece][block], 8 consecutive k of row (block, i5) per lane half
 template <int R, int NB, int KT>
 struct FragRegs {
@@ -230,7 +155,7 @@ struct FragRegs {
     constexpr int IMG = R * KT * 2;
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_b128_o<P * IMG + T * 32 * KT * 2>(v[P][T], img_addr + f.ka[KS]);
+      lds_read_b128<P * IMG + T * 32 * KT * 2>(v[P][T], img_addr + f.ka[KS]);
     });
   }
   template <int P>
@@ -252,8 +177,8 @@ struct FragRegsKM {
     constexpr int IMG = R * KT * 2;
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_tr_o<P * IMG + KS * 16 * R * 2>(lo[P][T], img_addr + f.tr[T][0]);
-      lds_read_tr_o<P * IMG + KS * 16 * R * 2>(hi[P][T], img_addr + f.tr[T][1]);
+      lds_read_tr<P * IMG + KS * 16 * R * 2>(lo[P][T], img_addr + f.tr[T][0]);
+      lds_read_tr<P * IMG + KS * 16 * R * 2>(hi[P][T], img_addr + f.tr[T][1]);
     });
   }
   template <int P>
@@ -263,7 +188,7 @@ struct FragRegsKM {
   }
   template <int P, int T>
   __device__ __forceinline__ bf16x8 get() const {
-    return __builtin_bit_cast(bf16x8, u32x4_t{lo[P][T][0], lo[P][T][1], hi[P][T][0], hi[P][T][1]});
+    return join_halves(lo[P][T], hi[P][T]);
   }
 };
 
@@ -309,7 +234,7 @@ struct FragRegs16 {
     constexpr int IMG = R * 64;
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_b128_o<P * IMG + T * 1024>(v[P][T], img_addr + f.ka);
+      lds_read_b128<P * IMG + T * 1024>(v[P][T], img_addr + f.ka);
     });
   }
   template <int P>
@@ -329,8 +254,8 @@ struct FragRegs16KM {
     constexpr int IMG = R * 64;
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_tr_o<P * IMG>(lo[P][T], img_addr + f.tr[T][0]);
-      lds_read_tr_o<P * IMG>(hi[P][T], img_addr + f.tr[T][1]);
+      lds_read_tr<P * IMG>(lo[P][T], img_addr + f.tr[T][0]);
+      lds_read_tr<P * IMG>(hi[P][T], img_addr + f.tr[T][1]);
     });
   }
   template <int P>
@@ -340,7 +265,7 @@ struct FragRegs16KM {
   }
   template <int P, int T>
   __device__ __forceinline__ bf16x8 get() const {
-    return __builtin_bit_cast(bf16x8, u32x4_t{lo[P][T][0], lo[P][T][1], hi[P][T][0], hi[P][T][1]});
+    return join_halves(lo[P][T], hi[P][T]);
   }
 };
 
@@ -354,7 +279,7 @@ struct Piece16<R, false, NB> {
   __device__ __forceinline__ void read(const Frag16<R, false, NB>& f, unsigned img_addr) {
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_b128_o<P * R * 64 + T * 1024>(v[T], img_addr + f.ka);
+      lds_read_b128<P * R * 64 + T * 1024>(v[T], img_addr + f.ka);
     });
   }
   __device__ __forceinline__ void tie_all() {
@@ -373,8 +298,8 @@ struct Piece16<R, true, NB> {
     const unsigned base = img_addr + f.kb;
     static_for<0, NB>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
-      lds_read_tr_o<P * R * 64>(lo[T], base + (f.xk ^ (unsigned)(T << 5)));
-      lds_read_tr_o<P * R * 64 + 4 * R * 2>(hi[T], base + (f.xk ^ (unsigned)((T << 5) | 16)));
+      lds_read_tr<P * R * 64>(lo[T], base + (f.xk ^ (unsigned)(T << 5)));
+      lds_read_tr<P * R * 64 + 4 * R * 2>(hi[T], base + (f.xk ^ (unsigned)((T << 5) | 16)));
     });
   }
   __device__ __forceinline__ void tie_all() {
@@ -382,7 +307,7 @@ struct Piece16<R, true, NB> {
     for (int t = 0; t < NB; ++t) { tie2(lo[t]); tie2(hi[t]); }
   }
   template <int T> __device__ __forceinline__ bf16x8 get() const {
-    return __builtin_bit_cast(bf16x8, u32x4_t{lo[T][0], lo[T][1], hi[T][0], hi[T][1]});
+    return join_halves(lo[T], hi[T]);
   }
 };
 
@@ -654,7 +579,7 @@ void gemm_s3p_kernel(const S3Group G) {
   constexpr int KS = KT / 16;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[ST * STAGE];
   const int nwork = G.start[4];
-  if (!XTR && !SK && xcd_work_item3(nwork, 0) < 0) return;        // (with riders every workgroup stays: it owns sum-of-squares slots)
+  if (!XTR && !SK && xcd_work_item(nwork, 0) < 0) return;        // (with riders every workgroup stays: it owns sum-of-squares slots)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   stamp_begin(G.p[0].stamp);
@@ -681,7 +606,7 @@ void gemm_s3p_kernel(const S3Group G) {
       skb = round == 0 ? sk_u0 - sk_t0 * G.sk_nk : 0;
       ske = min(G.sk_nk, skb + (sk_u1 - ustart));
     } else {
-      w = xcd_work_item3(nwork, round);
+      w = xcd_work_item(nwork, round);
     }
     it.valid = w >= 0;
     if (!it.valid) { it.p = 0; it.piece = it.m0 = it.n0 = it.kb = it.ke = 0; return it; }
@@ -691,7 +616,7 @@ void gemm_s3p_kernel(const S3Group G) {
     const int tile = local / g.nsplit;
     it.piece = local - tile * g.nsplit;
     int tmi, tni;
-    tile_coords3(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
+    tile_coords(tile, g.tiles_m, g.tiles_n, g.band_h, tmi, tni);
     it.m0 = tmi * BM; it.n0 = tni * BN;
     const int nk = (g.K + KT - 1) / KT;
     it.kb = (int)((long)nk * it.piece / g.nsplit);
@@ -771,7 +696,7 @@ void gemm_s3p_kernel(const S3Group G) {
       if (!c.valid) break;
       for (int kt = c.kb; kt < c.ke; ++kt) {
         // k-tile `consumed` has landed once at most the k-tiles issued after it are outstanding
-        if (issued - consumed - 1 >= ST - 2) wait_vm3<(ST - 2) * NDL>(); else wait_vm3<0>();
+        if (issued - consumed - 1 >= ST - 2) wait_vm<(ST - 2) * NDL>(); else wait_vm<0>();
         if (!(dbg & 64)) __builtin_amdgcn_s_barrier();
         issue_next();
         ++consumed;
@@ -1101,43 +1026,15 @@ template <int BM>
 void plan_tiles3(S3Args& g, int BN) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
-  // Band height of the walk (round 5): an XCD's workgroups run ~32 tiles of its chunk of the walk at a time -- a band_h x (32 / band_h)
-  // rectangle of the tile grid -- and its L2 fetches band_h row panels and 32 / band_h column panels for them: least for
-  // band_h = sqrt(32 BN / BM).  (Round 4 sized the band for L2 capacity, 1.5 MB of row panels: 2 rows at K = 768, every XCD then
-  // fetched EVERY weight panel -- 7.1 x the operand bytes on FFN-up forward.  The panels' k-tiles are consumed k-synchronously, so
-  // capacity is not the constraint.  Time is unchanged either way -- the re-fetches are Infinity-Cache hits -- but the fabric moves
-  // a third less: profiles/r05_pmc_traffic.json.)
-  long bh = 1;
-  while ((bh + 1) * (bh + 1) * (long)BM <= 32l * BN) ++bh;
-  g.band_h = (int)(bh > 16 ? 16 : bh);
+  g.band_h = tile_band_height(BM, BN);
   const int band_env = uniter_switches().x3_band_h;      // (lab switch)
   if (band_env > 0) g.band_h = band_env;
   if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
 }
 
-// workgroups of a persistent launch over `nwork` items: a multiple of 8 (one chunk of the work per XCD), one per CU at most
-int x3_chip_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 8 ? n / 8 * 8 : 256;
-  }();
-  return cus;
-}
-int x3_grid(int nwork, int max_wgs) {
-  int grid = (nwork + 7) / 8 * 8;
-  const int cus = x3_chip_cus();
-  int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : cus;       // one workgroup per CU: it owns the CU's LDS
-  if (g_uniter_cu_reserve > 0) {                          // CUs left to the data-parallel exchange's kernels
-    const int room = (cus - g_uniter_cu_reserve) / 8 * 8;
-    if (room >= 8 && cap > room) cap = room;
-  }
-  return grid > cap ? cap : grid;
-}
-
 template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int ST, int KT, int NWL, bool M16, int EPI, bool XTR = false>
 int launch_s3p(const S3Group& G, int max_wgs, hipStream_t st) {
-  const int grid = x3_grid(G.start[4], max_wgs);
+  const int grid = persistent_grid(G.start[4], max_wgs);
   hipLaunchKernelGGL((gemm_s3p_kernel<BM, BN, WM, WN, AKM, BKM, ST, KT, NWL, M16, EPI, XTR>), dim3(grid),
                      dim3(64 * ((BM / WM) * (BN / WN) + NWL)), 0, st, G);
   UCHECK_LAUNCH();
@@ -1149,16 +1046,16 @@ int launch_s3p(const S3Group& G, int max_wgs, hipStream_t st) {
 //            [partial sums: one 128 x 256 fp32 tile per workgroup]
 constexpr size_t SK_FLAG_BYTES = 16384;           // 512 workgroups x 8 compute waves x 4 bytes
 constexpr size_t SK_SLOT_BYTES = 128 * 256 * 4;
-size_t sk_ws_bytes_() { return SK_FLAG_BYTES + (size_t)x3_chip_cus() * SK_SLOT_BYTES; }
+size_t sk_ws_bytes_() { return SK_FLAG_BYTES + (size_t)gemm_chip_cus() * SK_SLOT_BYTES; }
 // grid of the balanced walk for `tiles` tiles of `nk` k-tiles each: every CU the launch may use -- or 0: the classic walk is as
 // good (its rounds are full), or the workspace is missing.  The hand-over (a 128-KB partial sum stored, flagged and added) is
 // priced at four k-tiles
 int x3_sk_grid(int tiles, int nk, int max_wgs, const void* ws, size_t ws_bytes) {
   if (!ws || ws_bytes < sk_ws_bytes_() || ((uintptr_t)ws & 255) != 0 || tiles <= 0 || nk <= 0) return 0;
-  const int cap = x3_grid(1 << 20, max_wgs);
+  const int cap = persistent_grid(1 << 20, max_wgs);
   const long units = (long)tiles * nk;
   if (cap > 512 || units >= (1l << 30) || units < 8l * cap) return 0;
-  const int g0 = x3_grid(tiles, max_wgs);
+  const int g0 = persistent_grid(tiles, max_wgs);
   const long classic = (long)((tiles + g0 - 1) / g0) * nk, balanced = (units + cap - 1) / cap + 4;
   return classic > balanced ? cap : 0;
 }
@@ -1291,8 +1188,8 @@ __global__ __launch_bounds__(256) void join3_kernel(const unsigned short* __rest
   float o[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    o[2 * e] = (bflo(w[2][e]) + bflo(w[1][e])) + bflo(w[0][e]);
-    o[2 * e + 1] = (bfhi(w[2][e]) + bfhi(w[1][e])) + bfhi(w[0][e]);
+    o[2 * e] = (bf_lo(w[2][e]) + bf_lo(w[1][e])) + bf_lo(w[0][e]);
+    o[2 * e + 1] = (bf_hi(w[2][e]) + bf_hi(w[1][e])) + bf_hi(w[0][e]);
   }
   *reinterpret_cast<f32x4*>(x + (size_t)r * ld + c8 * 8) = f32x4{o[0], o[1], o[2], o[3]};
   *reinterpret_cast<f32x4*>(x + (size_t)r * ld + c8 * 8 + 4) = f32x4{o[4], o[5], o[6], o[7]};
@@ -1315,8 +1212,8 @@ __global__ __launch_bounds__(256) void colsum3_kernel(const unsigned short* __re
                     v2 = *reinterpret_cast<const u32x4_t*>(p + 2 * ldx);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        s[2 * k] += (bflo(v2[k]) + bflo(v1[k])) + bflo(v0[k]);
-        s[2 * k + 1] += (bfhi(v2[k]) + bfhi(v1[k])) + bfhi(v0[k]);
+        s[2 * k] += (bf_lo(v2[k]) + bf_lo(v1[k])) + bf_lo(v0[k]);
+        s[2 * k + 1] += (bf_hi(v2[k]) + bf_hi(v1[k])) + bf_hi(v0[k]);
       }
     }
   }
@@ -1335,7 +1232,14 @@ bool x3_fits(size_t rows, int rs, int ps, int ext) { return ((rows + 256) * (siz
 }  // namespace
 
 size_t gemm_x3_sk_ws_bytes() { return sk_ws_bytes_(); }
-int gemm_chip_cus() { return x3_chip_cus(); }      // CUs of the current device, a multiple of 8 (shared with gemm_bf16_dma.hip)
+int gemm_chip_cus() {      // CUs of the current device, a multiple of 8
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 8 ? n / 8 * 8 : 256;
+  }();
+  return cus;
+}
 
 int riders_prepare(uniter_x3_riders_t& x, const char* who) {
   UCHECK_ARG(x.njobs >= 0 && x.njobs <= 4, "%s: at most 4 column-reduction jobs", who);
@@ -1405,7 +1309,7 @@ int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, i
     // launch may use (all of them, or what a data-parallel exchange leaves: g_uniter_cu_reserve)
     if (!a_kmajor) {
       int ns_;
-      x3_choose(M, N, K, x3_grid(1 << 20, 0), nsplit, &cfg, &ns_, !b_kmajor && !Cx);
+      x3_choose(M, N, K, persistent_grid(1 << 20, 0), nsplit, &cfg, &ns_, !b_kmajor && !Cx);
     }
   }
   hipStream_t st = (hipStream_t)stream;
@@ -1445,21 +1349,21 @@ void x3_choose(int M, int N, int K, int avail, int nsplit_fixed, int* cfg_out, i
 
 extern "C" int uniter_gemm_x3_plan(int M, int N, int K, int avail_cus, int nsplit_fixed, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_x3_plan: bad argument");
-  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : x3_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit);
+  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit);
   return 0;
 }
 
 // the same for a forward product (both operands k-contiguous) with an fp32 output: 128 x 192 tiles (cfg 5) compete too
 extern "C" int uniter_gemm_x3_plan_fwd32(int M, int N, int K, int avail_cus, int nsplit_fixed, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_x3_plan_fwd32: bad argument");
-  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : x3_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit, true);
+  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit, true);
   return 0;
 }
 
 // k-pieces of a product whose output goes to fp32 slabs, on `avail` CUs (0 = the chip's)
 int gemm_x3_pick_split_on(int M, int N, int K, int avail) {
   int c, n;
-  x3_choose(M, N, K, avail > 0 ? avail : x3_grid(1 << 20, 0), 0, &c, &n);
+  x3_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0), 0, &c, &n);
   return n;
 }
 
@@ -1603,7 +1507,7 @@ int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, con
     uniter_x3_riders_t& x = *riders;
     UCHECK_ARG(cfg != 4 || !x.colsum_out, "wgrad_x3_group: colsum_out rides on cfg 3 only (the 128 x 256 geometry has no registers for it: "
                "take the bias gradient from the producing product's column partials, uniter_gemm_x3_colpart, as a reduction job)");
-    x.grid = sk_grid > 0 ? sk_grid : x3_grid(total, max_wgs);
+    x.grid = sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs);
     UCHECK_RC(riders_prepare(x, "wgrad_x3_group"));
     G.x = x;
     if (sk_grid > 0)
@@ -1632,7 +1536,7 @@ int gemm_x3_wgrad_group_slots(int cfg, int n, const int* Mo, const int* No, int 
   const int total = wgrad_tiles(cfg, n, Mo, No);
   // (x3_sk_grid checks the pointer's alignment only: any aligned non-null value stands for the workspace here)
   const int sk_grid = (cfg == 4 && K > 0) ? x3_sk_grid(total, (K + 31) / 32, max_wgs, (const void*)256, sk_ws_bytes) : 0;
-  return (cfg == 4 ? 8 : 4) * (sk_grid > 0 ? sk_grid : x3_grid(total, max_wgs));
+  return (cfg == 4 ? 8 : 4) * (sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs));
 }
 
 // the smallest grid (a multiple of 8) on which these products' tiles take no more rounds than on one workgroup per CU
@@ -1640,7 +1544,7 @@ int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* N
   if (!Mo || !No || n < 1 || n > 4) return 0;
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
   const int total = wgrad_tiles(cfg, n, Mo, No);
-  const int full = x3_grid(total, 0);
+  const int full = persistent_grid(total, 0);
   const int rounds = (total + full - 1) / full;
   const int wgs = ((total + rounds - 1) / rounds + 7) / 8 * 8;
   return wgs < full ? wgs : full;

@@ -10,6 +10,8 @@
 // per-workgroup partial rows in a workspace, then a finalize kernel.
 #include <stdlib.h>
 #include "common.h"
+#include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 #include "philox.h"
 #include "rowops.h"
@@ -245,7 +247,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const unsigned short* __restrict__ X, int M, int N, int ld,
                                                           float* __restrict__ out, int rows_per_block) {
   __shared__ float red[4][64 * 8 + 8];
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 512 + lane * 8;
   float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -15,56 +15,9 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "gemm_internal.h"
 #include "philox.h"
 #include "switches.h"
-
-// internal helpers implemented in other translation units
-int launch_add_f32(float* out, const float* a, const float* b, size_t n, hipStream_t st);
-int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
-                 const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                 const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
-int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
-                  const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
-int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B,
-                     int ldb, float* C, int ldc, void* Cb, int ldcb, int epilogue, const float* bias,
-                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
-int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda,
-                    const void* B, int ldb, float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue,
-                    const float* bias, const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16,
-                    int ld_aux, int beta, void* stream);
-int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float* const* A, const float* const* B,
-                         float* const* dW, int overwrite, void* stream);
-int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, int psa,
-                const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride, void* Cx, int ldcx, int pscx,
-                int epilogue, const float* bias, const float* aux_in, float* aux_out, int ld_aux, void* stream,
-                float* colsum_part, void* sk_ws, size_t sk_ws_bytes);
-size_t gemm_x3_sk_ws_bytes();
-int gemm_x3_wgrad_default_cfg();
-int gemm_x3_pick_split(int M, int N, int K);
-int gemm_x3_pick_split_on(int M, int N, int K, int avail);
-int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B,
-                        float* const* dW, void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders,
-                        void* sk_ws, size_t sk_ws_bytes);
-int gemm_x3_wgrad_group_slots(int cfg, int n, const int* Mo, const int* No, int max_wgs, int K, size_t sk_ws_bytes);
-int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* No);
-int gemm_bf16v2_pick_split(int M, int N, int K);
-int gemm_b1p_pick_split(int M, int N, int K, int avail);
-int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                 float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue, const float* bias,
-                 const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16, int ld_aux, float* colpart, void* stream);
-int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs);
-int gemm_bf16v2_wgrad_pieces(int M, int N, int K);
-int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A,
-                            const void* const* B, float* const* dW, void* stream, int overwrite, int max_wgs,
-                            uniter_x3_riders_t* riders);
-int gemm_bf16v2_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs);
-int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No);
-int finalize_partials(const float* part, int nparts, size_t stride, float* out, int N, int beta, hipStream_t st);
-int finalize_partials_jobs(int njobs, const float* const* part, const int* nparts, const size_t* stride,
-                           float* const (*outs)[3], const int* nout, const int* seg, hipStream_t st);
-int ln_bwd_partial_rows(int M);
-int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int rows, int D, hipStream_t st);
 
 namespace {
 

@@ -17,13 +17,13 @@
 // The kernels test the whole byte for "skip", so 4 alone is invalid (it would update and count the chunk): callers pass
 // 0, 1, 2, 5 or 6 (include/uniter_hip.h).
 #include "common.h"
+#include "bf16_tile.h"
 
 namespace {
 
 constexpr int CHUNK = 64;
 
 __device__ __forceinline__ f32x4 widen4(const unsigned short* __restrict__ g16, size_t i) {
-  typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
   const u32x2_t w = reinterpret_cast<const u32x2_t*>(g16)[i];
   return f32x4{__builtin_bit_cast(float, w[0] << 16), __builtin_bit_cast(float, w[0] & 0xffff0000u),
                __builtin_bit_cast(float, w[1] << 16), __builtin_bit_cast(float, w[1] & 0xffff0000u)};
@@ -139,16 +139,15 @@ __device__ __forceinline__ void adam_store4(const AdamArgs& a, size_t i, size_t 
   // the forward kernels that share the chip with it from the L2s.  si: the item's place in the parameter buffers, i: in the mirror
   __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(a.p) + si);
   if (a.mirror) {
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    const bf16x4_t o = {(__bf16)p[0], (__bf16)p[1], (__bf16)p[2], (__bf16)p[3]};
-    bf16x4_t* m0 = reinterpret_cast<bf16x4_t*>(a.mirror) + i;      // (i: the item's place in the mirror's order)
+    const bf16x4 o = {(__bf16)p[0], (__bf16)p[1], (__bf16)p[2], (__bf16)p[3]};
+    bf16x4* m0 = reinterpret_cast<bf16x4*>(a.mirror) + i;      // (i: the item's place in the mirror's order)
     *m0 = o;
     if (a.mirror_ps) {      // x = x1 + x2 + x3 exactly (round-to-nearest residuals): the operands of csrc/gemm_split3.hip
       f32x4 r = {p[0] - (float)o[0], p[1] - (float)o[1], p[2] - (float)o[2], p[3] - (float)o[3]};
-      const bf16x4_t o2 = {(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
-      *reinterpret_cast<bf16x4_t*>(reinterpret_cast<unsigned short*>(m0) + a.mirror_ps) = o2;
+      const bf16x4 o2 = {(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
+      *reinterpret_cast<bf16x4*>(reinterpret_cast<unsigned short*>(m0) + a.mirror_ps) = o2;
       r = f32x4{r[0] - (float)o2[0], r[1] - (float)o2[1], r[2] - (float)o2[2], r[3] - (float)o2[3]};
-      *reinterpret_cast<bf16x4_t*>(reinterpret_cast<unsigned short*>(m0) + 2 * a.mirror_ps) = bf16x4_t{(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
+      *reinterpret_cast<bf16x4*>(reinterpret_cast<unsigned short*>(m0) + 2 * a.mirror_ps) = bf16x4{(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
     }
   }
   __builtin_nontemporal_store(m, reinterpret_cast<f32x4*>(a.m) + si);

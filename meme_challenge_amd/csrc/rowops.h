@@ -4,6 +4,7 @@
 // fully coalesced 1-KiB wave transaction.
 #pragma once
 #include "common.h"
+#include "bf16_tile.h"
 #include "philox.h"
 
 #ifdef __HIPCC__
@@ -26,13 +27,12 @@ __device__ __forceinline__ void row_store(const f32x4 (&v)[NV], float* __restric
 // bf16 (round-to-nearest-even) copy of a row: 4 elements = 8 bytes per lane and vector
 template <int NV>
 __device__ __forceinline__ void row_store_bf16(const f32x4 (&v)[NV], unsigned short* __restrict__ p, int H4, int lane) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     const int c = lane + 64 * k;
     if (c < H4) {
-      bf16x4_t o = {(__bf16)v[k][0], (__bf16)v[k][1], (__bf16)v[k][2], (__bf16)v[k][3]};
-      reinterpret_cast<bf16x4_t*>(p)[c] = o;
+      bf16x4 o = {(__bf16)v[k][0], (__bf16)v[k][1], (__bf16)v[k][2], (__bf16)v[k][3]};
+      reinterpret_cast<bf16x4*>(p)[c] = o;
     }
   }
 }
@@ -40,7 +40,6 @@ __device__ __forceinline__ void row_store_bf16(const f32x4 (&v)[NV], unsigned sh
 // p, p + H, p + 2 H: the operand copy of an fp32-accurate product on the bf16 matrix pipe
 template <int NV>
 __device__ __forceinline__ void row_store_x3(const f32x4 (&v)[NV], unsigned short* __restrict__ p, int H, int H4, int lane) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     const int c = lane + 64 * k;
@@ -48,8 +47,8 @@ __device__ __forceinline__ void row_store_x3(const f32x4 (&v)[NV], unsigned shor
       f32x4 r = v[k];
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) {
-        const bf16x4_t o = {(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
-        reinterpret_cast<bf16x4_t*>(p + (size_t)pc * H)[c] = o;
+        const bf16x4 o = {(__bf16)r[0], (__bf16)r[1], (__bf16)r[2], (__bf16)r[3]};
+        reinterpret_cast<bf16x4*>(p + (size_t)pc * H)[c] = o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) r[e] -= (float)o[e];
       }
@@ -155,10 +154,3 @@ __device__ __forceinline__ void block_col_reduce_store(const f32x4 (&acc)[NV], f
   }
 }
 #endif
-
-// host: out[n] (+)= sum_p part[p*stride + n]   (layernorm.hip)
-int finalize_partials(const float* part, int nparts, size_t stride, float* out, int N, int beta,
-                      hipStream_t st);
-// outs[j][c] += sum_p part[p*stride + j*H + c] for j < nout (<= 8); NULL outputs skipped
-int finalize_partials_multi(const float* part, int nparts, size_t stride, float* const* outs, int nout, int H,
-                            hipStream_t st);
