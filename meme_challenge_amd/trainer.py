@@ -14,14 +14,37 @@ zero_grad) is ONE fused kernel over the flat parameter buffer
 iteration needs no host synchronisation (the reference does `.item()` /
 `.cpu()` every iteration, train_template.py:121-124).
 """
+import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import torch
 
 from . import _lib
 from ._lib import check, ptr, UniterHipError
 from .model import CHUNK, ensure_store
+
+
+# The optimizer's environment variables (member, variable, parse), read by optim_switches() and nowhere else in this file; None = the
+# default.  FusedAdam keeps the first two from its construction and reads the others at every call.  INTEGRATION.md lists the names.
+_off_if_0 = lambda v: v != '0'
+_int = lambda v: None if v is None else int(v)
+OPTIM_SWITCHES = (
+    ('overlap_wgs', 'UNITER_ADAM_OVERLAP_WGS', lambda v: int(v) if v else None),    # grid of the blocks beside the next forward
+    ('word_rows', 'UNITER_ADAM_WORD_ROWS', lambda v: v == '1'),      # the word table's update split by rows (early_word_update)
+    ('lazy_zero', 'UNITER_LAZY_ZERO', _off_if_0),           # =0: zero_grad clears the encoder layers' weight gradients too
+    ('word_split', 'UNITER_ADAM_WORD_SPLIT', _off_if_0),    # =0: the word table stays inside the embeddings' block
+    ('emb_main', 'UNITER_ADAM_EMB_MAIN', _off_if_0),        # =0: the embeddings' remainder goes back on the side stream
+    ('word_wgs', 'UNITER_ADAM_WORD_WGS', _int),             # grid of the word table's launch (min(2048, 4 x the overlap grid))
+    ('early_wgs', 'UNITER_ADAM_EARLY_WGS', _int),           # grid of early_word_update's launch (the overlap grid)
+)
+OptimSwitches = namedtuple('OptimSwitches', [member for member, _, _ in OPTIM_SWITCHES])
+
+
+def optim_switches():
+    """The optimizer's switches as the environment states them now."""
+    return OptimSwitches(*[parse(os.environ.get(name)) for _, name, parse in OPTIM_SWITCHES])
 
 
 # --------------------------------------------------------------------------- #
@@ -89,6 +112,47 @@ def no_decay(name):
     return any(nd in name for nd in NO_DECAY)
 
 
+Hyper = namedtuple('Hyper', 'lr b1 b2 eps weight_decay step_count adamw')      # in the order the library's entry points take them
+Scale = namedtuple('Scale', 'grad_scale max_grad_norm zero_grads')
+# One launch of a step.  kind: 'flat' (the flat buffers' range [lo, hi)) or 'rows' (the looked-up rows of the word table [lo, hi));
+# stream: 'main' or 'side'; wait: the range that stream waits for through grad_ready in front of the launch, or None; event: None,
+# 'block' (for the forward pass's per-block list) or 'word' (the word table's extra event); clear_mask: behind it, on its stream
+Launch = namedtuple('Launch', 'kind lo hi stream max_wgs wait event clear_mask')
+
+
+def optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw):
+    """The launches of one FusedAdam.step in issue order, from plain values.  plan: _overlap_plan's (head, blocks, word) or None;
+    rows_ahead: _word_table's tuple when early_word_update ran for this step, else None; sw: optim_switches()."""
+    table = rows_ahead and (rows_ahead[0], rows_ahead[0] + rows_ahead[1] * rows_ahead[2])
+    if plan is None:            # everything on the caller's stream, behind ONE wait for the whole buffer
+        cuts = [0, numel] if not table else sorted({0, numel, *table})
+        return [Launch('rows' if (lo, hi) == table else 'flat', lo, hi, 'main', 0, (0, numel) if has_grad_ready and lo == 0 else None,
+                       None, False) for lo, hi in zip(cuts, cuts[1:])]
+    # The update is HBM-bound, the next forward MFMA-bound: run the encoder's blocks on the side stream in the order the forward
+    # needs them (embeddings, layer 0, 1, ..), one event per block; the next uniter_model_forward waits block by block
+    head, blocks, word = plan[0], plan[1], plan[2] if sw.word_split else None
+    if table and (word is None or word[0] != table[0]):
+        raise UniterHipError('FusedAdam.step: early_word_update needs the word table as its own optimizer launch '
+                             '(UNITER_ADAM_WORD_SPLIT=0 or an unexpected parameter layout)')
+    wait = lambda lo, hi: (lo, hi) if has_grad_ready else None          # each launch waits for the gradients of its own range
+    out = [Launch('flat', lo, hi, 'main', 0, wait(lo, hi), None, False) for lo, hi in head]      # pooler / heads: tiny, stay on the main stream
+    for k, (lo, hi) in enumerate(blocks):
+        if k or word is None:       # the embeddings have the chip to themselves; the layers share it with the forward: its grid
+            out.append(Launch('flat', lo, hi, 'side', overlap_wgs if k else 0, wait(lo, hi), 'block', False))
+            continue
+        # the word table is a launch of its own: the next forward's image branch reads no word embedding and starts behind the
+        # block's remainder, beside the table's 0.13 ms (grid: 512 workgroups 4.83, 1024 4.79 ms bf16 step).  With rows updated
+        # ahead it takes the looked-up rows, and the mask is cleared behind IT: the next step's note_tokens waits for that
+        wgs = sw.word_wgs if sw.word_wgs is not None else min(2048, 4 * overlap_wgs)
+        tbl = Launch('rows' if table else 'flat', word[0], word[1], 'side', wgs, wait(*word), 'word', bool(table))
+        if sw.emb_main and not has_grad_ready:
+            # the remainder on the MAIN stream: in stream order, not behind an event an idle queue picks up 40-150 us late
+            out += [tbl, Launch('flat', word[1], hi, 'main', 0, None, 'block', False)]
+        else:
+            out += [Launch('flat', word[1], hi, 'side', 0, wait(word[1], hi), 'block', False), tbl]
+    return out
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam (coupled L2) / AdamW over the model's flat buffers.
 
@@ -147,8 +211,8 @@ class FusedAdam(torch.optim.Optimizer):
         # GEMM workgroup cannot start on a CU while an optimizer workgroup sits there -- the blocks should be OUT OF THE WAY fast, not
         # thin: round 6 measured 9.52 ms (256), 9.42 (512), 9.35 (1024), 9.47 (no overlap at all) per step, bf16 unchanged
         # (profiles/r06_adam_wgs_ab.txt).  UNITER_ADAM_OVERLAP_WGS fixes it for every mode
-        self._overlap_wgs_env = os.environ.get('UNITER_ADAM_OVERLAP_WGS')
-        self._overlap_wgs = int(self._overlap_wgs_env) if self._overlap_wgs_env else None
+        sw = optim_switches()
+        self._overlap_wgs = sw.overlap_wgs
         self._pending = None
         self._plan_cache = None
         # the word-embedding table's update split by rows (round 6, uniter_adam_step_rows): note_tokens / early_word_update / step
@@ -156,10 +220,10 @@ class FusedAdam(torch.optim.Optimizer):
         # profiles/r06_word_rows_ab.txt: the 100 us the head of the next forward pass no longer waits for are CU-time the ahead-of-time
         # launch takes from the forward pass it runs beside, and behind the table the next forward's own first kernels bound the head)
         # (Adam / AdamW only: uniter_adam_step_rows knows no other rule, FusedAdamax / FusedSGD never split)
-        self.split_word_rows = self.KIND is None and os.environ.get('UNITER_ADAM_WORD_ROWS', '0') == '1'
+        self.split_word_rows = self.KIND is None and sw.word_rows
         self._rowmask = None        # one byte per row of the table: 1 = a token of the micro-batches since the last step looks it up
         self._rows_noted = False    # every micro-batch since the last step announced its ids (none had a dense table gradient)
-        self._early = None          # the rows without a gradient were updated ahead: (step_count, lr, betas, eps, wd, adamw, event)
+        self._early = None          # the rows without a gradient were updated ahead: (the Hyper of that launch, the event behind it)
         self._word_cache = None
         self._rowmask_clear = None  # event behind the mask's clearing (side stream)
         self._rowmask_ready = None  # event behind the mask's last fill (the stream note_tokens ran on)
@@ -187,15 +251,18 @@ class FusedAdam(torch.optim.Optimizer):
             covered = sorted(head + blocks)
             ok = ok and covered[0][0] == 0 and covered[-1][1] == st.numel and \
                 all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
-            word = None
-            if ok:      # the word-embedding table, when it opens the embeddings' bucket: its update is a launch of its own
-                name = next((n for n in st.names if n.endswith('embeddings.word_embeddings.weight')), None)
-                if name is not None and st.offsets[name] == blocks[0][0]:
-                    end = st.offsets[name] + (st.params[name].numel() + CHUNK - 1) // CHUNK * CHUNK
-                    if end < blocks[0][1]:
-                        word = (st.offsets[name], end)
+            # the word-embedding table, when it opens the embeddings' bucket and does not fill it: its update is a launch of its own
+            w = self._find_word_table() if ok else None
+            word = (w[1], w[2]) if w is not None and w[1] == blocks[0][0] and w[2] < blocks[0][1] else None
             self._plan_cache = (head, blocks, word) if ok else False
         return self._plan_cache or None
+
+    def _find_word_table(self):
+        """(name, offset, end padded to whole chunks) of the word-embedding table in the flat buffers, or None"""
+        st = self.store
+        name = next((n for n in st.names if n.endswith('embeddings.word_embeddings.weight')), None)
+        return None if name is None else (name, st.offsets[name],
+                                          st.offsets[name] + (st.params[name].numel() + CHUNK - 1) // CHUNK * CHUNK)
 
     NORM_BLOCKS = 256           # workgroups (= partial sums) per layer slice, on the side stream beside the input-gradient chain
     NORM_BLOCKS_LAST = 2048     # the embeddings' slice runs alone behind the backward pass: the whole chip
@@ -283,13 +350,11 @@ class FusedAdam(torch.optim.Optimizer):
         if not self.split_word_rows:
             return None
         if self._word_cache is None:
-            st = self.store
-            name = next((n for n in st.names if n.endswith('embeddings.word_embeddings.weight')), None)
-            wt = False
-            if name is not None:
-                V, H = st.params[name].shape
-                if int(H) % CHUNK == 0 and st.offsets[name] % CHUNK == 0:
-                    wt = (st.offsets[name], int(V), int(H), name)
+            w, wt = self._find_word_table(), False
+            if w is not None:
+                V, H = self.store.params[w[0]].shape
+                if int(H) % CHUNK == 0 and w[1] % CHUNK == 0:
+                    wt = (w[1], int(V), int(H), w[0])
             self._word_cache = wt
         return self._word_cache or None
 
@@ -330,36 +395,63 @@ class FusedAdam(torch.optim.Optimizer):
         wt = self._word_table()
         if wt is None or self._rows_noted is not True or self._early is not None:
             return False
-        st = self.store
         g0, g1 = self.param_groups
-        lr = float(g0['lr'])
-        if float(g1['lr']) != lr:
+        if float(g1['lr']) != float(g0['lr']):
             return False
-        off, V, H, name = wt
-        flags = self._row_flags(off, V * H, no_decay(name))
-        side = stream
-        if side is None:
-            enc = self.overlap_encoder
-            side = getattr(enc, '_side_stream', None) if enc is not None else None
-        if side is None:
-            side = _lib.shared_stream(st.device, 'side')
+        h = self._hyper(self.step_count + 1)
+        side = stream if stream is not None else self._stream('side')[0]
         # behind the mask's last fill only -- NOT behind everything queued on the current stream: called in front of the forward pass, the
         # launch then runs beside it like one more of the optimizer's blocks (the side stream holds the previous step's update ahead of it)
         if self._rowmask_ready is not None:
             side.wait_event(self._rowmask_ready)
-        b1, b2 = g0['betas']
-        import ctypes as C
-        wgs = int(os.environ.get('UNITER_ADAM_EARLY_WGS', self.overlap_workgroups))
-        check(_lib.lib().uniter_adam_step_rows(st.flat_params.data_ptr() + 4 * off, st.flat_grads.data_ptr() + 4 * off,
-                                               self.exp_avg.data_ptr() + 4 * off, self.exp_avg_sq.data_ptr() + 4 * off,
-                                               flags.data_ptr(), V * H, None, 1.0, 0.0, lr, float(b1), float(b2), float(g0['eps']),
-                                               float(g0['weight_decay']), self.step_count + 1, int(self.adamw), 0,
-                                               self._rowmask.data_ptr(), H, 0, wgs, C.c_void_p(side.cuda_stream)),
-              'uniter_adam_step_rows')
+        wgs = optim_switches().early_wgs
+        check(_lib.lib().uniter_adam_step_rows(*self._rows_args(wt, h, None, Scale(1.0, 0.0, 0), 0, self.overlap_workgroups if wgs is None
+                                                                else wgs, C.c_void_p(side.cuda_stream))), 'uniter_adam_step_rows')
         ev = torch.cuda.Event()
         ev.record(side)
-        self._early = (self.step_count + 1, lr, (float(b1), float(b2)), float(g0['eps']), float(g0['weight_decay']), bool(self.adamw), ev)
+        self._early = (h, ev)
         return True
+
+    def _hyper(self, step_count):
+        """The hyper-parameters of step `step_count` (one learning rate; the decay group's weight decay: the chunk flags say where it applies)"""
+        g0 = self.param_groups[0]
+        return Hyper(float(g0['lr']), *self._rule_args(g0), float(g0['weight_decay']), step_count, int(self.adamw))
+
+    def _stream(self, which, keep=False):
+        """(torch stream, its pointer) of 'main', the caller's, or 'side': the encoder's, else the process-wide one (keep: now the encoder's)"""
+        s = torch.cuda.current_stream() if which == 'main' else getattr(self.overlap_encoder, '_side_stream', None)
+        if s is None:
+            s = _lib.shared_stream(self.store.device, 'side')
+            if keep:
+                self.overlap_encoder._side_stream = s
+        return s, C.c_void_p(s.cuda_stream)
+
+    def _rows_args(self, wt, h, sumsq, scale, pass_, max_wgs, stream_ptr):
+        """Arguments of uniter_adam_step_rows for the word table `wt`.  pass_ 0: the rows the mask does NOT name, 1: those it names"""
+        st, (off, V, H, name) = self.store, wt
+        return (st.flat_params.data_ptr() + 4 * off, st.flat_grads.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
+                self.exp_avg_sq.data_ptr() + 4 * off, self._row_flags(off, V * H, no_decay(name)).data_ptr(), V * H, sumsq,
+                scale.grad_scale, scale.max_grad_norm, *h, scale.zero_grads, self._rowmask.data_ptr(), H, pass_, max_wgs, stream_ptr)
+
+    def _range_args(self, lo, hi, max_wgs, stream_ptr, h, scale, flags, grad_bf16, layers):
+        """Arguments of uniter_adam_step_x3p / uniter_optim_step for [lo, hi).  layers: the encoder layers' range when overlapped, or None"""
+        st = self.store
+        off = lo * 4
+        # the bf16 weight mirror (precision 'bf16') is written by the same kernel, on the same stream (precision 'fp32x3': its
+        # three bf16 pieces, piece p at mirror + p * numel).  It feeds the encoder LAYERS' dense products only: blocks outside
+        # them (the 24 M parameters of the embeddings, the heads) skip its 2 - 6 bytes per parameter
+        mirror = getattr(st, 'mirror', None)
+        if mirror is not None and layers is not None and not (lo >= layers[0] and hi <= layers[1]):
+            mirror = None
+        x3 = mirror is not None and getattr(st, 'mirror_pieces', 1) == 3
+        dst = st.pair_src() if x3 else None       # fp32x3: the layers' weights go to the mirror in the paired-row layout (the launch walks the mirror's order)
+        return (st.flat_params.data_ptr() + off, st.flat_grads.data_ptr() + off,
+                (grad_bf16.data_ptr() + lo * 2) if grad_bf16 is not None else None,
+                self.exp_avg.data_ptr() + off, (self.exp_avg_sq.data_ptr() + off) if self.exp_avg_sq is not None else None,
+                flags.data_ptr() + lo // CHUNK, hi - lo, ptr(self._sumsq),
+                scale.grad_scale, scale.max_grad_norm, *h, scale.zero_grads,
+                (mirror.data_ptr() + lo * 2) if mirror is not None else None, st.numel if x3 else 0,
+                (dst.data_ptr() + 8 * (lo // CHUNK)) if dst is not None else None, lo if dst is not None else 0, max_wgs, stream_ptr)
 
     def _row_flags(self, off, n, nodecay):
         """chunk flags of the word table for the row-split launches: every chunk on the update path (decay as the tensor's group says)"""
@@ -405,11 +497,79 @@ class FusedAdam(torch.optim.Optimizer):
 
     def grad_norm(self):
         """L2 norm of all gradients touched since the last zero_grad (device tensor)."""
-        st = self.store
-        check(_lib.lib().uniter_grad_sumsq(ptr(st.flat_grads), ptr(self._chunk_flags()), st.numel,
-                                           ptr(self._sumsq), ptr(self._ws), self._ws_bytes,
-                                           _lib.cur_stream()), 'uniter_grad_sumsq')
+        self._sumsq_range(0, self.store.numel, self._sumsq.data_ptr(), self._chunk_flags(), None)
         return self._sumsq.sqrt()
+
+    def _sumsq_range(self, lo, hi, out_ptr, flags, grad_bf16):
+        """sum of squares of the gradients in [lo, hi) -- the bf16 payload's where there is one -- into the double at out_ptr"""
+        name, g = ('uniter_grad_sumsq', self.store.flat_grads.data_ptr() + 4 * lo) if grad_bf16 is None else \
+            ('uniter_grad_sumsq_bf16', grad_bf16.data_ptr() + 2 * lo)
+        check(getattr(_lib.lib(), name)(g, flags.data_ptr() + lo // CHUNK, hi - lo, out_ptr, ptr(self._ws), self._ws_bytes,
+                                        _lib.cur_stream()), name)
+
+    def _clip_norm(self, flags, max_grad_norm, grad_ready, grad_bf16, grad_pieces):
+        """Leave the squared norm of all gradients in _sumsq when the step clips.  True: it did, and grad_ready is consumed."""
+        armed, self._np_blocks = self._np_blocks, 0           # (disarmed on every step, clipping or not)
+        if not (max_grad_norm and max_grad_norm > 0):
+            return False
+        st, lib = self.store, _lib.lib()
+        pieces = sorted(grad_pieces) if (grad_ready is not None and grad_pieces) else None
+        if pieces is not None and not (pieces[0][0] == 0 and pieces[-1][1] == st.numel and
+                                       all(a[1] == b[0] for a, b in zip(pieces, pieces[1:]))):
+            pieces = None                     # the slices do not tile the buffer: one pass over all of it
+        if armed and grad_ready is None and grad_bf16 is None:
+            # the backward pass left the norm as partial sums (attach_norm_hooks): join them
+            check(lib.uniter_sumsq_combine(ptr(self._np_buf), armed, ptr(self._sumsq), _lib.cur_stream()), 'uniter_sumsq_combine')
+        elif pieces is None or len(pieces) == 1:
+            if grad_ready is not None:
+                grad_ready(0, st.numel)
+            self._sumsq_range(0, st.numel, self._sumsq.data_ptr(), flags, grad_bf16)
+        else:
+            if self._parts is None or self._parts.numel() < len(pieces):
+                self._parts = torch.zeros(max(16, len(pieces)), dtype=torch.float64, device=st.device)
+            for k, (lo, hi) in enumerate(grad_pieces):        # issue order: the early collectives have landed long ago
+                grad_ready(lo, hi)
+                self._sumsq_range(lo, hi, self._parts.data_ptr() + 8 * k, flags, grad_bf16)
+            check(lib.uniter_sumsq_combine(ptr(self._parts), len(pieces), ptr(self._sumsq), _lib.cur_stream()), 'uniter_sumsq_combine')
+        return True
+
+    def _execute(self, sched, wt, early_ev, grad_ready, h, scale, flags, grad_bf16, layers):
+        """Issue optim_schedule's launches.  wt: the word table of a 'rows' launch; early_ev: what the main stream waits for first"""
+        lib = _lib.lib()
+        flat, kind, what = (lib.uniter_adam_step_x3p, (), 'uniter_adam_step') if self.KIND is None else \
+            (lib.uniter_optim_step, (self.KIND,), 'uniter_optim_step')
+        streams = {'main': self._stream('main')}
+        events = {'block': [], 'word': []}
+        for r in sched:
+            if r.stream not in streams:         # the first launch on the side stream: behind everything queued on the main stream so far
+                streams['side'] = self._stream('side', keep=True)
+                streams['side'][0].wait_stream(streams['main'][0])
+            s, sp = streams[r.stream]
+            if r.wait is not None:
+                if r.stream == 'main':
+                    grad_ready(*r.wait)
+                else:
+                    with torch.cuda.stream(s):
+                        grad_ready(*r.wait)
+            if early_ev is not None and r is sched[0]:
+                s.wait_event(early_ev)
+            if r.kind == 'rows':
+                check(lib.uniter_adam_step_rows(*self._rows_args(wt, h, ptr(self._sumsq), scale, 1, r.max_wgs, sp)), 'uniter_adam_step_rows')
+            else:
+                check(flat(*kind, *self._range_args(r.lo, r.hi, r.max_wgs, sp, h, scale, flags, grad_bf16, layers)), what)
+            if r.clear_mask:
+                with torch.cuda.stream(s):
+                    self._rowmask.zero_()
+                self._rowmask_clear = torch.cuda.Event()
+                self._rowmask_clear.record(s)
+            if r.event is not None:
+                ev = torch.cuda.Event()
+                ev.record(s)
+                events[r.event].append(ev)
+        if events['block']:
+            # the forward pass gets the blocks' events in its own order and the word table's behind them; join() waits for the last block
+            self.overlap_encoder._set_ready_events(events['block'] + events['word'])
+            self._pending = events['block'][-1]
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, max_grad_norm=0.0, zero_grads=True, grad_ready=None, grad_bf16=None,
@@ -428,189 +588,29 @@ class FusedAdam(torch.optim.Optimizer):
         if not st.is_current():
             raise UniterHipError('model parameters were moved after the optimizer was built')
         g0, g1 = self.param_groups
-        lr = float(g0['lr'])
-        if float(g1['lr']) != lr:
+        if float(g1['lr']) != float(g0['lr']):
             raise UniterHipError('FusedAdam needs one learning rate for both parameter groups')
-        lazy = bool(zero_grads) and self.lazy_zero_encoder is not None and os.environ.get('UNITER_LAZY_ZERO') != '0'
+        sw = optim_switches()
+        lazy = bool(zero_grads) and self.lazy_zero_encoder is not None and sw.lazy_zero
         flags = self._chunk_flags(lazy)
-        lib = _lib.lib()
-        if max_grad_norm and max_grad_norm > 0:
-            def sumsq(lo, hi, out_ptr):
-                if grad_bf16 is not None:
-                    check(lib.uniter_grad_sumsq_bf16(grad_bf16.data_ptr() + 2 * lo, flags.data_ptr() + lo // CHUNK, hi - lo,
-                                                     out_ptr, ptr(self._ws), self._ws_bytes, _lib.cur_stream()),
-                          'uniter_grad_sumsq_bf16')
-                else:
-                    check(lib.uniter_grad_sumsq(st.flat_grads.data_ptr() + 4 * lo, flags.data_ptr() + lo // CHUNK, hi - lo,
-                                                out_ptr, ptr(self._ws), self._ws_bytes, _lib.cur_stream()),
-                          'uniter_grad_sumsq')
-
-            armed, self._np_blocks = self._np_blocks, 0
-            pieces = sorted(grad_pieces) if (grad_ready is not None and grad_pieces) else None
-            if pieces is not None and not (pieces[0][0] == 0 and pieces[-1][1] == st.numel and
-                                           all(a[1] == b[0] for a, b in zip(pieces, pieces[1:]))):
-                pieces = None                     # the slices do not tile the buffer: one pass over all of it
-            if armed and grad_ready is None and grad_bf16 is None:
-                # the backward pass left the norm as partial sums (attach_norm_hooks): join them
-                check(lib.uniter_sumsq_combine(ptr(self._np_buf), armed, ptr(self._sumsq), _lib.cur_stream()),
-                      'uniter_sumsq_combine')
-            elif pieces is None or len(pieces) == 1:
-                if grad_ready is not None:
-                    grad_ready(0, st.numel)
-                sumsq(0, st.numel, self._sumsq.data_ptr())
-            else:
-                if self._parts is None or self._parts.numel() < len(pieces):
-                    self._parts = torch.zeros(max(16, len(pieces)), dtype=torch.float64, device=st.device)
-                for k, (lo, hi) in enumerate(grad_pieces):        # issue order: the early collectives have landed long ago
-                    grad_ready(lo, hi)
-                    sumsq(lo, hi, self._parts.data_ptr() + 8 * k)
-                check(lib.uniter_sumsq_combine(ptr(self._parts), len(pieces), ptr(self._sumsq), _lib.cur_stream()),
-                      'uniter_sumsq_combine')
+        if self._clip_norm(flags, max_grad_norm, grad_ready, grad_bf16, grad_pieces):
             grad_ready = None
-        else:
-            self._np_blocks = 0
         self.step_count += 1
-        b1, b2, eps = self._rule_args(g0)
-
-        mirror = getattr(st, 'mirror', None)
+        h = self._hyper(self.step_count)
+        scale = Scale(float(grad_scale), float(max_grad_norm or 0.0), int(bool(zero_grads)))
         enc = self.overlap_encoder
         plan = self._overlap_plan(enc) if enc is not None else None
-        # the mirror feeds the encoder LAYERS' dense products only: blocks outside them (the 24 M parameters of the embeddings,
-        # the heads) skip its 2 - 6 bytes per parameter
-        layers_rng = (min(b[0] for b in plan[1][1:]), max(b[1] for b in plan[1][1:])) if plan is not None and len(plan[1]) > 1 else None
-
-        def launch(lo, hi, stream_ptr, max_wgs=0):
-            off = lo * 4
-            mirror = getattr(st, 'mirror', None)
-            if mirror is not None and layers_rng is not None and not (lo >= layers_rng[0] and hi <= layers_rng[1]):
-                mirror = None
-            # the bf16 weight mirror (precision 'bf16') is written by the same kernel, on the same stream
-            # (precision 'fp32x3': its three bf16 pieces, piece p at mirror + p * numel)
-            x3 = mirror is not None and getattr(st, 'mirror_pieces', 1) == 3
-            dst = st.pair_src() if x3 else None       # fp32x3: the layers' weights go to the mirror in the paired-row layout (the launch walks the mirror's order)
-            args = (st.flat_params.data_ptr() + off, st.flat_grads.data_ptr() + off,
-                    (grad_bf16.data_ptr() + lo * 2) if grad_bf16 is not None else None,
-                    self.exp_avg.data_ptr() + off, (self.exp_avg_sq.data_ptr() + off) if self.exp_avg_sq is not None else None,
-                    flags.data_ptr() + lo // CHUNK, hi - lo, ptr(self._sumsq),
-                    float(grad_scale), float(max_grad_norm or 0.0), lr, b1, b2,
-                    eps, float(g0['weight_decay']), self.step_count,
-                    int(self.adamw), int(bool(zero_grads)),
-                    (mirror.data_ptr() + lo * 2) if mirror is not None else None,
-                    st.numel if x3 else 0,
-                    (dst.data_ptr() + 8 * (lo // CHUNK)) if dst is not None else None,
-                    lo if dst is not None else 0,
-                    max_wgs, stream_ptr)
-            if self.KIND is None:
-                check(lib.uniter_adam_step_x3p(*args), 'uniter_adam_step')
-            else:
-                check(lib.uniter_optim_step(self.KIND, *args), 'uniter_optim_step')
-
-        # the word-embedding table's rows without a gradient were updated ahead (early_word_update): its launch takes the looked-up rows
+        layers = (min(b[0] for b in plan[1][1:]), max(b[1] for b in plan[1][1:])) if plan is not None and len(plan[1]) > 1 else None
+        # the word table's rows without a gradient were updated ahead (early_word_update): its launch takes the looked-up rows, and
+        # without overlap the main stream waits for the ahead-of-time launch (overlapped, both run on the side stream)
         early, self._early = self._early, None
         wt = self._word_table() if early is not None else None
-        if early is not None:
-            ok = (wt is not None and early[:6] == (self.step_count, lr, (b1, b2), eps, float(g0['weight_decay']),
-                                                  bool(self.adamw)) and grad_bf16 is None)
-            if not ok:
-                raise UniterHipError('FusedAdam.step: the word-embedding rows without a gradient were updated ahead (early_word_update) '
-                                     'for step %d / lr %g, but this step runs with other hyper-parameters or a bf16 gradient payload'
-                                     % (early[0], early[1]))
-
-        def launch_word_rows(stream_ptr, max_wgs):
-            off, V, H, name = wt
-            rf = self._row_flags(off, V * H, no_decay(name))
-            check(lib.uniter_adam_step_rows(st.flat_params.data_ptr() + 4 * off, st.flat_grads.data_ptr() + 4 * off,
-                                            self.exp_avg.data_ptr() + 4 * off, self.exp_avg_sq.data_ptr() + 4 * off, rf.data_ptr(),
-                                            V * H, ptr(self._sumsq), float(grad_scale), float(max_grad_norm or 0.0), lr, b1,
-                                            b2, eps, float(g0['weight_decay']), self.step_count, int(self.adamw),
-                                            int(bool(zero_grads)), self._rowmask.data_ptr(), H, 1, max_wgs, stream_ptr),
-                  'uniter_adam_step_rows')
-
-        if plan is None:
-            if grad_ready is not None:
-                grad_ready(0, st.numel)
-            if early is None:
-                launch(0, st.numel, _lib.cur_stream())
-            else:
-                off, V, H, _ = wt
-                we = off + V * H
-                torch.cuda.current_stream().wait_event(early[6])
-                if off > 0:
-                    launch(0, off, _lib.cur_stream())
-                launch_word_rows(_lib.cur_stream(), 0)
-                if we < st.numel:
-                    launch(we, st.numel, _lib.cur_stream())
-        else:
-            # The update is HBM-bound, the next forward MFMA-bound: run the encoder's blocks on the
-            # side stream in the order the forward needs them (embeddings, layer 0, 1, ..), one event
-            # per block; the next uniter_model_forward waits block by block instead of for all of it.
-            head, blocks, word = plan
-            if os.environ.get('UNITER_ADAM_WORD_SPLIT') == '0':
-                word = None
-            if early is not None and (word is None or word[0] != wt[0]):
-                raise UniterHipError('FusedAdam.step: early_word_update needs the word table as its own optimizer launch '
-                                     '(UNITER_ADAM_WORD_SPLIT=0 or an unexpected parameter layout)')
-            main = torch.cuda.current_stream()
-            for lo, hi in head:                                  # pooler / heads: tiny, stay on this stream
-                if grad_ready is not None:
-                    grad_ready(lo, hi)
-                launch(lo, hi, _lib.cur_stream())
-            side = enc._side_stream
-            if side is None:
-                side = enc._side_stream = _lib.shared_stream(st.device, 'side')
-            side.wait_stream(main)
-            events = []
-            import ctypes as C
-
-            def block(lo, hi, max_wgs):
-                if grad_ready is not None:
-                    with torch.cuda.stream(side):
-                        grad_ready(lo, hi)
-                if early is not None and word is not None and (lo, hi) == tuple(word):
-                    # the table's looked-up rows only (the ahead-of-time launch ran on this stream: stream order), then the 64-element
-                    # padding behind the table, if the block has any
-                    we = wt[0] + wt[1] * wt[2]
-                    launch_word_rows(C.c_void_p(side.cuda_stream), max_wgs)
-                    # the row mask belongs to the micro-batches of THIS step: cleared right behind its last reader (NOT behind the layers'
-                    # blocks that follow on this stream: the next step's note_tokens waits for this event in front of its forward pass)
-                    with torch.cuda.stream(side):
-                        self._rowmask.zero_()
-                    self._rowmask_clear = torch.cuda.Event()
-                    self._rowmask_clear.record(side)
-                    if we < hi:
-                        launch(we, hi, C.c_void_p(side.cuda_stream), max_wgs)
-                else:
-                    launch(lo, hi, C.c_void_p(side.cuda_stream), max_wgs)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                return ev
-
-            word_ev = None
-            for k, (lo, hi) in enumerate(blocks):
-                # the embeddings' block has the chip to itself (the forward waits for it); the layers' blocks share it
-                # with the forward of the layers before them: a grid that leaves the forward its wave slots
-                if k == 0 and word is not None:
-                    # everything but the word table first (2 M parameters): the next forward's image branch reads no word
-                    # embedding and starts behind this launch, beside the table's 0.13 ms of streaming (grid capped at half the chip's wave
-                    # slots: the text branch of the next forward waits for this launch -- 512 workgroups 4.83, 1024 4.79 ms bf16 step)
-                    if os.environ.get('UNITER_ADAM_EMB_MAIN', '1') != '0' and grad_ready is None:
-                        # ... on the MAIN stream: the next forward's first kernels then follow it in stream order instead of
-                        # behind a cross-stream event that an idle queue picks up 40-150 us late
-                        word_ev = block(word[0], word[1], int(os.environ.get('UNITER_ADAM_WORD_WGS', min(2048, self.overlap_workgroups * 4))))
-                        launch(word[1], hi, _lib.cur_stream(), 0)
-                        ev = torch.cuda.Event()
-                        ev.record(main)
-                        events.append(ev)
-                    else:
-                        events.append(block(word[1], hi, 0))
-                        word_ev = block(word[0], word[1], int(os.environ.get('UNITER_ADAM_WORD_WGS', min(2048, self.overlap_workgroups * 4))))
-                else:
-                    events.append(block(lo, hi, 0 if k == 0 else self.overlap_workgroups))
-            last = events[-1]                    # the side stream's last launch: what join() waits for
-            if word_ev is not None:
-                events.append(word_ev)
-            enc._set_ready_events(events)
-            self._pending = last
+        if early is not None and (wt is None or early[0] != h or grad_bf16 is not None):
+            raise UniterHipError('FusedAdam.step: the word-embedding rows without a gradient were updated ahead (early_word_update) '
+                                 'for step %d / lr %g, but this step runs with other hyper-parameters or a bf16 gradient payload'
+                                 % (early[0].step_count, early[0].lr))
+        sched = optim_schedule(st.numel, plan, wt, grad_ready is not None, self.overlap_workgroups, sw)
+        self._execute(sched, wt, early[1] if early is not None and plan is None else None, grad_ready, h, scale, flags, grad_bf16, layers)
         if early is not None or self._rows_noted is not False:
             # the row mask belongs to the micro-batches of THIS step: clear it behind its last reader
             if self._rowmask is not None and not (plan is not None and early is not None):
