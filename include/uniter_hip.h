@@ -538,7 +538,11 @@ int uniter_bce_logits(const float* logits, const int64_t* labels, float pos_weig
  * model/pretrain.py:107-203; and forward_mrc, :205-233).  Dense / tied-decoder products are uniter_gemm_f32, the
  * LayerNorm uniter_ln_*; these are the remaining pieces.
  * ------------------------------------------------------------------------- */
-/* dst[r,:] = src[idx[r],:]           (_compute_masked_hidden, model/pretrain.py:129-133) */
+/* Indices and targets outside their range (row_gather, row_scatter_add, cross_entropy_fwd / _bwd): for memory safety only, a gather
+ * index and a cross-entropy target are clamped into [0, nsrc) / [0, C) -- the forward and the backward launch clamp alike, the
+ * int64 before it is narrowed -- and a scatter row whose index lies outside [0, ndst) is skipped.  None of this is an
+ * ignore-label: callers filter those before the call, as model/pretrain.py:122-124 does.
+ * dst[r,:] = src[idx[r],:]           (_compute_masked_hidden, model/pretrain.py:129-133) */
 int uniter_row_gather(const float* src, const int64_t* idx, float* dst, int n, int H, int nsrc, void* stream);
 /* dst[idx[r],:] += src[r,:]          (its backward; idx must be unique) */
 int uniter_row_scatter_add(const float* src, const int64_t* idx, float* dst, int n, int H, int ndst, void* stream);
@@ -555,7 +559,8 @@ int uniter_kl_div_fwd(const float* logits, const float* target, float* loss, flo
                       void* stream);
 int uniter_kl_div_bwd(const float* logits, const float* target, const float* lse, const float* dloss,
                       float* dlogits, int n, int C, int ld, void* stream);
-/* MRC (model/pretrain.py:227-228): out[r] = index of the first maximum of x[r, c0:C] (absolute column) */
+/* MRC (model/pretrain.py:227-228): out[r] = index of the first maximum of x[r, c0:C] (absolute column);
+ * c0 where every value of x[r, c0:C] is -inf (torch.max returns the first column) */
 int uniter_row_argmax(const float* x, int n, int C, int ld, int c0, int64_t* out, void* stream);
 /* F.mse_loss(pred, target, reduction='none') and its backward dpred = 2 (pred - target) dloss */
 int uniter_mse_fwd(const float* pred, const float* target, float* loss, size_t n, void* stream);

@@ -34,6 +34,13 @@ __global__ __launch_bounds__(256) void row_scatter_add_kernel(const float* __res
   for (int c = lane; c < H4; c += 64) dp[c] += sp[c];
 }
 
+// A target outside [0, C) is clamped into the range, for memory safety only and the same way in the forward and the backward
+// launch (callers filter ignore-labels before the call, model/pretrain.py:122-124); the int64 is clamped before it is narrowed.
+__device__ __forceinline__ int ce_target(const int64_t* __restrict__ targets, int row, int C) {
+  const long long t = targets[row];
+  return t < 0 ? 0 : (t >= C ? C - 1 : (int)t);
+}
+
 // one 256-thread workgroup per row: lse = log sum exp(logits), loss = lse - logits[target]
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits,
                                                      const int64_t* __restrict__ targets,
@@ -57,9 +64,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   if (tid == 0) {
     const float l = mx + logf(red[0] + red[1] + red[2] + red[3]);
     lse[row] = l;
-    long long t = targets[row];
-    t = t < 0 ? 0 : (t >= C ? C - 1 : t);
-    loss[row] = l - x[t];
+    loss[row] = l - x[ce_target(targets, row, C)];
   }
 }
 
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   if (c >= C) return;
   const float g = dloss[row];
   const float p = expf(logits[(size_t)row * ld + c] - lse[row]);
-  dlogits[(size_t)row * ld + c] = (p - (c == (int)targets[row] ? 1.0f : 0.0f)) * g;
+  dlogits[(size_t)row * ld + c] = (p - (c == ce_target(targets, row, C) ? 1.0f : 0.0f)) * g;
 }
 
 // row-wise log-sum-exp shared by the KL kernels (256 threads per row)
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ l
     dlogits[o + c] = expf(logits[o + c] - l) * s - dloss[o + c] * target[o + c];
 }
 
-// one wave per row: first maximum of x[row, c0:C]
+// one wave per row: first maximum of x[row, c0:C]; a row whose every value there is -inf gives c0 (torch.max: the first column)
 __global__ __launch_bounds__(256) void row_argmax_kernel(const float* __restrict__ x, int n, int C, int ld, int c0,
                                                          int64_t* __restrict__ out) {
   const int lane = threadIdx.x & 63;
