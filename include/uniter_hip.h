@@ -681,6 +681,23 @@ int uniter_optim_step(int kind, float* params, float* grads, const void* grads_b
                       float lr, float beta1, float beta2, float eps, float weight_decay, int step, int adamw,
                       int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element,
                       int max_workgroups, void* stream);
+/* uniter_optim_step with the hyper-parameters PER PARAMETER GROUP: the reference's get_optimizer takes a group_param_func
+ * (utils/optim_utils.py:9-30) and copies every key of a returned group -- its own lr above all -- into the group's decay and no-decay
+ * halves (text_based/train_pure_text.py:27-33,53-58: a head learning rate beside the base one).  Bits 3-7 of a chunk's flag byte are
+ * its group index 0 .. 31 (bits 0-2 as before: valid bytes are 0 and (group << 3) | {1, 2, 5, 6}); lr, beta1, beta2, eps and the derived
+ * lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step) -- formed in double on the host, once per group -- are those of groups[index],
+ * weight_decay is groups[index].weight_decay where flag & 3 == 2, else 0.  The clip coefficient stays ONE value from sumsq
+ * (clip_grad_norm_ runs over all parameters jointly).  A chunk whose flag & 3 is 0 or whose group index is >= n_groups is skipped like a
+ * 0 byte: not read, not written; the kernel never reads past the table.  `groups` is HOST memory (copied into the launch's arguments).
+ * Everything else -- the walk in the mirror's order (pair_src / first_element), the bf16 gradient payload, the mirror writes, zero_grads
+ * with the keep bit, max_workgroups, the rules per `kind` (momentum = beta1 for kind 3) -- is uniter_optim_step's; with one group and
+ * today's flag bytes the results are bit-identical to it.  n_groups outside 1 .. 32 or another kind: UNITER_E_ARG, nothing launched.
+ * uniter_optim_step and the uniter_adam_step* entry points keep their contract and valid bytes (they know no groups). */
+typedef struct { float lr, beta1, beta2, eps, weight_decay; } uniter_optim_group_t;
+int uniter_optim_step_groups(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                             const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
+                             const uniter_optim_group_t* groups, int n_groups, int step, int zero_grads, void* mirror,
+                             size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream);
 int uniter_mirror_refresh_x3(const float* params_base, size_t first, size_t n, void* mirror, size_t piece_stride,
                              const int* pair_dst, void* stream);
 int uniter_adam_step_rows(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,
@@ -808,12 +825,16 @@ int uniter_model_norm_partials_per_layer(const uniter_model_t* m);
 int uniter_model_set_wgrad_overwrite(uniter_model_t* m, int on);
 /* d_hidden: same layout as hidden_out.  Accumulates into the bound gradient buffers.
  * Stages let the caller interleave gradient all-reduce with backward:
- *   uniter_model_backward_begin, then layer nl-1 .. 0, then uniter_model_backward_embed. */
+ *   uniter_model_backward_begin, then layer nl-1 .. 0, then uniter_model_backward_embed.
+ * A frozen prefix (embeddings and layers 0 .. k-1 hold no trainable parameter: text_based/train_pure_text.py:27-33 freezes the lowest
+ * layers) needs no gradient below layer k: begin, then layer nl-1 .. k, then uniter_model_backward_end INSTEAD of _embed -- it joins
+ * the side stream and closes the pass; the gradient buffers of the layers below k and of the embeddings are not written. */
 int uniter_model_backward_begin(uniter_model_t* m, const uniter_batch_t* batch, const float* d_hidden,
                                 int all_layers, uint64_t seed, uint32_t offset,
                                 void* ws, size_t ws_bytes, void* stream, void* side_stream);
 int uniter_model_backward_layer(uniter_model_t* m, int layer);
 int uniter_model_backward_embed(uniter_model_t* m);
+int uniter_model_backward_end(uniter_model_t* m);
 /* convenience: begin + all layers + embed */
 int uniter_model_backward(uniter_model_t* m, const uniter_batch_t* batch, const float* d_hidden,
                           int all_layers, uint64_t seed, uint32_t offset,

@@ -34,6 +34,11 @@ class X3RidersC(C.Structure):
                 ('out', (C.c_void_p * 3) * 4), ('first_item', C.c_int * 5)]
 
 
+class OptimGroupC(C.Structure):
+    """uniter_optim_group_t (include/uniter_hip.h): one parameter group's hyper-parameters for uniter_optim_step_groups"""
+    _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float)]
+
+
 class UniterBatchC(C.Structure):
     _fields_ = [('input_ids', C.c_void_p), ('position_ids', C.c_void_p),
                 ('txt_type_ids', C.c_void_p), ('img_feat', C.c_void_p),
@@ -161,6 +166,7 @@ _SIGS = {
     'uniter_adam_step_x3': (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _I, _P]),
     'uniter_adam_step_x3p': (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
     'uniter_optim_step': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
+    'uniter_optim_step_groups': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _P, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
     'uniter_mirror_refresh_x3': (_I, [_P, _SZ, _SZ, _P, _SZ, _P, _P]),
     'uniter_model_set_weight_pairing': (_I, [_P, _I]),
     'uniter_adam_step_rows': (_I, [_P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _I, _I, _I, _P]),
@@ -182,6 +188,7 @@ _SIGS = {
     'uniter_model_backward_begin': (_I, [_P, C.POINTER(UniterBatchC), _P, _I, _U64, _U32, _P, _SZ, _P, _P]),
     'uniter_model_backward_layer': (_I, [_P, _I]),
     'uniter_model_backward_embed': (_I, [_P]),
+    'uniter_model_backward_end': (_I, [_P]),
     'uniter_model_backward': (_I, [_P, C.POINTER(UniterBatchC), _P, _I, _U64, _U32, _P, _SZ, _P, _P]),
     'uniter_prof_enable': (_I, [_P, _I]),
     'uniter_prof_enable_stamps': (_I, [_P, _I, _P]),

@@ -1188,9 +1188,19 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
     UCHECK_HIP(hipEventRecord(m->ev_emb2, ax));
     UCHECK_HIP(hipStreamWaitEvent(st, m->ev_emb2, 0));
   }
+  return uniter_model_backward_end(m);
+}
+
+// Closes a backward pass: uniter_model_backward_embed ends here, and a pass that stops above a frozen prefix (include/uniter_hip.h)
+// calls it in place of the embeddings' backward.
+extern "C" int uniter_model_backward_end(uniter_model_t* m) {
+  UCHECK_ARG(m, "backward_end: null model");
+  if (!m->bwd_open) { uniter_set_error("backward_end: call uniter_model_backward_begin first"); return UNITER_E_STATE; }
+  hipStream_t st = m->st, sd = m->side;
+  const int nl = m->cfg.num_hidden_layers;
   if (sd != st) {   // join: everything the caller does next on `stream` sees all gradients
-    UCHECK_HIP(hipEventRecord(m->ev_side[c.num_hidden_layers], sd));
-    UCHECK_HIP(hipStreamWaitEvent(st, m->ev_side[c.num_hidden_layers], 0));
+    UCHECK_HIP(hipEventRecord(m->ev_side[nl], sd));
+    UCHECK_HIP(hipStreamWaitEvent(st, m->ev_side[nl], 0));
   }
   m->bwd_open = false;
   m->wg_overwrite = false;       // one backward pass: the next one accumulates again

@@ -16,6 +16,10 @@
 //         (the encoder's weight gradients, uniter_model_set_wgrad_overwrite) -- 28 instead of 32 bytes per parameter.
 // The kernels test the whole byte for "skip", so 4 alone is invalid (it would update and count the chunk): callers pass
 // 0, 1, 2, 5 or 6 (include/uniter_hip.h).
+// uniter_optim_step_groups alone reads bits 3-7: the chunk's parameter group, 0 .. 31, whose row of a table of hyper-parameters
+// (lr, betas, eps, weight decay: utils/optim_utils.py:9-30 copies a group's own keys into its decay and no-decay halves) the chunk is
+// updated with; its valid bytes are 0 and (group << 3) | {1, 2, 5, 6}, and a group the table does not hold is a skip.  A frozen
+// tensor's chunks are 0 whatever gradient it received.  The clip coefficient stays one value per launch.
 #include "common.h"
 #include "bf16_tile.h"
 
@@ -106,14 +110,25 @@ struct AdamArgs {
 // accesses and the mirror writes are one skeleton (adam_kernel<RULE>), the arithmetic per element is the rule's (include/uniter_hip.h,
 // uniter_optim_step).  RULE_ADAM is torch.optim.Adam / AdamW as before (the adamw flag stays a launch argument).
 enum { RULE_ADAM = 0, RULE_ADAMAX = 1, RULE_SGD = 2 };
-template <int RULE>
-__device__ __forceinline__ void adam_update4(const AdamArgs& a, float coef, float wd, f32x4& p, const f32x4& g, f32x4& m, f32x4& v) {
+// Parameter groups (uniter_optim_step_groups): bits 3-7 of a chunk's flag byte name its group, and the hyper-parameters an element
+// is updated with are its group's row of a table instead of the launch's scalars.  The rows reach the kernel by value (a kernel
+// argument of MAX_GROUPS rows) and are staged into LDS once per workgroup, by ONE thread through compile-time indices -- a per-lane
+// index into a by-value argument would make the compiler copy the table into private memory; per item a lane then reads its group's
+// 32 bytes from LDS (the lanes of a group read one address: a broadcast).  GROUPED is a compile-time variant of the walk: the
+// instantiations behind every other entry point are the code they were.
+constexpr int MAX_GROUPS = 32;
+struct GroupRow { float lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, pad; };
+struct GroupTable { int n; GroupRow row[MAX_GROUPS]; };
+
+// H: where lr, b1, b2, eps, step_size and inv_sqrt_bc2 come from -- the launch's arguments or the chunk's GroupRow
+template <int RULE, class H>
+__device__ __forceinline__ void adam_update4(const H& a, int adamw, float coef, float wd, f32x4& p, const f32x4& g, f32x4& m, f32x4& v) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float gg = g[e] * coef;
     float pp = p[e];
     if constexpr (RULE == RULE_ADAM) {
-      if (a.adamw) pp *= 1.0f - a.lr * wd;
+      if (adamw) pp *= 1.0f - a.lr * wd;
       else gg += wd * pp;
       m[e] = a.b1 * m[e] + (1.0f - a.b1) * gg;
       v[e] = a.b2 * v[e] + (1.0f - a.b2) * gg * gg;
@@ -161,8 +176,23 @@ __device__ __forceinline__ bool any_nonzero(const f32x4& g) { return g[0] != 0.f
 // Two 16-byte elements per thread and iteration, all eight loads issued before the arithmetic: a grid of one or two
 // workgroups per CU (the launch that shares the chip with the next forward, see trainer.FusedAdam) still keeps
 // 32-64 KB per CU in flight.  (RULE_SGD: six loads, a.v is never touched and may be NULL.)
-template <int RULE>
-__global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
+template <bool GROUPED> struct WalkArgs { AdamArgs a; };
+template <> struct WalkArgs<true> { AdamArgs a; GroupTable t; };
+
+template <int RULE, bool GROUPED>
+__global__ __launch_bounds__(256) void adam_kernel(const WalkArgs<GROUPED> w) {
+  const AdamArgs& a = w.a;
+  __shared__ GroupRow rows[GROUPED ? MAX_GROUPS : 1];
+  int n_groups = 0;
+  if constexpr (GROUPED) {
+    n_groups = w.t.n;
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < MAX_GROUPS; ++k)
+        if (k < w.t.n) rows[k] = w.t.row[k];
+    }
+    __syncthreads();
+  }
   float coef = a.gscale;
   if (a.max_norm > 0.f && a.sumsq) {
     const float total = (float)sqrt(a.sumsq[0]) * a.gscale;         // norm of the averaged grads
@@ -186,11 +216,14 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     }
     uint8_t f0 = a.flags[(si * 4) / CHUNK];
     uint8_t f1 = two ? a.flags[(sj * 4) / CHUNK] : 0;
-    if (a.rowmask) {      // (one table, split by rows: this launch takes the rows on its side of the mask)
+    if constexpr (GROUPED) {      // a chunk off the update path, or of a group the table does not hold: a 0 byte
+      if ((f0 & 3) == 0 || (f0 >> 3) >= n_groups) f0 = 0;
+      if ((f1 & 3) == 0 || (f1 >> 3) >= n_groups) f1 = 0;
+    } else if (a.rowmask) {      // (one table, split by rows: this launch takes the rows on its side of the mask)
       if (f0 && (a.rowmask[((si * 4) / CHUNK) / a.row_chunks] != 0) != (a.rows_want != 0)) f0 = 0;
       if (f1 && (a.rowmask[((sj * 4) / CHUNK) / a.row_chunks] != 0) != (a.rows_want != 0)) f1 = 0;
     }
-    const bool no_g = a.rowmask && a.rows_want == 0;      // rows without a gradient this step: g == 0, unread
+    const bool no_g = !GROUPED && a.rowmask && a.rows_want == 0;      // rows without a gradient this step: g == 0, unread
     f32x4 p0, g0 = {0.f, 0.f, 0.f, 0.f}, m0, v0, p1, g1 = g0, m1, v1;
     if (f0) {
       p0 = NT_LOAD(a.p, si); if (!no_g) g0 = a.g16 ? widen4(a.g16, si) : NT_LOAD(a.g, si); m0 = NT_LOAD(a.m, si);
@@ -203,11 +236,15 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     // (gradients read from the bf16 payload: the fp32 buffer holds this rank's own sums, cleared whatever the payload says)
     if (f0) {
       const bool c0 = !no_g && a.zero_grads && !(f0 & 4) && (a.g16 != nullptr || any_nonzero(g0));
-      adam_update4<RULE>(a, coef, (f0 & 3) == 2 ? a.wd : 0.f, p0, g0, m0, v0); adam_store4<RULE>(a, i, si, p0, m0, v0, c0);
+      if constexpr (GROUPED) { const GroupRow h = rows[f0 >> 3]; adam_update4<RULE>(h, a.adamw, coef, (f0 & 3) == 2 ? h.wd : 0.f, p0, g0, m0, v0); }
+      else adam_update4<RULE>(a, a.adamw, coef, (f0 & 3) == 2 ? a.wd : 0.f, p0, g0, m0, v0);
+      adam_store4<RULE>(a, i, si, p0, m0, v0, c0);
     }
     if (f1) {
       const bool c1 = !no_g && a.zero_grads && !(f1 & 4) && (a.g16 != nullptr || any_nonzero(g1));
-      adam_update4<RULE>(a, coef, (f1 & 3) == 2 ? a.wd : 0.f, p1, g1, m1, v1); adam_store4<RULE>(a, j, sj, p1, m1, v1, c1);
+      if constexpr (GROUPED) { const GroupRow h = rows[f1 >> 3]; adam_update4<RULE>(h, a.adamw, coef, (f1 & 3) == 2 ? h.wd : 0.f, p1, g1, m1, v1); }
+      else adam_update4<RULE>(a, a.adamw, coef, (f1 & 3) == 2 ? a.wd : 0.f, p1, g1, m1, v1);
+      adam_store4<RULE>(a, j, sj, p1, m1, v1, c1);
     }
   }
 }
@@ -310,7 +347,7 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                           size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream);
+                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups = nullptr);
 
 extern "C" int uniter_adam_step_x3(float* params, float* grads, const void* grads_bf16, float* exp_avg,
                                    float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
@@ -360,7 +397,7 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                           size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream) {
+                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups) {
   UCHECK_SHAPE(mirror_piece_stride % 4 == 0 && (mirror_piece_stride == 0 || mirror_bf16), "adam_step: bad mirror piece stride");
   UCHECK_ARG(params && grads && exp_avg && (exp_avg_sq || rule == RULE_SGD) && chunk_flags, "adam_step: null pointer");
   UCHECK_SHAPE(((uintptr_t)grads_bf16 & 7) == 0, "adam_step: bf16 gradients must be 8-byte aligned");
@@ -387,9 +424,15 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
     const size_t full = (a.n4 + 511) / 512;
     nb = (int)(full < (size_t)max_workgroups ? (full < 1 ? 1 : full) : (size_t)max_workgroups);
   }
-  if (rule == RULE_ADAMAX) hipLaunchKernelGGL(adam_kernel<RULE_ADAMAX>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
-  else if (rule == RULE_SGD) hipLaunchKernelGGL(adam_kernel<RULE_SGD>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(adam_kernel<RULE_ADAM>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  if (groups) {      // (uniter_optim_step_groups: the scalars above are unused, every chunk reads its group's row)
+    const WalkArgs<true> wg = {a, *groups};
+    if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+    else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+    else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+  }
+  else if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
+  else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
+  else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
   UCHECK_LAUNCH();
   return 0;
 }
@@ -411,4 +454,30 @@ extern "C" int uniter_optim_step(int kind, float* params, float* grads, const vo
   return adam_step_impl(kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg, kind == 3 ? nullptr : exp_avg_sq,
                         chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, step, 0, zero_grads, mirror,
                         mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element, stream);
+}
+
+// uniter_optim_step with the hyper-parameters PER PARAMETER GROUP (include/uniter_hip.h): bits 3-7 of a chunk's flag name its row of
+// `groups` (host memory, copied into the launch's arguments); the clip coefficient stays one value for the launch.
+extern "C" int uniter_optim_step_groups(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
+                                        float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
+                                        float grad_scale, float max_norm, const uniter_optim_group_t* groups, int n_groups,
+                                        int step, int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src,
+                                        size_t first_element, int max_workgroups, void* stream) {
+  UCHECK_ARG(kind >= 0 && kind <= 3, "optim_step_groups: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)");
+  UCHECK_ARG(groups && n_groups >= 1 && n_groups <= MAX_GROUPS, "optim_step_groups: n_groups must be 1 .. 32 (got %d) with a table", n_groups);
+  UCHECK_ARG(step >= 1, "optim_step_groups: step must be >= 1");
+  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
+             "optim_step_groups: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
+  GroupTable t;
+  t.n = n_groups;
+  for (int k = 0; k < MAX_GROUPS; ++k) {
+    const uniter_optim_group_t& g = groups[k < n_groups ? k : 0];
+    const double bc1 = 1.0 - pow((double)g.beta1, (double)step);      // (formed in double, once per group, as adam_step_impl does)
+    const double bc2 = 1.0 - pow((double)g.beta2, (double)step);
+    t.row[k] = GroupRow{g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, (float)((double)g.lr / bc1), (float)(1.0 / sqrt(bc2)), 0.f};
+  }
+  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
+                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, 0.f, 0.f, 0.f, 0.f, 0.f, step,
+                        kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element,
+                        stream, &t);
 }

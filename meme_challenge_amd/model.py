@@ -779,6 +779,7 @@ class UniterModel(UniterPreTrainedModel):
         self._handle = None
         self._prefix_names = None
         self._applied_precision = None
+        self._floor_asked = 0        # freeze_prefix: the backward pass may end above this layer (backward_floor)
         object.__setattr__(self, '_store_root', None)
         self._ws_cache = {}
         self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
@@ -892,13 +893,17 @@ class UniterModel(UniterPreTrainedModel):
             ids = {id(p): n for n, p in root.named_parameters()}
             self._prefix_names = {n: ids[id(p)] for n, p in self.named_parameters()}
             self._touch_lists = {}
-        key = (bool(batch.input_ids), bool(batch.img_feat), bool(batch.img_masks))
+        floor = self.backward_floor()
+        key = (bool(batch.input_ids), bool(batch.img_feat), bool(batch.img_masks), floor)
         if key in self._touch_lists:
             return self._touch_lists[key]
+        mine = dict(self.named_parameters())
         out = []
         for local, full in self._prefix_names.items():
             if local.startswith('pooler.'):
                 continue
+            if floor > 0 and not mine[local].requires_grad:
+                continue         # below the floor of a frozen prefix: the backward pass does not go there
             if local.startswith('img_embeddings.'):
                 if not batch.img_feat:
                     continue
@@ -939,14 +944,51 @@ class UniterModel(UniterPreTrainedModel):
         hook = self._grad_hook
         if hook is not None:
             hook('begin', None, side or main)
-        for l in range(nl - 1, -1, -1):
+        # a frozen prefix (freeze_prefix): nothing below layer `floor` holds a trainable parameter, so the pass ends above it --
+        # no backward of those layers, none of the embeddings -- and the hooks see the layers that ran
+        floor = self.backward_floor()
+        for l in range(nl - 1, floor - 1, -1):
             check(lib.uniter_model_backward_layer(self._handle, l), 'uniter_model_backward_layer')
             if hook is not None:
                 hook('layer', l, side or main)
+        if floor > 0:
+            check(lib.uniter_model_backward_end(self._handle), 'uniter_model_backward_end')
+            st.touch(self._touched_names(batch))
+            return
         check(lib.uniter_model_backward_embed(self._handle), 'uniter_model_backward_embed')
         st.touch(self._touched_names(batch))
         if hook is not None:
             hook('embed', None, main)
+
+    def freeze_prefix(self, n_layers, embeddings=True):
+        """Hold the lowest part of the model fixed, as the reference's fine-tuning recipe does (text_based/train_pure_text.py:27-33):
+        requires_grad = False on the text and image embeddings (`embeddings`) and on encoder layers < n_layers.  Call it before
+        the optimizer is built (trainer.get_optimizer reads requires_grad once, as torch optimizers read their parameter list).
+        Returns the backward pass's floor (backward_floor): with it > 0 a training step runs no backward below that layer."""
+        nl = self.config.num_hidden_layers
+        frozen = [self.encoder.layer[l] for l in range(max(0, min(int(n_layers), nl)))]
+        if embeddings:
+            frozen += [self.embeddings, self.img_embeddings]
+        for mod in frozen:
+            for p_ in mod.parameters():
+                p_.requires_grad = False
+        self._touch_lists = {}
+        self._floor_asked = nl
+        self._floor_asked = self.backward_floor()
+        return self._floor_asked
+
+    def backward_floor(self):
+        """The first encoder layer the backward pass has to visit: k when freeze_prefix was called and the embeddings and layers
+        0 .. k-1 (still) hold no trainable parameter, else 0.  Any other pattern -- a frozen layer above a trainable one, trainable
+        embeddings, requires_grad cleared by hand -- runs the full pass, and the optimizer ignores what it does not own."""
+        if self._floor_asked <= 0:
+            return 0
+        if any(p_.requires_grad for mod in (self.embeddings, self.img_embeddings) for p_ in mod.parameters()):
+            return 0
+        k, nl = 0, min(self._floor_asked, self.config.num_hidden_layers)
+        while k < nl and not any(p_.requires_grad for p_ in self.encoder.layer[k].parameters()):
+            k += 1
+        return k
 
     def norm_partials_per_layer(self):
         """Partial sums of the clip norm each layer's backward leaves by itself in the CURRENT precision (fp32x3: its
@@ -1076,12 +1118,16 @@ class UniterModel(UniterPreTrainedModel):
         if self.pack_padded and b.L <= _lib.lib().uniter_attn_varlen_max_len():
             self._pack(b, keep, attention_mask, gather_index, seq_lens)
 
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        trainable = next((p for p in self.parameters() if p.requires_grad), None)
+        grad = torch.is_grad_enabled() and trainable is not None
         mode = 0 if not grad else (1 if self.training else 2)
         seed, offset = self._seed, self._offset
         if mode == 1:
             self._offset = (self._offset + 1) & 0xFFFFFFFF
-        anchor = self.embeddings.LayerNorm.weight if grad else self.embeddings.LayerNorm.weight.detach()
+        anchor = self.embeddings.LayerNorm.weight
+        if grad and not anchor.requires_grad:      # (frozen embeddings: any trainable parameter makes autograd call the backward pass)
+            anchor = trainable
+        anchor = anchor if grad else anchor.detach()
         hidden = _UniterFn.apply(anchor, self, b, keep, bool(output_all_encoded_layers), mode, seed, offset)
         if output_all_encoded_layers:
             return [hidden[i] for i in range(self.config.num_hidden_layers)]

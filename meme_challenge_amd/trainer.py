@@ -4,7 +4,7 @@ Mirrors:
   nn.BCEWithLogitsLoss(pos_weight)            train_template.py:64-65
   TrainerTemplate.calculate_loss              train_template.py:95-126
   TrainerTemplate.average_gradients           train_template.py:89-92
-  get_optimizer (param-group split, Adam/AdamW) utils/optim_utils.py:9-46
+  get_optimizer (group_param_func, param-group split, Adam/AdamW/Adamax/SGD) utils/optim_utils.py:9-46
   init_scheduler (warmup / warmup_cosine / step / multi_step)  train_template.py:72-82
   TrainerUniter.{train,eval,test}_iter_step    train_uniter.py:58-81
 
@@ -113,6 +113,10 @@ def no_decay(name):
 
 
 Hyper = namedtuple('Hyper', 'lr b1 b2 eps weight_decay step_count adamw')      # in the order the library's entry points take them
+# the same stretch of uniter_optim_step_groups' arguments: the table of per-group hyper-parameters (an _lib.OptimGroupC array) in
+# the place of the scalars; `rows` repeats it as plain tuples (lr, b1, b2, eps, weight_decay) so that two steps' values compare
+GroupHyper = namedtuple('GroupHyper', 'table n_groups step_count')
+MAX_PARAM_GROUPS = 32       # bits 3-7 of a chunk's flag byte
 Scale = namedtuple('Scale', 'grad_scale max_grad_norm zero_grads')
 # One launch of a step.  kind: 'flat' (the flat buffers' range [lo, hi)) or 'rows' (the looked-up rows of the word table [lo, hi));
 # stream: 'main' or 'side'; wait: the range that stream waits for through grad_ready in front of the launch, or None; event: None,
@@ -120,9 +124,72 @@ Scale = namedtuple('Scale', 'grad_scale max_grad_norm zero_grads')
 Launch = namedtuple('Launch', 'kind lo hi stream max_wgs wait event clear_mask')
 
 
-def optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw):
+def group_layout(named, weight_decay, group_param_func=None):
+    """utils/optim_utils.py:9-30 on plain values: the (name, parameter) pairs, grouped by `group_param_func` (the pairs -> a list of
+    dicts whose 'params' are such pairs; None: one group of everything), each group split into its decay and its no-decay half in
+    the reference's order [decay_0, nodecay_0, decay_1, ..], every key other than 'params' / 'weight_decay' copied into both.
+    -> the list of dicts, 'params' still (name, parameter) pairs.  Every parameter must be named exactly once."""
+    named = list(named)
+    if group_param_func is None:
+        groups = [{'params': named}]
+    else:
+        groups = group_param_func(named)
+        if not isinstance(groups, (list, tuple)) or not groups or not all(
+                isinstance(g, dict) and isinstance(g.get('params'), (list, tuple)) and
+                all(isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], str) for e in g['params']) for g in groups):
+            raise UniterHipError("group_param_func must return a non-empty list of dicts whose 'params' are (name, parameter) "
+                                 'pairs (utils/optim_utils.py:9-30); got %s' % (type(groups).__name__ if not isinstance(groups, (list, tuple))
+                                                                               else 'a list that holds something else'))
+        if 2 * len(groups) > MAX_PARAM_GROUPS:
+            raise UniterHipError('group_param_func returned %d groups: at most %d (each becomes a decay and a no-decay group, and '
+                                 '%d fit the chunk flags)' % (len(groups), MAX_PARAM_GROUPS // 2, MAX_PARAM_GROUPS))
+        seen, known = set(), {n for n, _ in named}
+        for g in groups:
+            for n, _ in g['params']:
+                if n in seen:
+                    raise UniterHipError('group_param_func names parameter %r twice' % n)
+                if n not in known:
+                    raise UniterHipError('group_param_func names %r, which is no parameter of the model' % n)
+                seen.add(n)
+        left = [n for n, _ in named if n not in seen]
+        if left:
+            raise UniterHipError('group_param_func leaves %d parameter(s) out, the first of them %r' % (len(left), left[0]))
+    out = []
+    for g in groups:
+        extra = {k: v for k, v in g.items() if k not in ('params', 'weight_decay')}
+        out.append(dict(extra, params=[(n, p) for n, p in g['params'] if not no_decay(n)], weight_decay=weight_decay))
+        out.append(dict(extra, params=[(n, p) for n, p in g['params'] if no_decay(n)], weight_decay=0.0))
+    return out
+
+
+def chunk_flag_bytes(nchunks, offsets, sizes, touched, frozen=(), keep=(), group_bits=None):
+    """The optimizer's flag byte per 64-element chunk, from plain values.  offsets / sizes: name -> first element / element count;
+    touched: the names that received a gradient; frozen: names that are never updated (byte 0 whatever `touched` says -- neither
+    the step nor the norm kernels read or write them); keep: names whose gradient zero_grads leaves alone (+ 4).
+    group_bits None: 1 (no weight decay) / 2 (weight decay) by name, as every entry point but uniter_optim_step_groups takes them;
+    else name -> (group index, decays): (index << 3) | 2 or 1."""
+    host = torch.zeros(nchunks, dtype=torch.uint8)
+    for n in touched:
+        if n in frozen:
+            continue
+        o, k = offsets[n] // CHUNK, (sizes[n] + CHUNK - 1) // CHUNK
+        if group_bits is None:
+            byte = 1 if no_decay(n) else 2
+        else:
+            index, decays = group_bits[n]
+            byte = (index << 3) | (2 if decays else 1)
+        host[o:o + k] = byte + (4 if n in keep else 0)
+    return host
+
+
+def optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw, trainable=None):
     """The launches of one FusedAdam.step in issue order, from plain values.  plan: _overlap_plan's (head, blocks, word) or None;
-    rows_ahead: _word_table's tuple when early_word_update ran for this step, else None; sw: optim_switches()."""
+    rows_ahead: _word_table's tuple when early_word_update ran for this step, else None; sw: optim_switches(); trainable: the
+    element ranges [(lo, hi), ..] that hold parameters the optimizer updates, or None = everything: a launch whose range meets
+    none of them is dropped, together with its event (frozen parameters: FusedAdam._trainable_ranges)."""
+    if trainable is not None:
+        live = lambda r: any(lo < r.hi and r.lo < hi for lo, hi in trainable)
+        return [r for r in optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw) if live(r)]
     table = rows_ahead and (rows_ahead[0], rows_ahead[0] + rows_ahead[1] * rows_ahead[2])
     if plan is None:            # everything on the caller's stream, behind ONE wait for the whole buffer
         cuts = [0, numel] if not table else sorted({0, numel, *table})
@@ -156,9 +223,12 @@ def optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw):
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam (coupled L2) / AdamW over the model's flat buffers.
 
-    ``param_groups`` keeps the reference's two-group layout (decay / no-decay) so
+    ``param_groups`` keeps the reference's layout -- a decay and a no-decay group, or such a pair per group a
+    ``group_param_func`` returns (group_layout), each with the keys (``lr``, ..) the function gave it -- so
     LR schedulers written against torch optimizers keep working; the arithmetic is
-    one kernel launch.  ``step()`` also performs ``average_gradients`` (``grad_scale``)
+    one kernel launch, which reads a chunk's hyper-parameters from its group's row once the groups differ
+    (uniter_optim_step_groups).  Parameters whose ``requires_grad`` is False when the optimizer is built are never
+    read or written.  ``step()`` also performs ``average_gradients`` (``grad_scale``)
     and ``clip_grad_norm_`` (``max_grad_norm``) when asked to, and zeroes the
     gradients (the reference calls ``zero_grad`` right after ``step``).
 
@@ -170,16 +240,20 @@ class FusedAdam(torch.optim.Optimizer):
     KIND = None             # None: torch.optim.Adam / AdamW through uniter_adam_step_x3p; 2 / 3: uniter_optim_step's Adamax / SGD
     SECOND_STATE = True     # the rule keeps exp_avg_sq (Adam's second moment, Adamax's infinity norm)
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False, defaults=None):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False, defaults=None, group_param_func=None, layout=None):
         self.model = model
         self.store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
-        named = list(model.named_parameters())
-        decay = [p for n, p in named if not no_decay(n)]
-        nodecay = [p for n, p in named if no_decay(n)]
+        if layout is None:      # (get_optimizer passes the layout it already built: `group_param_func` is called once)
+            layout = group_layout(list(model.named_parameters()), weight_decay, group_param_func)
         if defaults is None:
             defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        super().__init__([{'params': decay, 'weight_decay': weight_decay},
-                          {'params': nodecay, 'weight_decay': 0.0}], defaults)
+        super().__init__([dict(g, params=[p for _, p in g['params']]) for g in layout], defaults)
+        # per parameter, under the store's names: its param_group and whether that is a decay half; and the frozen ones --
+        # requires_grad is read HERE, once, as torch optimizers read their parameter list
+        by_id = {id(p): (k, k % 2 == 0) for k, g in enumerate(layout) for _, p in g['params']}
+        params = getattr(self.store, 'params', {})
+        self._group_of = {n: by_id[id(p)] for n, p in params.items() if id(p) in by_id}
+        self._frozen = frozenset(n for n, p in params.items() if not p.requires_grad)
         self.adamw = bool(adamw)
         self.step_count = 0
         st = self.store
@@ -276,8 +350,8 @@ class FusedAdam(torch.optim.Optimizer):
         joins the partial sums (one 1-workgroup launch) instead of streaming all 440 MB of gradients once more
         behind the backward pass.  Single process only: with a data-parallel exchange attached the norm is that of the
         REDUCED gradients (dp.GradSync.pieces)."""
-        if getattr(encoder, '_grad_hook', None) is not None:
-            return False
+        if getattr(encoder, '_grad_hook', None) is not None or self._frozen:
+            return False         # (frozen parameters: the partial sums cover whole layers; the flag-aware pass takes the norm)
         st = self.store
         nb = len(st.bucket_ranges)
         nl = encoder.config.num_hidden_layers
@@ -346,12 +420,12 @@ class FusedAdam(torch.optim.Optimizer):
     # -- the word-embedding table, row by row ---------------------------------------------------------------------------
     def _word_table(self):
         """(offset, rows, row length) of the word-embedding table in the flat buffers, or None (no such tensor, a row length
-        that is no multiple of the optimizer's 64-element chunks, or the split switched off)."""
+        that is no multiple of the optimizer's 64-element chunks, a frozen table, or the split switched off)."""
         if not self.split_word_rows:
             return None
         if self._word_cache is None:
             w, wt = self._find_word_table(), False
-            if w is not None:
+            if w is not None and w[0] not in self._frozen:      # (the row-split launches know no frozen chunk: a frozen table has none)
                 V, H = self.store.params[w[0]].shape
                 if int(H) % CHUNK == 0 and w[1] % CHUNK == 0:
                     wt = (w[1], int(V), int(H), w[0])
@@ -395,8 +469,7 @@ class FusedAdam(torch.optim.Optimizer):
         wt = self._word_table()
         if wt is None or self._rows_noted is not True or self._early is not None:
             return False
-        g0, g1 = self.param_groups
-        if float(g1['lr']) != float(g0['lr']):
+        if not self._uniform():
             return False
         h = self._hyper(self.step_count + 1)
         side = stream if stream is not None else self._stream('side')[0]
@@ -416,6 +489,28 @@ class FusedAdam(torch.optim.Optimizer):
         """The hyper-parameters of step `step_count` (one learning rate; the decay group's weight decay: the chunk flags say where it applies)"""
         g0 = self.param_groups[0]
         return Hyper(float(g0['lr']), *self._rule_args(g0), float(g0['weight_decay']), step_count, int(self.adamw))
+
+    def _uniform(self):
+        """Do all parameter groups step with the same hyper-parameters -- one lr, one set of betas / momentum and eps, ONE weight
+        decay on the decay halves and none elsewhere?  Then the step is the launch with scalars it always was."""
+        gs = self.param_groups
+        g0 = gs[0]
+        one = (float(g0['lr']), self._rule_args(g0))
+        return all((float(g['lr']), self._rule_args(g)) == one and
+                   float(g['weight_decay']) == (float(g0['weight_decay']) if k % 2 == 0 else 0.0) for k, g in enumerate(gs))
+
+    def _group_hyper(self, step_count):
+        """The table of uniter_optim_step_groups: one row per parameter group, in param_groups' order"""
+        gs = self.param_groups
+        table = (_lib.OptimGroupC * len(gs))(*[_lib.OptimGroupC(float(g['lr']), *self._rule_args(g), float(g['weight_decay'])) for g in gs])
+        return GroupHyper(table, len(gs), step_count)
+
+    def _trainable_ranges(self):
+        """Element ranges of the tensors this optimizer updates, or None when nothing is frozen (optim_schedule's `trainable`)"""
+        if not self._frozen:
+            return None
+        st = self.store
+        return [(st.offsets[n], st.offsets[n] + st.params[n].numel()) for n in st.names if n not in self._frozen]
 
     def _stream(self, which, keep=False):
         """(torch stream, its pointer) of 'main', the caller's, or 'side': the encoder's, else the process-wide one (keep: now the encoder's)"""
@@ -476,18 +571,19 @@ class FusedAdam(torch.optim.Optimizer):
     LAZY_SUFFIXES = ('attention.self.query.weight', 'attention.self.key.weight', 'attention.self.value.weight',
                      'attention.output.dense.weight', 'intermediate.dense.weight', 'output.dense.weight')
 
-    def _chunk_flags(self, lazy=False):
+    def _chunk_flags(self, lazy=False, grouped=False):
+        """grouped: the bytes of uniter_optim_step_groups -- the tensor's parameter group in bits 3-7, and weight decay (2) wherever
+        the group's own weight_decay is not 0"""
         st = self.store
-        key = (frozenset(st.touched), bool(lazy))
+        decays = tuple(float(g['weight_decay']) != 0.0 for g in self.param_groups) if grouped else None
+        key = (frozenset(st.touched), bool(lazy)) if not grouped else (frozenset(st.touched), bool(lazy), decays)
         if key != self._flags_key:
             flags = self._flags_cache.get(key)
             if flags is None:
-                host = torch.zeros(st.numel // CHUNK, dtype=torch.uint8)
-                for n in st.touched:
-                    o = st.offsets[n] // CHUNK
-                    k = (st.params[n].numel() + CHUNK - 1) // CHUNK
-                    keep = 4 if (lazy and '.encoder.layer.' in '.' + n and n.endswith(self.LAZY_SUFFIXES)) else 0
-                    host[o:o + k] = (1 if no_decay(n) else 2) + keep
+                keep = [n for n in st.touched if lazy and '.encoder.layer.' in '.' + n and n.endswith(self.LAZY_SUFFIXES)]
+                bits = {n: (k, decays[k]) for n, (k, _) in self._group_of.items()} if grouped else None
+                host = chunk_flag_bytes(st.numel // CHUNK, st.offsets, {n: st.params[n].numel() for n in st.touched}, st.touched,
+                                        self._frozen, frozenset(keep), bits)
                 flags = host.to(st.device)
                 if len(self._flags_cache) < 16:
                     self._flags_cache[key] = flags
@@ -517,7 +613,7 @@ class FusedAdam(torch.optim.Optimizer):
         if pieces is not None and not (pieces[0][0] == 0 and pieces[-1][1] == st.numel and
                                        all(a[1] == b[0] for a, b in zip(pieces, pieces[1:]))):
             pieces = None                     # the slices do not tile the buffer: one pass over all of it
-        if armed and grad_ready is None and grad_bf16 is None:
+        if armed and grad_ready is None and grad_bf16 is None and not self._frozen:
             # the backward pass left the norm as partial sums (attach_norm_hooks): join them
             check(lib.uniter_sumsq_combine(ptr(self._np_buf), armed, ptr(self._sumsq), _lib.cur_stream()), 'uniter_sumsq_combine')
         elif pieces is None or len(pieces) == 1:
@@ -533,13 +629,16 @@ class FusedAdam(torch.optim.Optimizer):
             check(lib.uniter_sumsq_combine(ptr(self._parts), len(pieces), ptr(self._sumsq), _lib.cur_stream()), 'uniter_sumsq_combine')
         return True
 
-    def _execute(self, sched, wt, early_ev, grad_ready, h, scale, flags, grad_bf16, layers):
-        """Issue optim_schedule's launches.  wt: the word table of a 'rows' launch; early_ev: what the main stream waits for first"""
+    def _execute(self, sched, wt, early_ev, grad_ready, h, scale, flags, grad_bf16, layers, blocks=None):
+        """Issue optim_schedule's launches.  wt: the word table of a 'rows' launch; early_ev: what the main stream waits for first;
+        blocks: the plan's blocks when launches may have been dropped from `sched` (frozen parameters), else None"""
         lib = _lib.lib()
         flat, kind, what = (lib.uniter_adam_step_x3p, (), 'uniter_adam_step') if self.KIND is None else \
             (lib.uniter_optim_step, (self.KIND,), 'uniter_optim_step')
+        if isinstance(h, GroupHyper):       # every 'flat' launch with its chunks' own hyper-parameters
+            flat, kind, what = lib.uniter_optim_step_groups, (int(self.adamw) if self.KIND is None else self.KIND,), 'uniter_optim_step_groups'
         streams = {'main': self._stream('main')}
-        events = {'block': [], 'word': []}
+        events, by_range = {'block': [], 'word': []}, {}
         for r in sched:
             if r.stream not in streams:         # the first launch on the side stream: behind everything queued on the main stream so far
                 streams['side'] = self._stream('side', keep=True)
@@ -566,10 +665,21 @@ class FusedAdam(torch.optim.Optimizer):
                 ev = torch.cuda.Event()
                 ev.record(s)
                 events[r.event].append(ev)
-        if events['block']:
+                by_range[(r.lo, r.hi)] = ev
+        if events['block'] or events['word']:
             # the forward pass gets the blocks' events in its own order and the word table's behind them; join() waits for the last block
-            self.overlap_encoder._set_ready_events(events['block'] + events['word'])
-            self._pending = events['block'][-1]
+            ready = events['block'] + events['word']
+            if blocks is not None and len(events['block']) != len(blocks):
+                # launches were dropped (frozen blocks): the forward pass still takes one event per block, in its order -- a block
+                # without an update gets an event of the main stream, which the forward pass (on that stream) is behind already
+                idle = torch.cuda.Event()
+                idle.record(streams['main'][0])
+                ready = [next((ev for (lo, hi), ev in by_range.items() if b[0] <= lo and hi <= b[1] and ev in events['block']), idle)
+                         for b in blocks] + events['word']
+            self.overlap_encoder._set_ready_events(ready)
+            self._pending = (events['block'] or events['word'])[-1]     # (only the word table trainable: its launch is the last)
+        elif blocks is not None:
+            self.overlap_encoder._set_ready_events([])      # every block frozen: the forward pass waits for nothing of this step
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, max_grad_norm=0.0, zero_grads=True, grad_ready=None, grad_bf16=None,
@@ -587,16 +697,14 @@ class FusedAdam(torch.optim.Optimizer):
         st = self.store
         if not st.is_current():
             raise UniterHipError('model parameters were moved after the optimizer was built')
-        g0, g1 = self.param_groups
-        if float(g1['lr']) != float(g0['lr']):
-            raise UniterHipError('FusedAdam needs one learning rate for both parameter groups')
+        grouped = not self._uniform()
         sw = optim_switches()
         lazy = bool(zero_grads) and self.lazy_zero_encoder is not None and sw.lazy_zero
-        flags = self._chunk_flags(lazy)
+        flags = self._chunk_flags(lazy, grouped)
         if self._clip_norm(flags, max_grad_norm, grad_ready, grad_bf16, grad_pieces):
             grad_ready = None
         self.step_count += 1
-        h = self._hyper(self.step_count)
+        h = self._group_hyper(self.step_count) if grouped else self._hyper(self.step_count)
         scale = Scale(float(grad_scale), float(max_grad_norm or 0.0), int(bool(zero_grads)))
         enc = self.overlap_encoder
         plan = self._overlap_plan(enc) if enc is not None else None
@@ -605,12 +713,15 @@ class FusedAdam(torch.optim.Optimizer):
         # without overlap the main stream waits for the ahead-of-time launch (overlapped, both run on the side stream)
         early, self._early = self._early, None
         wt = self._word_table() if early is not None else None
-        if early is not None and (wt is None or early[0] != h or grad_bf16 is not None):
+        if early is not None and (wt is None or grouped or early[0] != h or grad_bf16 is not None):
             raise UniterHipError('FusedAdam.step: the word-embedding rows without a gradient were updated ahead (early_word_update) '
                                  'for step %d / lr %g, but this step runs with other hyper-parameters or a bf16 gradient payload'
                                  % (early[0].step_count, early[0].lr))
-        sched = optim_schedule(st.numel, plan, wt, grad_ready is not None, self.overlap_workgroups, sw)
-        self._execute(sched, wt, early[1] if early is not None and plan is None else None, grad_ready, h, scale, flags, grad_bf16, layers)
+        trainable = self._trainable_ranges()
+        sched = optim_schedule(st.numel, plan, wt, grad_ready is not None, self.overlap_workgroups, sw,
+                               **({} if trainable is None else {'trainable': trainable}))
+        self._execute(sched, wt, early[1] if early is not None and plan is None else None, grad_ready, h, scale, flags, grad_bf16, layers,
+                      **({} if trainable is None or plan is None else {'blocks': plan[1]}))
         if early is not None or self._rows_noted is not False:
             # the row mask belongs to the micro-batches of THIS step: clear it behind its last reader
             if self._rowmask is not None and not (plan is not None and early is not None):
@@ -639,8 +750,9 @@ class FusedAdamax(FusedAdam):
 
     KIND = 2
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(model, lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=False)
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, group_param_func=None, layout=None):
+        super().__init__(model, lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=False, group_param_func=group_param_func,
+                         layout=layout)
 
 
 class FusedSGD(FusedAdam):
@@ -655,9 +767,10 @@ class FusedSGD(FusedAdam):
     KIND = 3
     SECOND_STATE = False
 
-    def __init__(self, model, lr, momentum=0.0, weight_decay=0.0):
+    def __init__(self, model, lr, momentum=0.0, weight_decay=0.0, group_param_func=None, layout=None):
         super().__init__(model, lr, weight_decay=weight_decay, adamw=False,
-                         defaults=dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+                         defaults=dict(lr=lr, momentum=momentum, weight_decay=weight_decay), group_param_func=group_param_func,
+                         layout=layout)
 
     def _rule_args(self, group):
         return float(group['momentum']), 0.0, 0.0
@@ -701,21 +814,24 @@ class TorchOptimizerStep(object):
 
 
 def get_optimizer(model, config, group_param_func=None, fused=True):
-    """utils/optim_utils.py:9-46: two parameter groups (weight decay off for biases and LayerNorm), then the
-    optimizer by name.  All four run as the fused HIP step; fused=False runs adamax / sgd as torch.optim's own update
-    (TorchOptimizerStep)."""
-    if group_param_func is not None:
-        raise UniterHipError('custom parameter grouping is not supported (INTEGRATION.md: out of scope)')
+    """utils/optim_utils.py:9-46: the parameter groups -- everything, or what `group_param_func` returns (a list of dicts whose
+    'params' are (name, parameter) pairs; every other key, an 'lr' of the group's own above all, is copied), each split into a
+    decay and a no-decay group (weight decay off for biases and LayerNorm) -- then the optimizer by name.  All four run as the
+    fused HIP step; fused=False runs adamax / sgd as torch.optim's own update (TorchOptimizerStep)."""
     name = config['optimizer']
     if name in ('adam', 'adamw'):
         return FusedAdam(model, lr=config['lr'], betas=(config['beta1'], config['beta2']),
-                         weight_decay=config['weight_decay'], adamw=(name == 'adamw'))
+                         weight_decay=config['weight_decay'], adamw=(name == 'adamw'), group_param_func=group_param_func)
     if name not in ('adamax', 'sgd'):
         raise ValueError('invalid optimizer %r' % name)
     store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
-    named = list(store.params.items())
-    groups = [{'params': [p for n, p in named if not no_decay(n)], 'weight_decay': config['weight_decay']},
-              {'params': [p for n, p in named if no_decay(n)], 'weight_decay': 0.0}]
+    # ONE layout for the torch optimizer and the fused class: `group_param_func` is called once, with the model's own names as
+    # the reference calls it (without one the names only decide decay / no decay, and the store's order is kept)
+    named = list(store.params.items()) if group_param_func is None else list(model.named_parameters())
+    layout = group_layout(named, config['weight_decay'], group_param_func)
+    groups = [dict(g, params=[p for _, p in g['params']]) for g in layout]
+    if group_param_func is None:
+        layout = None           # (the fused classes order their two groups as the model names its parameters, as they always did)
     if name == 'adamax':             # utils/optim_utils.py:36-37: torch's default betas, the config's are not passed
         inner = torch.optim.Adamax(groups, lr=config['lr'])
     else:                            # :41-43: momentum = beta1
@@ -723,10 +839,10 @@ def get_optimizer(model, config, group_param_func=None, fused=True):
     if not fused:
         return TorchOptimizerStep(model, inner)
     # the torch optimizer carries the reference's hyper-parameters (its defaults where the reference passes none)
-    g0 = inner.param_groups[0]
+    d = inner.defaults
     if name == 'adamax':
-        return FusedAdamax(model, lr=g0['lr'], betas=tuple(g0['betas']), eps=g0['eps'], weight_decay=g0['weight_decay'])
-    return FusedSGD(model, lr=g0['lr'], momentum=g0['momentum'], weight_decay=g0['weight_decay'])
+        return FusedAdamax(model, lr=d['lr'], betas=tuple(d['betas']), eps=d['eps'], weight_decay=config['weight_decay'], layout=layout)
+    return FusedSGD(model, lr=d['lr'], momentum=d['momentum'], weight_decay=config['weight_decay'], layout=layout)
 
 
 # --------------------------------------------------------------------------- #
