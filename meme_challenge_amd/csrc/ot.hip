@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NT) void ot_fwd_kernel(const OtArgs a) {
       const bool pad = xp[m] || yp[n];
       const float c = pad ? 0.f : 1.f - acc[j] / (nx[m] * ny[n]);        // ot.py:19-20, :74
       C[e] = c;
-      A[n * M + m] = pad ? 0.f : __expf(-c / a.beta);                    // ot.py:43, :49
+      A[n * M + m] = pad ? 0.f : expf(-c / a.beta);                      // ot.py:43, :49 (libm: within an ulp at every c / beta)
       T[n * M + m] = pad ? 0.f : 1.f;                                    // ot.py:42, :48
     }
   }
@@ -182,14 +182,16 @@ __global__ __launch_bounds__(NT) void ot_bwd_kernel(const OtArgs a) {
         if (d < a.D) out[d] = dn[j];                        // first pass: d(normalised row); finished below
       }
     }
-    // through x / max(|x|, eps): (dn - xn (xn . dn)) / |x| above the clamp, dn / eps at it
+    // through x / max(|x|, eps): (dn - xn (xn . dn)) / |x| above the clamp, dn / eps at it.  The projection is taken with the
+    // normalised row xn = x / |x| itself, not with x (x . dn) / |x|^2: for D == 1 xn is exactly +-1 and the gradient, which is
+    // identically zero there, comes out as an exact zero instead of a rounding residue of dn / |x|.
     float dot = 0.f, sq = 0.f;
-    for (int d = lane; d < a.D; d += 64) { dot += own[d] * out[d]; sq += own[d] * own[d]; }
+    for (int d = lane; d < a.D; d += 64) { dot += (own[d] / nown) * out[d]; sq += own[d] * own[d]; }
     dot = wave_sum(dot); sq = wave_sum(sq);
     const bool clamped = sqrtf(sq) < a.eps;
     for (int d = lane; d < a.D; d += 64) {
       const float dn = out[d];
-      out[d] = clamped ? dn / a.eps : (dn - own[d] * (dot / (nown * nown))) / nown;
+      out[d] = clamped ? dn / a.eps : (dn - (own[d] / nown) * dot) / nown;
     }
   }
 }
