@@ -498,6 +498,45 @@ int uniter_img_embed_bwd(const float* dcat, const float* imgfc, const float* pos
                          float p_drop, uint64_t seed, uint32_t offset,
                          void* ws, size_t ws_bytes, void* stream);
 size_t uniter_embed_bwd_ws_bytes(int rows, int H);
+/* The same two backward passes, bit-reproducible: the result is a function of the inputs alone (ids, dcat, parameters, seed and
+ * offset, the gradient buffers' prior contents), not of which wave or stream gets there first.  No float atomics; the argument
+ * lists, the `+=` semantics and every value's meaning are those of the calls above.
+ *   Order.  The rows that read one table row (after the forward's clamping of the ids; pos_bcast as in the forward) are summed
+ *   in ascending row index: rows are ranked stably by key, the ranks are cut into chunks of 32, the rows of one key inside a
+ *   chunk are added left to right, the chunk sums of that key are added in ascending chunk order, and the total is added to the
+ *   table row by one plain read-modify-write: table[key] = table[key] + total.  A table row that exactly one row reads therefore
+ *   receives prior + that row's gradient, exactly.  Word id 0 (padding_idx) receives nothing.  dgamma / dbeta and the other
+ *   column sums are the two-stage sums of the calls above, which are order-fixed already; dWp / dbp are summed per 32 rows
+ *   and those partial sums are added in ascending order.
+ *   Limit.  The rank compares every row with every other row: B * T and B * R up to UNITER_EMBED_DET_MAX_ROWS each,
+ *   UNITER_E_SHAPE beyond (a flagship batch is 16 x 128 text rows; 32 x 128 and a packed ragged batch fit).  H <= 1024.
+ *   Token-type table.  Both calls add into the same dtype: _txt_ adds the text rows' share (row 0 when type_ids is NULL), _img_
+ *   the regions' share (row 1 when img_type_ids is NULL), each by plain read-modify-writes.  The caller orders the two calls of
+ *   one step -- text, then image, on one stream or behind an event -- unless both id arrays are NULL, when they touch different
+ *   rows and may run side by side.  Text then image gives dtype = (prior + text share) + image share.
+ *   Workspace: uniter_embed_bwd_det_ws_bytes(txt_rows, img_rows, H) bytes are enough for a _txt_ call of txt_rows rows and for
+ *   an _img_ call of img_rows rows (one call at a time; a _txt_ call checks against (B * T, 0, H), an _img_ call against
+ *   (0, B * R, H)): the column partials of uniter_embed_bwd_ws_bytes, rows * H floats of per-row gradients, and per table two
+ *   ints per row and 2 * H floats per chunk. */
+#define UNITER_EMBED_DET_MAX_ROWS 16384
+int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
+                             const int64_t* type_ids, const float* word, const float* pos,
+                             const float* type, const float* gamma,
+                             float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta,
+                             int B, int T, int S, int H, int vocab, int max_pos, int type_vocab, int pos_bcast,
+                             float p_drop, uint64_t seed, uint32_t offset,
+                             void* ws, size_t ws_bytes, void* stream);
+int uniter_img_embed_bwd_det(const float* dcat, const float* imgfc, const float* pos7,
+                             const int64_t* img_type_ids, const float* Wp, const float* bp,
+                             const float* type, const float* g_i, const float* b_i,
+                             const float* g_p, const float* b_p, const float* g_f,
+                             const float* stats, float* d_imgfc, float* d_posfc,
+                             float* dWp, float* dbp, float* dtype,
+                             float* dg_i, float* db_i, float* dg_p, float* db_p, float* dg_f, float* db_f,
+                             int B, int R, int T0, int S, int H, int type_vocab,
+                             float p_drop, uint64_t seed, uint32_t offset,
+                             void* ws, size_t ws_bytes, void* stream);
+size_t uniter_embed_bwd_det_ws_bytes(int txt_rows, int img_rows, int H);
 
 /* ------------------------------------------------------------------------- *
  * Pooler + classification head (replaces BertPooler.forward model/layer.py:179-185
@@ -815,6 +854,14 @@ int uniter_model_set_aux_stream(uniter_model_t* m, void* aux_stream);
  * pass.  Without it a collective's workgroups take CUs as persistent workgroups exit, and the launch that counted on all 256 runs its
  * last workgroups -- and their whole static share of the tiles -- behind them.  0 (default) = every CU. */
 int uniter_model_set_cu_reserve(uniter_model_t* m, int cus);
+/* Bit-reproducible embedding gradients, per model handle (default 0): with `on` the forward passes that follow size the extra
+ * workspace (uniter_embed_bwd_det_ws_bytes) and their uniter_model_backward_embed calls uniter_txt_embed_bwd_det /
+ * uniter_img_embed_bwd_det.  With both token-type id arrays NULL the text branch still runs beside the image branch on the
+ * auxiliary stream (they touch different token-type rows); with explicit ids on either side the two run on one stream, text then
+ * image.  Set it before the forward pass whose backward it is to cover: a plan keeps the setting it was made with.  Everything
+ * else of the step is unchanged -- the encoder's products are atomic-free in precisions 2 and 3; what is not yet order-fixed
+ * elsewhere is listed in DESIGN.md. */
+int uniter_model_set_deterministic(uniter_model_t* m, int on);
 int uniter_model_norm_partials_per_layer(const uniter_model_t* m);
 /* Gradient accumulation semantics without the clearing pass (optimizer.zero_grad, train_template.py:107): after an optimizer
  * step that did NOT clear the encoder layers' weight gradients (uniter_adam_step*: chunk flag + 4), announce it here and the

@@ -104,6 +104,7 @@ _SIGS = {
     'uniter_model_set_norm_partials': (_I, [_P, _P, _SZ]),
     'uniter_model_set_aux_stream': (_I, [_P, _P]),
     'uniter_model_set_cu_reserve': (_I, [_P, _I]),
+    'uniter_model_set_deterministic': (_I, [_P, _I]),
     'uniter_model_norm_partials_per_layer': (_I, [_P]),
     'uniter_colsum_x3_add': (_I, [_P, _I, _I, _I, _P, _P]),
     'uniter_cast_bf16': (_I, [_P, _P, _SZ, _P]),
@@ -140,6 +141,10 @@ _SIGS = {
     'uniter_txt_embed_bwd': (_I, [_P] * 13 + [_I] * 8 + [_F, _U64, _U32, _P, _SZ, _P]),
     'uniter_img_embed_bwd': (_I, [_P] * 24 + [_I] * 6 + [_F, _U64, _U32, _P, _SZ, _P]),
     'uniter_embed_bwd_ws_bytes': (_SZ, [_I, _I]),
+    # the order-fixed (bit-reproducible) forms: argument lists of their twins
+    'uniter_txt_embed_bwd_det': (_I, [_P] * 13 + [_I] * 8 + [_F, _U64, _U32, _P, _SZ, _P]),
+    'uniter_img_embed_bwd_det': (_I, [_P] * 24 + [_I] * 6 + [_F, _U64, _U32, _P, _SZ, _P]),
+    'uniter_embed_bwd_det_ws_bytes': (_SZ, [_I, _I, _I]),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'uniter_pooler_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_linear_small_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

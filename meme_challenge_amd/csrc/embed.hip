@@ -12,7 +12,10 @@
 // the cheap forward pieces instead of saving them; embedding-table gradients are
 // scattered with fp32 atomics issued as 256-B contiguous wave transactions (the
 // fast shape, MI355X_MICROARCH.md "Global float atomics"); affine / type grads use
-// deterministic two-stage column reductions.
+// deterministic two-stage column reductions.  The opt-in deterministic backward (uniter_*_embed_bwd_det, below the atomic
+// kernels' entry points) sums the same table gradients in an order fixed by the inputs: per-row gradients to a workspace, a stable
+// rank of the rows by table key, chunk sums, one plain read-modify-write per key.
+#include <type_traits>
 #include "common.h"
 #include "gemm_internal.h"
 #include "philox.h"
@@ -109,8 +112,11 @@ __device__ __forceinline__ void row_atomic_add(const f32x4 (&v)[NV], float* buf,
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int NV>
-__global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const TxtArgs a) {
+// DET: the row's table gradient goes to the workspace drow[row][H] with plain 16-byte stores instead of the atomic scatter
+struct TxtDetArgs : TxtArgs { float* drow; };
+
+template <int NV, bool DET = false>
+__global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const std::conditional_t<DET, TxtDetArgs, TxtArgs> a) {
   __shared__ __attribute__((aligned(16))) float red[4 * NV * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, H4 = a.H >> 2;
   float* abuf = red + wave * NV * 256;   // per-wave staging for atomics (reused for the reduce)
@@ -129,10 +135,15 @@ __global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const TxtArgs a) {
     float mean, rstd;
     row_stats<NV>(e, a.H, H4, lane, mean, rstd);
     row_ln_bwd<NV>(d, e, g, mean, rstd, dg, db, a.H, H4, lane);     // d <- d(sum of the three lookups)
+    if constexpr (DET) {
+      row_store<NV>(d, a.drow + (size_t)row * a.H, H4, lane);
+      if (!a.type_ids) row_add<NV>(dt0, d);
+    } else {
     if (id != 0) row_atomic_add<NV>(d, abuf, a.dword + (size_t)id * a.H, a.H, H4, lane);  // padding_idx=0
     row_atomic_add<NV>(d, abuf, a.dpos + (size_t)pid * a.H, a.H, H4, lane);
     if (a.type_ids) row_atomic_add<NV>(d, abuf, a.dtype + (size_t)tt * a.H, a.H, H4, lane);
     else row_add<NV>(dt0, d);
+    }
   }
   float* part = a.part + (size_t)blockIdx.x * 3 * a.H;
   block_col_reduce_store<NV>(dg, red, part, H4, lane, wave);
@@ -178,8 +189,10 @@ __global__ __launch_bounds__(256) void img_embed_fwd_kernel(const ImgArgs a) {
   if (a.stats && lane < 6) a.stats[(size_t)row * 6 + lane] = st[lane];
 }
 
-template <int NV>
-__global__ __launch_bounds__(256) void img_embed_bwd_kernel(const ImgArgs a) {
+struct ImgDetArgs : ImgArgs { float* drow; };
+
+template <int NV, bool DET = false>
+__global__ __launch_bounds__(256) void img_embed_bwd_kernel(const std::conditional_t<DET, ImgDetArgs, ImgArgs> a) {
   __shared__ __attribute__((aligned(16))) float red[4 * NV * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, H4 = a.H >> 2;
   float* abuf = red + wave * NV * 256;
@@ -216,8 +229,13 @@ __global__ __launch_bounds__(256) void img_embed_bwd_kernel(const ImgArgs a) {
       row_add<NV>(f, t);
     }
     row_ln_bwd<NV>(d, f, gf, st[4], st[5], acc[0], acc[1], a.H, H4, lane);      // d <- df
+    if constexpr (DET) {
+      if (a.type_ids) row_store<NV>(d, a.drow + (size_t)row * a.H, H4, lane);
+      else row_add<NV>(acc[6], d);
+    } else {
     if (a.type_ids) row_atomic_add<NV>(d, abuf, a.dtype + (size_t)tid * a.H, a.H, H4, lane);
     else row_add<NV>(acc[6], d);
+    }
     f32x4 d2[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) d2[k] = d[k];
@@ -249,6 +267,157 @@ __global__ __launch_bounds__(256) void pos_linear_wgrad_kernel(const float* __re
 #pragma unroll
   for (int k = 0; k < 7; ++k) atomicAdd(dWp + (size_t)c * 7 + k, s[k]);
   atomicAdd(dbp + c, s[7]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Deterministic table gradients (uniter_txt_embed_bwd_det / uniter_img_embed_bwd_det): no float atomics, the order of every sum
+// fixed by the ids alone.
+//   1. the row pass (DET above) leaves row r's table gradient in drow[r][H];
+//   2. det_rank_kernel gives every row its stable rank by table key, rank(r) = #{r' : key[r'] < key[r] or (key[r'] == key[r] and
+//      r' < r)} -- a permutation, so order[rank] = r and skey[rank] = key[r] are plain stores with one writer each.  A run of
+//      equal keys in rank order is a segment: the rows that read one table row, in ascending row index;
+//   3. det_chunk_kernel: the ranks are cut into chunks of DET_CHUNK; one wave per chunk sums each run of equal keys inside its
+//      chunk in rank order (ascending row index).  A run that is a whole segment is added to its table row there and then; a run
+//      whose segment goes on beyond the chunk is left as a piece: slot 0 of the chunk when the segment began in an earlier
+//      chunk, slot 1 when it begins in this chunk (at most one run of each kind per chunk);
+//   4. det_owner_kernel: the chunk a multi-chunk segment begins in owns it: its wave adds the pieces in ascending chunk order
+//      (slot 1 of its own chunk, then slot 0 of the following ones) and adds the total to the table row.
+// So table[key] <- table[key] + (((p_0 + p_1) + p_2) + ...), p_i = ((d[r_0] + d[r_1]) + ...) over the chunk's rows of that key in
+// ascending row index; one owner per key and launch, one plain read-modify-write.  `skip` names the key whose table row stays
+// as it is (the word table's padding_idx 0).
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int DET_RANK_WG = 256;     // rows one workgroup ranks (one per thread)
+constexpr int DET_RANK_TILE = 1024;  // keys staged through LDS at a time
+constexpr int DET_CHUNK = 32;        // ranked rows per chunk
+constexpr int DET_WG_ROWS = 32;      // rows per partial of the position projection's weight gradient (pos_linear_wgrad_kernel's)
+
+struct DetTable {
+  const int64_t* ids;   // the table's ids, as the forward reads them
+  float* grad;          // [hi][H]
+  int* order;           // [rows]: order[rank] = row
+  int* skey;            // [rows]: skey[rank] = key
+  float* piece;         // [chunks][2][H]
+  int hi;               // keys are clamped to 0 .. hi - 1 (clampi, as txt_row_sum / the image kernels)
+  int bcast_T;          // > 0: row r reads ids[r % bcast_T] (pos_bcast)
+  int skip;             // key whose table row receives nothing; -1: none
+};
+struct DetArgs {
+  DetTable t[3];
+  const float* drow;
+  int rows, H;
+};
+
+__device__ __forceinline__ int det_key(const DetTable& t, int row) {
+  return clampi(t.ids[t.bcast_T > 0 ? row % t.bcast_T : row], t.hi);
+}
+
+// grid (ceil(rows / DET_RANK_WG), tables)
+__global__ __launch_bounds__(DET_RANK_WG) void det_rank_kernel(const DetArgs a) {
+  __shared__ int keys[DET_RANK_TILE];
+  const DetTable t = a.t[blockIdx.y];
+  const int r = blockIdx.x * DET_RANK_WG + threadIdx.x;
+  const int mine = r < a.rows ? det_key(t, r) : 0;
+  int rank = 0;
+  for (int base = 0; base < a.rows; base += DET_RANK_TILE) {
+    const int n = min(DET_RANK_TILE, a.rows - base);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += DET_RANK_WG) keys[i] = det_key(t, base + i);
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+      const int k = keys[i];
+      rank += (k < mine || (k == mine && base + i < r)) ? 1 : 0;
+    }
+  }
+  if (r < a.rows) { t.order[rank] = r; t.skey[rank] = mine; }
+}
+
+template <int NV>
+__device__ __forceinline__ void det_table_add(const f32x4 (&acc)[NV], float* g, int H4, int lane) {
+  f32x4 v[NV];
+  row_load<NV>(v, g, H4, lane);
+  row_add<NV>(v, acc);
+  row_store<NV>(v, g, H4, lane);
+}
+
+// grid (ceil(chunks / 4), tables): one wave per chunk
+template <int NV>
+__global__ __launch_bounds__(256) void det_chunk_kernel(const DetArgs a) {
+  const DetTable t = a.t[blockIdx.y];
+  const int lane = threadIdx.x & 63, H4 = a.H >> 2;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int r0 = c * DET_CHUNK;
+  if (r0 >= a.rows) return;
+  const int r1 = min(a.rows, r0 + DET_CHUNK);
+  const int prev = r0 > 0 ? t.skey[r0 - 1] : -1, next = r1 < a.rows ? t.skey[r1] : -1;     // (keys are >= 0)
+  int i = r0;
+  while (i < r1) {
+    const int k = t.skey[i];
+    f32x4 acc[NV];
+    row_load<NV>(acc, a.drow + (size_t)t.order[i] * a.H, H4, lane);
+    int j = i + 1;
+    for (; j < r1 && t.skey[j] == k; ++j) {
+      f32x4 v[NV];
+      row_load<NV>(v, a.drow + (size_t)t.order[j] * a.H, H4, lane);
+      row_add<NV>(acc, v);
+    }
+    const bool open_l = i == r0 && k == prev, open_r = j == r1 && k == next;
+    if (open_l || open_r) row_store<NV>(acc, t.piece + ((size_t)c * 2 + (open_l ? 0 : 1)) * a.H, H4, lane);
+    else if (k != t.skip) det_table_add<NV>(acc, t.grad + (size_t)k * a.H, H4, lane);
+    i = j;
+  }
+}
+
+// grid as det_chunk_kernel, behind it: the chunk whose last run begins a segment that goes on owns that segment
+template <int NV>
+__global__ __launch_bounds__(256) void det_owner_kernel(const DetArgs a) {
+  const DetTable t = a.t[blockIdx.y];
+  const int lane = threadIdx.x & 63, H4 = a.H >> 2;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int r0 = c * DET_CHUNK, r1 = min(a.rows, r0 + DET_CHUNK);
+  if (r1 >= a.rows) return;                                            // (the last chunk, or none: nothing goes on behind it)
+  const int k = t.skey[r1 - 1];
+  if (t.skey[r1] != k || k == t.skip) return;
+  if (r0 > 0 && t.skey[r0] == k && t.skey[r0 - 1] == k) return;        // the whole chunk lies inside a segment an earlier chunk owns
+  f32x4 acc[NV];
+  row_load<NV>(acc, t.piece + ((size_t)c * 2 + 1) * a.H, H4, lane);
+  const int chunks = (a.rows + DET_CHUNK - 1) / DET_CHUNK;
+  for (int cc = c + 1; cc < chunks && t.skey[cc * DET_CHUNK] == k; ++cc) {
+    f32x4 v[NV];
+    row_load<NV>(v, t.piece + (size_t)cc * 2 * a.H, H4, lane);
+    row_add<NV>(acc, v);
+  }
+  det_table_add<NV>(acc, t.grad + (size_t)k * a.H, H4, lane);
+}
+
+// pos_linear_wgrad_kernel with the chunk's eight sums stored to part[chunk][c][8] instead of added atomically ...
+__global__ __launch_bounds__(256) void pos_linear_wgrad_part_kernel(const float* __restrict__ d_posfc,
+                                                                    const float* __restrict__ pos7, float* __restrict__ part,
+                                                                    int rows, int H) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int r0 = blockIdx.y * DET_WG_ROWS, r1 = min(rows, r0 + DET_WG_ROWS);
+  if (c >= H) return;
+  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r = r0; r < r1; ++r) {
+    const float dv = d_posfc[(size_t)r * H + c];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) s[k] += dv * pos7[(size_t)r * 7 + k];
+    s[7] += dv;
+  }
+  f32x4* o = reinterpret_cast<f32x4*>(part + ((size_t)blockIdx.y * H + c) * 8);
+  o[0] = f32x4{s[0], s[1], s[2], s[3]};
+  o[1] = f32x4{s[4], s[5], s[6], s[7]};
+}
+
+// ... and folded over the chunks in ascending order: thread (c, k) owns dWp[c][k] (k < 7) or dbp[c] (k = 7)
+__global__ __launch_bounds__(256) void pos_linear_wgrad_fold_kernel(const float* __restrict__ part, float* __restrict__ dWp,
+                                                                    float* __restrict__ dbp, int chunks, int H) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * 8) return;
+  const int c = i >> 3, k = i & 7;
+  float s = part[i];
+  for (int ch = 1; ch < chunks; ++ch) s += part[(size_t)ch * H * 8 + i];
+  if (k < 7) dWp[(size_t)c * 7 + k] += s;
+  else dbp[c] += s;
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ cat,
@@ -461,6 +630,157 @@ extern "C" int uniter_img_embed_bwd(const float* dcat, const float* imgfc, const
   UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)7 * H, outs, 7, H, st));
   hipLaunchKernelGGL(pos_linear_wgrad_kernel, dim3((H + 255) / 256, (B * R + 31) / 32), dim3(256), 0, st,
                      d_posfc, pos7, dWp, dbp, B * R, H);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the deterministic backward's entry points (include/uniter_hip.h) ----
+#define NV_DISPATCH_DET(KERNEL, GRID, ARG)                                                     \
+  switch ((H / 4 + 63) / 64) {                                                                 \
+    case 1: hipLaunchKernelGGL((KERNEL<1, true>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 2: hipLaunchKernelGGL((KERNEL<2, true>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 3: hipLaunchKernelGGL((KERNEL<3, true>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 4: hipLaunchKernelGGL((KERNEL<4, true>), GRID, dim3(256), 0, st, ARG); break;         \
+    default: uniter_set_error("embed: hidden size %d unsupported (max 1024)", H);              \
+             return UNITER_E_SHAPE;                                                            \
+  }
+
+namespace {
+
+// the workspace of one _det call: column partials | drow | per table: order, skey, pieces | position-projection partials
+struct DetWs {
+  float* part; float* drow; int* order[3]; int* skey[3]; float* piece[3]; float* wpart;
+  size_t bytes;
+};
+DetWs det_carve(void* ws, int rows, int H, int ncol, int ntab, bool wgrad) {
+  DetWs w = {};
+  char* base = (char*)ws;
+  size_t off = 0;
+  auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += align_up(n * 4, 16); return p; };
+  const size_t chunks = ((size_t)rows + DET_CHUNK - 1) / DET_CHUNK;
+  w.part = (float*)take((size_t)bwd_blocks(rows) * ncol * H);
+  w.drow = (float*)take((size_t)rows * H);
+  for (int i = 0; i < ntab; ++i) {
+    w.order[i] = (int*)take(rows);
+    w.skey[i] = (int*)take(rows);
+    w.piece[i] = (float*)take(chunks * 2 * H);
+  }
+  if (wgrad) w.wpart = (float*)take((((size_t)rows + DET_WG_ROWS - 1) / DET_WG_ROWS) * H * 8);
+  w.bytes = off;
+  return w;
+}
+
+// rank, chunk sums and owners of `ntab` tables over the same drow
+int det_fold(DetArgs& d, int ntab, hipStream_t st) {
+  const int H = d.H, chunks = (d.rows + DET_CHUNK - 1) / DET_CHUNK;
+  hipLaunchKernelGGL(det_rank_kernel, dim3((d.rows + DET_RANK_WG - 1) / DET_RANK_WG, ntab), dim3(DET_RANK_WG), 0, st, d);
+  UCHECK_LAUNCH();
+  const dim3 grid((chunks + 3) / 4, ntab);
+  NV_DISPATCH(det_chunk_kernel, grid, d);
+  UCHECK_LAUNCH();
+  if (chunks > 1) {
+    NV_DISPATCH(det_owner_kernel, grid, d);
+    UCHECK_LAUNCH();
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t uniter_embed_bwd_det_ws_bytes(int txt_rows, int img_rows, int H) {
+  const size_t t = txt_rows > 0 ? det_carve(nullptr, txt_rows, H, 3, 3, false).bytes : 0;
+  const size_t i = img_rows > 0 ? det_carve(nullptr, img_rows, H, 7, 1, true).bytes : 0;
+  return t > i ? t : i;
+}
+
+extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
+                                        const int64_t* type_ids, const float* word, const float* pos,
+                                        const float* type, const float* gamma, float* dword, float* dpos,
+                                        float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H,
+                                        int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop,
+                                        uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
+  UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && dword && dpos && dtype &&
+             dgamma && dbeta && ws, "txt_embed_bwd_det: null pointer");
+  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_bwd_det: bad shape (H %% 4, H <= 1024, T <= S)");
+  UCHECK_SHAPE((long long)B * T <= UNITER_EMBED_DET_MAX_ROWS, "txt_embed_bwd_det: %lld rows, the stable rank covers at most %d",
+               (long long)B * T, UNITER_EMBED_DET_MAX_ROWS);
+  if (B * T <= 0) return 0;
+  const int rows = B * T;
+  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_det_ws_bytes(rows, 0, H), "txt_embed_bwd_det: workspace too small");
+  const DetWs w = det_carve(ws, rows, H, 3, 3, false);
+  TxtDetArgs a = {};
+  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
+  a.type = type; a.gamma = gamma; a.dcat = dcat; a.dword = dword; a.dpos = dpos; a.dtype = dtype;
+  a.part = w.part; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
+  a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
+  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
+  a.drow = w.drow;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = bwd_blocks(rows);
+  NV_DISPATCH_DET(txt_embed_bwd_kernel, dim3(nblk), a);
+  UCHECK_LAUNCH();
+  float* outs[3] = {dgamma, dbeta, type_ids ? nullptr : dtype};
+  UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)3 * H, outs, 3, H, st));
+  DetArgs d = {};
+  d.drow = w.drow; d.rows = rows; d.H = H;
+  const int64_t* src[3] = {input_ids, position_ids, type_ids};
+  float* grad[3] = {dword, dpos, dtype};
+  const int hi[3] = {vocab, max_pos, type_vocab};
+  const int ntab = type_ids ? 3 : 2;
+  for (int i = 0; i < ntab; ++i) {
+    DetTable& t = d.t[i];
+    t.ids = src[i]; t.grad = grad[i]; t.order = w.order[i]; t.skey = w.skey[i]; t.piece = w.piece[i]; t.hi = hi[i];
+    t.bcast_T = (i == 1 && pos_bcast) ? T : 0;
+    t.skip = i == 0 ? 0 : -1;                           // padding_idx = 0
+  }
+  return det_fold(d, ntab, st);
+}
+
+extern "C" int uniter_img_embed_bwd_det(const float* dcat, const float* imgfc, const float* pos7,
+                                        const int64_t* img_type_ids, const float* Wp, const float* bp,
+                                        const float* type, const float* g_i, const float* b_i, const float* g_p,
+                                        const float* b_p, const float* g_f, const float* stats, float* d_imgfc,
+                                        float* d_posfc, float* dWp, float* dbp, float* dtype, float* dg_i,
+                                        float* db_i, float* dg_p, float* db_p, float* dg_f, float* db_f, int B,
+                                        int R, int T0, int S, int H, int type_vocab, float p_drop, uint64_t seed,
+                                        uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
+  UCHECK_ARG(dcat && imgfc && pos7 && Wp && bp && type && g_i && b_i && g_p && b_p && g_f && stats &&
+             d_imgfc && d_posfc && dWp && dbp && dtype && dg_i && db_i && dg_p && db_p && dg_f && db_f && ws,
+             "img_embed_bwd_det: null pointer");
+  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T0 + R <= S && type_vocab >= 2,
+               "img_embed_bwd_det: bad shape (H %% 4, H <= 1024, T0 + R <= S, type_vocab >= 2)");
+  UCHECK_SHAPE((long long)B * R <= UNITER_EMBED_DET_MAX_ROWS, "img_embed_bwd_det: %lld rows, the stable rank covers at most %d",
+               (long long)B * R, UNITER_EMBED_DET_MAX_ROWS);
+  if (B * R <= 0) return 0;
+  const int rows = B * R;
+  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_det_ws_bytes(0, rows, H), "img_embed_bwd_det: workspace too small");
+  const DetWs w = det_carve(ws, rows, H, 7, 1, true);
+  ImgDetArgs a = {};
+  a.imgfc = imgfc; a.pos7 = pos7; a.type_ids = img_type_ids; a.Wp = Wp; a.bp = bp; a.type = type;
+  a.g_i = g_i; a.b_i = b_i; a.g_p = g_p; a.b_p = b_p; a.g_f = g_f; a.stats = const_cast<float*>(stats);
+  a.dcat = dcat; a.d_imgfc = d_imgfc; a.d_posfc = d_posfc; a.dtype = dtype; a.part = w.part;
+  a.B = B; a.R = R; a.T0 = T0; a.S = S; a.H = H; a.type_vocab = type_vocab;
+  a.drop = make_drop(p_drop, seed, offset, SITE_IMG_EMB);
+  a.drow = w.drow;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = bwd_blocks(rows);
+  NV_DISPATCH_DET(img_embed_bwd_kernel, dim3(nblk), a);
+  UCHECK_LAUNCH();
+  float* outs[7] = {dg_f, db_f, dg_i, db_i, dg_p, db_p, img_type_ids ? nullptr : dtype + H};
+  UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)7 * H, outs, 7, H, st));
+  if (img_type_ids) {
+    DetArgs d = {};
+    d.drow = w.drow; d.rows = rows; d.H = H;
+    DetTable& t = d.t[0];
+    t.ids = img_type_ids; t.grad = dtype; t.order = w.order[0]; t.skey = w.skey[0]; t.piece = w.piece[0];
+    t.hi = type_vocab; t.bcast_T = 0; t.skip = -1;
+    UCHECK_RC(det_fold(d, 1, st));
+  }
+  const int wchunks = (rows + DET_WG_ROWS - 1) / DET_WG_ROWS;
+  hipLaunchKernelGGL(pos_linear_wgrad_part_kernel, dim3((H + 255) / 256, wchunks), dim3(256), 0, st, d_posfc, pos7, w.wpart,
+                     rows, H);
+  UCHECK_LAUNCH();
+  hipLaunchKernelGGL(pos_linear_wgrad_fold_kernel, dim3((H * 8 + 255) / 256), dim3(256), 0, st, w.wpart, dWp, dbp, wchunks, H);
   UCHECK_LAUNCH();
   return 0;
 }

@@ -104,6 +104,7 @@ struct Plan {
   // the LayerNorm row pass that consumes them): K = intermediate (FFN-down forward, FFN-up dgrad), K = 3 hidden (QKV dgrad)
   int ns_ki, ns_k3h;
   bool packed;      // rows = valid positions only (uniter_batch_t::cu_seqlens)
+  bool det;         // the embedding backward of this plan is the order-fixed one (uniter_model_set_deterministic when the plan was made)
   int wg_group;           // precision 2: the layer's four weight gradients as one whole-K-tile launch (0 = stream-K, 1 / 4 = LDS stages cfg)
   float* wg_slabs;        // precision 2: k-piece slabs of the split-K weight-gradient GEMMs (side stream, reused by every layer)
   unsigned char* hid_keepb;   // hidden-dropout keep flags of every layer's two sites, drawn ahead (round 5); stride hid_stride per site
@@ -154,6 +155,7 @@ struct uniter_model {
   uint32_t offset = 0;
   hipStream_t st = nullptr, side = nullptr;
   bool bwd_open = false;
+  bool deterministic = false;     // uniter_model_set_deterministic: the embedding backward of the plans made from now on runs order-fixed
   int cu_reserve = 0;             // uniter_model_set_cu_reserve: CUs the persistent launches of this model's calls leave free
   hipStream_t aux = nullptr;      // uniter_model_set_aux_stream: launches that depend on nothing the step computes (dropout keep flags)
   hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr, ev_aux2 = nullptr;
@@ -196,6 +198,7 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   pl.T0 = has_txt ? T : 0;
   pl.S = pl.T0 + (has_img ? R : 0);
   pl.packed = Mrows >= 0;
+  pl.det = false;
   pl.M = pl.packed ? Mrows : B * L;
   const size_t M = (size_t)pl.M;
   Carver cv(ws);
@@ -286,6 +289,11 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
     pl.col_ws = cv.raw(pl.col_ws_bytes);
     const int rows = B * (T > R ? T : R);
     pl.emb_ws_bytes = uniter_embed_bwd_ws_bytes(rows, H);
+    pl.det = m->deterministic;
+    if (pl.det) {     // emb_ws / emb_ws2 hold the order-fixed passes' per-row gradients, ranks and chunk sums as well
+      const size_t d = uniter_embed_bwd_det_ws_bytes(has_txt ? B * T : 0, (int)BR, H);
+      if (d > pl.emb_ws_bytes) pl.emb_ws_bytes = d;
+    }
     pl.emb_ws = cv.raw(pl.emb_ws_bytes);
     pl.emb_ws2 = cv.raw(pl.emb_ws_bytes);
     pl.emb_ws3 = cv.raw(pl.emb_ws_bytes);
@@ -1145,7 +1153,10 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
   // runs there, beside the image branch; batches with mixed token-type ids (one side explicit, the other implicit) keep one stream,
   // whose order serializes the two writers of the token-type table's gradient.  UNITER_EMBED_BWD_PAR=0 keeps one stream (switches.h)
   const bool par_env = uniter_switches().embed_bwd_par;
-  const bool types_alike = (b.txt_type_ids == nullptr) == (b.img_type_ids == nullptr);
+  // The order-fixed passes (uniter_model_set_deterministic) add to the token-type table by plain read-modify-writes: side by side
+  // only where the two branches touch different rows (both id arrays NULL: text row 0, regions row 1); else one stream, text then image
+  const bool types_alike = pl.det ? (b.txt_type_ids == nullptr && b.img_type_ids == nullptr)
+                                  : (b.txt_type_ids == nullptr) == (b.img_type_ids == nullptr);
   hipStream_t ax = (par_env && m->aux && m->aux != st && m->aux != sd && pl.has_txt && pl.has_img && types_alike) ? m->aux : nullptr;
   if (ax) {
     if (!m->ev_emb0) UCHECK_HIP(hipEventCreateWithFlags(&m->ev_emb0, hipEventDisableTiming));
@@ -1155,13 +1166,13 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
     UCHECK_HIP(hipStreamWaitEvent(ax, m->ev_emb0, 0));
   }
   if (pl.has_txt)
-    UCHECK_RC(uniter_txt_embed_bwd(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD),
+    UCHECK_RC((pl.det ? uniter_txt_embed_bwd_det : uniter_txt_embed_bwd)(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD),
                                    m->P(P_POS), m->P(P_TYPE), m->P(P_ELN_G), m->G(P_WORD), m->G(P_POS),
                                    m->G(P_TYPE), m->G(P_ELN_G), m->G(P_ELN_B), B, T, S, H, c.vocab_size,
                                    c.max_position_embeddings, c.type_vocab_size, b.pos_bcast, ph, m->seed,
                                    m->offset, ax ? pl.emb_ws2 : pl.emb_ws, pl.emb_ws_bytes, ax ? ax : st));
   if (pl.has_img) {
-    UCHECK_RC(uniter_img_embed_bwd(pl.dcat, pl.imgfc, b.img_pos_feat, b.img_type_ids, m->P(P_POSL_W),
+    UCHECK_RC((pl.det ? uniter_img_embed_bwd_det : uniter_img_embed_bwd)(pl.dcat, pl.imgfc, b.img_pos_feat, b.img_type_ids, m->P(P_POSL_W),
                                    m->P(P_POSL_B), m->P(P_TYPE), m->P(P_ILN_G), m->P(P_ILN_B), m->P(P_PLN_G),
                                    m->P(P_PLN_B), m->P(P_FLN_G), pl.img_stats, pl.d_imgfc, pl.d_posfc,
                                    m->G(P_POSL_W), m->G(P_POSL_B), m->G(P_TYPE), m->G(P_ILN_G), m->G(P_ILN_B),
@@ -1210,6 +1221,12 @@ extern "C" int uniter_model_backward_end(uniter_model_t* m) {
 extern "C" int uniter_model_set_cu_reserve(uniter_model_t* m, int cus) {
   UCHECK_ARG(m && cus >= 0 && cus <= 128, "set_cu_reserve: 0 .. 128 CUs");
   m->cu_reserve = cus;
+  return 0;
+}
+
+extern "C" int uniter_model_set_deterministic(uniter_model_t* m, int on) {
+  UCHECK_ARG(m, "set_deterministic: null model");
+  m->deterministic = on != 0;
   return 0;
 }
 

@@ -679,6 +679,8 @@ class _UniterFn(torch.autograd.Function):
             model._warned_long_attn = True
         # (before the workspace is sized: the backward pass's k-pieces are planned for the CUs a gradient exchange leaves it)
         check(lib.uniter_model_set_cu_reserve(model._handle, int(getattr(model, 'cu_reserve', 0))), 'uniter_model_set_cu_reserve')
+        # (likewise before the workspace is sized: the order-fixed embedding backward keeps per-row gradients there)
+        model._apply_deterministic()
         nbytes = lib.uniter_model_ws_bytes(model._handle, B, batch.T if batch.input_ids else 0,
                                            batch.R if batch.img_feat else 0, L, mode)
         ws = model._get_ws(nbytes, mode)
@@ -790,6 +792,8 @@ class UniterModel(UniterPreTrainedModel):
         self._norm_parts = None
         # CUs the persistent matrix kernels leave to the kernels of a data-parallel gradient exchange (dp.attach sets it)
         self.cu_reserve = 0
+        self._deterministic = False
+        self._applied_deterministic = False
         self._side_stream = None
         self.use_side_stream = True
         # 'fp32'; 'bf16': bf16 MFMA GEMMs on bf16-resident operands (weight mirror + bf16 activation copies),
@@ -798,6 +802,29 @@ class UniterModel(UniterPreTrainedModel):
         self.pack_padded = False     # True: compute the valid positions only (see _pack); padded outputs are 0
 
     # -- plumbing ------------------------------------------------------------
+    @property
+    def deterministic(self):
+        """Bit-reproducible embedding gradients (default False; uniter_model_set_deterministic).  With it on, the backward pass
+        sums the gradients of the word, position and token-type tables and of the regions' 7-d position projection in an order
+        fixed by the batch's ids (ascending row index per table row: include/uniter_hip.h, uniter_txt_embed_bwd_det) instead of
+        scattering them with float atomics, so two runs from the same state give the same bits for every `embeddings.*` and
+        `img_embeddings.*` gradient -- given the same gradient arriving from the encoder, which holds in precision 'fp32x3'
+        (its input-gradient chain has no atomics).  It covers nothing else: the encoder's query|key|value bias gradients, the
+        column sums outside the fused launches and the native-fp32 image projection are not order-fixed.
+        It applies to the forward passes that follow; batches of more than 16384 text rows or regions are refused."""
+        return self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        self._deterministic = bool(on)
+        self._apply_deterministic()
+
+    def _apply_deterministic(self):
+        # a new handle starts with it off: a model that never turns it on never makes the call
+        if self._handle is not None and self._applied_deterministic != self._deterministic:
+            check(_lib.lib().uniter_model_set_deterministic(self._handle, int(self._deterministic)), 'uniter_model_set_deterministic')
+            self._applied_deterministic = self._deterministic
+
     def set_dropout_seed(self, seed, offset=0):
         self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self._offset = int(offset)
@@ -836,6 +863,7 @@ class UniterModel(UniterPreTrainedModel):
             self._handle = h
             self._prefix_names = None
             self._applied_precision = None
+            self._applied_deterministic = False
         if self.precision not in ('fp32', 'fp32x3', 'bf16', 'bf16_hybrid'):
             raise ValueError("precision must be 'fp32', 'fp32x3', 'bf16' or 'bf16_hybrid'")
         if self.precision == 'bf16' and (self.config.hidden_size % 64 or self.config.intermediate_size % 64):
