@@ -303,6 +303,28 @@ int uniter_ln_bwd_rows_slabs_x3(const float* dy, int nslab, size_t slab_stride, 
 /* out[n] += sum_m X[m, n] for a bf16 matrix X [M, ld] (bias gradient of a dense layer from the bf16 gradient of its
  * output; replaces the autograd sum of model/layer.py:140 in the bf16 mode).  N % 8 == 0, ld % 8 == 0. */
 int uniter_colsum_bf16_add(const void* X, int M, int N, int ld, float* out, void* stream);
+/* The two column sums above in a FIXED order, without float atomics (the deterministic plans of uniter_model_set_deterministic), so
+ * that the same input gives the same bits and numpy can restate the result bit for bit (tests/colsum_det_ref.py; the library is built
+ * with -ffp-contract=off):
+ *   1. rows are cut into blocks of UNITER_COLSUM_DET_ROWS = 64 consecutive rows, block k = rows 64 k .. 64 k + 63 (the last one ragged);
+ *   2. inside a block, row-lane w = 0..3 adds rows r0 + w, r0 + w + 4, ... in ascending order, starting from 0; an x3 element is
+ *      (p2 + p1) + p0, a bf16 element is widened;
+ *   3. the block's partial is P = (s0 + s1) + (s2 + s3), stored to ws[block][cols] with plain stores;
+ *   4. a second launch adds the partials in ascending block index and does one plain read-modify-write per column:
+ *      out[c] = out[c] + (((P0 + P1) + P2) + ...).
+ * ws: uniter_colsum_det_ws_bytes(rows, cols) bytes, 4-byte aligned; cols, ld multiples of 8, the operand 16-byte aligned (as above). */
+#define UNITER_COLSUM_DET_ROWS 64
+size_t uniter_colsum_det_ws_bytes(int rows, int cols);
+int uniter_colsum_x3_add_det(const void* x3, int rows, int cols, int ldx, float* out, void* ws, size_t ws_bytes, void* stream);
+int uniter_colsum_bf16_add_det(const void* X, int M, int N, int ld, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The NEXT attention-backward call of this host thread (uniter_attn_x3_bwd, uniter_attn_b16x_bwd, uniter_attn_bwd_ex, uniter_attn_bwd_ex_x3,
+ * uniter_attn_bf16_bwd; uniter_attn_bwd and uniter_attn_bwd_varlen emit no partials and only clear it) writes its per-sample
+ * query|key|value bias partials in a fixed order: every wave stores its 64 column sums (a fixed in-wave shuffle tree) to an LDS slot
+ * of its own with plain stores, and behind a barrier one thread per column adds the slots in ascending wave index,
+ * bias_part[c] = ((w0 + w1) + w2) + ... -- wave w holds rows 16 w .. 16 w + 15 in attention_x3.hip, the merged 32-row block w in
+ * attention_f32.hip / attention_bf16.hip.  No LDS or global atomics; dqkv, its piece / bf16 copies and delta are the same bits as
+ * without the flag.  The call that takes the flag clears it, a refused call included.  Returns 0. */
+int uniter_attn_bwd_set_next_det(int on);
 /* out[i] += sum_s slabs[s * slab_stride + i], i < n: folds the fp32 k-piece slabs of a split-K weight-gradient product
  * (uniter_gemm_bf16v2_cfg with a_kmajor = b_kmajor = 1, nsplit > 1) into the gradient buffer -- what autograd's
  * accumulation into .grad does for model/layer.py's nn.Linear weights.  n, slab_stride multiples of 4. */
@@ -854,14 +876,30 @@ int uniter_model_set_aux_stream(uniter_model_t* m, void* aux_stream);
  * pass.  Without it a collective's workgroups take CUs as persistent workgroups exit, and the launch that counted on all 256 runs its
  * last workgroups -- and their whole static share of the tiles -- behind them.  0 (default) = every CU. */
 int uniter_model_set_cu_reserve(uniter_model_t* m, int cus);
-/* Bit-reproducible embedding gradients, per model handle (default 0): with `on` the forward passes that follow size the extra
- * workspace (uniter_embed_bwd_det_ws_bytes) and their uniter_model_backward_embed calls uniter_txt_embed_bwd_det /
- * uniter_img_embed_bwd_det.  With both token-type id arrays NULL the text branch still runs beside the image branch on the
- * auxiliary stream (they touch different token-type rows); with explicit ids on either side the two run on one stream, text then
- * image.  Set it before the forward pass whose backward it is to cover: a plan keeps the setting it was made with.  Everything
- * else of the step is unchanged -- the encoder's products are atomic-free in precisions 2 and 3; what is not yet order-fixed
- * elsewhere is listed in DESIGN.md. */
+/* Bit-reproducible forward + backward, per model handle (default 0): with `on` every sum of the passes that follow runs in a fixed
+ * order, so their results are a function of the batch, the parameters, the dropout seed and offset and the buffers' prior contents.
+ *  - Embeddings: the forward passes size the extra workspace (uniter_embed_bwd_det_ws_bytes) and uniter_model_backward_embed calls
+ *    uniter_txt_embed_bwd_det / uniter_img_embed_bwd_det.  With both token-type id arrays NULL the text branch still runs beside the
+ *    image branch on the auxiliary stream (they touch different token-type rows); with explicit ids on either side the two run on
+ *    one stream, text then image.
+ *  - Attention: every backward call takes uniter_attn_bwd_set_next_det.
+ *  - Column sums: intermediate.dense's bias gradient, where no rider takes it, comes from uniter_colsum_x3_add_det /
+ *    uniter_colsum_bf16_add_det; their partials use the layer's dU column-partial buffer, so the workspace does not grow for them.
+ *  - Dense products: no stream-K form (float atomics in arrival order) -- the region projection's weight gradient and the ungrouped
+ *    weight gradients run on whole tiles, one adder per element; the native-fp32 region projection takes its bias-epilogue form
+ *    whatever UNITER_IMG_SK says.
+ * Set it before the forward pass whose backward it is to cover: a plan keeps the setting it was made with.  With it off nothing
+ * changes: same launches, same workspace.  Out of scope: the pretraining heads, the multi-rank gradient exchange, lab-switch
+ * schedules.
+ * uniter_model_deterministic_coverage: which parts of the LAST forward's plan run no arrival-ordered sum, as a mask of UNITER_DET_*;
+ * 0 with the switch off.  A lab switch that puts the plan on a form that was not order-fixed clears that part's bit, it does not fail. */
+#define UNITER_DET_EMBED 1
+#define UNITER_DET_ATTN 2
+#define UNITER_DET_COLSUM 4
+#define UNITER_DET_GEMM 8
+#define UNITER_DET_ALL 15
 int uniter_model_set_deterministic(uniter_model_t* m, int on);
+int uniter_model_deterministic_coverage(const uniter_model_t* m);
 int uniter_model_norm_partials_per_layer(const uniter_model_t* m);
 /* Gradient accumulation semantics without the clearing pass (optimizer.zero_grad, train_template.py:107): after an optimizer
  * step that did NOT clear the encoder layers' weight gradients (uniter_adam_step*: chunk flag + 4), announce it here and the

@@ -69,6 +69,8 @@ _SIGS = {
     'uniter_ln_bwd_rows_slabs': (_I, [_P, _I, _SZ, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _U32, _U32, _P, _SZ, _P]),
     'uniter_slab_reduce_add': (_I, [_P, _I, _SZ, _P, _SZ, _P]),
     'uniter_colsum_bf16_add': (_I, [_P, _I, _I, _I, _P, _P]),
+    'uniter_colsum_bf16_add_det': (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
+    'uniter_colsum_det_ws_bytes': (_SZ, [_I, _I]),
     'uniter_wgrad_bf16_group': (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _P]),
     'uniter_wgrad_f32_group': (_I, [_I, _P, _P, _I, _P, _P, _P, _I, _P]),
     'uniter_ln_bwd_b16': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _U64, _U32, _U32, _P, _SZ, _P]),
@@ -105,8 +107,11 @@ _SIGS = {
     'uniter_model_set_aux_stream': (_I, [_P, _P]),
     'uniter_model_set_cu_reserve': (_I, [_P, _I]),
     'uniter_model_set_deterministic': (_I, [_P, _I]),
+    'uniter_model_deterministic_coverage': (_I, [_P]),
+    'uniter_attn_bwd_set_next_det': (_I, [_I]),
     'uniter_model_norm_partials_per_layer': (_I, [_P]),
     'uniter_colsum_x3_add': (_I, [_P, _I, _I, _I, _P, _P]),
+    'uniter_colsum_x3_add_det': (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     'uniter_cast_bf16': (_I, [_P, _P, _SZ, _P]),
     'uniter_attn_bwd_ws_bytes': (_SZ, [_I, _I, _I]),
     'uniter_attn_varlen_max_len': (_I, []),

@@ -24,3 +24,9 @@ thread_local unsigned long long* g_uniter_stamp_slot = nullptr;
 thread_local int g_uniter_launch_prio = 0;
 thread_local int g_uniter_cu_reserve = 0;
 thread_local const unsigned char* g_uniter_drop_bits = nullptr;
+thread_local int g_uniter_attn_bwd_det = 0;
+// the NEXT attention-backward call of this host thread writes its per-sample bias partials in a fixed order (include/uniter_hip.h)
+extern "C" int uniter_attn_bwd_set_next_det(int on) {
+  g_uniter_attn_bwd_det = on != 0;
+  return 0;
+}

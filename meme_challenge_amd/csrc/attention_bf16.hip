@@ -213,6 +213,20 @@ __device__ __forceinline__ void acc_colsum(float* red, const f32x16& a0, const f
   }
 }
 
+// the order-fixed form (uniter_attn_bwd_set_next_det): the same in-wave tree, then the wave STORES its 64 column sums to a slot of its
+// own (a wave without valid lanes stores zeros)
+__device__ __forceinline__ void store_colsum(float* slot, const f32x16& a0, const f32x16& a1, bool valid, int i, int h) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float s0 = half_sum(valid ? a0[r] : 0.f), s1 = half_sum(valid ? a1[r] : 0.f);
+    if (i == 0) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * h;
+      slot[d] = s0;
+      slot[32 + d] = s1;
+    }
+  }
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 
 __device__ __forceinline__ void stage_mask(float* mb, const Args& a, int b, int Lb, int Lr, int tid, int nthr) {
@@ -340,7 +354,11 @@ __global__ __launch_bounds__(768) void attn_b16_fwd_kernel(const Args a, int Lr)
 
 // ------------------------------------------------- backward: dQ, delta, Pd / dS scratch ---
 // LDS: K row-major | V row-major | K transposed | mask bias
-template <bool QB16>
+// DET (uniter_attn_bwd_set_next_det): the per-sample bias partials in a fixed order, no LDS atomics, as in attention_f32.hip: the wave
+// that holds a 32-row block's merged result (half 0, block w) stores its column sums to a slot of its own, [Lr / 32][128] floats
+// behind the 192 at red_off (3 KB more LDS at L = 192); after the barrier one thread per column adds the slots in ascending block
+// index, bias_part[c] = ((w0 + w1) + w2) + ...  dqkv, its bf16 copy and delta are the same bits.
+template <bool QB16, bool DET>
 __device__ __forceinline__ void b16_dq_body(const Args& a, int Lr, int red_off) {
   u16* Kb = reinterpret_cast<u16*>(smem_raw);
   u16* Vb = Kb + Lr * KLD;
@@ -381,7 +399,7 @@ __device__ __forceinline__ void b16_dq_body(const Args& a, int Lr, int red_off) 
       }
     }
     stage_mask(mb, a, b, Lb, Lr, tid, nthr);
-    for (int t = tid; t < 192; t += nthr) red[t] = 0.f;        // (a 32-row workgroup has only 128 threads)
+    if constexpr (!DET) for (int t = tid; t < 192; t += nthr) red[t] = 0.f;        // (a 32-row workgroup has only 128 threads)
     sk.store_rm(Kb, Lr, tid, nthr);
     sk.store_tr(Kt, Lr, tid, nthr);
     sv.store_rm(Vb, Lr, tid, nthr);
@@ -456,22 +474,32 @@ __device__ __forceinline__ void b16_dq_body(const Args& a, int Lr, int red_off) 
       const size_t off = ((size_t)sp.row0 + q) * ld + head * D;
       store_rowT(a.dqkv ? a.dqkv + off : nullptr, a.dqkv_b16 ? a.dqkv_b16 + off : nullptr, dq0, dq1, 1.0f, h);
     }
-    if (a.bias_part) acc_colsum(red, dq0, dq1, vq, i, h);
+    if constexpr (DET) { if (a.bias_part) store_colsum(red + 192 + qb * 64, dq0, dq1, vq, i, h); }
+    else if (a.bias_part) acc_colsum(red, dq0, dq1, vq, i, h);
   }
   if (a.bias_part) {
     __syncthreads();
+    if constexpr (DET) {
+      if (tid < 64) {
+        float sum = red[192 + tid];
+        for (int w = 1; w < nblk; ++w) sum += red[192 + w * 64 + tid];
+        a.bias_part[(size_t)b * 3 * a.H + head * D + tid] = sum;
+      }
+    } else {
     if (tid < 64) a.bias_part[(size_t)b * 3 * a.H + head * D + tid] = red[tid];
+    }
   }
 }
 
 template <bool QB16>
 __global__ __launch_bounds__(768) void attn_b16_dq_kernel(const Args a, int Lr, int red_off) {
   set_wave_prio(a.prio);      // critical path of the step: ahead of the side stream's weight gradients (common.h)
-  b16_dq_body<QB16>(a, Lr, red_off);
+  b16_dq_body<QB16, false>(a, Lr, red_off);
 }
 
 // ------------------------------------------------------------ backward: dK, dV ---
 // LDS: Q transposed | dO transposed.  dV^T[d][key] = sum_q dO[q][d] Pd[q][key], dK^T = sum_q Q[q][d] dS[q][key]
+template <bool DET>
 __device__ __forceinline__ void b16_dkv_body(const Args& a, int Lr, int red_off) {
   u16* Qt = reinterpret_cast<u16*>(smem_raw);
   u16* dOt = Qt + D * TLD;
@@ -496,7 +524,7 @@ __device__ __forceinline__ void b16_dkv_body(const Args& a, int Lr, int red_off)
       sq.load(static_cast<const float*>(a.qkv) + boff, ld, Lb, Lr, tid, nthr);
       sq.store_tr(Qt, Lr, tid, nthr);
     }
-    for (int t = tid; t < 192; t += nthr) red[t] = 0.f;        // (a 32-row workgroup has only 128 threads)
+    if constexpr (!DET) for (int t = tid; t < 192; t += nthr) red[t] = 0.f;        // (a 32-row workgroup has only 128 threads)
     sdo.store_tr(dOt, Lr, tid, nthr);
   }
   const int key = kb * 32 + i;
@@ -540,18 +568,29 @@ __device__ __forceinline__ void b16_dkv_body(const Args& a, int Lr, int red_off)
       store_rowT(a.dqkv ? a.dqkv + off + a.H : nullptr, a.dqkv_b16 ? a.dqkv_b16 + off + a.H : nullptr, dk0, dk1, 1.0f, h);
       store_rowT(a.dqkv ? a.dqkv + off + 2 * a.H : nullptr, a.dqkv_b16 ? a.dqkv_b16 + off + 2 * a.H : nullptr, dv0, dv1, 1.0f, h);
     }
+    if constexpr (DET) {      // slots [Lr / 32][128]: dK | dV of key block kb
+      if (a.bias_part) { store_colsum(red + 192 + kb * 128, dk0, dk1, vk, i, h); store_colsum(red + 192 + kb * 128 + 64, dv0, dv1, vk, i, h); }
+    } else
     if (a.bias_part) { acc_colsum(red + 64, dk0, dk1, vk, i, h); acc_colsum(red + 128, dv0, dv1, vk, i, h); }
   }
   if (a.bias_part) {
     __syncthreads();
+    if constexpr (DET) {
+      for (int t = tid; t < 128; t += nthr) {
+        float sum = red[192 + t];
+        for (int w = 1; w < nblk; ++w) sum += red[192 + w * 128 + t];
+        a.bias_part[(size_t)b * 3 * a.H + (1 + (t >> 6)) * a.H + head * D + (t & 63)] = sum;
+      }
+    } else {
     for (int t = tid; t < 128; t += nthr)
       a.bias_part[(size_t)b * 3 * a.H + (1 + (t >> 6)) * a.H + head * D + (t & 63)] = red[64 + t];
+    }
   }
 }
 
 __global__ __launch_bounds__(768) void attn_b16_dkv_kernel(const Args a, int Lr, int red_off) {
   set_wave_prio(a.prio);      // critical path of the step: ahead of the side stream's weight gradients (common.h)
-  b16_dkv_body(a, Lr, red_off);
+  b16_dkv_body<false>(a, Lr, red_off);
 }
 
 // Both passes in one launch (attention_f32.hip, attn_bwd_fused_split_kernel): a workgroup's dK / dV pass reads only the Pd / dS
@@ -559,9 +598,26 @@ __global__ __launch_bounds__(768) void attn_b16_dkv_kernel(const Args a, int Lr,
 template <bool QB16>
 __global__ __launch_bounds__(768) void attn_b16_bwd_fused_kernel(const Args a, int Lr, int red_dq, int red_dkv) {
   set_wave_prio(a.prio);
-  b16_dq_body<QB16>(a, Lr, red_dq);
+  b16_dq_body<QB16, false>(a, Lr, red_dq);
   __syncthreads();
-  b16_dkv_body(a, Lr, red_dkv);
+  b16_dkv_body<false>(a, Lr, red_dkv);
+}
+// the three launches above with the order-fixed bias partials (b16_dq_body<QB16, true>)
+template <bool QB16>
+__global__ __launch_bounds__(768) void attn_b16_dq_det_kernel(const Args a, int Lr, int red_off) {
+  set_wave_prio(a.prio);
+  b16_dq_body<QB16, true>(a, Lr, red_off);
+}
+__global__ __launch_bounds__(768) void attn_b16_dkv_det_kernel(const Args a, int Lr, int red_off) {
+  set_wave_prio(a.prio);
+  b16_dkv_body<true>(a, Lr, red_off);
+}
+template <bool QB16>
+__global__ __launch_bounds__(768) void attn_b16_bwd_fused_det_kernel(const Args a, int Lr, int red_dq, int red_dkv) {
+  set_wave_prio(a.prio);
+  b16_dq_body<QB16, true>(a, Lr, red_dq);
+  __syncthreads();
+  b16_dkv_body<true>(a, Lr, red_dkv);
 }
 
 template <typename K>
@@ -622,6 +678,7 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
                                     void* dqkv_bf16, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                     int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                     size_t ws_bytes, void* stream) {
+  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_bf16_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
   UCHECK_ARG(ws_bytes >= uniter_attn_bf16_bwd_ws_bytes(B, L, nh), "attn_bf16_bwd: workspace too small");
@@ -636,6 +693,34 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
   const size_t red_dq = max3((size_t)(2 * Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4, 0);
   const size_t red_dkv = max3((size_t)(2 * D * TLD) * 2, (size_t)nblk * 64 * 64 * 4, 0);
   const size_t lds_dq = red_dq + 192 * 4, lds_dkv = red_dkv + 192 * 4;
+  if (det && bias_part) {      // (uniter_attn_bwd_set_next_det; the slots: [nblk][128] floats behind the 192)
+    const size_t slots = (size_t)nblk * 128 * 4;
+    hipStream_t st = (hipStream_t)stream;
+    if (uniter_switches().attn_bwd_fused) {
+      const size_t lds = (lds_dq > lds_dkv ? lds_dq : lds_dkv) + slots;
+      if (a.qb16) {
+        UCHECK_RC(set_lds(attn_b16_bwd_fused_det_kernel<true>, lds));
+        hipLaunchKernelGGL(attn_b16_bwd_fused_det_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds, st, a, Lr, (int)red_dq, (int)red_dkv);
+      } else {
+        UCHECK_RC(set_lds(attn_b16_bwd_fused_det_kernel<false>, lds));
+        hipLaunchKernelGGL(attn_b16_bwd_fused_det_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds, st, a, Lr, (int)red_dq, (int)red_dkv);
+      }
+      UCHECK_LAUNCH();
+      return 0;
+    }
+    UCHECK_RC(set_lds(attn_b16_dkv_det_kernel, lds_dkv + slots));
+    if (a.qb16) {
+      UCHECK_RC(set_lds(attn_b16_dq_det_kernel<true>, lds_dq + slots));
+      hipLaunchKernelGGL(attn_b16_dq_det_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds_dq + slots, st, a, Lr, (int)red_dq);
+    } else {
+      UCHECK_RC(set_lds(attn_b16_dq_det_kernel<false>, lds_dq + slots));
+      hipLaunchKernelGGL(attn_b16_dq_det_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds_dq + slots, st, a, Lr, (int)red_dq);
+    }
+    UCHECK_LAUNCH();
+    hipLaunchKernelGGL(attn_b16_dkv_det_kernel, dim3(B * nh), dim3(Lr * 4), lds_dkv + slots, st, a, Lr, (int)red_dkv);
+    UCHECK_LAUNCH();
+    return 0;
+  }
   if (uniter_switches().attn_bwd_fused) {
     const size_t lds = lds_dq > lds_dkv ? lds_dq : lds_dkv;
     if (a.qb16) {

@@ -636,6 +636,20 @@ __device__ __forceinline__ void acc_colsum(float* red, const f32x16& a0, const f
   }
 }
 
+// the order-fixed form (uniter_attn_bwd_set_next_det): the same in-wave tree, then the wave STORES its 64 column sums to a slot of its
+// own (a wave without valid lanes stores zeros)
+__device__ __forceinline__ void store_colsum(float* slot, const f32x16& a0, const f32x16& a1, bool valid, int i, int h) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float s0 = half_sum(valid ? a0[r] : 0.f), s1 = half_sum(valid ? a1[r] : 0.f);
+    if (i == 0) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * h;
+      slot[d] = s0;
+      slot[32 + d] = s1;
+    }
+  }
+}
+
 struct SampleSpan { int row0, Lb, nb; };
 __device__ __forceinline__ SampleSpan sample_span(const AttnArgs& a, int b) {
   SampleSpan s;
@@ -751,6 +765,11 @@ __global__ __launch_bounds__(768) void attn_fwd_split_kernel(const AttnArgs a, i
 }
 
 // (no __restrict__ on the scratch pointers of the two bodies: the fused kernel runs both on the same memory)
+// DET (uniter_attn_bwd_set_next_det): the per-sample bias partials in a fixed order, no LDS atomics.  The waves that hold a 32-row block's
+// merged result (half 0, block index w = 0 .. Lr / 32 - 1) each store their 64 column sums to a slot of their own, [Lr / 32][128] floats
+// behind the 192 of `red` (3 KB more LDS at L = 192: 109,824 bytes in all); after the barrier one thread per column adds the slots in
+// ascending block index, bias_part[c] = ((w0 + w1) + w2) + ...  Nothing else differs: dqkv, its copies and delta are the same bits.
+template <bool DET>
 __device__ __forceinline__ void bwd_dq_split_body(const AttnArgs& a, int Lr, float* pd_ws, float* ds_ws) {
   float* Ks = dyn_smem;
   float* Vs = Ks + Lr * LDT;
@@ -777,7 +796,7 @@ __device__ __forceinline__ void bwd_dq_split_body(const AttnArgs& a, int Lr, flo
     f32x4 of[8];
     load_row_frags(of, a.ctx + ((size_t)sp.row0 + q) * a.H + head * D, vq, h);
     stage_mask(mb, a, b, Lb, Lr, tid, nthr);
-    for (int t = tid; t < 192; t += nthr) dyn_smem[2 * Lr * LDT + 2 * Lr + t] = 0.f;      // (a 32-row workgroup has only 128 threads)
+    if constexpr (!DET) for (int t = tid; t < 192; t += nthr) dyn_smem[2 * Lr * LDT + 2 * Lr + t] = 0.f;      // (a 32-row workgroup has only 128 threads)
     stg.store(Ks, Vs, Lr, tid, nthr);
 #pragma unroll
     for (int kb = 0; kb < 8; ++kb)
@@ -848,11 +867,20 @@ __device__ __forceinline__ void bwd_dq_split_body(const AttnArgs& a, int Lr, flo
       if (a.dqkv) store_rowT(a.dqkv + ((size_t)sp.row0 + q) * ld + head * D, dq0, dq1, 1.0f, h);
       if (a.dqkv_b16) store_rowT_copy(a.dqkv_b16, a.b16_pieces, (size_t)sp.row0 + q, ld, head * D, dq0, dq1, 1.0f, h);
     }
-    if (a.bias_part) acc_colsum(red, dq0, dq1, vq, i, h);
+    if constexpr (DET) { if (a.bias_part) store_colsum(red + 192 + qb * 64, dq0, dq1, vq, i, h); }
+    else if (a.bias_part) acc_colsum(red, dq0, dq1, vq, i, h);
   }
   if (a.bias_part) {
     __syncthreads();
+    if constexpr (DET) {
+      if (tid < 64) {
+        float sum = red[192 + tid];
+        for (int w = 1; w < nblk; ++w) sum += red[192 + w * 64 + tid];
+        a.bias_part[(size_t)b * 3 * a.H + head * D + tid] = sum;
+      }
+    } else {
     if (tid < 64) a.bias_part[(size_t)b * 3 * a.H + head * D + tid] = red[tid];
+    }
   }
   ASTAMP(1, 6);
 }
@@ -860,10 +888,11 @@ __device__ __forceinline__ void bwd_dq_split_body(const AttnArgs& a, int Lr, flo
 __global__ __launch_bounds__(768) void attn_bwd_dq_split_kernel(const AttnArgs a, int Lr, float* __restrict__ pd_ws,
                                                                 float* __restrict__ ds_ws) {
   set_wave_prio(a.prio);      // critical path of the step: ahead of the side stream's weight gradients (common.h)
-  bwd_dq_split_body(a, Lr, pd_ws, ds_ws);
+  bwd_dq_split_body<false>(a, Lr, pd_ws, ds_ws);
 }
 
 // dV^T[d][key] = sum_q dO[q][d] Pd[q][key],  dK^T[d][key] = sum_q Q[q][d] dS[q][key]
+template <bool DET>
 __device__ __forceinline__ void bwd_dkv_split_body(const AttnArgs& a, int Lr, const float* pd_ws, const float* ds_ws) {
   float* Qs = dyn_smem;
   float* dOs = Qs + Lr * LDT;
@@ -878,7 +907,7 @@ __device__ __forceinline__ void bwd_dkv_split_body(const AttnArgs& a, int Lr, co
   const float* base = a.qkv + (size_t)sp.row0 * ld + head * D;
   Stage2<4> stg;
   stg.load(base, ld, a.dctx + (size_t)sp.row0 * a.H + head * D, a.H, Lb, Lr, tid, nthr);
-  for (int t = tid; t < 192; t += nthr) dyn_smem[2 * Lr * LDT + 2 * Lr + t] = 0.f;      // (a 32-row workgroup has only 128 threads)
+  if constexpr (!DET) for (int t = tid; t < 192; t += nthr) dyn_smem[2 * Lr * LDT + 2 * Lr + t] = 0.f;      // (a 32-row workgroup has only 128 threads)
   const int key = kb * 32 + i;
   const bool vk = key < Lb;
   const int qmid = ((sp.nb + 1) >> 1) * 32;
@@ -946,12 +975,23 @@ __device__ __forceinline__ void bwd_dkv_split_body(const AttnArgs& a, int Lr, co
         store_rowT_copy(a.dqkv_b16, a.b16_pieces, (size_t)sp.row0 + key, ld, 2 * a.H + head * D, dv0, dv1, 1.0f, h);
       }
     }
+    if constexpr (DET) {      // slots [Lr / 32][128]: dK | dV of key block kb
+      if (a.bias_part) { store_colsum(red + 192 + kb * 128, dk0, dk1, vk, i, h); store_colsum(red + 192 + kb * 128 + 64, dv0, dv1, vk, i, h); }
+    } else
     if (a.bias_part) { acc_colsum(red + 64, dk0, dk1, vk, i, h); acc_colsum(red + 128, dv0, dv1, vk, i, h); }
   }
   if (a.bias_part) {
     __syncthreads();
+    if constexpr (DET) {
+      for (int t = tid; t < 128; t += nthr) {
+        float sum = red[192 + t];
+        for (int w = 1; w < nblk; ++w) sum += red[192 + w * 128 + t];
+        a.bias_part[(size_t)b * 3 * a.H + (1 + (t >> 6)) * a.H + head * D + (t & 63)] = sum;
+      }
+    } else {
     for (int t = tid; t < 128; t += nthr)
       a.bias_part[(size_t)b * 3 * a.H + (1 + (t >> 6)) * a.H + head * D + (t & 63)] = red[64 + t];
+    }
   }
 }
 
@@ -959,7 +999,7 @@ __global__ __launch_bounds__(768) void attn_bwd_dkv_split_kernel(const AttnArgs 
                                                                  const float* __restrict__ pd_ws,
                                                                  const float* __restrict__ ds_ws) {
   set_wave_prio(a.prio);      // critical path of the step: ahead of the side stream's weight gradients (common.h)
-  bwd_dkv_split_body(a, Lr, pd_ws, ds_ws);
+  bwd_dkv_split_body<false>(a, Lr, pd_ws, ds_ws);
 }
 
 // Both passes in ONE launch: a workgroup's dK / dV pass reads only what its own dQ pass left in the scratch (the Pd / dS blocks
@@ -968,11 +1008,28 @@ __global__ __launch_bounds__(768) void attn_bwd_dkv_split_kernel(const AttnArgs 
 // 12-wave, 107-KB workgroup needs an empty CU, and between two launches the other stream's GEMM workgroups move in.
 __global__ __launch_bounds__(768) void attn_bwd_fused_split_kernel(const AttnArgs a, int Lr, float* pd_ws, float* ds_ws) {
   set_wave_prio(a.prio);
-  bwd_dq_split_body(a, Lr, pd_ws, ds_ws);
+  bwd_dq_split_body<false>(a, Lr, pd_ws, ds_ws);
   // workgroup scope is enough (and an agent-scope fence is a write-back of the L2): the waves of a workgroup share a CU, the
   // vector L1 writes through, and no wave has read these scratch lines in this launch
   __syncthreads();
-  bwd_dkv_split_body(a, Lr, pd_ws, ds_ws);
+  bwd_dkv_split_body<false>(a, Lr, pd_ws, ds_ws);
+}
+// the three launches above with the order-fixed bias partials (bwd_dq_split_body<true>)
+__global__ __launch_bounds__(768) void attn_bwd_dq_split_det_kernel(const AttnArgs a, int Lr, float* __restrict__ pd_ws,
+                                                                    float* __restrict__ ds_ws) {
+  set_wave_prio(a.prio);
+  bwd_dq_split_body<true>(a, Lr, pd_ws, ds_ws);
+}
+__global__ __launch_bounds__(768) void attn_bwd_dkv_split_det_kernel(const AttnArgs a, int Lr, const float* __restrict__ pd_ws,
+                                                                     const float* __restrict__ ds_ws) {
+  set_wave_prio(a.prio);
+  bwd_dkv_split_body<true>(a, Lr, pd_ws, ds_ws);
+}
+__global__ __launch_bounds__(768) void attn_bwd_fused_split_det_kernel(const AttnArgs a, int Lr, float* pd_ws, float* ds_ws) {
+  set_wave_prio(a.prio);
+  bwd_dq_split_body<true>(a, Lr, pd_ws, ds_ws);
+  __syncthreads();
+  bwd_dkv_split_body<true>(a, Lr, pd_ws, ds_ws);
 }
 
 // Dropout keep flags of the attention probabilities for `nlayers` layers at once, in the layout the L <= 192 kernels store
@@ -1020,8 +1077,24 @@ int make_args(AttnArgs& a, int B, int L, int nh, float p_drop, uint64_t seed, ui
   return 0;
 }
 
-int launch_bwd_split(const AttnArgs& a, int Lr, float* pd_ws, float* ds_ws, hipStream_t st) {
+int launch_bwd_split(const AttnArgs& a, int Lr, float* pd_ws, float* ds_ws, hipStream_t st, bool det) {
   const size_t lds = res_lds_bytes(Lr);
+  if (det && a.bias_part) {      // (uniter_attn_bwd_set_next_det; the slots: [Lr / 32][128] floats behind `red`)
+    const size_t lds_det = lds + (size_t)(Lr / 32) * 128 * sizeof(float);
+    if (bwd_fused()) {
+      UCHECK_RC(set_dyn_lds(attn_bwd_fused_split_det_kernel, lds_det));
+      hipLaunchKernelGGL(attn_bwd_fused_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
+      UCHECK_LAUNCH();
+      return 0;
+    }
+    UCHECK_RC(set_dyn_lds(attn_bwd_dq_split_det_kernel, lds_det));
+    UCHECK_RC(set_dyn_lds(attn_bwd_dkv_split_det_kernel, lds_det));
+    hipLaunchKernelGGL(attn_bwd_dq_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
+    UCHECK_LAUNCH();
+    hipLaunchKernelGGL(attn_bwd_dkv_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
+    UCHECK_LAUNCH();
+    return 0;
+  }
   if (bwd_fused()) {
     UCHECK_RC(set_dyn_lds(attn_bwd_fused_split_kernel, lds));
     hipLaunchKernelGGL(attn_bwd_fused_split_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws);
@@ -1086,6 +1159,7 @@ extern "C" int uniter_attn_bwd_varlen(const float* qkv, const int32_t* cu_seqlen
                                       const float* lse, const float* dctx, float* dqkv, float* delta, int B,
                                       int Lmax, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                       uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  (void)take_attn_bwd_det();      // (this form emits no bias partials: nothing to order)
   UCHECK_ARG(qkv && cu_seqlens && ctx && lse && dctx && dqkv && delta && ws, "attn_bwd_varlen: null pointer");
   const int Lr = (Lmax + 31) / 32 * 32;
   UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_bwd_varlen: Lmax %d > %d", Lmax, uniter_attn_varlen_max_len());
@@ -1096,7 +1170,7 @@ extern "C" int uniter_attn_bwd_varlen(const float* qkv, const int32_t* cu_seqlen
   a.dctx = dctx; a.dqkv = dqkv; a.delta = delta;
   float* pd_ws = (float*)ws;
   float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream);
+  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, false);
 }
 
 // General forms: mask XOR cu_seqlens, optional bf16 copies of the outputs (split kernels only: L <= 192).
@@ -1170,16 +1244,17 @@ static int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32
                            const float* ctx, const float* lse, const float* dctx, float* dqkv,
                            void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                            int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                           size_t ws_bytes, void* stream);
+                           size_t ws_bytes, void* stream, bool det);
 
 extern "C" int uniter_attn_bwd_ex(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
                                   const float* ctx, const float* lse, const float* dctx, float* dqkv,
                                   void* dqkv_bf16, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                   int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                   size_t ws_bytes, void* stream) {
+  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
   UCHECK_ARG(dqkv, "attn_bwd_ex: dqkv is NULL");
   return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, 1, bias_part, keep_bits, delta, B, L, nh,
-                         p_drop, seed, offset, site, ws, ws_bytes, stream);
+                         p_drop, seed, offset, site, ws, ws_bytes, stream, det);
 }
 
 extern "C" int uniter_attn_bwd_ex_x3(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
@@ -1187,16 +1262,17 @@ extern "C" int uniter_attn_bwd_ex_x3(const float* qkv, const float* attn_mask, c
                                      void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                      int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                      size_t ws_bytes, void* stream) {
+  const bool det = take_attn_bwd_det();
   UCHECK_ARG(dqkv_x3 && ((uintptr_t)dqkv_x3 & 7) == 0, "attn_bwd_ex_x3: dqkv_x3 is NULL or misaligned");
   return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_x3, 3, bias_part, keep_bits, delta, B, L, nh,
-                         p_drop, seed, offset, site, ws, ws_bytes, stream);
+                         p_drop, seed, offset, site, ws, ws_bytes, stream, det);
 }
 
 static int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
                            const float* ctx, const float* lse, const float* dctx, float* dqkv,
                            void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                            int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                           size_t ws_bytes, void* stream) {
+                           size_t ws_bytes, void* stream, bool det) {
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_bwd_ex: null pointer, or not exactly one of attn_mask / cu_seqlens");
   const int Lr = (L + 31) / 32 * 32;
@@ -1208,7 +1284,7 @@ static int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32
   a.dctx = dctx; a.dqkv = dqkv; a.dqkv_b16 = (unsigned short*)dqkv_bf16; a.b16_pieces = pieces; a.bias_part = bias_part; a.keep_bits = (unsigned short*)keep_bits; a.delta = delta;
   float* pd_ws = (float*)ws;
   float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream);
+  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, det);
 }
 
 extern "C" size_t uniter_attn_bwd_ws_bytes(int B, int L, int nh) {
@@ -1221,6 +1297,7 @@ extern "C" int uniter_attn_bwd(const float* qkv, const float* attn_mask, const f
                                const float* lse, const float* dctx, float* dqkv, float* delta, int B,
                                int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  (void)take_attn_bwd_det();      // (no bias partials here either)
   UCHECK_ARG(qkv && attn_mask && ctx && lse && dctx && dqkv && delta, "attn_bwd: null pointer");
   UCHECK_ARG(ws_bytes >= uniter_attn_bwd_ws_bytes(B, L, nh) && (ws || ws_bytes == 0 || uniter_attn_bwd_ws_bytes(B, L, nh) == 0),
              "attn_bwd: workspace too small (uniter_attn_bwd_ws_bytes)");
@@ -1232,7 +1309,7 @@ extern "C" int uniter_attn_bwd(const float* qkv, const float* attn_mask, const f
   if (Lr <= SPLIT_MAX_LR && split_enabled()) {
     float* pd_ws = (float*)ws;
     float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-    return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream);
+    return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, false);
   }
   if (Lr <= RES_MAX_LR) {
     const size_t lds = res_lds_bytes(Lr);

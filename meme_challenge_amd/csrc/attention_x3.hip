@@ -326,6 +326,21 @@ __device__ __forceinline__ void acc_colsum(float* red, const f32x4 (&acc)[4], fl
   }
 }
 
+// the order-fixed form: the same shuffle tree, then the wave STORES its 64 column sums to a slot of its own (slot[0..63]); a wave
+// without valid rows stores zeros
+__device__ __forceinline__ void store_colsum(float* slot, const f32x4 (&acc)[4], float mul, bool valid, int i, int g) {
+#pragma unroll
+  for (int db = 0; db < 4; ++db) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = valid ? acc[db][r] * mul : 0.f;
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (i == 0) slot[16 * db + 4 * g + r] = v;
+    }
+  }
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 
 __device__ __forceinline__ void stage_mask(float* mb, const Args& a, int b, int Lb, int Lr, int tid, int nthr) {
@@ -478,9 +493,18 @@ __global__ __launch_bounds__(768) void attn_x3_fwd_kernel(const Args a, int Lr) 
 // --------------------------------------------------------------- backward ---
 // LDS: operand pieces 1 | operand pieces 2 | mask bias | lse | delta | column sums | keep words
 // LAB (measurement builds, -DUNITER_X3_LAB + UNITER_ATTN_X3_LAB=bits): 1 = no pass-1 loop, 2 = no pass-2 loop, 4 = no MFMAs,
-// 8 = Q, K, V read as pieces (StagePieces)
+// 8 = Q, K, V read as pieces (StagePieces)   (16 is no lab bit: X3_DET below)
+// DET (uniter_attn_bwd_set_next_det): the per-sample query|key|value bias partials in a fixed order, no LDS atomics.  Every wave
+// stores its 64 column sums (in-wave shuffle tree as before) to a slot of its own: dQ's at the end of pass 1 into [waves][64] floats
+// behind the keep words (3 KB more LDS at L = 192, which fits beside the 155,136 bytes of the rest), dK's and dV's at the end of pass 2
+// into [waves][128] floats at the start of the operand images, which are dead behind a barrier.  Then one thread per column adds the
+// waves' slots in ascending wave index: bias_part[c] = ((w0 + w1) + w2) + ...  Everything else is the same code, so dqkv, its
+// copies and delta are the same bits as without the flag.  It is the bit X3_DET of LAB -- no lab switch, but one more variant of the same
+// body, and the default instantiation <NP, QB16, 0> keeps its name and its instruction stream.
+constexpr int X3_DET = 16;
 template <int NP, bool QB16, int LAB>
 __global__ __launch_bounds__(768) void attn_x3_bwd_kernel(const Args a, int Lr) {
+  constexpr bool DET = (LAB & X3_DET) != 0;
   set_wave_prio(a.prio);
   u8* I1 = smem_raw;                    // pass 1: K, pass 2: Q
   u8* I2 = smem_raw + NP * IMG;         // pass 1: V, pass 2: dO
@@ -549,7 +573,7 @@ __global__ __launch_bounds__(768) void attn_x3_bwd_kernel(const Args a, int Lr) 
         split8<NP>(x, y, dof[s]);
       }
       stage_mask(mb, a, b, Lb, Lr, tid, nthr);
-      for (int t = tid; t < 192; t += nthr) red[t] = 0.f;
+      if constexpr (!DET) for (int t = tid; t < 192; t += nthr) red[t] = 0.f;
       if (drop) {
         const unsigned* src = reinterpret_cast<const unsigned*>(a.keep_bits + (size_t)bh * a.L * nblk * 2);
         for (int t = tid; t < Lb * nblk; t += nthr) reinterpret_cast<unsigned*>(kb_s)[t] = src[t];
@@ -616,7 +640,11 @@ __global__ __launch_bounds__(768) void attn_x3_bwd_kernel(const Args a, int Lr) 
       store_row<NP>(vr, a.dqkv ? a.dqkv + row * ld + head * D : nullptr, a.dqkv_x3 ? a.dqkv_x3 + row * NP * ld + head * D : nullptr, ld,
                 dq, a.scale, g);
     }
-    if (a.bias_part) acc_colsum(red, dq, a.scale, vr, i, g);
+    if constexpr (DET) {
+      if (a.bias_part) store_colsum(reinterpret_cast<float*>(kb_s + Lr * nblk * 2) + wave * 64, dq, a.scale, vr, i, g);
+    } else {
+      if (a.bias_part) acc_colsum(red, dq, a.scale, vr, i, g);
+    }
   }
 
   // ---- pass 2: dK, dV for keys rw; queries from the images of Q and dO.  Nothing is loaded again: this wave's K and V rows
@@ -718,12 +746,31 @@ __global__ __launch_bounds__(768) void attn_x3_bwd_kernel(const Args a, int Lr) 
       store_row<NP>(vr, a.dqkv ? a.dqkv + row * ld + 2 * a.H + head * D : nullptr,
                 a.dqkv_x3 ? a.dqkv_x3 + row * NP * ld + 2 * a.H + head * D : nullptr, ld, dv, 1.0f, g);
     }
+    if constexpr (DET) {
+      if (a.bias_part) {
+        const float* qs = reinterpret_cast<const float*>(kb_s + Lr * nblk * 2);      // [waves][64]: dQ, stored at the end of pass 1
+        float* kvs = reinterpret_cast<float*>(I1);                                   // [waves][128]: dK | dV
+        const int nw = nthr >> 6;
+        __syncthreads();                                   // every wave is done with the images of Q and dO
+        store_colsum(kvs + wave * 128, dk, a.scale, vr, i, g);
+        store_colsum(kvs + wave * 128 + 64, dv, 1.0f, vr, i, g);
+        __syncthreads();
+        for (int t = tid; t < 192; t += nthr) {
+          const float* src = t < 64 ? qs + t : kvs + (t - 64);
+          const int stride = t < 64 ? 64 : 128;
+          float sum = src[0];
+          for (int w = 1; w < nw; ++w) sum += src[w * stride];
+          a.bias_part[(size_t)b * 3 * a.H + (t >> 6) * a.H + head * D + (t & 63)] = sum;
+        }
+      }
+    } else {
     if (a.bias_part) {
       acc_colsum(red + 64, dk, a.scale, vr, i, g);
       acc_colsum(red + 128, dv, 1.0f, vr, i, g);
       __syncthreads();
       for (int t = tid; t < 192; t += nthr)
         a.bias_part[(size_t)b * 3 * a.H + (t >> 6) * a.H + head * D + (t & 63)] = red[t];
+    }
     }
   }
 }
@@ -759,9 +806,16 @@ int launch_fwd(const Args& a, hipStream_t st) {
 }
 
 template <int NP, bool QB16>
-int launch_bwd(const Args& a, hipStream_t st) {
+int launch_bwd(const Args& a, hipStream_t st, bool det) {
   const int Lr = (a.L + 31) / 32 * 32;
   const size_t lds = (size_t)2 * NP * IMG + (size_t)3 * Lr * 4 + 192 * 4 + (size_t)Lr * (Lr / 32) * 4;
+  if (det) {      // (uniter_attn_bwd_set_next_det: the dQ slots, [Lr / 16 waves][64] floats, behind the keep words)
+    const size_t lds_det = lds + (size_t)(Lr / 16) * 64 * 4;
+    UCHECK_RC(set_lds(attn_x3_bwd_kernel<NP, QB16, X3_DET>, lds_det));
+    hipLaunchKernelGGL((attn_x3_bwd_kernel<NP, QB16, X3_DET>), dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr);
+    UCHECK_LAUNCH();
+    return 0;
+  }
 #ifdef UNITER_X3_LAB
   if constexpr (NP == 3 && !QB16) {
     const int lab = uniter_switch_attn_x3_lab();
@@ -801,6 +855,7 @@ extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, cons
                                   const float* lse, const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv,
                                   void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh,
                                   float p_drop, void* stream) {
+  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
   UCHECK_ARG(dctx_slabs >= 1 && dctx_slabs <= 4 && (dctx_slabs == 1 || dctx_slab_stride % 4 == 0),
              "attn_x3_bwd: dctx_slabs %d (1..4) / slab stride not a multiple of 4 elements", dctx_slabs);
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_x3) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
@@ -812,7 +867,7 @@ extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, cons
   a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
   a.dctx = dctx; a.dctx_slabs = dctx_slabs; a.dctx_slab_stride = dctx_slab_stride;
   a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_x3; a.bias_part = bias_part; a.delta = delta;
-  return launch_bwd<3, false>(a, (hipStream_t)stream);
+  return launch_bwd<3, false>(a, (hipStream_t)stream, det);
 }
 
 // The bf16 mode's attention in the same decomposition (one wave per 16 rows, one LDS image per operand read row-wise and
@@ -835,6 +890,7 @@ extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const floa
                                     const float* ctx, const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16,
                                     float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh, float p_drop,
                                     void* stream) {
+  const bool det = take_attn_bwd_det();
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_b16x_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
   UCHECK_ARG(((uintptr_t)dqkv_bf16 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0 &&
@@ -844,5 +900,5 @@ extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const floa
   a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
   a.dctx = dctx; a.dctx_slabs = 1; a.dctx_slab_stride = 0;
   a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_bf16; a.bias_part = bias_part; a.delta = delta;
-  return qkv_is_bf16 ? launch_bwd<1, true>(a, (hipStream_t)stream) : launch_bwd<1, false>(a, (hipStream_t)stream);
+  return qkv_is_bf16 ? launch_bwd<1, true>(a, (hipStream_t)stream, det) : launch_bwd<1, false>(a, (hipStream_t)stream, det);
 }

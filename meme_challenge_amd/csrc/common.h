@@ -63,6 +63,16 @@ static inline const unsigned char* take_drop_bits() {
   return p;
 }
 
+// The NEXT attention-backward launch of this host thread writes its per-sample bias partials in a fixed order (uniter_attn_bwd_set_next_det;
+// model.cpp sets it in front of each attention backward of a deterministic plan, the call that reads it resets it -- a refused call
+// included: every attention-backward entry point takes it first).  thread_local, as the channels above.
+extern thread_local int g_uniter_attn_bwd_det;
+static inline bool take_attn_bwd_det() {
+  const int d = g_uniter_attn_bwd_det;
+  g_uniter_attn_bwd_det = 0;
+  return d != 0;
+}
+
 // CUs the persistent matrix kernels leave free (uniter_model_set_cu_reserve: the collectives of a data-parallel exchange run beside the
 // backward pass and need CUs of their own -- a persistent launch that counts on all of them leaves its last workgroups queued behind
 // the collective's and their whole share of the tiles late).  Set by every model call from its handle; thread_local as the channels above.

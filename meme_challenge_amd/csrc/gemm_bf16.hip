@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256, (wgs_per_cu<BM, BN, AKM || BKM, RES>())) void 
 }
 
 template <int BM, int BN, bool AKM, bool BKM, bool RES = false>
-int launch_b(GemmArgsB g, hipStream_t st, int slots) {
+int launch_b(GemmArgsB g, hipStream_t st, int slots, bool no_sk) {
   if (BM == 64 && BN == 64) slots = 768;     // three 64x64 workgroups per CU (wgs_per_cu)
   // weight gradients: 512 stream-K pieces unless UNITER_WGRAD_SLOTS names another count (switches.h)
   const int sk_slots = uniter_switches().wgrad_slots;
@@ -491,7 +491,7 @@ int launch_b(GemmArgsB g, hipStream_t st, int slots) {
   g.band_h = (int)(bh < 1 ? 1 : (bh > 16 ? 16 : bh));
   if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
   const int grid = tiles < slots ? (tiles + 7) / 8 * 8 : slots;
-  if (g.beta == 1 && g.epi == UNITER_EPI_NONE && !g.colsum_part && tiles >= 8) {
+  if (!no_sk && g.beta == 1 && g.epi == UNITER_EPI_NONE && !g.colsum_part && tiles >= 8) {
     const int rounds = (tiles + slots - 1) / slots;
     const bool uneven = (long)tiles * 100 < (long)rounds * slots * 88;
     const long units = (long)tiles * ((g.K + BKB - 1) / BKB);
@@ -507,21 +507,21 @@ int launch_b(GemmArgsB g, hipStream_t st, int slots) {
 }
 
 template <bool AKM, bool BKM>
-int dispatch_b(int cfg, const GemmArgsB& g, hipStream_t st) {
+int dispatch_b(int cfg, const GemmArgsB& g, hipStream_t st, bool no_sk) {
   switch (cfg) {
-    case 1: return launch_b<128, 128, AKM, BKM>(g, st, 512);
-    case 2: return launch_b<64, 128, AKM, BKM>(g, st, 512);
-    case 3: return launch_b<128, 64, AKM, BKM>(g, st, 512);
-    case 4: return launch_b<64, 64, AKM, BKM>(g, st, 1024);
+    case 1: return launch_b<128, 128, AKM, BKM>(g, st, 512, no_sk);
+    case 2: return launch_b<64, 128, AKM, BKM>(g, st, 512, no_sk);
+    case 3: return launch_b<128, 64, AKM, BKM>(g, st, 512, no_sk);
+    case 4: return launch_b<64, 64, AKM, BKM>(g, st, 1024, no_sk);
     default: uniter_set_error("gemm_bf16: bad cfg %d", cfg); return UNITER_E_ARG;
   }
 }
 
 template <bool AKM, bool BKM>
-int dispatch_r(int cfg, const GemmArgsB& g, hipStream_t st) {
+int dispatch_r(int cfg, const GemmArgsB& g, hipStream_t st, bool no_sk) {
   switch (cfg) {
-    case 1: return launch_b<128, 128, AKM, BKM, true>(g, st, 512);
-    case 4: return launch_b<64, 64, AKM, BKM, true>(g, st, 1024);
+    case 1: return launch_b<128, 128, AKM, BKM, true>(g, st, 512, no_sk);
+    case 4: return launch_b<64, 64, AKM, BKM, true>(g, st, 1024, no_sk);
     default: uniter_set_error("gemm_bf16res: bad cfg %d (1 or 4)", cfg); return UNITER_E_ARG;
   }
 }
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
 // All-bf16 operands (resident activations / weight mirror), fp32 accumulate, fp32 and / or bf16 output.
 int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B,
                      int ldb, float* C, int ldc, void* Cb, int ldcb, int epilogue, const float* bias,
-                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream) {
+                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16res: bad argument");
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16res: bad epilogue %d", epilogue);
   UCHECK_ARG(!(a_kmajor && !b_kmajor), "gemm_bf16res: layout (A k-major, B k-contiguous) is not built");
@@ -571,9 +571,9 @@ int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, c
     cfg = (t128 >= 1024 || (!a_kmajor && e128 > e64)) ? 1 : 4;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (!a_kmajor && !b_kmajor) return dispatch_r<false, false>(cfg, g, st);
-  if (!a_kmajor && b_kmajor) return dispatch_r<false, true>(cfg, g, st);
-  return dispatch_r<true, true>(cfg, g, st);
+  if (!a_kmajor && !b_kmajor) return dispatch_r<false, false>(cfg, g, st, no_sk != 0);
+  if (!a_kmajor && b_kmajor) return dispatch_r<false, true>(cfg, g, st, no_sk != 0);
+  return dispatch_r<true, true>(cfg, g, st, no_sk != 0);
 }
 
 extern "C" int uniter_gemm_bf16res_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A,
@@ -603,7 +603,7 @@ extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* str
 // not cover (K % 64 != 0, offsets beyond 31 bits) run on the exact fp32 kernel instead.
 int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
                   const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream) {
+                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C, "gemm_bf16: bad argument");
   const bool ok = (K % BKB == 0 || (a_kmajor && b_kmajor)) && lda % 4 == 0 && ldb % 4 == 0 &&
                   ((size_t)M + 128) * ldc * 4 < (1ull << 31) && ((size_t)M + 128) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31) &&
@@ -613,7 +613,7 @@ int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, cons
                   ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0;
   if (!ok)
     return gemm_f32_run(0, 0, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in, aux_out,
-                        ld_aux, beta, colsum_part, stream);
+                        ld_aux, beta, colsum_part, stream, no_sk);
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16: bad epilogue %d", epilogue);
   GemmArgsB g;
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
@@ -629,10 +629,10 @@ int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, cons
     cfg = t128 >= 448 ? 1 : 4;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (!a_kmajor && !b_kmajor) return dispatch_b<false, false>(cfg, g, st);
-  if (!a_kmajor && b_kmajor) return dispatch_b<false, true>(cfg, g, st);
-  if (a_kmajor && b_kmajor) return dispatch_b<true, true>(cfg, g, st);
-  return dispatch_b<true, false>(cfg, g, st);
+  if (!a_kmajor && !b_kmajor) return dispatch_b<false, false>(cfg, g, st, no_sk != 0);
+  if (!a_kmajor && b_kmajor) return dispatch_b<false, true>(cfg, g, st, no_sk != 0);
+  if (a_kmajor && b_kmajor) return dispatch_b<true, true>(cfg, g, st, no_sk != 0);
+  return dispatch_b<true, false>(cfg, g, st, no_sk != 0);
 }
 
 extern "C" int uniter_gemm_bf16_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,

@@ -753,7 +753,7 @@ int launch_v3(GemmArgs g, hipStream_t st, int slots, bool allow_sk = true) {
 }
 
 template <bool AKM, bool BKM, int TAG>
-int dispatch_cfg(int cfg, const GemmArgs& g, hipStream_t st) {
+int dispatch_cfg(int cfg, const GemmArgs& g, hipStream_t st, bool no_sk) {
   switch (cfg) {
     case 1: return launch<128, 128, AKM, BKM, TAG>(g, st);
     case 2: return launch<64, 128, AKM, BKM, TAG>(g, st);
@@ -764,9 +764,9 @@ int dispatch_cfg(int cfg, const GemmArgs& g, hipStream_t st) {
                         (size_t)(BKM ? g.K : g.N) * g.ldb * 4 < (1ull << 31) &&
                         ((size_t)g.M + 128) * g.ldc * 4 < (1ull << 31) &&
                         ((size_t)g.M + 128) * (g.ld_aux > 0 ? g.ld_aux : 1) * 4 < (1ull << 31);
-      if (!fast) return dispatch_cfg<AKM, BKM, TAG>(cfg == 21 ? 1 : 4, g, st);      // one-tile-per-workgroup kernel
-      if (cfg == 21) return launch_v3<128, 128, AKM, BKM, TAG>(g, st, 512);
-      return launch_v3<64, 64, AKM, BKM, TAG>(g, st, 1024, cfg != 25);
+      if (!fast) return dispatch_cfg<AKM, BKM, TAG>(cfg == 21 ? 1 : 4, g, st, no_sk);      // one-tile-per-workgroup kernel
+      if (cfg == 21) return launch_v3<128, 128, AKM, BKM, TAG>(g, st, 512, !no_sk);
+      return launch_v3<64, 64, AKM, BKM, TAG>(g, st, 1024, cfg != 25 && !no_sk);
     }
     default: uniter_set_error("gemm: bad cfg %d", cfg); return UNITER_E_ARG;
   }
@@ -828,7 +828,7 @@ extern "C" int uniter_wgrad_f32_group(int n, const int* M, const int* N, int K, 
 int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,
                  int lda, const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part,
-                 void* stream) {
+                 void* stream, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad dims %d %d %d", M, N, K);
   UCHECK_ARG(A && B && C, "gemm: null operand");
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm: bad epilogue %d", epilogue);
@@ -856,10 +856,10 @@ int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int
   }
   hipStream_t st = (hipStream_t)stream;
   if (!a_kmajor && !b_kmajor)
-    return tag ? dispatch_cfg<false, false, 1>(cfg, g, st) : dispatch_cfg<false, false, 0>(cfg, g, st);
-  if (!a_kmajor && b_kmajor) return dispatch_cfg<false, true, 0>(cfg, g, st);
-  if (a_kmajor && b_kmajor) return dispatch_cfg<true, true, 0>(cfg, g, st);
-  return dispatch_cfg<true, false, 0>(cfg, g, st);
+    return tag ? dispatch_cfg<false, false, 1>(cfg, g, st, no_sk != 0) : dispatch_cfg<false, false, 0>(cfg, g, st, no_sk != 0);
+  if (!a_kmajor && b_kmajor) return dispatch_cfg<false, true, 0>(cfg, g, st, no_sk != 0);
+  if (a_kmajor && b_kmajor) return dispatch_cfg<true, true, 0>(cfg, g, st, no_sk != 0);
+  return dispatch_cfg<true, false, 0>(cfg, g, st, no_sk != 0);
 }
 
 extern "C" int uniter_gemm_f32_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K,

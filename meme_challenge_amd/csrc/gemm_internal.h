@@ -5,15 +5,21 @@
 #include "common.h"
 
 // ---- dense products: gemm_f32.hip, gemm_bf16.hip, gemm_bf16_dma.hip, gemm_bf16_p.hip, gemm_split3.hip ----
+// no_sk (the three *_run below): never the stream-K form, whose partial tiles meet in float atomics in arrival order -- a C += then
+// runs on whole tiles, one adder per element (the plans of uniter_model_set_deterministic).  gemm_bf16v2_run has no such form: its
+// C += is one workgroup per tile (split-K with beta is refused).
 int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
                  const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                 const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
+                 const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
+                 int no_sk = 0);
 int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
                   const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
+                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
+                  int no_sk = 0);
 int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B,
                      int ldb, float* C, int ldc, void* Cb, int ldcb, int epilogue, const float* bias,
-                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream);
+                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
+                     int no_sk = 0);
 int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda,
                     const void* B, int ldb, float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue,
                     const float* bias, const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16,
@@ -52,6 +58,8 @@ int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No);
 int launch_add_f32(float* out, const float* a, const float* b, size_t n, hipStream_t st);
 // out[n] (+)= sum_p part[p*stride + n]
 int finalize_partials(const float* part, int nparts, size_t stride, float* out, int N, int beta, hipStream_t st);
+// second pass of the order-fixed column sums (uniter_colsum_*_add_det): out[c] = out[c] + (((P0 + P1) + P2) + ...) over part[nblocks][cols]
+int colsum_det_finish(const float* part, int nblocks, int cols, float* out, hipStream_t st);
 // outs[j][c] += sum_p part[p*stride + j*H + c] for j < nout (<= 8); NULL outputs skipped
 int finalize_partials_multi(const float* part, int nparts, size_t stride, float* const* outs, int nout, int H,
                             hipStream_t st);

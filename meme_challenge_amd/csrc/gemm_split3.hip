@@ -1226,6 +1226,37 @@ __global__ __launch_bounds__(256) void colsum3_kernel(const unsigned short* __re
   }
 }
 
+// the order-fixed form (uniter_colsum_x3_add_det, include/uniter_hip.h states the order): block (bx, by) covers the same 512 columns
+// and the 64 rows by * 64 .. + 64, and STORES its partial row to part[by][cols] -- no atomics; colsum_det_finish adds the rows of
+// partials in ascending block index
+__global__ __launch_bounds__(256) void colsum3_det_kernel(const unsigned short* __restrict__ x3, int rows, int cols, int ldx,
+                                                          float* __restrict__ part) {
+  __shared__ float red[4][64 * 8 + 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 512 + lane * 8;
+  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c < cols) {
+    const int r1 = min(rows, (int)(blockIdx.y + 1) * UNITER_COLSUM_DET_ROWS);
+    for (int r = blockIdx.y * UNITER_COLSUM_DET_ROWS + wave; r < r1; r += 4) {
+      const unsigned short* p = x3 + (size_t)r * 3 * ldx + c;
+      const u32x4_t v0 = *reinterpret_cast<const u32x4_t*>(p), v1 = *reinterpret_cast<const u32x4_t*>(p + ldx),
+                    v2 = *reinterpret_cast<const u32x4_t*>(p + 2 * ldx);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s[2 * k] += (bf_lo(v2[k]) + bf_lo(v1[k])) + bf_lo(v0[k]);
+        s[2 * k + 1] += (bf_hi(v2[k]) + bf_hi(v1[k])) + bf_hi(v0[k]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) red[wave][lane * 8 + k] = s[k];
+  __syncthreads();
+  for (int k = threadIdx.x; k < 512; k += 256) {
+    const int cc = blockIdx.x * 512 + k;
+    if (cc < cols) part[(size_t)blockIdx.y * cols + cc] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  }
+}
+
 // 31-bit buffer offsets: the largest byte offset an x3 operand of `rows` rows is addressed with (tile overhang included)
 bool x3_fits(size_t rows, int rs, int ps, int ext) { return ((rows + 256) * (size_t)rs + 2 * (size_t)ps + ext) * 2 < (1ull << 31); }
 
@@ -1455,6 +1486,19 @@ extern "C" int uniter_colsum_x3_add(const void* x3, int rows, int cols, int ldx,
                      (const unsigned short*)x3, rows, cols, ldx, out, rpb);
   UCHECK_LAUNCH();
   return 0;
+}
+
+// the same sums in a fixed order, two passes, no float atomics (include/uniter_hip.h); ws: uniter_colsum_det_ws_bytes(rows, cols)
+extern "C" int uniter_colsum_x3_add_det(const void* x3, int rows, int cols, int ldx, float* out, void* ws, size_t ws_bytes, void* stream) {
+  UCHECK_ARG(x3 && out && ws && rows > 0 && cols > 0 && ldx >= cols, "colsum_x3_add_det: bad argument");
+  UCHECK_SHAPE(cols % 8 == 0 && ldx % 8 == 0 && ((uintptr_t)x3 & 15) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)ws & 3) == 0,
+               "colsum_x3_add_det: cols, ldx multiples of 8, a 16-byte aligned operand and 4-byte aligned out / ws required");
+  UCHECK_ARG(ws_bytes >= uniter_colsum_det_ws_bytes(rows, cols), "colsum_x3_add_det: workspace too small");
+  const int nb = (rows + UNITER_COLSUM_DET_ROWS - 1) / UNITER_COLSUM_DET_ROWS;
+  hipLaunchKernelGGL(colsum3_det_kernel, dim3((cols + 511) / 512, nb), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)x3, rows, cols, ldx, (float*)ws);
+  UCHECK_LAUNCH();
+  return colsum_det_finish((const float*)ws, nb, cols, out, (hipStream_t)stream);
 }
 
 // dW_p[M_p, N_p] (+)= A_p^T B_p for up to four products of one reduction length K (A_p [K][3][M_p], B_p [K][3][N_p] x3,

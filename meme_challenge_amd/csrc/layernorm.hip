@@ -270,6 +270,54 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const unsigned short* 
   }
 }
 
+// the order-fixed form (uniter_colsum_bf16_add_det, include/uniter_hip.h states the order): the same 512 columns and the 64 rows
+// by * 64 .. + 64 per block, whose partial row is STORED to part[by][N] -- no atomics
+__global__ __launch_bounds__(256) void colsum_bf16_det_kernel(const unsigned short* __restrict__ X, int M, int N, int ld,
+                                                              float* __restrict__ part) {
+  __shared__ float red[4][64 * 8 + 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 512 + lane * 8;
+  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c < N) {
+    const int r1 = min(M, (int)(blockIdx.y + 1) * UNITER_COLSUM_DET_ROWS);
+    for (int r = blockIdx.y * UNITER_COLSUM_DET_ROWS + wave; r < r1; r += 4) {
+      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(X + (size_t)r * ld + c);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s[2 * k] += __builtin_bit_cast(float, v[k] << 16);
+        s[2 * k + 1] += __builtin_bit_cast(float, v[k] & 0xffff0000u);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) red[wave][lane * 8 + k] = s[k];
+  __syncthreads();
+  for (int j = threadIdx.x; j < 512; j += 256) {
+    const int col = blockIdx.x * 512 + j;
+    if (col < N) part[(size_t)blockIdx.y * N + col] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+  }
+}
+
+// second pass of the order-fixed column sums: out[c] = out[c] + (((P0 + P1) + P2) + ...), the blocks' partial rows in ascending index,
+// one thread per column, one plain read-modify-write.  (Not finalize_partials: its 16 slices interleave the partials.)  Eight loads in
+// flight per thread; the adds stay one chain, which is the stated order
+__global__ __launch_bounds__(256) void colsum_det_finish_kernel(const float* __restrict__ part, int nblocks, int cols,
+                                                                float* __restrict__ out) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  float t = part[c];
+  int b = 1;
+  for (; b + 8 <= nblocks; b += 8) {
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = part[(size_t)(b + k) * cols + c];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t += v[k];
+  }
+  for (; b < nblocks; ++b) t += part[(size_t)b * cols + c];
+  out[c] = out[c] + t;
+}
+
 // out[i] += sum_s slab[s * stride + i]: the k-pieces of a split-K weight-gradient GEMM (fp32 partial tiles written with
 // plain 16-byte stores) folded into the gradient buffer -- one streaming pass instead of float atomics at 1.3 TB/s
 __global__ __launch_bounds__(256) void slab_reduce_add_kernel(const float* __restrict__ slabs, int nslab, size_t stride4,
@@ -388,6 +436,30 @@ extern "C" int uniter_colsum_bf16_add(const void* X, int M, int N, int ld, float
                      (const unsigned short*)X, M, N, ld, out, rpb);
   UCHECK_LAUNCH();
   return 0;
+}
+
+int colsum_det_finish(const float* part, int nblocks, int cols, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(colsum_det_finish_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, part, nblocks, cols, out);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t uniter_colsum_det_ws_bytes(int rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return (size_t)((rows + UNITER_COLSUM_DET_ROWS - 1) / UNITER_COLSUM_DET_ROWS) * cols * sizeof(float);
+}
+
+// out[n] = out[n] + sum_m X[m, n] for a bf16 X in a fixed order, two passes, no float atomics (include/uniter_hip.h)
+extern "C" int uniter_colsum_bf16_add_det(const void* X, int M, int N, int ld, float* out, void* ws, size_t ws_bytes, void* stream) {
+  UCHECK_ARG(X && out && ws && M > 0 && N > 0 && ld >= N, "colsum_bf16_det: bad argument");
+  UCHECK_SHAPE(N % 8 == 0 && ld % 8 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)ws & 3) == 0,
+               "colsum_bf16_det: N, ld multiples of 8, a 16-byte aligned operand and 4-byte aligned out / ws required");
+  UCHECK_ARG(ws_bytes >= uniter_colsum_det_ws_bytes(M, N), "colsum_bf16_det: workspace too small");
+  const int nb = (M + UNITER_COLSUM_DET_ROWS - 1) / UNITER_COLSUM_DET_ROWS;
+  hipLaunchKernelGGL(colsum_bf16_det_kernel, dim3((N + 511) / 512, nb), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)X, M, N, ld, (float*)ws);
+  UCHECK_LAUNCH();
+  return colsum_det_finish((const float*)ws, nb, N, out, (hipStream_t)stream);
 }
 
 #define LN_DISPATCH(NVv, KERNEL, GRID, ...) LN_DISPATCH_T(NVv, KERNEL, GRID, 256, __VA_ARGS__)

@@ -104,7 +104,8 @@ struct Plan {
   // the LayerNorm row pass that consumes them): K = intermediate (FFN-down forward, FFN-up dgrad), K = 3 hidden (QKV dgrad)
   int ns_ki, ns_k3h;
   bool packed;      // rows = valid positions only (uniter_batch_t::cu_seqlens)
-  bool det;         // the embedding backward of this plan is the order-fixed one (uniter_model_set_deterministic when the plan was made)
+  bool det;         // every sum of this plan's backward pass runs in a fixed order (uniter_model_set_deterministic when the plan was made):
+                    // the embedding passes, the attention kernels' bias partials, the column sums, no stream-K dense product
   int wg_group;           // precision 2: the layer's four weight gradients as one whole-K-tile launch (0 = stream-K, 1 / 4 = LDS stages cfg)
   float* wg_slabs;        // precision 2: k-piece slabs of the split-K weight-gradient GEMMs (side stream, reused by every layer)
   unsigned char* hid_keepb;   // hidden-dropout keep flags of every layer's two sites, drawn ahead (round 5); stride hid_stride per site
@@ -155,7 +156,7 @@ struct uniter_model {
   uint32_t offset = 0;
   hipStream_t st = nullptr, side = nullptr;
   bool bwd_open = false;
-  bool deterministic = false;     // uniter_model_set_deterministic: the embedding backward of the plans made from now on runs order-fixed
+  bool deterministic = false;     // uniter_model_set_deterministic: the plans made from now on run order-fixed (Plan::det)
   int cu_reserve = 0;             // uniter_model_set_cu_reserve: CUs the persistent launches of this model's calls leave free
   hipStream_t aux = nullptr;      // uniter_model_set_aux_stream: launches that depend on nothing the step computes (dropout keep flags)
   hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr, ev_aux2 = nullptr;
@@ -335,6 +336,8 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
   int cfg = 0;
   const bool wgrad = kind == UNITER_K_GEMM_WGRAD && akm && bkm && (beta == 1 || beta == -1);
   const Precision prec = m->plan.prec;
+  // a deterministic plan never takes the stream-K form of a C += (float atomics in arrival order): whole tiles, one adder per element
+  const int no_sk = m->plan.det ? 1 : 0;
   if (wgrad && (prec == PREC_F32 || prec == PREC_X3)) {
     // a layer's weight gradients by output shape: whole-K tiles (cfg 25, UNITER_WGRAD_WHOLE's bit) or UNITER_WGRAD_CFG's stream-K tiles
     cfg = sw.wgrad_cfg;
@@ -352,9 +355,9 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
   g_uniter_launch_prio = kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio;
   if (prec == PREC_BF16_MFMA || prec == PREC_BF16)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
     return gemm_bf16_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias, aux_in, aux_out, ld_aux, beta,
-                         colsum_part, st);
+                         colsum_part, st, no_sk);
   return gemm_f32_run(cfg, kind == UNITER_K_GEMM_FFN_UP_FWD, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias,
-                      aux_in, aux_out, ld_aux, beta, colsum_part, st);
+                      aux_in, aux_out, ld_aux, beta, colsum_part, st, no_sk);
 }
 
 // One dense product of encoder layer l against weight w (L_QW, L_OW, L_W1, L_W2): c = epilogue(a . W^T), or with b_kmajor the input
@@ -537,12 +540,14 @@ int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, const WgradProduc
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, st);
     if (pieces == 0 || !pl.wg_slabs)
       return gemm_bf16res_run(0, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, t.dW[p], No, nullptr, 0, UNITER_EPI_NONE, nullptr, nullptr,
-                              nullptr, 0, 1, nullptr, st);
+                              nullptr, 0, 1, nullptr, st, pl.det ? 1 : 0);      // (deterministic plan: whole tiles, no stream-K)
     UCHECK_RC(gemm_bf16v2_run(0, pieces, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, pl.wg_slabs, No, (long)Mo * No, nullptr, 0,
                               UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0, st));
   }
   return uniter_slab_reduce_add(pl.wg_slabs, pieces, (size_t)Mo * No, t.dW[p], (size_t)Mo * No, st);
 }
+// bytes of LayerBufs::du_csum (make_plan): one row of I partial sums per 32 rows
+inline size_t du_csum_bytes(int M, int I) { return (size_t)((M + 31) / 32) * I * sizeof(float); }
 // Products idx[0 .. n) as ONE launch of whole-K tiles on the weight-gradient stream (gemm_bf16v2_wgrad_group / gemm_x3_wgrad_group by
 // precision); colsum_after: followed by the column sums of dU (product 0's A operand), which nothing riding on the launch has taken
 int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t, const int* idx, int n, int cfg, int max_wgs,
@@ -560,6 +565,11 @@ int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t,
     else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders));
   }
   if (!colsum_after) return 0;
+  if (pl.det) {      // in a fixed order; the block partials go to the layer's dU column-partial buffer, which nothing else uses without riders
+    const LayerBufs& lb = pl.layers[l];
+    return (x3 ? uniter_colsum_x3_add_det : uniter_colsum_bf16_add_det)(t.A[0], pl.M, t.Mo[0], t.Mo[0], m->LG(l, L_B1), lb.du_csum,
+                                                                       du_csum_bytes(pl.M, t.Mo[0]), sd);
+  }
   return (x3 ? uniter_colsum_x3_add : uniter_colsum_bf16_add)(t.A[0], pl.M, t.Mo[0], t.Mo[0], m->LG(l, L_B1), sd);      // intermediate.dense bias gradient
 }
 
@@ -801,7 +811,8 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     // with K = 2048 -- as a stream-K accumulation on top of the bias rows it fills the chip (fp32: 58 -> 25 us)
     const long t64 = (long)((B * R + 63) / 64) * ((H + 63) / 64);
     // (UNITER_IMG_SK; native fp32 only: the float atomics make the sum's order vary from run to run, switches.h)
-    if (sw.img_sk && pl.prec == PREC_F32 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
+    // (nor with uniter_model_set_deterministic on: the bias-epilogue form whatever the switch says)
+    if (sw.img_sk && !m->deterministic && pl.prec == PREC_F32 && t64 >= 8 && t64 <= 600 && c.img_dim >= 1024 && c.img_dim % 64 == 0 && H % 4 == 0) {
       UCHECK_RC(uniter_bias_rows(m->P(P_IMG_B), pl.imgfc, B * R, H, st));
       UCHECK_RC(gemm(m, 0, st, 0, 0, B * R, H, c.img_dim, feat, c.img_dim, m->P(P_IMG_W), c.img_dim, pl.imgfc, H,
                      UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 1));
@@ -1014,6 +1025,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     const float* mask = pl.packed ? nullptr : m->batch.attention_mask;
     const int32_t* cu_seqlens = pl.packed ? m->batch.cu_seqlens : nullptr;
     unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;      // attention_x3.hip's kernels (the forward pass of a saved plan left the flags)
+    if (pl.det) g_uniter_attn_bwd_det = 1;      // the call below takes it: its bias partials in a fixed order (uniter_attn_bwd_set_next_det)
     switch (pl.attn_bwd) {
     case ATTN_B16X:
       UCHECK_RC(uniter_attn_b16x_bwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, lb.qb_part, keep_rd, lb.delta,
@@ -1094,7 +1106,9 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   } else if (pl.prec == PREC_BF16) {
     UCHECK_RC(wgrad_b16(m, pl, sd, wp, 1));
     UCHECK_RC(wgrad_b16(m, pl, sd, wp, 0));
-    UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));      // intermediate.dense bias gradient
+    // intermediate.dense bias gradient (deterministic plan: in a fixed order, partials in the otherwise unused dU column-partial buffer)
+    if (pl.det) UCHECK_RC(uniter_colsum_bf16_add_det(lb.dub, M, I, I, m->LG(l, L_B1), lb.du_csum, du_csum_bytes(M, I), sd));
+    else UCHECK_RC(uniter_colsum_bf16_add(lb.dub, M, I, I, m->LG(l, L_B1), sd));
     UCHECK_RC(wgrad_b16(m, pl, sd, wp, 3));
     UCHECK_RC(wgrad_b16(m, pl, sd, wp, 2));
   } else {
@@ -1228,6 +1242,20 @@ extern "C" int uniter_model_set_deterministic(uniter_model_t* m, int on) {
   UCHECK_ARG(m, "set_deterministic: null model");
   m->deterministic = on != 0;
   return 0;
+}
+
+// What of the last forward's plan runs no arrival-ordered sum (UNITER_DET_*; 0 with the switch off or behind an inference pass).
+// The embedding passes, the attention kernels' bias partials and the column sums are order-fixed in every schedule a deterministic
+// plan can take; the dense products are one adder per element everywhere except on the balanced walk of the fp32x3 products
+// (UNITER_X3_BALANCED, a lab switch: its partial tiles meet through a workspace in an order that was not audited), which clears the
+// GEMM bit -- and the COLSUM bit with it when the riders' reductions ride on such a launch.
+extern "C" int uniter_model_deterministic_coverage(const uniter_model_t* m) {
+  if (!m || !m->deterministic || !m->plan.det || m->plan.mode == 0) return 0;
+  const Plan& pl = m->plan;
+  int mask = UNITER_DET_EMBED | UNITER_DET_ATTN | UNITER_DET_COLSUM | UNITER_DET_GEMM;
+  if (pl.sk_main || pl.sk_side) mask &= ~UNITER_DET_GEMM;
+  if (pl.sk_side) mask &= ~UNITER_DET_COLSUM;
+  return mask;
 }
 
 extern "C" int uniter_model_set_aux_stream(uniter_model_t* m, void* aux_stream) {

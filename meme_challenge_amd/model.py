@@ -804,15 +804,43 @@ class UniterModel(UniterPreTrainedModel):
     # -- plumbing ------------------------------------------------------------
     @property
     def deterministic(self):
-        """Bit-reproducible embedding gradients (default False; uniter_model_set_deterministic).  With it on, the backward pass
-        sums the gradients of the word, position and token-type tables and of the regions' 7-d position projection in an order
-        fixed by the batch's ids (ascending row index per table row: include/uniter_hip.h, uniter_txt_embed_bwd_det) instead of
-        scattering them with float atomics, so two runs from the same state give the same bits for every `embeddings.*` and
-        `img_embeddings.*` gradient -- given the same gradient arriving from the encoder, which holds in precision 'fp32x3'
-        (its input-gradient chain has no atomics).  It covers nothing else: the encoder's query|key|value bias gradients, the
-        column sums outside the fused launches and the native-fp32 image projection are not order-fixed.
-        It applies to the forward passes that follow; batches of more than 16384 text rows or regions are refused."""
+        """Bit-reproducible training step (default False; uniter_model_set_deterministic).  With it on, every sum of the forward
+        and backward pass runs in a fixed order, so two runs from the same state give the same bits in the logits and in EVERY
+        parameter gradient -- and, with the fused optimizer step (order-fixed already), in every parameter and moment after N
+        steps.  Covered, in precisions 'fp32', 'fp32x3' and 'bf16', padded and packed batches:
+          * the embedding tables' gradients, summed in an order fixed by the batch's ids instead of scattered with float atomics
+            (include/uniter_hip.h, uniter_txt_embed_bwd_det);
+          * the attention backward kernels' per-sample query|key|value bias partials (per-wave slots added in ascending wave
+            index: uniter_attn_bwd_set_next_det);
+          * the column sums of intermediate.dense's bias gradient where no fused launch takes them (uniter_colsum_*_add_det);
+          * the dense products: no stream-K form -- the region projection's weight gradient and forward, the ungrouped weight
+            gradients.
+        Not covered: UniterForPretraining's heads, the multi-rank gradient exchange, schedules selected by
+        lab switches (`deterministic_coverage` then reports a cleared bit).  It applies to the forward passes that follow;
+        batches of more than 16384 text rows or regions are refused.  With it off nothing changes."""
         return self._deterministic
+
+    # uniter_model_deterministic_coverage's bits (include/uniter_hip.h)
+    DET_EMBED, DET_ATTN, DET_COLSUM, DET_GEMM, DET_ALL = 1, 2, 4, 8, 15
+    _DET_PARTS = ((1, 'embedding gradients'), (2, 'attention bias partials'), (4, 'column sums'), (8, 'dense products'))
+
+    @property
+    def deterministic_coverage(self):
+        """Which parts of the last training forward's plan run no arrival-ordered sum: a mask of DET_EMBED | DET_ATTN | DET_COLSUM |
+        DET_GEMM (uniter_model_deterministic_coverage); 0 with `deterministic` off or before the first forward pass."""
+        if self._handle is None:
+            return 0
+        return int(_lib.lib().uniter_model_deterministic_coverage(self._handle))
+
+    @property
+    def bit_reproducible(self):
+        """True when the last training forward's plan is order-fixed throughout (deterministic_coverage == DET_ALL)."""
+        return self.deterministic_coverage == self.DET_ALL
+
+    def deterministic_missing(self):
+        """names of the parts the last plan does NOT cover (empty when bit_reproducible)"""
+        mask = self.deterministic_coverage
+        return [name for bit, name in self._DET_PARTS if not mask & bit]
 
     @deterministic.setter
     def deterministic(self, on):

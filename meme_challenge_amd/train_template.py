@@ -485,7 +485,8 @@ class TrainerTemplate(object):
              ('max_grad_norm', int, 5), ('pos_wt', float, 1), ('lr', float, 1e-4), ('warmup_steps', int, 50),
              ('weight_decay', float, 1e-3), ('max_epoch', int, 20), ('lr_decay_step', float, 3),
              ('lr_decay_factor', float, 0.8), ('patience', float, 5), ('early_stop_thresh', float, 1e-3),
-             ('seed', int, 42), ('log_every', int, 2000), ('parallel_computing', bool, False))
+             ('seed', int, 42), ('log_every', int, 2000), ('parallel_computing', bool, False),
+             ('deterministic', None, False))      # additive: bit-reproducible steps (UniterModel.deterministic)
 
     @classmethod
     def add_default_argparse(cls, parser, defaults=dict()):

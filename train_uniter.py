@@ -9,7 +9,8 @@ libuniter_hip.so.
     torchrun --nproc-per-node 8 train_uniter.py ... --parallel_computing True      # DP over RCCL
 
 Additive flags (not in the reference): --synthetic N (write a synthetic dataset in the reference's
-on-disk format under --data_path and train on it), --hash_tokenizer (offline tokenizer).
+on-disk format under --data_path and train on it), --hash_tokenizer (offline tokenizer), --deterministic (every sum of the
+step in a fixed order: same seed, same bits in every parameter; UniterModel.deterministic).
 """
 import argparse
 import json
@@ -69,6 +70,8 @@ class TrainerUniter(TrainerTemplate):
             LOGGER.info('precision fp32x3 needs hidden / intermediate sizes %% 32 == 0: this model runs the native fp32 kernels')
             prec = 'fp32'
         self.model.uniter_model.precision = prec
+        # --deterministic: applied to the library handle when it is created (lazily, at the first forward pass)
+        self.model.uniter_model.deterministic = bool(self.config.get('deterministic', False))
 
     def load_model(self):
         uniter_config = resolve_config(self.config['config'])
@@ -93,6 +96,11 @@ class TrainerUniter(TrainerTemplate):
     def train_iter_step(self):
         self.preds = self._forward(self.batch)
         self.calculate_loss(self.preds, self.batch['labels'], grad_step=True)
+        if self.config.get('deterministic') and not getattr(self, '_det_reported', False):
+            self._det_reported = True        # once per run: what of this run's plan a lab switch keeps arrival-ordered
+            missing = self.model.uniter_model.deterministic_missing()
+            if missing:
+                LOGGER.info('--deterministic: not order-fixed in this run: %s' % ', '.join(missing))
 
     def test_iter_step(self, batch):
         return self._forward(batch).squeeze()
