@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include "common.h"
+#include "gemm_internal.h"
 
 static thread_local char g_err[512] = "";
 
@@ -18,15 +19,18 @@ extern "C" const char* uniter_build_info(void) {
   return "libuniter_hip gfx950 fp32-mfma (built " __DATE__ " " __TIME__ ")";
 }
 
-// the "next launch" side channel of common.h: one per HOST THREAD, so that two threads driving two model handles (cross-
-// validation folds in threads, a DataParallel-style caller) can never take each other's stamp slot or wave priority
-thread_local unsigned long long* g_uniter_stamp_slot = nullptr;
-thread_local int g_uniter_launch_prio = 0;
-thread_local int g_uniter_cu_reserve = 0;
-thread_local const unsigned char* g_uniter_drop_bits = nullptr;
-thread_local int g_uniter_attn_bwd_det = 0;
-// the NEXT attention-backward call of this host thread writes its per-sample bias partials in a fixed order (include/uniter_hip.h)
+// The NEXT attention-backward call of this host thread writes its per-sample bias partials in a fixed order (include/uniter_hip.h).
+// A hand-over of the C ABI only: the public attention-backward wrappers take it as their first statement (a refused call and the forms
+// that emit no bias partials included) and pass it down as an argument; the model's schedule passes Plan::det to the internal entry
+// points (gemm_internal.h) instead.
+// One per HOST THREAD, so that two threads driving the library can never take each other's flag.
+static thread_local int g_attn_bwd_next_det = 0;
 extern "C" int uniter_attn_bwd_set_next_det(int on) {
-  g_uniter_attn_bwd_det = on != 0;
+  g_attn_bwd_next_det = on != 0;
   return 0;
+}
+bool attn_bwd_take_next_det() {
+  const int d = g_attn_bwd_next_det;
+  g_attn_bwd_next_det = 0;
+  return d != 0;
 }

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 #include "philox.h"
 
@@ -678,7 +679,16 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
                                     void* dqkv_bf16, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                     int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                     size_t ws_bytes, void* stream) {
-  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
+  const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
+  return attn_bf16_bwd_run(qkv, qkv_is_bf16, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, bias_part, keep_bits, delta, B, L, nh,
+                           p_drop, seed, offset, site, ws, ws_bytes, stream, det);
+}
+
+// det: the per-sample bias partials in a fixed order (the model's Plan::det; the C ABI: uniter_attn_bwd_set_next_det)
+int attn_bf16_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
+                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
+                      float* delta, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
+                      size_t ws_bytes, void* stream, bool det) {
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_bf16_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
   UCHECK_ARG(ws_bytes >= uniter_attn_bf16_bwd_ws_bytes(B, L, nh), "attn_bf16_bwd: workspace too small");
@@ -693,7 +703,7 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
   const size_t red_dq = max3((size_t)(2 * Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4, 0);
   const size_t red_dkv = max3((size_t)(2 * D * TLD) * 2, (size_t)nblk * 64 * 64 * 4, 0);
   const size_t lds_dq = red_dq + 192 * 4, lds_dkv = red_dkv + 192 * 4;
-  if (det && bias_part) {      // (uniter_attn_bwd_set_next_det; the slots: [nblk][128] floats behind the 192)
+  if (det && bias_part) {      // (the slots: [nblk][128] floats behind the 192)
     const size_t slots = (size_t)nblk * 128 * 4;
     hipStream_t st = (hipStream_t)stream;
     if (uniter_switches().attn_bwd_fused) {

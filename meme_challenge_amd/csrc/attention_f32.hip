@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 #include "philox.h"
 
@@ -1159,7 +1160,7 @@ extern "C" int uniter_attn_bwd_varlen(const float* qkv, const int32_t* cu_seqlen
                                       const float* lse, const float* dctx, float* dqkv, float* delta, int B,
                                       int Lmax, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                       uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  (void)take_attn_bwd_det();      // (this form emits no bias partials: nothing to order)
+  (void)attn_bwd_take_next_det();      // (this form emits no bias partials: nothing to order)
   UCHECK_ARG(qkv && cu_seqlens && ctx && lse && dctx && dqkv && delta && ws, "attn_bwd_varlen: null pointer");
   const int Lr = (Lmax + 31) / 32 * 32;
   UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_bwd_varlen: Lmax %d > %d", Lmax, uniter_attn_varlen_max_len());
@@ -1240,18 +1241,12 @@ static int attn_fwd_pre_run(const float* qkv, const float* attn_mask, const int3
   return 0;
 }
 
-static int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
-                           const float* ctx, const float* lse, const float* dctx, float* dqkv,
-                           void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
-                           int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                           size_t ws_bytes, void* stream, bool det);
-
 extern "C" int uniter_attn_bwd_ex(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
                                   const float* ctx, const float* lse, const float* dctx, float* dqkv,
                                   void* dqkv_bf16, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                   int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                   size_t ws_bytes, void* stream) {
-  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
+  const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
   UCHECK_ARG(dqkv, "attn_bwd_ex: dqkv is NULL");
   return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, 1, bias_part, keep_bits, delta, B, L, nh,
                          p_drop, seed, offset, site, ws, ws_bytes, stream, det);
@@ -1262,17 +1257,17 @@ extern "C" int uniter_attn_bwd_ex_x3(const float* qkv, const float* attn_mask, c
                                      void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L,
                                      int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                      size_t ws_bytes, void* stream) {
-  const bool det = take_attn_bwd_det();
+  const bool det = attn_bwd_take_next_det();
   UCHECK_ARG(dqkv_x3 && ((uintptr_t)dqkv_x3 & 7) == 0, "attn_bwd_ex_x3: dqkv_x3 is NULL or misaligned");
   return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_x3, 3, bias_part, keep_bits, delta, B, L, nh,
                          p_drop, seed, offset, site, ws, ws_bytes, stream, det);
 }
 
-static int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
-                           const float* ctx, const float* lse, const float* dctx, float* dqkv,
-                           void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
-                           int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                           size_t ws_bytes, void* stream, bool det) {
+int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
+                    const float* ctx, const float* lse, const float* dctx, float* dqkv,
+                    void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
+                    int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
+                    size_t ws_bytes, void* stream, bool det) {
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_bwd_ex: null pointer, or not exactly one of attn_mask / cu_seqlens");
   const int Lr = (L + 31) / 32 * 32;
@@ -1297,7 +1292,7 @@ extern "C" int uniter_attn_bwd(const float* qkv, const float* attn_mask, const f
                                const float* lse, const float* dctx, float* dqkv, float* delta, int B,
                                int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  (void)take_attn_bwd_det();      // (no bias partials here either)
+  (void)attn_bwd_take_next_det();      // (no bias partials here either)
   UCHECK_ARG(qkv && attn_mask && ctx && lse && dctx && dqkv && delta, "attn_bwd: null pointer");
   UCHECK_ARG(ws_bytes >= uniter_attn_bwd_ws_bytes(B, L, nh) && (ws || ws_bytes == 0 || uniter_attn_bwd_ws_bytes(B, L, nh) == 0),
              "attn_bwd: workspace too small (uniter_attn_bwd_ws_bytes)");

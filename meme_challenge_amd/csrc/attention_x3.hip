@@ -30,6 +30,7 @@
 #include <type_traits>
 #include "common.h"
 #include "bf16_tile.h"
+#include "gemm_internal.h"
 #include "switches.h"
 
 namespace {
@@ -851,11 +852,10 @@ extern "C" int uniter_attn_x3_fwd(const float* qkv, const float* attn_mask, cons
   return launch_fwd<3, false>(a, (hipStream_t)stream);
 }
 
-extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
-                                  const float* lse, const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv,
-                                  void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh,
-                                  float p_drop, void* stream) {
-  const bool det = take_attn_bwd_det();      // (first: a refused call takes the flag with it)
+// det: the per-sample bias partials in a fixed order (the model's Plan::det; the C ABI: uniter_attn_bwd_set_next_det)
+int attn_x3_bwd_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx, const float* lse,
+                    const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv, void* dqkv_x3, float* bias_part,
+                    const void* keep_bits, float* delta, int B, int L, int nh, float p_drop, void* stream, bool det) {
   UCHECK_ARG(dctx_slabs >= 1 && dctx_slabs <= 4 && (dctx_slabs == 1 || dctx_slab_stride % 4 == 0),
              "attn_x3_bwd: dctx_slabs %d (1..4) / slab stride not a multiple of 4 elements", dctx_slabs);
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_x3) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
@@ -868,6 +868,15 @@ extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, cons
   a.dctx = dctx; a.dctx_slabs = dctx_slabs; a.dctx_slab_stride = dctx_slab_stride;
   a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_x3; a.bias_part = bias_part; a.delta = delta;
   return launch_bwd<3, false>(a, (hipStream_t)stream, det);
+}
+
+extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
+                                  const float* lse, const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv,
+                                  void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh,
+                                  float p_drop, void* stream) {
+  const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
+  return attn_x3_bwd_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dctx_slabs, dctx_slab_stride, dqkv, dqkv_x3, bias_part, keep_bits,
+                         delta, B, L, nh, p_drop, stream, det);
 }
 
 // The bf16 mode's attention in the same decomposition (one wave per 16 rows, one LDS image per operand read row-wise and
@@ -886,11 +895,9 @@ extern "C" int uniter_attn_b16x_fwd(const void* qkv, int qkv_is_bf16, const floa
   return qkv_is_bf16 ? launch_fwd<1, true>(a, (hipStream_t)stream) : launch_fwd<1, false>(a, (hipStream_t)stream);
 }
 
-extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens,
-                                    const float* ctx, const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16,
-                                    float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh, float p_drop,
-                                    void* stream) {
-  const bool det = take_attn_bwd_det();
+int attn_b16x_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
+                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
+                      float* delta, int B, int L, int nh, float p_drop, void* stream, bool det) {
   UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
              "attn_b16x_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
   UCHECK_ARG(((uintptr_t)dqkv_bf16 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0 &&
@@ -901,4 +908,13 @@ extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const floa
   a.dctx = dctx; a.dctx_slabs = 1; a.dctx_slab_stride = 0;
   a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_bf16; a.bias_part = bias_part; a.delta = delta;
   return qkv_is_bf16 ? launch_bwd<1, true>(a, (hipStream_t)stream, det) : launch_bwd<1, false>(a, (hipStream_t)stream, det);
+}
+
+extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens,
+                                    const float* ctx, const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16,
+                                    float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh, float p_drop,
+                                    void* stream) {
+  const bool det = attn_bwd_take_next_det();
+  return attn_b16x_bwd_run(qkv, qkv_is_bf16, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, bias_part, keep_bits, delta, B, L,
+                           nh, p_drop, stream, det);
 }

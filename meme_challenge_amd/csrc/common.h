@@ -26,57 +26,31 @@ void uniter_set_error(const char* fmt, ...);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// In-kernel launch stamps (uniter_prof_enable_stamps; bench.py's per-family roofline): when non-null, the NEXT GEMM
-// launch stores every workgroup's start and end time (100 MHz real-time clock) into its own words of this device slot
-// ([2][STAMP_WGS]: starts, then ends) -- two plain 8-byte stores per workgroup, reduced on the host afterwards.
-// Measured alternatives: a HIP event pair around each launch costs ~7 us on the stream and breaks the overlap of the
-// two backward streams (fp32 step +11 %, bf16 +27 %); 64-bit atomicMin / atomicMax into ONE slot serialise at the
-// memory side (~50 ns each, thousands per launch: +16 % / +35 %).  The launch that reads the pointer resets it.
-// thread_local: the model call that sets it and the launch that takes it run on one host thread (the schedule of a model call
-// is one C function); another thread's launches have their own.
 #define STAMP_WGS 1024
-extern thread_local unsigned long long* g_uniter_stamp_slot;
-static inline unsigned long long* take_stamp_slot() {
-  unsigned long long* s = g_uniter_stamp_slot;
-  g_uniter_stamp_slot = nullptr;
-  return s;
-}
 
-// Wave priority of the NEXT matrix-kernel launch (0 = default, 1..3 = s_setprio level at kernel entry; the launch that reads
-// it resets it).  fp32 matrix and vector instructions share one issue pipe per SIMD and two kernels that share a CU are
-// arbitrated wave by wave by priority, then age: the model's schedule gives the kernels of its critical path (forward,
-// input-gradient chain, attention, row passes) a higher level than the weight-gradient launches of the side stream, which have
-// slack (HIP stream priorities do not reach this arbitration: measured no effect).  thread_local, as the stamp slot.
-extern thread_local int g_uniter_launch_prio;
-static inline int take_launch_prio() {
-  const int p = g_uniter_launch_prio;
-  g_uniter_launch_prio = 0;
-  return p;
-}
-
-// Dropout keep flags drawn ahead for the NEXT LayerNorm row pass (model.cpp sets it, the launch that reads it resets it): see
-// DropCfg::bits.  thread_local, as the channels above.
-extern thread_local const unsigned char* g_uniter_drop_bits;
-static inline const unsigned char* take_drop_bits() {
-  const unsigned char* p = g_uniter_drop_bits;
-  g_uniter_drop_bits = nullptr;
-  return p;
-}
-
-// The NEXT attention-backward launch of this host thread writes its per-sample bias partials in a fixed order (uniter_attn_bwd_set_next_det;
-// model.cpp sets it in front of each attention backward of a deterministic plan, the call that reads it resets it -- a refused call
-// included: every attention-backward entry point takes it first).  thread_local, as the channels above.
-extern thread_local int g_uniter_attn_bwd_det;
-static inline bool take_attn_bwd_det() {
-  const int d = g_uniter_attn_bwd_det;
-  g_uniter_attn_bwd_det = 0;
-  return d != 0;
-}
-
-// CUs the persistent matrix kernels leave free (uniter_model_set_cu_reserve: the collectives of a data-parallel exchange run beside the
-// backward pass and need CUs of their own -- a persistent launch that counts on all of them leaves its last workgroups queued behind
-// the collective's and their whole share of the tiles late).  Set by every model call from its handle; thread_local as the channels above.
-extern thread_local int g_uniter_cu_reserve;
+// What one GEMM launch is told besides its operands.  The caller builds it at the call and every internal launcher
+// (gemm_internal.h) takes it as an argument: nothing is carried from one call to the next.  The C ABI's wrappers pass
+// LaunchOpts{}: no stamps, default priority, the whole chip.
+struct LaunchOpts {
+  // In-kernel launch stamps (uniter_prof_enable_stamps; bench.py's per-family roofline): when non-null, THIS launch
+  // stores every workgroup's start and end time (100 MHz real-time clock) into its own words of this device slot
+  // ([2][STAMP_WGS]: starts, then ends) -- two plain 8-byte stores per workgroup, reduced on the host afterwards.
+  // Measured alternatives: a HIP event pair around each launch costs ~7 us on the stream and breaks the overlap of the
+  // two backward streams (fp32 step +11 %, bf16 +27 %); 64-bit atomicMin / atomicMax into ONE slot serialise at the
+  // memory side (~50 ns each, thousands per launch: +16 % / +35 %).
+  unsigned long long* stamp = nullptr;
+  // Wave priority of THIS launch (0 = default, 1..3 = s_setprio level at kernel entry).  fp32 matrix and vector
+  // instructions share one issue pipe per SIMD and two kernels that share a CU are arbitrated wave by wave by priority,
+  // then age: the model's schedule gives the kernels of its critical path (forward, input-gradient chain, attention, row
+  // passes) a higher level than the weight-gradient launches of the side stream, which have slack (HIP stream priorities
+  // do not reach this arbitration: measured no effect).
+  int prio = 0;
+  // CUs a persistent launch leaves free (uniter_model_set_cu_reserve: the collectives of a data-parallel exchange run
+  // beside the backward pass and need CUs of their own -- a persistent launch that counts on all of them leaves its last
+  // workgroups queued behind the collective's and their whole share of the tiles late).  A model call passes the reserve
+  // of its running pass (uniter_model::launch_reserve).
+  int cu_reserve = 0;
+};
 
 #ifdef __HIPCC__
 // uniform branch around the immediate-operand instruction

@@ -538,9 +538,11 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
 }  // namespace
 
 // All-bf16 operands (resident activations / weight mirror), fp32 accumulate, fp32 and / or bf16 output.
+// lo: the stamp slot only -- these kernels set no wave priority (lo.prio is ignored here and in gemm_bf16_run) and are not persistent.
 int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B,
                      int ldb, float* C, int ldc, void* Cb, int ldcb, int epilogue, const float* bias,
-                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream, int no_sk) {
+                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
+                     const LaunchOpts& lo, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16res: bad argument");
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16res: bad epilogue %d", epilogue);
   UCHECK_ARG(!(a_kmajor && !b_kmajor), "gemm_bf16res: layout (A k-major, B k-contiguous) is not built");
@@ -557,8 +559,7 @@ int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, c
   g.Cb = (unsigned short*)Cb; g.ldcb = ldcb;
   g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux; g.beta = beta;
   g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = take_stamp_slot();
-  (void)take_launch_prio();
+  g.stamp = lo.stamp;
   if (cfg == 0) {
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     // measured (tests/tools/gemm_lab.py at M = 1424 / 2624 / 5248, profiles/r01_gemm_bf16_resident_tiles.txt): a
@@ -585,7 +586,7 @@ extern "C" int uniter_gemm_bf16res_cfg(int cfg, int a_kmajor, int b_kmajor, int 
   UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
              "gemm_bf16res: epilogue needs aux_in");
   return gemm_bf16res_run(cfg, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, C_bf16, ldcb, epilogue, bias,
-                          aux_in, aux_out, ld_aux, beta, nullptr, stream);
+                          aux_in, aux_out, ld_aux, beta, nullptr, stream, LaunchOpts{});
 }
 
 extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* stream) {
@@ -600,10 +601,11 @@ extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* str
 }
 
 // Same contract as gemm_f32_run, contraction on the bf16 matrix pipe.  Shapes the bf16 kernel does
-// not cover (K % 64 != 0, offsets beyond 31 bits) run on the exact fp32 kernel instead.
+// not cover (K % 64 != 0, offsets beyond 31 bits) run on the exact fp32 kernel instead, which is handed lo whole.
 int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
                   const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream, int no_sk) {
+                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
+                  const LaunchOpts& lo, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C, "gemm_bf16: bad argument");
   const bool ok = (K % BKB == 0 || (a_kmajor && b_kmajor)) && lda % 4 == 0 && ldb % 4 == 0 &&
                   ((size_t)M + 128) * ldc * 4 < (1ull << 31) && ((size_t)M + 128) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31) &&
@@ -613,15 +615,14 @@ int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, cons
                   ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0;
   if (!ok)
     return gemm_f32_run(0, 0, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in, aux_out,
-                        ld_aux, beta, colsum_part, stream, no_sk);
+                        ld_aux, beta, colsum_part, stream, lo, no_sk);
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16: bad epilogue %d", epilogue);
   GemmArgsB g;
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
   g.Cb = nullptr; g.ldcb = 0;
   g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux; g.beta = beta;
   g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = take_stamp_slot();
-  (void)take_launch_prio();
+  g.stamp = lo.stamp;
   if (cfg == 0) {
     // operand delivery bound: the biggest tile that still fills the chip
     // measured on MI355X (tests/tools/gemm_bf16_exp.py): 128x128 only pays once it fills the chip
@@ -644,5 +645,5 @@ extern "C" int uniter_gemm_bf16_cfg(int cfg, int a_kmajor, int b_kmajor, int M, 
   UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
              "gemm_bf16: epilogue needs aux_in");
   return gemm_bf16_run(cfg, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in, aux_out,
-                       ld_aux, beta, nullptr, stream);
+                       ld_aux, beta, nullptr, stream, LaunchOpts{});
 }

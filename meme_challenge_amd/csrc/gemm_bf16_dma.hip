@@ -41,7 +41,7 @@ struct GArgsD {
   int ld_aux;
   int tiles_m, tiles_n, band_h, nsplit;
   unsigned long long* stamp;    // optional {first start, last end} slot (common.h)
-  int prio;      // wave priority (common.h: g_uniter_launch_prio)
+  int prio;      // wave priority (common.h: LaunchOpts::prio)
   int dbg;       // measurement builds only (tests/tools/gemm_v2_lab.py): 1 = drop every output store, 2 = skip the k-loop
 };
 
@@ -593,7 +593,7 @@ int dispatch_epi(int cfg, const GArgsD& g, hipStream_t st) {
 int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda,
                     const void* B, int ldb, float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue,
                     const float* bias, const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16,
-                    int ld_aux, int beta, void* stream) {
+                    int ld_aux, int beta, void* stream, const LaunchOpts& lo) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16v2: bad argument");
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16v2: bad epilogue %d", epilogue);
   UCHECK_ARG(!a_kmajor || (b_kmajor && epilogue == UNITER_EPI_NONE && !Cb),
@@ -614,7 +614,7 @@ int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int 
     UCHECK_ARG(!a_kmajor && !beta, "gemm_bf16v2: cfg %d (persistent kernels) runs forward / input-gradient layouts without accumulate "
                "(weight gradients: uniter_wgrad_bf16_group, cfg 7)", cfg & 0xff);
     return gemm_b1p_run(cfg & 0xff, nsplit, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, c_split_stride, Cb, ldcb, epilogue, bias, aux_in,
-                        aux_in_bf16, aux_out, aux_out_bf16, ld_aux, nullptr, stream);
+                        aux_in_bf16, aux_out, aux_out_bf16, ld_aux, nullptr, stream, lo);
   }
   GArgsD g;
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
@@ -622,8 +622,8 @@ int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int 
   g.aux_in = aux_in; g.aux_in_bf16 = aux_in_bf16; g.aux_out = aux_out; g.aux_out_bf16 = aux_out_bf16; g.ld_aux = ld_aux;
   g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.nsplit = nsplit;
   g.dbg = cfg >> 8; cfg &= 0xff;
-  g.stamp = take_stamp_slot();
-  g.prio = take_launch_prio();
+  g.stamp = lo.stamp;
+  g.prio = lo.prio;
   if (cfg == 0) {
     // few tiles and one k-piece (the attention-output products: 126 tiles of 128 x 128 for 256 CUs): 64 x 128 tiles,
     // twice the workgroups (12.0 -> 10.6 us forward, 11.7 -> 10.0 us input gradient; profiles/r02_gemm_bf16_v2.txt)
@@ -638,14 +638,15 @@ int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int 
 
 // dW_p[M_p, N_p] += A_p^T B_p for up to four products of one reduction length K (A_p [K, M_p], B_p [K, N_p] bf16,
 // dW_p fp32 with leading dimension N_p), one launch; cfg 1 = two LDS stages (two workgroups per CU), 4 = three.
+// lo: the stamp slot and the reserve; this launch runs at the default wave priority whatever lo.prio says (cfg 7 is handed lo whole).
 // workgroups of the grouped launch over `total` tiles: a multiple of 8, capped (max_wgs > 0: by the caller; else
 // UNITER_WGRAD_GROUP_WGS, default 256 = one workgroup per CU walking its tiles: switches.h).  Not persistent_grid
 // (gemm_internal.h): the default cap is the switch, not the chip's CUs, and a cap below 8 leaves the grid uncapped
-static int wgrad_group_grid(int total, int max_wgs) {
+static int wgrad_group_grid(int total, int max_wgs, int cu_reserve) {
   int grid = (total + 7) / 8 * 8;
   int cap = max_wgs >= 8 ? max_wgs / 8 * 8 : uniter_switches().wgrad_group_wgs;
-  if (g_uniter_cu_reserve > 0 && cap >= 8) {              // CUs left to the data-parallel exchange's kernels (common.h)
-    const int room = (gemm_chip_cus() - g_uniter_cu_reserve) / 8 * 8;
+  if (cu_reserve > 0 && cap >= 8) {                       // CUs left to the data-parallel exchange's kernels (LaunchOpts::cu_reserve)
+    const int room = (gemm_chip_cus() - cu_reserve) / 8 * 8;
     if (room >= 8 && cap > room) cap = room;
   }
   if (cap >= 8 && grid > cap) grid = cap;
@@ -657,15 +658,15 @@ static int wgrad_group_tiles(int n, const int* Mo, const int* No) {
   return total;
 }
 // sum-of-squares slots a launch with riders writes (4 per workgroup)
-int gemm_bf16v2_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs) {
+int gemm_bf16v2_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs, int cu_reserve) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
-  return 4 * wgrad_group_grid(wgrad_group_tiles(n, Mo, No), max_wgs);
+  return 4 * wgrad_group_grid(wgrad_group_tiles(n, Mo, No), max_wgs, cu_reserve);
 }
 // the smallest grid on which the tiles take no more rounds than on one workgroup per CU
-int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No) {
+int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No, int cu_reserve) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
   const int total = wgrad_group_tiles(n, Mo, No);
-  const int full = wgrad_group_grid(total, 0);
+  const int full = wgrad_group_grid(total, 0, cu_reserve);
   const int rounds = (total + full - 1) / full;
   const int wgs = ((total + rounds - 1) / rounds + 7) / 8 * 8;
   return wgs < full ? wgs : full;
@@ -673,12 +674,11 @@ int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No) {
 
 int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A,
                             const void* const* B, float* const* dW, void* stream, int overwrite, int max_wgs,
-                            uniter_x3_riders_t* riders) {
+                            uniter_x3_riders_t* riders, const LaunchOpts& lo) {
   UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_group: bad argument");
-  if (cfg == 7) return gemm_b1p_wgrad_group(n, Mo, No, K, A, B, dW, stream, overwrite, max_wgs, riders);      // 128 x 256 tiles, persistent
+  if (cfg == 7) return gemm_b1p_wgrad_group(n, Mo, No, K, A, B, dW, stream, overwrite, max_wgs, riders, lo);      // 128 x 256 tiles, persistent
   GGroupD G;
   memset(&G.x, 0, sizeof(G.x));
-  unsigned long long* stamp = take_stamp_slot();
   int total = 0;
   for (int p = 0; p < 4; ++p) {
     G.start[p] = total;
@@ -692,13 +692,13 @@ int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K,
     g.M = Mo[p]; g.N = No[p]; g.K = K; g.A = A[p]; g.lda = Mo[p]; g.B = B[p]; g.ldb = No[p]; g.C = dW[p]; g.ldc = No[p];
     g.c_split_stride = 0; g.Cb = nullptr; g.ldcb = 0; g.epi = overwrite ? UNITER_EPI_NONE : UNITER_EPI_ADD; g.bias = nullptr;
     g.aux_in = overwrite ? nullptr : dW[p]; g.aux_in_bf16 = 0; g.aux_out = nullptr; g.aux_out_bf16 = 0; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = stamp; g.dbg = 0; g.prio = 0;
+    g.nsplit = 1; g.stamp = lo.stamp; g.dbg = 0; g.prio = 0;
     plan_tiles<128>(g, 128);
     total += g.tiles_m * g.tiles_n;
   }
   G.start[4] = total;
   for (int p = n; p < 4; ++p) G.start[p] = total;
-  const int grid = wgrad_group_grid(total, max_wgs);
+  const int grid = wgrad_group_grid(total, max_wgs, lo.cu_reserve);
   hipStream_t st = (hipStream_t)stream;
   if (riders) {
     UCHECK_ARG(cfg != 4, "wgrad_group: riders ride on the two-stage form (cfg 1)");
@@ -723,20 +723,20 @@ int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K,
 
 extern "C" int uniter_wgrad_bf16_group(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                        const void* const* B, float* const* dW, void* stream) {
-  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, 0, 0, nullptr);
+  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, 0, 0, nullptr, LaunchOpts{});
 }
 
 extern "C" int uniter_wgrad_bf16_group_riders(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                               const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                               uniter_x3_riders_t* riders, void* stream) {
-  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders);
+  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, LaunchOpts{});
 }
 extern "C" int uniter_wgrad_bf16_group_slots(int n, const int* M, const int* N, int max_wgs) {
-  return gemm_bf16v2_wgrad_group_slots(n, M, N, max_wgs);
+  return gemm_bf16v2_wgrad_group_slots(n, M, N, max_wgs, 0);
 }
 // the same for a given geometry of the grouped launch: cfg 7 (persistent 128 x 256 tiles, gemm_bf16_p.hip) writes 8 slots per workgroup
 extern "C" int uniter_wgrad_bf16_group_slots_cfg(int cfg, int n, const int* M, const int* N, int max_wgs) {
-  return cfg == 7 ? gemm_b1p_wgrad_group_slots(n, M, N, max_wgs) : gemm_bf16v2_wgrad_group_slots(n, M, N, max_wgs);
+  return cfg == 7 ? gemm_b1p_wgrad_group_slots(n, M, N, max_wgs, 0) : gemm_bf16v2_wgrad_group_slots(n, M, N, max_wgs, 0);
 }
 
 // Split-K choice for the GEMMs whose N is the hidden size (measured on MI355X, tests/tools/gemm_v2_lab.py,
@@ -775,5 +775,5 @@ extern "C" int uniter_gemm_bf16v2_cfg(int cfg, int nsplit, int a_kmajor, int b_k
   UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || aux_out,
              "gemm_bf16v2: epilogue needs aux_out");
   return gemm_bf16v2_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, c_split_stride, C_bf16, ldcb,
-                         epilogue, bias, aux_in, aux_in_bf16, aux_out, aux_out_bf16, ld_aux, beta, stream);
+                         epilogue, bias, aux_in, aux_in_bf16, aux_out, aux_out_bf16, ld_aux, beta, stream, LaunchOpts{});
 }

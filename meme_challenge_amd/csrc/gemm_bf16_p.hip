@@ -443,8 +443,8 @@ void plan_tiles_p(P1Args& g, int BM, int BN) {
 }
 
 template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int ST, int EPI, bool XTR = false>
-int launch_p1(const P1Group& G, int max_wgs, hipStream_t st) {
-  const int grid = persistent_grid(G.start[4], max_wgs);
+int launch_p1(const P1Group& G, int max_wgs, int cu_reserve, hipStream_t st) {
+  const int grid = persistent_grid(G.start[4], max_wgs, cu_reserve);
   hipLaunchKernelGGL((gemm_b1p_kernel<BM, BN, WM, WN, AKM, BKM, ST, 4, EPI, XTR>), dim3(grid), dim3(64 * ((BM / WM) * (BN / WN) + 4)), 0, st, G);
   UCHECK_LAUNCH();
   return 0;
@@ -453,12 +453,12 @@ int launch_p1(const P1Group& G, int max_wgs, hipStream_t st) {
 // geometry: 6 = 128 x 128 tiles (4 compute waves of 64 x 64 + 4 loaders, three 32-KB stages), 7 = 128 x 256 (8 compute waves, three
 // 48-KB stages = 144 KB: one workgroup per CU), 8 = 128 x 192 (8 compute waves of 64 x 48, three 40-KB stages; forward layout only)
 template <bool BKM, int EPI>
-int dispatch_geo(int cfg, const P1Group& G, hipStream_t st) {
+int dispatch_geo(int cfg, const P1Group& G, int cu_reserve, hipStream_t st) {
   switch (cfg) {
-    case 6: return launch_p1<128, 128, 64, 64, false, BKM, 3, EPI>(G, 0, st);
-    case 7: return launch_p1<128, 256, 64, 64, false, BKM, 3, EPI>(G, 0, st);
+    case 6: return launch_p1<128, 128, 64, 64, false, BKM, 3, EPI>(G, 0, cu_reserve, st);
+    case 7: return launch_p1<128, 256, 64, 64, false, BKM, 3, EPI>(G, 0, cu_reserve, st);
     case 8:
-      if constexpr (!BKM) return launch_p1<128, 192, 64, 48, false, BKM, 3, EPI>(G, 0, st);
+      if constexpr (!BKM) return launch_p1<128, 192, 64, 48, false, BKM, 3, EPI>(G, 0, cu_reserve, st);
     default: uniter_set_error("gemm_bf16p: bad cfg %d (6 = 128 x 128, 7 = 128 x 256, 8 = 128 x 192 with k-contiguous weights only)", cfg); return UNITER_E_ARG;
   }
 }
@@ -493,20 +493,21 @@ void b1p_choose(int M, int N, int K, int avail, int nsplit_fixed, bool b_kmajor,
 // product of the bf16 mode on `avail_cus` CUs (0 = the chip's): geometry 6 / 7 / 8 and k-pieces.  Host arithmetic, no launch.
 extern "C" int uniter_gemm_bf16p_plan(int M, int N, int K, int avail_cus, int nsplit_fixed, int b_kmajor, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_bf16p_plan: bad argument");
-  b1p_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, b_kmajor != 0, cfg, nsplit);
+  b1p_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0, 0), nsplit_fixed, b_kmajor != 0, cfg, nsplit);
   return 0;
 }
 
-int gemm_b1p_pick_split(int M, int N, int K, int avail) {
+int gemm_b1p_pick_split(int M, int N, int K, int avail, int cu_reserve) {
   int c, n;
-  b1p_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0), 0, false, &c, &n);
+  b1p_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0, cu_reserve), 0, false, &c, &n);
   return n;
 }
 
 // C / Cb = epi(A . B^T) on bf16 operands (fp32 accumulate): the persistent loader / compute kernels.  cfg 6..8 (dispatch_geo), 0 = choose.
 int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                  float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue, const float* bias,
-                 const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16, int ld_aux, float* colpart, void* stream) {
+                 const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16, int ld_aux, float* colpart, void* stream,
+                 const LaunchOpts& lo) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16p: bad argument");
   UCHECK_ARG(epilogue == UNITER_EPI_NONE || epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_BIAS_GELU_D ||
              epilogue == UNITER_EPI_MUL, "gemm_bf16p: epilogue %d is not built for the persistent kernels (none, bias, + aux, bias + GELU + gelu', x aux)", epilogue);
@@ -526,7 +527,7 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
                "gemm_bf16p: operand beyond 31-bit offsets");
   if (cfg == 0) {
     int ns_;
-    b1p_choose(M, N, K, persistent_grid(1 << 20, 0), nsplit, b_kmajor != 0, &cfg, &ns_);
+    b1p_choose(M, N, K, persistent_grid(1 << 20, 0, lo.cu_reserve), nsplit, b_kmajor != 0, &cfg, &ns_);
   }
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
@@ -534,8 +535,8 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.c_split_stride = c_split_stride;
   g.Cb = (unsigned short*)Cb; g.ldcb = ldcb; g.bias = bias; g.aux_in = aux_in; g.aux_in_bf16 = aux_in_bf16; g.aux_out = aux_out;
   g.aux_out_bf16 = aux_out_bf16; g.ld_aux = ld_aux; g.nsplit = nsplit; g.colpart = colpart;
-  g.stamp = take_stamp_slot();
-  g.prio = take_launch_prio();
+  g.stamp = lo.stamp;
+  g.prio = lo.prio;
   plan_tiles_p(g, 128, cfg == 7 ? 256 : cfg == 8 ? 192 : 128);
   const int total = g.tiles_m * g.tiles_n * nsplit;
   for (int p = 1; p < 4; ++p) G.p[p] = g;
@@ -544,16 +545,16 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
   hipStream_t st = (hipStream_t)stream;
   if (b_kmajor) {
     switch (epilogue) {
-      case UNITER_EPI_NONE: return dispatch_geo<true, P1_NONE>(cfg, G, st);
-      case UNITER_EPI_ADD: return dispatch_geo<true, P1_ADD>(cfg, G, st);
-      case UNITER_EPI_MUL: return dispatch_geo<true, P1_MUL>(cfg, G, st);
+      case UNITER_EPI_NONE: return dispatch_geo<true, P1_NONE>(cfg, G, lo.cu_reserve, st);
+      case UNITER_EPI_ADD: return dispatch_geo<true, P1_ADD>(cfg, G, lo.cu_reserve, st);
+      case UNITER_EPI_MUL: return dispatch_geo<true, P1_MUL>(cfg, G, lo.cu_reserve, st);
       default: uniter_set_error("gemm_bf16p: epilogue %d is not built for k-major weights (none, + aux, x aux)", epilogue); return UNITER_E_ARG;
     }
   }
   switch (epilogue) {
-    case UNITER_EPI_NONE: return dispatch_geo<false, P1_NONE>(cfg, G, st);
-    case UNITER_EPI_BIAS: return dispatch_geo<false, P1_BIAS>(cfg, G, st);
-    case UNITER_EPI_BIAS_GELU_D: return dispatch_geo<false, P1_BIAS_GELU_D>(cfg, G, st);
+    case UNITER_EPI_NONE: return dispatch_geo<false, P1_NONE>(cfg, G, lo.cu_reserve, st);
+    case UNITER_EPI_BIAS: return dispatch_geo<false, P1_BIAS>(cfg, G, lo.cu_reserve, st);
+    case UNITER_EPI_BIAS_GELU_D: return dispatch_geo<false, P1_BIAS_GELU_D>(cfg, G, lo.cu_reserve, st);
     default: uniter_set_error("gemm_bf16p: epilogue %d is not built for k-contiguous weights (none, bias, bias + GELU + gelu')", epilogue); return UNITER_E_ARG;
   }
 }
@@ -566,16 +567,16 @@ static int b1p_wgrad_tiles(int n, const int* Mo, const int* No) {
   for (int p = 0; p < n; ++p) total += ((Mo[p] + 127) / 128) * ((No[p] + 255) / 256);
   return total;
 }
-int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs) {
+int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs, int cu_reserve) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
-  return 8 * persistent_grid(b1p_wgrad_tiles(n, Mo, No), max_wgs);
+  return 8 * persistent_grid(b1p_wgrad_tiles(n, Mo, No), max_wgs, cu_reserve);
 }
+// lo: the stamp slot and the reserve; the launch runs at the default wave priority whatever lo.prio says
 int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B, float* const* dW,
-                         void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders) {
+                         void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders, const LaunchOpts& lo) {
   UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_bf16p_group: bad argument");
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
-  unsigned long long* stamp = take_stamp_slot();
   int total = 0;
   for (int p = 0; p < 4; ++p) {
     G.start[p] = total;
@@ -589,7 +590,7 @@ int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void*
     g.M = Mo[p]; g.N = No[p]; g.K = K; g.A = A[p]; g.lda = Mo[p]; g.B = B[p]; g.ldb = No[p]; g.C = dW[p]; g.ldc = No[p];
     g.c_split_stride = 0; g.Cb = nullptr; g.ldcb = 0; g.bias = nullptr;
     g.aux_in = overwrite ? nullptr : dW[p]; g.aux_in_bf16 = 0; g.aux_out = nullptr; g.aux_out_bf16 = 0; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = stamp; g.prio = 0; g.colpart = nullptr;
+    g.nsplit = 1; g.stamp = lo.stamp; g.prio = 0; g.colpart = nullptr;
     plan_tiles_p(g, 128, 256);
     total += g.tiles_m * g.tiles_n;
   }
@@ -599,12 +600,12 @@ int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void*
   if (riders) {
     UCHECK_ARG(!riders->colsum_out, "wgrad_bf16p_group: colsum_out does not ride on the 128 x 256 geometry (take the bias gradient from the "
                "producing product's column partials as a reduction job)");
-    riders->grid = persistent_grid(total, max_wgs);
+    riders->grid = persistent_grid(total, max_wgs, lo.cu_reserve);
     UCHECK_RC(riders_prepare(*riders, "wgrad_bf16p_group"));
     G.x = *riders;
-    return overwrite ? launch_p1<128, 256, 64, 64, true, true, 3, P1_NONE, true>(G, max_wgs, st)
-                     : launch_p1<128, 256, 64, 64, true, true, 3, P1_ADD, true>(G, max_wgs, st);
+    return overwrite ? launch_p1<128, 256, 64, 64, true, true, 3, P1_NONE, true>(G, max_wgs, lo.cu_reserve, st)
+                     : launch_p1<128, 256, 64, 64, true, true, 3, P1_ADD, true>(G, max_wgs, lo.cu_reserve, st);
   }
-  return overwrite ? launch_p1<128, 256, 64, 64, true, true, 3, P1_NONE>(G, max_wgs, st)
-                   : launch_p1<128, 256, 64, 64, true, true, 3, P1_ADD>(G, max_wgs, st);
+  return overwrite ? launch_p1<128, 256, 64, 64, true, true, 3, P1_NONE>(G, max_wgs, lo.cu_reserve, st)
+                   : launch_p1<128, 256, 64, 64, true, true, 3, P1_ADD>(G, max_wgs, lo.cu_reserve, st);
 }

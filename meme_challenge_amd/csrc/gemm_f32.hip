@@ -49,7 +49,7 @@ struct GemmArgs {
   int band_h;
   float* colsum_part;   // optional [ceil(M/32)][N]: per-32-row-block column sums of the stored C (v3 only)
   unsigned long long* stamp;    // optional {first start, last end} slot (common.h)
-  int prio;                     // wave priority (common.h: g_uniter_launch_prio)
+  int prio;                     // wave priority (common.h: LaunchOpts::prio)
 };
 
 __device__ __forceinline__ float buf_ld_f32(__amdgpu_buffer_rsrc_t r, int voff, int soff, int aux) {
@@ -786,7 +786,7 @@ int choose_cfg(int M, int N) {
 // dW_p[Mo_p, No_p] (+)= A_p^T B_p, p < n <= 4, A_p [K, Mo_p], B_p [K, No_p] fp32 (gemm_f32_wgrad_group_kernel); returns
 // UNITER_E_SHAPE for shapes the grouped kernel does not take (the caller then launches the products one by one)
 int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float* const* A, const float* const* B,
-                         float* const* dW, int overwrite, void* stream) {
+                         float* const* dW, int overwrite, void* stream, const LaunchOpts& lo) {
   UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_group_f32: bad argument");
   GemmGroup G = {};
   int total = 0;
@@ -809,7 +809,7 @@ int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float
   }
   G.start[4] = total;
   for (int p = n; p < 4; ++p) G.start[p] = total;
-  G.K = K; G.overwrite = overwrite; G.prio = take_launch_prio(); G.stamp = take_stamp_slot();
+  G.K = K; G.overwrite = overwrite; G.prio = lo.prio; G.stamp = lo.stamp;
   const int slots_env = uniter_switches().wgrad_group_f32_slots;
   const int slots = slots_env >= 8 ? slots_env / 8 * 8 : 1024;
   const int grid = total < slots ? (total + 7) / 8 * 8 : slots;
@@ -820,7 +820,7 @@ int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float
 
 extern "C" int uniter_wgrad_f32_group(int n, const int* M, const int* N, int K, const float* const* A, const float* const* B,
                                       float* const* dW, int overwrite, void* stream) {
-  return gemm_f32_wgrad_group(n, M, N, K, A, B, dW, overwrite, stream);
+  return gemm_f32_wgrad_group(n, M, N, K, A, B, dW, overwrite, stream, LaunchOpts{});
 }
 
 // tag != 0 selects a separately named instantiation of the x @ W^T kernel (TAG template
@@ -828,7 +828,7 @@ extern "C" int uniter_wgrad_f32_group(int n, const int* M, const int* N, int K, 
 int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,
                  int lda, const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part,
-                 void* stream, int no_sk) {
+                 void* stream, const LaunchOpts& lo, int no_sk) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad dims %d %d %d", M, N, K);
   UCHECK_ARG(A && B && C, "gemm: null operand");
   UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm: bad epilogue %d", epilogue);
@@ -846,8 +846,8 @@ int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
   g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux;
   g.beta = beta; g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = take_stamp_slot();
-  g.prio = take_launch_prio();
+  g.stamp = lo.stamp;
+  g.prio = lo.prio;
   if (cfg == 0) cfg = choose_cfg(M, N);
   if (colsum_part) {
     const bool fast = (K % BK == 0 || (a_kmajor && b_kmajor)) && (size_t)(a_kmajor ? K : M) * lda * 4 < (1ull << 31) &&
@@ -867,7 +867,7 @@ extern "C" int uniter_gemm_f32_cfg(int cfg, int a_kmajor, int b_kmajor, int M, i
                                    int ldc, int epilogue, const float* bias, const float* aux_in,
                                    float* aux_out, int ld_aux, int beta, void* stream) {
   return gemm_f32_run(cfg, 0, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in,
-                      aux_out, ld_aux, beta, nullptr, stream);
+                      aux_out, ld_aux, beta, nullptr, stream, LaunchOpts{});
 }
 
 extern "C" int uniter_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,

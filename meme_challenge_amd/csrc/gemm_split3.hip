@@ -1033,8 +1033,8 @@ void plan_tiles3(S3Args& g, int BN) {
 }
 
 template <int BM, int BN, int WM, int WN, bool AKM, bool BKM, int ST, int KT, int NWL, bool M16, int EPI, bool XTR = false>
-int launch_s3p(const S3Group& G, int max_wgs, hipStream_t st) {
-  const int grid = persistent_grid(G.start[4], max_wgs);
+int launch_s3p(const S3Group& G, int max_wgs, int cu_reserve, hipStream_t st) {
+  const int grid = persistent_grid(G.start[4], max_wgs, cu_reserve);
   hipLaunchKernelGGL((gemm_s3p_kernel<BM, BN, WM, WN, AKM, BKM, ST, KT, NWL, M16, EPI, XTR>), dim3(grid),
                      dim3(64 * ((BM / WM) * (BN / WN) + NWL)), 0, st, G);
   UCHECK_LAUNCH();
@@ -1050,12 +1050,12 @@ size_t sk_ws_bytes_() { return SK_FLAG_BYTES + (size_t)gemm_chip_cus() * SK_SLOT
 // grid of the balanced walk for `tiles` tiles of `nk` k-tiles each: every CU the launch may use -- or 0: the classic walk is as
 // good (its rounds are full), or the workspace is missing.  The hand-over (a 128-KB partial sum stored, flagged and added) is
 // priced at four k-tiles
-int x3_sk_grid(int tiles, int nk, int max_wgs, const void* ws, size_t ws_bytes) {
+int x3_sk_grid(int tiles, int nk, int max_wgs, int cu_reserve, const void* ws, size_t ws_bytes) {
   if (!ws || ws_bytes < sk_ws_bytes_() || ((uintptr_t)ws & 255) != 0 || tiles <= 0 || nk <= 0) return 0;
-  const int cap = persistent_grid(1 << 20, max_wgs);
+  const int cap = persistent_grid(1 << 20, max_wgs, cu_reserve);
   const long units = (long)tiles * nk;
   if (cap > 512 || units >= (1l << 30) || units < 8l * cap) return 0;
-  const int g0 = persistent_grid(tiles, max_wgs);
+  const int g0 = persistent_grid(tiles, max_wgs, cu_reserve);
   const long classic = (long)((tiles + g0 - 1) / g0) * nk, balanced = (units + cap - 1) / cap + 4;
   return classic > balanced ? cap : 0;
 }
@@ -1081,16 +1081,16 @@ int launch_s3p_sk(S3Group& G, int grid, void* ws, hipStream_t st) {
 //   5: 128 x 192 tiles (forward layout, fp32 output): 8 compute waves of 64 x 48, two stages of 60 KB -- for products whose N is a
 //      multiple of 192 and whose 128 x 256 tiles leave CUs idle (the QKV product at configs[1]: 189 tiles of 128 x 256, 252 of 128 x 192)
 template <bool AKM, bool BKM, int EPI>
-int dispatch_cfg3p(int cfg, const S3Group& G, int max_wgs, hipStream_t st) {
+int dispatch_cfg3p(int cfg, const S3Group& G, int max_wgs, int cu_reserve, hipStream_t st) {
   switch (cfg) {
-    case 1: return launch_s3p<128, 128, 64, 32, AKM, BKM, 3, 32, 4, false, EPI>(G, max_wgs, st);
-    case 2: return launch_s3p<128, 128, 64, 64, AKM, BKM, 3, 32, 4, false, EPI>(G, max_wgs, st);
-    case 3: return launch_s3p<128, 128, 64, 64, AKM, BKM, 3, 32, 4, true, EPI>(G, max_wgs, st);
+    case 1: return launch_s3p<128, 128, 64, 32, AKM, BKM, 3, 32, 4, false, EPI>(G, max_wgs, cu_reserve, st);
+    case 2: return launch_s3p<128, 128, 64, 64, AKM, BKM, 3, 32, 4, false, EPI>(G, max_wgs, cu_reserve, st);
+    case 3: return launch_s3p<128, 128, 64, 64, AKM, BKM, 3, 32, 4, true, EPI>(G, max_wgs, cu_reserve, st);
     case 4:
-      if constexpr (!AKM) return launch_s3p<128, 256, 64, 64, AKM, BKM, 2, 32, 4, true, EPI>(G, max_wgs, st);
+      if constexpr (!AKM) return launch_s3p<128, 256, 64, 64, AKM, BKM, 2, 32, 4, true, EPI>(G, max_wgs, cu_reserve, st);
       // (weight gradients keep the 128 x 128 whole-K tiles)
     case 5:
-      if constexpr (!AKM && !BKM) return launch_s3p<128, 192, 64, 48, AKM, BKM, 2, 32, 4, true, EPI>(G, max_wgs, st);
+      if constexpr (!AKM && !BKM) return launch_s3p<128, 192, 64, 48, AKM, BKM, 2, 32, 4, true, EPI>(G, max_wgs, cu_reserve, st);
       // (forward layout only)
     default: uniter_set_error("gemm_x3: bad cfg %d (1..5; 4 not for weight gradients, 5 for the forward layout only)", cfg); return UNITER_E_ARG;
   }
@@ -1099,7 +1099,7 @@ int dispatch_cfg3p(int cfg, const S3Group& G, int max_wgs, hipStream_t st) {
 struct SkWs { void* p; size_t bytes; };
 
 template <bool AKM, bool BKM, int EPI>
-int dispatch_cfg3(int cfg, const S3Args& g, hipStream_t st, SkWs sk) {
+int dispatch_cfg3(int cfg, const S3Args& g, hipStream_t st, SkWs sk, int cu_reserve) {
   S3Group G;
   memset(&G.x, 0, sizeof(G.x));
   G.sk_part = nullptr; G.sk_flag = nullptr; G.sk_units = G.sk_nk = 0;
@@ -1111,25 +1111,25 @@ int dispatch_cfg3(int cfg, const S3Args& g, hipStream_t st, SkWs sk) {
   // the balanced walk: built for the forward products with a bias epilogue (the QKV product: 189 tiles of 128 x 256 at configs[1])
   if constexpr (!AKM && !BKM && EPI == S3_BIAS) {
     if (cfg == 4 && g.nsplit == 1) {
-      const int grid = x3_sk_grid(total, (g.K + 31) / 32, 0, sk.p, sk.bytes);
+      const int grid = x3_sk_grid(total, (g.K + 31) / 32, 0, cu_reserve, sk.p, sk.bytes);
       if (grid > 0) return launch_s3p_sk<128, 256, 64, 64, AKM, BKM, 2, 32, 4, true, EPI, false>(G, grid, sk.p, st);
     }
   }
-  return dispatch_cfg3p<AKM, BKM, EPI>(cfg, G, 0, st);
+  return dispatch_cfg3p<AKM, BKM, EPI>(cfg, G, 0, cu_reserve, st);
 }
 
 template <bool AKM, bool BKM>
-int dispatch_epi3(int cfg, const S3Args& g, int epi, hipStream_t st, SkWs sk) {
+int dispatch_epi3(int cfg, const S3Args& g, int epi, hipStream_t st, SkWs sk, int cu_reserve) {
   // forward products (weights k-contiguous): none / bias / bias + GELU; input gradients (weights k-major): none / add / mul;
   // weight gradients (both k-major): none / add
-  if (epi == UNITER_EPI_NONE) return dispatch_cfg3<AKM, BKM, S3_NONE>(cfg, g, st, sk);
+  if (epi == UNITER_EPI_NONE) return dispatch_cfg3<AKM, BKM, S3_NONE>(cfg, g, st, sk, cu_reserve);
   if constexpr (!AKM && !BKM) {
-    if (epi == UNITER_EPI_BIAS) return dispatch_cfg3<AKM, BKM, S3_BIAS>(cfg, g, st, sk);
-    if (epi == UNITER_EPI_BIAS_GELU_D) return dispatch_cfg3<AKM, BKM, S3_BIAS_GELU_D>(cfg, g, st, sk);
+    if (epi == UNITER_EPI_BIAS) return dispatch_cfg3<AKM, BKM, S3_BIAS>(cfg, g, st, sk, cu_reserve);
+    if (epi == UNITER_EPI_BIAS_GELU_D) return dispatch_cfg3<AKM, BKM, S3_BIAS_GELU_D>(cfg, g, st, sk, cu_reserve);
   } else {
-    if (epi == UNITER_EPI_ADD) return dispatch_cfg3<AKM, BKM, S3_ADD>(cfg, g, st, sk);
+    if (epi == UNITER_EPI_ADD) return dispatch_cfg3<AKM, BKM, S3_ADD>(cfg, g, st, sk, cu_reserve);
     if constexpr (!AKM) {
-      if (epi == UNITER_EPI_MUL) return dispatch_cfg3<AKM, BKM, S3_MUL>(cfg, g, st, sk);
+      if (epi == UNITER_EPI_MUL) return dispatch_cfg3<AKM, BKM, S3_MUL>(cfg, g, st, sk, cu_reserve);
     }
   }
   uniter_set_error("gemm_x3: epilogue %d is not built for this operand layout", epi);
@@ -1296,7 +1296,7 @@ void x3_choose(int M, int N, int K, int avail, int nsplit_fixed, int* cfg_out, i
 int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, int psa,
                 const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride, void* Cx, int ldcx, int pscx,
                 int epilogue, const float* bias, const float* aux_in, float* aux_out, int ld_aux, void* stream,
-                float* colsum_part, void* sk_ws, size_t sk_ws_bytes) {
+                float* colsum_part, void* sk_ws, size_t sk_ws_bytes, const LaunchOpts& lo) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cx), "gemm_x3: bad argument");
   UCHECK_ARG(!a_kmajor || (b_kmajor && !Cx && (epilogue == UNITER_EPI_NONE || epilogue == UNITER_EPI_ADD)),
              "gemm_x3: A k-major only as the weight-gradient layout (both operands k-major, fp32 output, none / add)");
@@ -1323,8 +1323,8 @@ int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, i
   g.dbg = cfg >> 8; g.b_paired = (cfg >> 6) & 1; cfg &= 0x3f;      // (cfg | 64: B in the paired-row layout of the weight mirror)
   UCHECK_ARG(!g.b_paired || (!a_kmajor && N % 2 == 0 && ldb % 32 == 0), "gemm_x3: paired rows are the layout of a weight (B, forward or input-gradient "
              "product) with an even number of rows and a row length that is a multiple of 32");
-  g.stamp = take_stamp_slot();
-  g.prio = take_launch_prio();
+  g.stamp = lo.stamp;
+  g.prio = lo.prio;
   UCHECK_ARG((cfg & 0xff) != 5 || (!a_kmajor && !b_kmajor && !Cx), "gemm_x3: cfg 5 (128 x 192 tiles) is built for the forward layout with an fp32 output");
   UCHECK_ARG(!colsum_part || (epilogue == UNITER_EPI_MUL && nsplit == 1 && (cfg == 0 || cfg >= 3) && ((uintptr_t)colsum_part & 15) == 0 && N % 4 == 0),
              "gemm_x3: column partials ride on the x aux epilogue of the 16x16x32 geometries (cfg 0, 3, 4), one k-piece");
@@ -1337,16 +1337,16 @@ int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, i
     // 1-KiB instruction per ~45 cycles and CU), and a 128 x 256 tile stages 72 KB per k-tile for twice the products of a 128 x 128
     // one's 48 KB: measured 1.75 x the time per k-tile for 2 x the work (profiles/r05_gemm_x3_lab.txt: QKV forward 61.0 -> 54.9 us,
     // FFN-up forward 76.7 -> 69.5, FFN-down input gradient 72.9 -> 65.2).  x3_choose prices both geometries on the CUs this
-    // launch may use (all of them, or what a data-parallel exchange leaves: g_uniter_cu_reserve)
+    // launch may use (all of them, or what a data-parallel exchange leaves: lo.cu_reserve)
     if (!a_kmajor) {
       int ns_;
-      x3_choose(M, N, K, persistent_grid(1 << 20, 0), nsplit, &cfg, &ns_, !b_kmajor && !Cx);
+      x3_choose(M, N, K, persistent_grid(1 << 20, 0, lo.cu_reserve), nsplit, &cfg, &ns_, !b_kmajor && !Cx);
     }
   }
   hipStream_t st = (hipStream_t)stream;
   const SkWs sk = {sk_ws, sk_ws_bytes};
-  if (a_kmajor) return dispatch_epi3<true, true>(cfg, g, epilogue, st, sk);
-  return b_kmajor ? dispatch_epi3<false, true>(cfg, g, epilogue, st, sk) : dispatch_epi3<false, false>(cfg, g, epilogue, st, sk);
+  if (a_kmajor) return dispatch_epi3<true, true>(cfg, g, epilogue, st, sk, lo.cu_reserve);
+  return b_kmajor ? dispatch_epi3<false, true>(cfg, g, epilogue, st, sk, lo.cu_reserve) : dispatch_epi3<false, false>(cfg, g, epilogue, st, sk, lo.cu_reserve);
 }
 
 // Tile geometry (cfg 3 = 128 x 128 persistent, cfg 4 = 128 x 256 one-round) and k-pieces of a forward / input-gradient product on
@@ -1380,21 +1380,21 @@ void x3_choose(int M, int N, int K, int avail, int nsplit_fixed, int* cfg_out, i
 
 extern "C" int uniter_gemm_x3_plan(int M, int N, int K, int avail_cus, int nsplit_fixed, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_x3_plan: bad argument");
-  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit);
+  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0, 0), nsplit_fixed, cfg, nsplit);
   return 0;
 }
 
 // the same for a forward product (both operands k-contiguous) with an fp32 output: 128 x 192 tiles (cfg 5) compete too
 extern "C" int uniter_gemm_x3_plan_fwd32(int M, int N, int K, int avail_cus, int nsplit_fixed, int* cfg, int* nsplit) {
   UCHECK_ARG(M > 0 && N > 0 && K > 0 && cfg && nsplit && nsplit_fixed >= 0 && nsplit_fixed <= 8, "gemm_x3_plan_fwd32: bad argument");
-  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0), nsplit_fixed, cfg, nsplit, true);
+  x3_choose(M, N, K, avail_cus > 0 ? avail_cus : persistent_grid(1 << 20, 0, 0), nsplit_fixed, cfg, nsplit, true);
   return 0;
 }
 
-// k-pieces of a product whose output goes to fp32 slabs, on `avail` CUs (0 = the chip's)
-int gemm_x3_pick_split_on(int M, int N, int K, int avail) {
+// k-pieces of a product whose output goes to fp32 slabs, on `avail` CUs (0 = the chip's minus cu_reserve)
+int gemm_x3_pick_split_on(int M, int N, int K, int avail, int cu_reserve) {
   int c, n;
-  x3_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0), 0, &c, &n);
+  x3_choose(M, N, K, avail > 0 ? avail : persistent_grid(1 << 20, 0, cu_reserve), 0, &c, &n);
   return n;
 }
 
@@ -1411,7 +1411,7 @@ extern "C" int uniter_gemm_x3_cfg(int cfg, int nsplit, int a_kmajor, int b_kmajo
                                   void* C_x3, int ldcx, int pscx, int epilogue, const float* bias, const float* aux_in,
                                   float* aux_out, int ld_aux, void* stream) {
   return gemm_x3_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, c_split_stride, C_x3, ldcx,
-                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, nullptr, 0);
+                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, nullptr, 0, LaunchOpts{});
 }
 
 // the same, with the workspace of the balanced walk (uniter_gemm_x3_balanced_ws_bytes; its first 16 KB zero before the first launch,
@@ -1423,7 +1423,7 @@ extern "C" int uniter_gemm_x3_cfg_ws(int cfg, int nsplit, int a_kmajor, int b_km
                                      void* C_x3, int ldcx, int pscx, int epilogue, const float* bias, const float* aux_in,
                                      float* aux_out, int ld_aux, void* ws, size_t ws_bytes, void* stream) {
   return gemm_x3_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, c_split_stride, C_x3, ldcx,
-                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, ws, ws_bytes);
+                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, ws, ws_bytes, LaunchOpts{});
 }
 
 // the same product, also leaving partial column sums of its output: colsum_part[(i, n)] = sum of the output rows 64 i .. 64 i + 63
@@ -1433,7 +1433,7 @@ extern "C" int uniter_gemm_x3_colpart(int cfg, int a_kmajor, int b_kmajor, int M
                                       const void* B, int ldb, int psb, float* C, int ldc, void* C_x3, int ldcx, int pscx,
                                       const float* aux_in, int ld_aux, float* colsum_part, void* stream) {
   return gemm_x3_run(cfg, 1, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, 0, C_x3, ldcx, pscx, UNITER_EPI_MUL,
-                     nullptr, aux_in, nullptr, ld_aux, stream, colsum_part, nullptr, 0);
+                     nullptr, aux_in, nullptr, ld_aux, stream, colsum_part, nullptr, 0, LaunchOpts{});
 }
 
 extern "C" int uniter_split3(const float* x, int rows, int cols, int ld, void* x3, size_t row_stride, size_t piece_stride,
@@ -1502,7 +1502,8 @@ extern "C" int uniter_colsum_x3_add_det(const void* x3, int rows, int cols, int 
 }
 
 // dW_p[M_p, N_p] (+)= A_p^T B_p for up to four products of one reduction length K (A_p [K][3][M_p], B_p [K][3][N_p] x3,
-// dW_p fp32 with leading dimension N_p), one launch of whole-K tiles.
+// dW_p fp32 with leading dimension N_p), one launch of whole-K tiles.  lo: the stamp slot and the reserve; the launch runs at the
+// default wave priority whatever lo.prio says.
 // tile width of the grouped weight-gradient launch: cfg 4 = 128 x 256 tiles (round 5), else 128 x 128
 static int wgrad_bn(int cfg) { return cfg == 4 ? 256 : 128; }
 static int wgrad_tiles(int cfg, int n, const int* Mo, const int* No) {
@@ -1515,13 +1516,12 @@ int gemm_x3_wgrad_default_cfg() { return uniter_switches().x3_wgrad_cfg; }
 
 int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B,
                         float* const* dW, void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders,
-                        void* sk_ws, size_t sk_ws_bytes) {
+                        void* sk_ws, size_t sk_ws_bytes, const LaunchOpts& lo) {
   UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_x3_group: bad argument");
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
   S3Group G;
   memset(&G.x, 0, sizeof(G.x));
   G.sk_part = nullptr; G.sk_flag = nullptr; G.sk_units = G.sk_nk = 0;
-  unsigned long long* stamp = take_stamp_slot();
   int total = 0;
   for (int p = 0; p < 4; ++p) {
     G.start[p] = total;
@@ -1536,7 +1536,7 @@ int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, con
     g.C = dW[p]; g.ldc = No[p];
     g.c_split_stride = 0; g.Cx = nullptr; g.ldcx = 0; g.pscx = 0; g.bias = nullptr;
     g.aux_in = overwrite ? nullptr : dW[p]; g.aux_out = nullptr; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = stamp; g.prio = 0; g.dbg = 0; g.colpart = nullptr; g.b_paired = 0;
+    g.nsplit = 1; g.stamp = lo.stamp; g.prio = 0; g.dbg = 0; g.colpart = nullptr; g.b_paired = 0;
     plan_tiles3<128>(g, wgrad_bn(cfg));
     total += g.tiles_m * g.tiles_n;
   }
@@ -1544,51 +1544,51 @@ int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, con
   for (int p = n; p < 4; ++p) G.start[p] = total;
   hipStream_t st = (hipStream_t)stream;
   // the balanced walk (128 x 256 tiles, a workspace given): 216 tiles for UNITER-base on 256 CUs -- 82 k-tiles per workgroup become 70
-  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (K + 31) / 32, max_wgs, sk_ws, sk_ws_bytes) : 0;
+  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (K + 31) / 32, max_wgs, lo.cu_reserve, sk_ws, sk_ws_bytes) : 0;
   if (riders) {
     // riders ride on the v_mfma_f32_16x16x32_bf16 geometries: 4 compute waves of 64 x 64 (cfg 3) or the 128 x 256 tile's 8 (cfg 4)
     UCHECK_ARG(cfg == 3 || cfg == 4, "wgrad_x3_group: riders need cfg 3 or 4");
     uniter_x3_riders_t& x = *riders;
     UCHECK_ARG(cfg != 4 || !x.colsum_out, "wgrad_x3_group: colsum_out rides on cfg 3 only (the 128 x 256 geometry has no registers for it: "
                "take the bias gradient from the producing product's column partials, uniter_gemm_x3_colpart, as a reduction job)");
-    x.grid = sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs);
+    x.grid = sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs, lo.cu_reserve);
     UCHECK_RC(riders_prepare(x, "wgrad_x3_group"));
     G.x = x;
     if (sk_grid > 0)
       return overwrite ? launch_s3p_sk<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE, true>(G, sk_grid, sk_ws, st)
                        : launch_s3p_sk<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD, true>(G, sk_grid, sk_ws, st);
     if (cfg == 4)
-      return overwrite ? launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE, true>(G, max_wgs, st)
-                       : launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD, true>(G, max_wgs, st);
-    return overwrite ? launch_s3p<128, 128, 64, 64, true, true, 3, 32, 4, true, S3_NONE, true>(G, max_wgs, st)
-                     : launch_s3p<128, 128, 64, 64, true, true, 3, 32, 4, true, S3_ADD, true>(G, max_wgs, st);
+      return overwrite ? launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE, true>(G, max_wgs, lo.cu_reserve, st)
+                       : launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD, true>(G, max_wgs, lo.cu_reserve, st);
+    return overwrite ? launch_s3p<128, 128, 64, 64, true, true, 3, 32, 4, true, S3_NONE, true>(G, max_wgs, lo.cu_reserve, st)
+                     : launch_s3p<128, 128, 64, 64, true, true, 3, 32, 4, true, S3_ADD, true>(G, max_wgs, lo.cu_reserve, st);
   }
   if (sk_grid > 0)
     return overwrite ? launch_s3p_sk<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE, false>(G, sk_grid, sk_ws, st)
                      : launch_s3p_sk<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD, false>(G, sk_grid, sk_ws, st);
   if (cfg == 4)
-    return overwrite ? launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE>(G, max_wgs, st)
-                     : launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD>(G, max_wgs, st);
-  return overwrite ? dispatch_cfg3p<true, true, S3_NONE>(cfg, G, max_wgs, st) : dispatch_cfg3p<true, true, S3_ADD>(cfg, G, max_wgs, st);
+    return overwrite ? launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_NONE>(G, max_wgs, lo.cu_reserve, st)
+                     : launch_s3p<128, 256, 64, 64, true, true, 2, 32, 4, true, S3_ADD>(G, max_wgs, lo.cu_reserve, st);
+  return overwrite ? dispatch_cfg3p<true, true, S3_NONE>(cfg, G, max_wgs, lo.cu_reserve, st) : dispatch_cfg3p<true, true, S3_ADD>(cfg, G, max_wgs, lo.cu_reserve, st);
 }
 
 // sum-of-squares slots a launch with riders writes (one per compute wave: 4 per workgroup, 8 with 128 x 256 tiles) for these products;
 // K > 0 and a workspace size: the launch is given the balanced walk's workspace (it then runs on every CU it may use)
-int gemm_x3_wgrad_group_slots(int cfg, int n, const int* Mo, const int* No, int max_wgs, int K, size_t sk_ws_bytes) {
+int gemm_x3_wgrad_group_slots(int cfg, int n, const int* Mo, const int* No, int max_wgs, int K, size_t sk_ws_bytes, int cu_reserve) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
   const int total = wgrad_tiles(cfg, n, Mo, No);
   // (x3_sk_grid checks the pointer's alignment only: any aligned non-null value stands for the workspace here)
-  const int sk_grid = (cfg == 4 && K > 0) ? x3_sk_grid(total, (K + 31) / 32, max_wgs, (const void*)256, sk_ws_bytes) : 0;
-  return (cfg == 4 ? 8 : 4) * (sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs));
+  const int sk_grid = (cfg == 4 && K > 0) ? x3_sk_grid(total, (K + 31) / 32, max_wgs, cu_reserve, (const void*)256, sk_ws_bytes) : 0;
+  return (cfg == 4 ? 8 : 4) * (sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs, cu_reserve));
 }
 
 // the smallest grid (a multiple of 8) on which these products' tiles take no more rounds than on one workgroup per CU
-int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* No) {
+int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* No, int cu_reserve) {
   if (!Mo || !No || n < 1 || n > 4) return 0;
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
   const int total = wgrad_tiles(cfg, n, Mo, No);
-  const int full = persistent_grid(total, 0);
+  const int full = persistent_grid(total, 0, cu_reserve);
   const int rounds = (total + full - 1) / full;
   const int wgs = ((total + rounds - 1) / rounds + 7) / 8 * 8;
   return wgs < full ? wgs : full;
@@ -1597,10 +1597,10 @@ int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* N
 extern "C" int uniter_wgrad_x3_group_riders(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                             const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                             uniter_x3_riders_t* riders, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, nullptr, 0);
+  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, nullptr, 0, LaunchOpts{});
 }
 extern "C" int uniter_wgrad_x3_group_slots(int cfg, int n, const int* M, const int* N, int max_wgs) {
-  return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, 0, 0);
+  return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, 0, 0, 0);
 }
 // the same two with the workspace of the balanced walk (uniter_gemm_x3_balanced_ws_bytes, rules as uniter_gemm_x3_cfg_ws; riders may
 // be NULL): with 128 x 256 tiles that do not fill whole rounds the launch is cut into equal runs of k-tiles and runs on every CU it
@@ -1608,13 +1608,13 @@ extern "C" int uniter_wgrad_x3_group_slots(int cfg, int n, const int* M, const i
 extern "C" int uniter_wgrad_x3_group_ws(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                         const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                         uniter_x3_riders_t* riders, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, ws, ws_bytes);
+  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, ws, ws_bytes, LaunchOpts{});
 }
 extern "C" int uniter_wgrad_x3_group_slots_ws(int cfg, int n, const int* M, const int* N, int K, int max_wgs, size_t ws_bytes) {
-  return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, K, ws_bytes);
+  return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, K, ws_bytes, 0);
 }
 
 extern "C" int uniter_wgrad_x3_group(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                      const void* const* B, float* const* dW, int overwrite, int max_wgs, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, nullptr, nullptr, 0);
+  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, nullptr, nullptr, 0, LaunchOpts{});
 }

@@ -486,10 +486,21 @@ extern "C" int uniter_ln_fwd_b16(const float* x, const float* res, const float* 
   return uniter_ln_fwd_slabs(x, 1, 0, res, gamma, beta, z_out, y, y_bf16, mean, rstd, M, H, p_drop, seed, offset, site, stream);
 }
 
-static int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
-                      const float* beta, float* z_out, float* y, void* y_bf16, int pieces, float* mean, float* rstd,
-                      int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
-  const unsigned char* ahead = take_drop_bits();      // (first thing: a call that fails below must not leave the pointer to the next one)
+// The keep flags the NEXT public LayerNorm row pass of this host thread reads instead of drawing them (uniter_ln_set_next_keep_bits, at
+// the end of this file).  A hand-over of the C ABI only: the four public *_slabs wrappers take it as their first statement -- a call
+// refused further down has taken it too -- and pass it to ln_fwd_run / ln_bwd_rows_run, which the model's schedule calls directly.
+static thread_local const unsigned char* g_next_keep_bits = nullptr;
+static const unsigned char* take_next_keep_bits() {
+  const unsigned char* p = g_next_keep_bits;
+  g_next_keep_bits = nullptr;
+  return p;
+}
+
+// keep_bits: this pass's dropout keep flags drawn ahead (DropCfg::bits), or NULL = draw them
+int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
+               const float* beta, float* z_out, float* y, void* y_bf16, int pieces, float* mean, float* rstd,
+               int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, const unsigned char* keep_bits,
+               void* stream) {
   UCHECK_ARG(x && gamma && beta && y, "ln_fwd: null pointer");
   UCHECK_ARG(nslab >= 1 && (nslab == 1 || slab_stride >= (size_t)M * H), "ln_fwd: bad slab count / stride");
   UCHECK_ARG((mean == nullptr) == (rstd == nullptr), "ln_fwd: mean/rstd must both be given or NULL");
@@ -498,7 +509,7 @@ static int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float
   if (M <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DropCfg drop = make_drop(p_drop, seed, offset, site);
-  drop.bits = drop.active ? ahead : nullptr;
+  drop.bits = drop.active ? keep_bits : nullptr;
   const int nv = (H / 4 + 63) / 64;
   LN_DISPATCH(nv, ln_fwd_kernel, dim3((M + 3) / 4), x, res, gamma, beta, z_out, y, mean, rstd, M, H, drop,
               (unsigned short*)y_bf16, nslab, slab_stride, pieces);
@@ -510,16 +521,17 @@ extern "C" int uniter_ln_fwd_slabs(const float* x, int nslab, size_t slab_stride
                                    const float* beta, float* z_out, float* y, void* y_bf16, float* mean, float* rstd,
                                    int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
                                    void* stream) {
-  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_bf16, 1, mean, rstd, M, H, p_drop, seed, offset, site, stream);
+  const unsigned char* ahead = take_next_keep_bits();
+  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_bf16, 1, mean, rstd, M, H, p_drop, seed, offset, site, ahead, stream);
 }
 
 extern "C" int uniter_ln_fwd_slabs_x3(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
                                       const float* beta, float* z_out, float* y, void* y_x3, float* mean, float* rstd,
                                       int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
                                       void* stream) {
-  if (H % 8 != 0 || ((uintptr_t)y_x3 & 15) != 0) take_drop_bits();      // (a refused call consumes the hand-over, as in ln_fwd_run)
+  const unsigned char* ahead = take_next_keep_bits();
   UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)y_x3 & 15) == 0, "ln_fwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
-  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_x3, 3, mean, rstd, M, H, p_drop, seed, offset, site, stream);
+  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_x3, 3, mean, rstd, M, H, p_drop, seed, offset, site, ahead, stream);
 }
 
 extern "C" size_t uniter_ln_bwd_ws_bytes(int M, int H) {
@@ -555,11 +567,10 @@ extern "C" int uniter_ln_bwd_rows(const float* dy, const float* z, const float* 
                                   site, ws, ws_bytes, stream);
 }
 
-static int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
-                           const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16, int pieces,
-                           int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-                           uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  const unsigned char* ahead = take_drop_bits();      // (first thing, as in the forward pass)
+int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
+                    const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16, int pieces,
+                    int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
+                    uint32_t site, const unsigned char* keep_bits, void* ws, size_t ws_bytes, void* stream) {
   UCHECK_ARG(dy && z && mean && rstd && gamma && ws, "ln_bwd: null pointer");
   UCHECK_ARG(nslab >= 1 && (nslab == 1 || slab_stride >= (size_t)M * H), "ln_bwd: bad slab count / stride");
   UCHECK_ARG(dz || dx || dx_bf16, "ln_bwd: need dz or dx");
@@ -568,7 +579,7 @@ static int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const
   if (M <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DropCfg drop = make_drop(p_drop, seed, offset, site);
-  drop.bits = drop.active ? ahead : nullptr;
+  drop.bits = drop.active ? keep_bits : nullptr;
   const int nv = (H / 4 + 63) / 64;
   const int nblk = ln_bwd_blocks(M);
   float* part = (float*)ws;
@@ -599,18 +610,19 @@ extern "C" int uniter_ln_bwd_rows_slabs(const float* dy, int nslab, size_t slab_
                                         const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16,
                                         int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
                                         uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  const unsigned char* ahead = take_next_keep_bits();
   return ln_bwd_rows_run(dy, nslab, slab_stride, z, mean, rstd, gamma, dz, dx, dx_bf16, 1, want_dbias, M, H, p_drop, seed,
-                         offset, site, ws, ws_bytes, stream);
+                         offset, site, ahead, ws, ws_bytes, stream);
 }
 
 extern "C" int uniter_ln_bwd_rows_slabs_x3(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
                                            const float* rstd, const float* gamma, float* dz, float* dx, void* dx_x3,
                                            int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
                                            uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  if (H % 8 != 0 || ((uintptr_t)dx_x3 & 15) != 0) take_drop_bits();
+  const unsigned char* ahead = take_next_keep_bits();
   UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)dx_x3 & 15) == 0, "ln_bwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
   return ln_bwd_rows_run(dy, nslab, slab_stride, z, mean, rstd, gamma, dz, dx, dx_x3, 3, want_dbias, M, H, p_drop, seed,
-                         offset, site, ws, ws_bytes, stream);
+                         offset, site, ahead, ws, ws_bytes, stream);
 }
 
 // internal: the partial-row count / row stride of a row pass over M rows (for finalize_partials_jobs)
@@ -629,7 +641,7 @@ extern "C" int uniter_ln_bwd_finalize(const void* ws, size_t ws_bytes, int M, in
 // The row passes draw their dropout flags with ten Philox rounds per 4-element group (1.5 us of a 9-us forward pass, 1.8 of an
 // 11-us backward pass, twice each per layer): a function of (seed, offset, site, index) alone, so all of a step's sites are drawn in ONE
 // launch on the auxiliary stream beside the head of the forward pass, as nibbles -- bits[s][g >> 1] >> 4 (g & 1) = the keep flags
-// of group g of site s -- and the passes read 3 bytes per lane and row instead (DropCfg::bits, through g_uniter_drop_bits).
+// of group g of site s -- and the passes read 3 bytes per lane and row instead (DropCfg::bits).
 // Same flags bit for bit (tests/test_layernorm_gpu.py::test_keep_flags_drawn_ahead_are_the_row_passes_own).
 __global__ __launch_bounds__(256) void hidden_keep_bits_kernel(unsigned* __restrict__ bits, size_t site_words, int nsites, uint32_t site_a0,
                                                                uint32_t site_b0, uint32_t site_step, size_t words, DropCfg d) {
@@ -663,6 +675,6 @@ extern "C" int uniter_hidden_keep_bits_gen(void* bits, size_t site_stride_bytes,
 // the keep flags the NEXT LayerNorm row pass of this host thread reads instead of drawing them (NULL = draw); tests and callers
 // that drive the row passes themselves
 extern "C" int uniter_ln_set_next_keep_bits(const void* site_bits) {
-  g_uniter_drop_bits = (const unsigned char*)site_bits;
+  g_next_keep_bits = (const unsigned char*)site_bits;
   return 0;
 }

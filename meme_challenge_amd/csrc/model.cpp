@@ -157,7 +157,9 @@ struct uniter_model {
   hipStream_t st = nullptr, side = nullptr;
   bool bwd_open = false;
   bool deterministic = false;     // uniter_model_set_deterministic: the plans made from now on run order-fixed (Plan::det)
-  int cu_reserve = 0;             // uniter_model_set_cu_reserve: CUs the persistent launches of this model's calls leave free
+  int cu_reserve = 0;             // uniter_model_set_cu_reserve: CUs the persistent launches of this model's backward pass leave free
+  int launch_reserve = 0;         // ... and of the pass that is running: 0 from uniter_model_forward on (no collective of the step is in flight
+                                  // during its forward pass), cu_reserve from the backward calls on -- LaunchOpts::cu_reserve of every launch
   hipStream_t aux = nullptr;      // uniter_model_set_aux_stream: launches that depend on nothing the step computes (dropout keep flags)
   hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr, ev_aux2 = nullptr;
   hipEvent_t ev_emb0 = nullptr, ev_emb1 = nullptr, ev_emb2 = nullptr;      // embedding backward: main <-> auxiliary stream
@@ -213,13 +215,17 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   const bool res = pl.prec == PREC_BF16, x3 = pl.prec == PREC_X3;
   pl.hid_keepb = nullptr; pl.hid_stride = 0; pl.hid_on = false;
   const size_t pc = x3 ? 3 : 1;       // bf16 elements per value in the operand copies
+  // The plan is made by the forward pass, which reserves no CU (uniter_model_forward: launch_reserve = 0), and sized ahead of it by
+  // uniter_model_ws_bytes, which must carve the same plan whatever pass ran last on the handle: the forward products' k-pieces are
+  // chosen for the whole chip, the backward pass's (x3) for x3_backward_cus.
+  const int fwd_reserve = 0;
   pl.embb = pl.copies() ? cv.h(pc * M * H) : nullptr;
   pl.ns_ki = res ? gemm_bf16v2_pick_split(pl.M, H, I) : x3 ? gemm_x3_pick_split(pl.M, H, I) : 1;
   pl.ns_k3h = res ? gemm_bf16v2_pick_split(pl.M, H, 3 * H) : x3 ? gemm_x3_pick_split(pl.M, H, 3 * H) : 1;
   if (res && (sw.b16_persist & 2)) {
     // round 6: the N = hidden products on the persistent kernels are planned by their own cost model (one workgroup per CU: two
     // k-pieces fill the chip where gemm_dma_kernel's two workgroups per CU wanted four -- two slabs less for the row pass behind)
-    const int a = gemm_b1p_pick_split(pl.M, H, I, 0), b = gemm_b1p_pick_split(pl.M, H, 3 * H, 0);
+    const int a = gemm_b1p_pick_split(pl.M, H, I, 0, fwd_reserve), b = gemm_b1p_pick_split(pl.M, H, 3 * H, 0, fwd_reserve);
     if (a > 1) pl.ns_ki = a;
     if (b > 1) pl.ns_k3h = b;
   }
@@ -229,10 +235,10 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
     // (the forward pass runs before any collective of its step: it keeps every CU; the backward pass's products are planned for the
     // CUs it will have)
     const int avail_b = x3_backward_cus(m);
-    pl.ns_ki = gemm_x3_pick_split_on(pl.M, H, I, 0); pl.ns_kh = gemm_x3_pick_split_on(pl.M, H, H, 0);
-    pl.ns_ki_b = gemm_x3_pick_split_on(pl.M, H, I, avail_b);
-    pl.ns_kh_b = gemm_x3_pick_split_on(pl.M, H, H, avail_b);
-    pl.ns_k3h_b = pl.ns_k3h = gemm_x3_pick_split_on(pl.M, H, 3 * H, avail_b);
+    pl.ns_ki = gemm_x3_pick_split_on(pl.M, H, I, 0, fwd_reserve); pl.ns_kh = gemm_x3_pick_split_on(pl.M, H, H, 0, fwd_reserve);
+    pl.ns_ki_b = gemm_x3_pick_split_on(pl.M, H, I, avail_b, 0);      // (avail_b > 0 is the CU count: no reserve on top of it)
+    pl.ns_kh_b = gemm_x3_pick_split_on(pl.M, H, H, avail_b, 0);
+    pl.ns_k3h_b = pl.ns_k3h = gemm_x3_pick_split_on(pl.M, H, 3 * H, avail_b, 0);
   }
   const size_t s_ki = (size_t)pl.ns_ki, s_k3h = (size_t)pl.ns_k3h, s_kh = (size_t)pl.ns_kh;
   const size_t s_ki_b = (size_t)pl.ns_ki_b, s_kh_b = (size_t)pl.ns_kh_b;
@@ -311,11 +317,12 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
 
 struct ProfScope {
   uniter_model* m; hipStream_t st; bool on;
+  unsigned long long* stamp = nullptr;      // the stamp slot this scope reserved for the GEMM launched inside it (LaunchOpts::stamp), or none
   ProfScope(uniter_model* m_, int kind, hipStream_t st_) : m(m_), st(st_), on(false) {
     if (m->stamp_buf && kind && kind != UNITER_K_ATTN_FWD && kind != UNITER_K_ATTN_BWD && kind != UNITER_K_LN &&
         kind != UNITER_K_LN_BWD && m->stamp_used < m->stamp_cap) {
-      m->stamp_tag[m->stamp_used] = kind;                     // the GEMM launched inside this scope takes the slot
-      g_uniter_stamp_slot = m->stamp_buf + (size_t)2 * STAMP_WGS * m->stamp_used++;
+      m->stamp_tag[m->stamp_used] = kind;                     // the GEMM launched inside this scope is given the slot
+      stamp = m->stamp_buf + (size_t)2 * STAMP_WGS * m->stamp_used++;
     }
     if (m->prof_kind && kind && (m->prof_kind == kind || m->prof_kind < 0) && m->prof_used + 2 <= m->prof_ev.size()) {
       on = true;
@@ -352,12 +359,12 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
     else { UCHECK_HIP(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(float), st)); beta = 1; }
   }
   // wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h; UNITER_MAIN_PRIO, default 0)
-  g_uniter_launch_prio = kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio;
+  const LaunchOpts lo = {ps.stamp, kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio, m->launch_reserve};
   if (prec == PREC_BF16_MFMA || prec == PREC_BF16)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
     return gemm_bf16_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias, aux_in, aux_out, ld_aux, beta,
-                         colsum_part, st, no_sk);
+                         colsum_part, st, lo, no_sk);
   return gemm_f32_run(cfg, kind == UNITER_K_GEMM_FFN_UP_FWD, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias,
-                      aux_in, aux_out, ld_aux, beta, colsum_part, st, no_sk);
+                      aux_in, aux_out, ld_aux, beta, colsum_part, st, lo, no_sk);
 }
 
 // One dense product of encoder layer l against weight w (L_QW, L_OW, L_W1, L_W2): c = epilogue(a . W^T), or with b_kmajor the input
@@ -382,13 +389,13 @@ int linear(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int
   ProfScope ps(m, kind, st);
   if (pl.prec == PREC_X3) {
     const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && sw.x3_cfg_ffn_up_fwd) ? sw.x3_cfg_ffn_up_fwd : sw.x3_cfg;
-    g_uniter_launch_prio = sw.main_prio_x3;
+    const LaunchOpts lo = {ps.stamp, sw.main_prio_x3, m->launch_reserve};
     // (every product of this helper runs on the main stream: the balanced walk's main-stream workspace)
     // (cfg | 64: the weight's pieces in the paired-row layout -- full 128-byte source lines for the loaders of the forward products)
     return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), pieces, 0, bkm, M, N, K, a.b, 3 * K, K, m->WB(l, w), ldw, (int)m->mirror_numel, C, N,
-                       (long)M * N, c.b, 3 * N, N, epi, bias, aux_in, aux_out, N, st, colpart, pl.sk_main, pl.sk_main ? pl.sk_bytes : 0);
+                       (long)M * N, c.b, 3 * N, N, epi, bias, aux_in, aux_out, N, st, colpart, pl.sk_main, pl.sk_main ? pl.sk_bytes : 0, lo);
   }
-  g_uniter_launch_prio = sw.main_prio_bf16;
+  const LaunchOpts lo = {ps.stamp, sw.main_prio_bf16, m->launch_reserve};
   const int aux_in_b16 = epi == UNITER_EPI_MUL || epi == UNITER_EPI_DGELU, aux_out_b16 = epi == UNITER_EPI_BIAS_GELU || epi == UNITER_EPI_BIAS_GELU_D;
   const int ldcb = c.b ? N : 0;
   // round 6: the persistent loader / compute kernels (csrc/gemm_bf16_p.hip) for the products UNITER_B16_PERSIST names (default: none):
@@ -404,10 +411,10 @@ int linear(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int
   if (colpart) {      // (the product that writes dU also leaves its column partials: the persistent 128 x 256 kernel's epilogue)
     UCHECK_ARG(epi_ok && K % 64 == 0 && pieces == 1, "linear: column partials ride on the persistent kernels");
     return gemm_b1p_run(7, 1, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in, aux_in_b16, aux_out,
-                        aux_out_b16, ld_aux, colpart, st);
+                        aux_out_b16, ld_aux, colpart, st, lo);
   }
   return gemm_bf16v2_run(cfg, pieces, 0, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in,
-                         aux_in_b16, aux_out, aux_out_b16, ld_aux, 0, st);
+                         aux_in_b16, aux_out, aux_out_b16, ld_aux, 0, st, lo);
 }
 // The attention kernel of a plan's forward pass (`keep_pre`: the forward drew the dropout keep flags ahead of its kernels) or of its
 // backward pass (bwd).  The kernels of attention_x3.hip (ATTN_X3, ATTN_B16X) read the keep flags and draw none, so with dropout they
@@ -437,13 +444,13 @@ int x3_backward_cus(const uniter_model* m) {
 }
 // The grouped weight-gradient launch of layer l's backward pass (precision 2 or 3: four products, Mo = {I, H, 3H, H}, No = {H, I, H, H}):
 // what rides on it, its geometry, its grid cap, and -- with riders -- the clip-norm slots it fills.  Read by backward_layer, which
-// launches it, and by uniter_model_norm_partials_per_layer, which announces its slots.
+// launches it, and by uniter_model_norm_partials_per_layer, which announces its slots.  cu_reserve: CUs the launch leaves free.
 struct WgradGroup {
   bool riders = false;    // the layer's column reductions, intermediate.dense's bias gradient and its clip-norm share ride on the launch
   bool colpart = false;   // ... and dU's column sums (that bias gradient) start as column partials of the product that writes dU
   int cfg = 0, max_wgs = 0, slots = 0;
 };
-WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l) {
+WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l, int cu_reserve) {
   const Switches& sw = uniter_switches();
   const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size;
   const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
@@ -455,8 +462,8 @@ WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l) {
     g.cfg = g.riders ? (sw.x3_cfg == 3 ? 3 : 0) : sw.x3_cfg;
     // UNITER_WGRAD_X3_WGS = n forces a grid for every layer (0 = one workgroup per CU); unset, layer 0 takes the smallest grid that
     // needs no more rounds (switches.h) and every other layer one workgroup per CU
-    g.max_wgs = sw.wgrad_x3_wgs >= 0 ? sw.wgrad_x3_wgs : (l == 0 ? gemm_x3_wgrad_group_balanced_wgs(0, 4, Mo, No) : 0);
-    if (g.riders) g.slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, g.max_wgs, pl.M, pl.sk_side ? pl.sk_bytes : 0);
+    g.max_wgs = sw.wgrad_x3_wgs >= 0 ? sw.wgrad_x3_wgs : (l == 0 ? gemm_x3_wgrad_group_balanced_wgs(0, 4, Mo, No, cu_reserve) : 0);
+    if (g.riders) g.slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, g.max_wgs, pl.M, pl.sk_side ? pl.sk_bytes : 0, cu_reserve);
     return g;
   }
   // precision 2: riders only on UNITER_B16_RIDERS=1 -- except with the launch on the persistent 128 x 256-tile kernel (UNITER_B16_PERSIST
@@ -469,7 +476,7 @@ WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l) {
   g.colpart = p7 && g.riders;
   g.cfg = pl.wg_group == 4 ? 4 : (p7 ? 7 : 1);      // (4: three LDS stages; 7: 216 whole-K tiles of 128 x 256 on the persistent kernel)
   g.max_wgs = 0;                                   // (the grid cap of UNITER_WGRAD_GROUP_WGS / its default)
-  if (g.riders) g.slots = p7 ? gemm_b1p_wgrad_group_slots(4, Mo, No, g.max_wgs) : gemm_bf16v2_wgrad_group_slots(4, Mo, No, g.max_wgs);
+  if (g.riders) g.slots = p7 ? gemm_b1p_wgrad_group_slots(4, Mo, No, g.max_wgs, cu_reserve) : gemm_bf16v2_wgrad_group_slots(4, Mo, No, g.max_wgs, cu_reserve);
   return g;
 }
 // the side work of layer l's backward as riders of its grouped weight-gradient launch (product 0 must be dW1 = dU^T y1: its A
@@ -509,11 +516,13 @@ int ln_fwd(uniter_model* m, hipStream_t st, int l, int second, const float* t, i
   const Plan& pl = m->plan;
   const bool save = pl.mode != 0;
   const int g = second ? L_LN2_G : L_LN1_G;      // (its bias follows it)
+  const int H = m->cfg.hidden_size;
   ProfScope ps(m, UNITER_K_LN, st);
-  g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;
-  return (pl.prec == PREC_X3 ? uniter_ln_fwd_slabs_x3 : uniter_ln_fwd_slabs)(
-      t, pieces, pieces > 1 ? (size_t)pl.M * m->cfg.hidden_size : 0, resid, m->LP(l, g), m->LP(l, g + 1), z, y.f, y.b, save ? mean : nullptr, save ? rstd : nullptr, pl.M,
-      m->cfg.hidden_size, ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), st);
+  const unsigned char* keep = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;
+  const bool x3 = pl.prec == PREC_X3;
+  if (x3) UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)y.b & 15) == 0, "ln_fwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
+  return ln_fwd_run(t, pieces, pieces > 1 ? (size_t)pl.M * H : 0, resid, m->LP(l, g), m->LP(l, g + 1), z, y.f, y.b, x3 ? 3 : 1, save ? mean : nullptr,
+                    save ? rstd : nullptr, pl.M, H, ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), keep, st);
 }
 // its backward row pass: dy is `pieces` slabs [M][H]; g takes the dropped gradient (fp32 and / or operand copy), ws the column partials
 int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, int pieces, const float* z, const float* mean,
@@ -521,10 +530,11 @@ int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, 
   const Plan& pl = m->plan;
   const int H = m->cfg.hidden_size;
   ProfScope ps(m, UNITER_K_LN_BWD, st);
-  g_uniter_drop_bits = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;      // (the forward pass's flags)
-  return (pl.prec == PREC_X3 ? uniter_ln_bwd_rows_slabs_x3 : uniter_ln_bwd_rows_slabs)(
-      dy, pieces, (size_t)pl.M * H, z, mean, rstd, m->LP(l, second ? L_LN2_G : L_LN1_G), dz, g.f, g.b, 1, pl.M, H, ph, m->seed, m->offset,
-      second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), ws, pl.ln_ws_bytes, st);
+  const unsigned char* keep = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;      // (the forward pass's flags)
+  const bool x3 = pl.prec == PREC_X3;
+  if (x3) UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)g.b & 15) == 0, "ln_bwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
+  return ln_bwd_rows_run(dy, pieces, (size_t)pl.M * H, z, mean, rstd, m->LP(l, second ? L_LN2_G : L_LN1_G), dz, g.f, g.b, x3 ? 3 : 1, 1, pl.M, H, ph,
+                         m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), keep, ws, pl.ln_ws_bytes, st);
 }
 // The four weight gradients of a layer in PREC_BF16 / PREC_X3, dW[p] [Mo[p], No[p]] += A[p]^T B[p] over the plan's M rows, in the grouped
 // launch's order {W1, W2, QKV, attention output}.  Product 0 must be dW1 = dU^T y1: its A operand's column sums are intermediate.dense's
@@ -538,11 +548,12 @@ int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, const WgradProduc
   const int pieces = gemm_bf16v2_wgrad_pieces(Mo, No, K);
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, st);
+    const LaunchOpts lo = {ps.stamp, 0, m->launch_reserve};
     if (pieces == 0 || !pl.wg_slabs)
       return gemm_bf16res_run(0, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, t.dW[p], No, nullptr, 0, UNITER_EPI_NONE, nullptr, nullptr,
-                              nullptr, 0, 1, nullptr, st, pl.det ? 1 : 0);      // (deterministic plan: whole tiles, no stream-K)
+                              nullptr, 0, 1, nullptr, st, lo, pl.det ? 1 : 0);      // (deterministic plan: whole tiles, no stream-K)
     UCHECK_RC(gemm_bf16v2_run(0, pieces, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, pl.wg_slabs, No, (long)Mo * No, nullptr, 0,
-                              UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0, st));
+                              UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0, st, lo));
   }
   return uniter_slab_reduce_add(pl.wg_slabs, pieces, (size_t)Mo * No, t.dW[p], (size_t)Mo * No, st);
 }
@@ -561,8 +572,9 @@ int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t,
   const int overwrite = m->wg_overwrite ? 1 : 0;
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-    if (x3) UCHECK_RC(gemm_x3_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, pl.sk_side, pl.sk_side ? pl.sk_bytes : 0));
-    else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders));
+    const LaunchOpts lo = {ps.stamp, 0, m->launch_reserve};
+    if (x3) UCHECK_RC(gemm_x3_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, pl.sk_side, pl.sk_side ? pl.sk_bytes : 0, lo));
+    else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, lo));
   }
   if (!colsum_after) return 0;
   if (pl.det) {      // in a fixed order; the block partials go to the layer's dU column-partial buffer, which nothing else uses without riders
@@ -709,7 +721,7 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
                                     int all_layers, int train, uint64_t seed, uint32_t offset, void* ws,
                                     size_t ws_bytes, void* stream) {
   UCHECK_ARG(m && hidden_out && ws, "model_forward: null pointer");
-  g_uniter_cu_reserve = 0;      // (no collective of this step is in flight during its forward pass: the reserve is the backward pass's)
+  m->launch_reserve = 0;      // (no collective of this step is in flight during its forward pass: the reserve is the backward pass's)
   UCHECK_ARG(train >= 0 && train <= 2, "model_forward: train must be 0, 1 or 2");
   UCHECK_RC(validate_batch(m, b));
   UCHECK_ARG(((uintptr_t)ws & 255) == 0, "model_forward: workspace must be 256-byte aligned");
@@ -939,7 +951,7 @@ extern "C" int uniter_model_backward_begin(uniter_model_t* m, const uniter_batch
 
 extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   UCHECK_ARG(m, "backward_layer: null model");
-  g_uniter_cu_reserve = m->cu_reserve;
+  m->launch_reserve = m->cu_reserve;
   if (!m->bwd_open) { uniter_set_error("backward_layer: call uniter_model_backward_begin first"); return UNITER_E_STATE; }
   const uniter_config_t& c = m->cfg;
   const int H = c.hidden_size, I = c.intermediate_size, nl = c.num_hidden_layers, nh = c.num_attention_heads;
@@ -995,7 +1007,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   const int ns_dctx = (pl.attn_bwd == ATTN_X3 && sw.dctx_split) ? pl.ns_kh_b : 1;
   const int epi_du = pl.gelu_d ? UNITER_EPI_MUL : UNITER_EPI_DGELU;
   // what rides on the layer's grouped weight-gradient launch (precisions 2 and 3), and that launch's geometry
-  const WgradGroup wg = copies ? wgrad_group(m, pl, l) : WgradGroup();
+  const WgradGroup wg = copies ? wgrad_group(m, pl, l, m->launch_reserve) : WgradGroup();
   // dU = (g2 . W2) * gelu'(u): with operand copies it exists only as one (operand of the next product and of intermediate.dense's weight
   // gradient).  Its column sums (that layer's bias gradient) start here as column partials: per 32 rows in the fp32 kernels; with operand
   // copies only when riders of the 128 x 256 weight-gradient geometry finish them (one row of partial sums per 64 rows of dU)
@@ -1025,31 +1037,31 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     const float* mask = pl.packed ? nullptr : m->batch.attention_mask;
     const int32_t* cu_seqlens = pl.packed ? m->batch.cu_seqlens : nullptr;
     unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;      // attention_x3.hip's kernels (the forward pass of a saved plan left the flags)
-    if (pl.det) g_uniter_attn_bwd_det = 1;      // the call below takes it: its bias partials in a fixed order (uniter_attn_bwd_set_next_det)
+    // (pl.det: the kernel's bias partials in a fixed order)
     switch (pl.attn_bwd) {
     case ATTN_B16X:
-      UCHECK_RC(uniter_attn_b16x_bwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, lb.qb_part, keep_rd, lb.delta,
-                                     B, L, nh, pa, st));
+      UCHECK_RC(attn_b16x_bwd_run(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, lb.qb_part, keep_rd, lb.delta,
+                                  B, L, nh, pa, st, pl.det));
       break;
     case ATTN_BF16_PRE:
-      UCHECK_RC(uniter_attn_bf16_bwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx,
-                                     nullptr /* fp32 dqkv has no reader in this mode: bias partials are fused */,
-                                     lb.dqkvb, lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset,
-                                     SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
+      UCHECK_RC(attn_bf16_bwd_run(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx,
+                                  nullptr /* fp32 dqkv has no reader in this mode: bias partials are fused */,
+                                  lb.dqkvb, lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset,
+                                  SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
       break;
     case ATTN_X3:
-      UCHECK_RC(uniter_attn_x3_bwd(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, ns_dctx, MH, nullptr, lb.dqkvb, lb.qb_part, keep_rd,
-                                   lb.delta, B, L, nh, pa, st));
+      UCHECK_RC(attn_x3_bwd_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, ns_dctx, MH, nullptr, lb.dqkvb, lb.qb_part, keep_rd,
+                                lb.delta, B, L, nh, pa, st, pl.det));
       break;
     case ATTN_F32_PRE_X3:      // dqkv leaves the kernel as x3 pieces only: nothing reads an fp32 copy in this mode
-      UCHECK_RC(uniter_attn_bwd_ex_x3(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb,
-                                      lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
-                                      pl.attn_ws, pl.attn_ws_bytes, st));
+      UCHECK_RC(attn_bwd_ex_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, 3,
+                                lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
+                                pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
       break;
     case ATTN_F32_PRE:
-      UCHECK_RC(uniter_attn_bwd_ex(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr,
-                                   lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
-                                   pl.attn_ws, pl.attn_ws_bytes, st));
+      UCHECK_RC(attn_bwd_ex_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr, 1,
+                                lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
+                                pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
       break;
     case ATTN_F32:      // (never packed)
       UCHECK_RC(uniter_attn_bwd(lb.qkv, mask, lb.ctx, lb.lse, lb.dctx, lb.dqkv, lb.delta, B, L,
@@ -1123,7 +1135,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
       const float* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x.f};
       float* const dWs[4] = {m->LG(l, L_W2), m->LG(l, L_W1), m->LG(l, L_OW), m->LG(l, L_QW)};
       ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      const int rc = gemm_f32_wgrad_group(4, Mo, No, M, As, Bs, dWs, m->wg_overwrite ? 1 : 0, sd);
+      const int rc = gemm_f32_wgrad_group(4, Mo, No, M, As, Bs, dWs, m->wg_overwrite ? 1 : 0, sd, LaunchOpts{ps.stamp, 0, m->launch_reserve});
       if (rc == 0) grouped = true;
       else if (rc != UNITER_E_SHAPE) return rc;
     }
@@ -1146,7 +1158,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
 
 extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
   UCHECK_ARG(m, "backward_embed: null model");
-  g_uniter_cu_reserve = m->cu_reserve;
+  m->launch_reserve = m->cu_reserve;
   if (!m->bwd_open) { uniter_set_error("backward_embed: call uniter_model_backward_begin first"); return UNITER_E_STATE; }
   const uniter_config_t& c = m->cfg;
   const int H = c.hidden_size;
@@ -1277,7 +1289,9 @@ extern "C" int uniter_model_norm_partials_per_layer(const uniter_model_t* m) {
   // (answers for the plan of the LAST forward: its grouped launch -- very long batches of precision 2 keep stream-K --, its row count
   // as the reduction length, its workspace of the balanced walk.  An upper bound over layers: layer 1's grid, one workgroup per CU,
   // where layer 0's balanced grid fills fewer slots)
-  const WgradGroup g = wgrad_group(m, m->plan, 1);
+  // Reserve 0, whatever pass ran last on this handle: the count the trainer sizes its slot buffer with, asked after the forward pass (or
+  // before backward_begin), when no CU is reserved.  A backward pass that leaves CUs free runs a smaller grid and fills fewer slots.
+  const WgradGroup g = wgrad_group(m, m->plan, 1, 0);
   if (!g.riders || (m->plan.prec == PREC_BF16 && m->plan.mode == 0)) return 0;
   //  a plan whose joint length is beyond the fused query|key|value bias partials (L > uniter_attn_varlen_max_len(), or
   // UNITER_ATTN_SPLIT=0) writes that bias gradient by a separate column-sum launch BEHIND the riders' launch: its squares would reach
@@ -1385,7 +1399,6 @@ extern "C" int uniter_prof_enable_stamps(uniter_model_t* m, int on, void* stream
     m->stamp_buf = nullptr; m->stamp_cap = m->stamp_used = 0;
   }
   (void)stream;
-  g_uniter_stamp_slot = nullptr;
   return 0;
 }
 

@@ -70,7 +70,7 @@ struct Switches {
   bool embed_bwd_par;
 
   // ------------------------------------------------------------------- wave priority of the main stream's GEMMs
-  // UNITER_MAIN_PRIO (int, default 0): wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h).
+  // UNITER_MAIN_PRIO (int, default 0): wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h: LaunchOpts::prio).
   // fp32: measured WORSE (14.09 against 13.73 ms per step with level 2: the input-gradient GEMM then starves the weight-gradient
   // launch it shares the matrix pipe with, and the chain waits for that launch at the layer's end), so the default is 0 here
   int main_prio;
