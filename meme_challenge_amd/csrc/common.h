@@ -111,7 +111,9 @@ __device__ __forceinline__ float erf_fast(float a) {
 //   erfc(|x|/sqrt 2) = P(t) E,  t = 1 / (1 + p |x| / sqrt 2)   (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7),
 // so Phi(x) = 1 - H (x >= 0) or H (x < 0) with H = P E / 2, and phi(x) = E / sqrt(2 pi).  17 VALU operations, two of
 // them transcendental (v_rcp, v_exp), against 25 for erf_fast + a separate exp.  Checked against float64 over
-// [-12, 12]: |Phi| 3.0e-7, |gelu| 4.2e-7, |gelu'| 3.0e-7 (the tail x < 0 is formed without cancellation).
+// [-12, 12]: |Phi| 3.0e-7, |gelu| 4.2e-7, |gelu'| 3.2e-7 (the tail x < 0 is formed without cancellation).  Measured on the
+// device through the GEMM epilogues (tests/test_gemm_f64_gpu.py; a dense search of 400 000 points per window): gelu 4.22e-7
+// near x = 3.11, gelu' 3.20e-7 near x = 0.075.
 __device__ __forceinline__ void gelu_pair_fast(float x, float& g, float& dg) {
   const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x), 0.23164189f, 1.0f));     // p / sqrt 2
   float P = 0.5307027145f;                       // a5 / 2 .. a1 / 2
