@@ -759,6 +759,30 @@ int uniter_optim_step_groups(int kind, float* params, float* grads, const void* 
                              const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
                              const uniter_optim_group_t* groups, int n_groups, int step, int zero_grads, void* mirror,
                              size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream);
+/* uniter_optim_step / uniter_optim_step_groups that also keep an EXPONENTIAL MOVING AVERAGE of the parameters (the weights a
+ * fine-tuning run evaluates and checkpoints in place of the raw ones; the reference has no counterpart -- it replaces nothing there).
+ * The argument lists are those of the two entry points with `avg, avg_weight` in front of max_workgroups; avg points at the element
+ * `params` points at (16-byte aligned, n floats).  Every element the launch updates -- chunk flag & 3 != 0, for the grouped form a
+ * group inside the table; in the walk by pair_src the element of `params` the item updates, not its place in the mirror -- also gets
+ *     a' = a + avg_weight * (p' - a)          evaluated in fp32 in this order: the difference, the product, the sum
+ * with p' the fp32 parameter this launch has just computed for it.  avg_weight = 1 - decay is ONE value per launch, in [0, 1]
+ * (0 leaves avg as it is, bit for bit where finite; 1 copies p').  A skipped chunk's average is neither read nor written: a tensor
+ * without a gradient in a step, or a frozen one, keeps its average (torch.optim.swa_utils would go on averaging it).  params, grads,
+ * both moments and the mirror come out bit-identical to the entry point without the average.  Traffic: 8 more bytes per updated
+ * parameter (read a, write a'; p' is in registers), 40 instead of 32 for Adam -- a separate pass behind the step streams 12 (it
+ * reads p again).  There is no row-split form (uniter_adam_step_rows knows no average).  avg == NULL, avg_weight outside [0, 1]
+ * (NaN included) or a kind outside 0 .. 3: UNITER_E_ARG with a message, nothing launched; every other refusal is that of the
+ * entry point without the average. */
+int uniter_optim_step_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                          const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, int step, int adamw,
+                          int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element,
+                          float* avg, float avg_weight, int max_workgroups, void* stream);
+int uniter_optim_step_groups_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                 const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
+                                 const uniter_optim_group_t* groups, int n_groups, int step, int zero_grads, void* mirror,
+                                 size_t mirror_piece_stride, const int* pair_src, size_t first_element, float* avg, float avg_weight,
+                                 int max_workgroups, void* stream);
 int uniter_mirror_refresh_x3(const float* params_base, size_t first, size_t n, void* mirror, size_t piece_stride,
                              const int* pair_dst, void* stream);
 int uniter_adam_step_rows(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,

@@ -177,6 +177,8 @@ _SIGS = {
     'uniter_adam_step_x3p': (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
     'uniter_optim_step': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
     'uniter_optim_step_groups': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _P, _I, _I, _I, _P, _SZ, _P, _SZ, _I, _P]),
+    'uniter_optim_step_avg': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _SZ, _P, _SZ, _P, _F, _I, _P]),
+    'uniter_optim_step_groups_avg': (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _F, _F, _P, _I, _I, _I, _P, _SZ, _P, _SZ, _P, _F, _I, _P]),
     'uniter_mirror_refresh_x3': (_I, [_P, _SZ, _SZ, _P, _SZ, _P, _P]),
     'uniter_model_set_weight_pairing': (_I, [_P, _I]),
     'uniter_adam_step_rows': (_I, [_P, _P, _P, _P, _P, _SZ, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _I, _I, _I, _P]),

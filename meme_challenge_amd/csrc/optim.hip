@@ -176,11 +176,27 @@ __device__ __forceinline__ bool any_nonzero(const f32x4& g) { return g[0] != 0.f
 // Two 16-byte elements per thread and iteration, all eight loads issued before the arithmetic: a grid of one or two
 // workgroups per CU (the launch that shares the chip with the next forward, see trainer.FusedAdam) still keeps
 // 32-64 KB per CU in flight.  (RULE_SGD: six loads, a.v is never touched and may be NULL.)
-template <bool GROUPED> struct WalkArgs { AdamArgs a; };
-template <> struct WalkArgs<true> { AdamArgs a; GroupTable t; };
+// AVG (uniter_optim_step_avg / uniter_optim_step_groups_avg): an exponential moving average of the parameters as one more stream of
+// the same walk.  Every item on the update path reads its 16 bytes of `avg` with the other loads and writes
+//   a' = a + w (p' - a)         (three fp32 operations in this order; p' = the parameter the item has just computed, still in registers)
+// behind the parameter's own stores: 8 bytes per parameter, where a separate pass reads p once more (12).  avg is indexed like p (si, the
+// item's place in the parameter buffers, whatever order the mirror is walked in); a skipped item neither reads nor writes it.  The two
+// arguments live in a part of WalkArgs that only the AVG instantiations have: AdamArgs, and with it the kernel arguments and the code
+// of every other instantiation, stay what they were.
+struct AvgArgs { float* avg; float w; };
+template <bool GROUPED, bool AVG> struct WalkArgs { AdamArgs a; };
+template <> struct WalkArgs<true, false> { AdamArgs a; GroupTable t; };
+template <> struct WalkArgs<false, true> { AdamArgs a; AvgArgs e; };
+template <> struct WalkArgs<true, true> { AdamArgs a; GroupTable t; AvgArgs e; };
 
-template <int RULE, bool GROUPED>
-__global__ __launch_bounds__(256) void adam_kernel(const WalkArgs<GROUPED> w) {
+__device__ __forceinline__ void avg_store4(const AvgArgs& e, size_t si, const f32x4& p, f32x4 x) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = x[k] + e.w * (p[k] - x[k]);
+  __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(e.avg) + si);
+}
+
+template <int RULE, bool GROUPED, bool AVG>
+__global__ __launch_bounds__(256) void adam_kernel(const WalkArgs<GROUPED, AVG> w) {
   const AdamArgs& a = w.a;
   __shared__ GroupRow rows[GROUPED ? MAX_GROUPS : 1];
   int n_groups = 0;
@@ -224,14 +240,16 @@ __global__ __launch_bounds__(256) void adam_kernel(const WalkArgs<GROUPED> w) {
       if (f1 && (a.rowmask[((sj * 4) / CHUNK) / a.row_chunks] != 0) != (a.rows_want != 0)) f1 = 0;
     }
     const bool no_g = !GROUPED && a.rowmask && a.rows_want == 0;      // rows without a gradient this step: g == 0, unread
-    f32x4 p0, g0 = {0.f, 0.f, 0.f, 0.f}, m0, v0, p1, g1 = g0, m1, v1;
+    f32x4 p0, g0 = {0.f, 0.f, 0.f, 0.f}, m0, v0, p1, g1 = g0, m1, v1, e0, e1;
     if (f0) {
       p0 = NT_LOAD(a.p, si); if (!no_g) g0 = a.g16 ? widen4(a.g16, si) : NT_LOAD(a.g, si); m0 = NT_LOAD(a.m, si);
       if constexpr (RULE != RULE_SGD) v0 = NT_LOAD(a.v, si);
+      if constexpr (AVG) e0 = NT_LOAD(w.e.avg, si);
     }
     if (f1) {
       p1 = NT_LOAD(a.p, sj); if (!no_g) g1 = a.g16 ? widen4(a.g16, sj) : NT_LOAD(a.g, sj); m1 = NT_LOAD(a.m, sj);
       if constexpr (RULE != RULE_SGD) v1 = NT_LOAD(a.v, sj);
+      if constexpr (AVG) e1 = NT_LOAD(w.e.avg, sj);
     }
     // (gradients read from the bf16 payload: the fp32 buffer holds this rank's own sums, cleared whatever the payload says)
     if (f0) {
@@ -239,12 +257,14 @@ __global__ __launch_bounds__(256) void adam_kernel(const WalkArgs<GROUPED> w) {
       if constexpr (GROUPED) { const GroupRow h = rows[f0 >> 3]; adam_update4<RULE>(h, a.adamw, coef, (f0 & 3) == 2 ? h.wd : 0.f, p0, g0, m0, v0); }
       else adam_update4<RULE>(a, a.adamw, coef, (f0 & 3) == 2 ? a.wd : 0.f, p0, g0, m0, v0);
       adam_store4<RULE>(a, i, si, p0, m0, v0, c0);
+      if constexpr (AVG) avg_store4(w.e, si, p0, e0);
     }
     if (f1) {
       const bool c1 = !no_g && a.zero_grads && !(f1 & 4) && (a.g16 != nullptr || any_nonzero(g1));
       if constexpr (GROUPED) { const GroupRow h = rows[f1 >> 3]; adam_update4<RULE>(h, a.adamw, coef, (f1 & 3) == 2 ? h.wd : 0.f, p1, g1, m1, v1); }
       else adam_update4<RULE>(a, a.adamw, coef, (f1 & 3) == 2 ? a.wd : 0.f, p1, g1, m1, v1);
       adam_store4<RULE>(a, j, sj, p1, m1, v1, c1);
+      if constexpr (AVG) avg_store4(w.e, sj, p1, e1);
     }
   }
 }
@@ -347,7 +367,7 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                           size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups = nullptr);
+                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups = nullptr, const AvgArgs* avg = nullptr);
 
 extern "C" int uniter_adam_step_x3(float* params, float* grads, const void* grads_bf16, float* exp_avg,
                                    float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
@@ -397,7 +417,7 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
                           float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
                           size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups) {
+                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups, const AvgArgs* avg) {
   UCHECK_SHAPE(mirror_piece_stride % 4 == 0 && (mirror_piece_stride == 0 || mirror_bf16), "adam_step: bad mirror piece stride");
   UCHECK_ARG(params && grads && exp_avg && (exp_avg_sq || rule == RULE_SGD) && chunk_flags, "adam_step: null pointer");
   UCHECK_SHAPE(((uintptr_t)grads_bf16 & 7) == 0, "adam_step: bf16 gradients must be 8-byte aligned");
@@ -424,15 +444,28 @@ static int adam_step_impl(int rule, float* params, float* grads, const void* gra
     const size_t full = (a.n4 + 511) / 512;
     nb = (int)(full < (size_t)max_workgroups ? (full < 1 ? 1 : full) : (size_t)max_workgroups);
   }
-  if (groups) {      // (uniter_optim_step_groups: the scalars above are unused, every chunk reads its group's row)
-    const WalkArgs<true> wg = {a, *groups};
-    if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-    else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-    else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+  if (avg) {         // (the _avg entry points: the same walk with the average's stream, see AvgArgs)
+    if (groups) {
+      const WalkArgs<true, true> wg = {a, *groups, *avg};
+      if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+      else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+      else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+    } else {
+      const WalkArgs<false, true> wa = {a, *avg};
+      if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
+      else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
+      else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
+    }
   }
-  else if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
-  else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
-  else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false>{a});
+  else if (groups) {      // (uniter_optim_step_groups: the scalars above are unused, every chunk reads its group's row)
+    const WalkArgs<true, false> wg = {a, *groups};
+    if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+    else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+    else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
+  }
+  else if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
+  else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
+  else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
   UCHECK_LAUNCH();
   return 0;
 }
@@ -480,4 +513,55 @@ extern "C" int uniter_optim_step_groups(int kind, float* params, float* grads, c
                         kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, 0.f, 0.f, 0.f, 0.f, 0.f, step,
                         kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element,
                         stream, &t);
+}
+
+// uniter_optim_step / uniter_optim_step_groups with an exponential moving average of the parameters updated by the same launch
+// (include/uniter_hip.h): avg points at the element `params` points at; a' = a + avg_weight (p' - a) on every updated element.
+// Every argument is checked HERE, before anything is launched; the launch itself is adam_step_impl's.
+static int avg_args_ok(const char* who, int kind, const float* avg, float avg_weight, const void* mirror, size_t mirror_piece_stride,
+                       const int* pair_src, size_t first_element) {
+  UCHECK_ARG(kind >= 0 && kind <= 3, "%s: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)", who);
+  UCHECK_ARG(avg, "%s: avg is NULL", who);
+  UCHECK_ARG(avg_weight >= 0.f && avg_weight <= 1.f, "%s: avg_weight must lie in [0, 1] (got %g)", who, (double)avg_weight);
+  UCHECK_SHAPE(((uintptr_t)avg & 15) == 0, "%s: avg must be 16-byte aligned", who);
+  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
+             "%s: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table", who);
+  return 0;
+}
+
+extern "C" int uniter_optim_step_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
+                                     float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
+                                     float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                                     float weight_decay, int step, int adamw, int zero_grads, void* mirror,
+                                     size_t mirror_piece_stride, const int* pair_src, size_t first_element, float* avg,
+                                     float avg_weight, int max_workgroups, void* stream) {
+  if (int rc = avg_args_ok("optim_step_avg", kind, avg, avg_weight, mirror, mirror_piece_stride, pair_src, first_element)) return rc;
+  const AvgArgs e = {avg, avg_weight};
+  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
+                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay,
+                        step, kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src,
+                        (long)first_element, stream, nullptr, &e);
+}
+
+extern "C" int uniter_optim_step_groups_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
+                                            float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
+                                            float grad_scale, float max_norm, const uniter_optim_group_t* groups, int n_groups,
+                                            int step, int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src,
+                                            size_t first_element, float* avg, float avg_weight, int max_workgroups, void* stream) {
+  if (int rc = avg_args_ok("optim_step_groups_avg", kind, avg, avg_weight, mirror, mirror_piece_stride, pair_src, first_element)) return rc;
+  UCHECK_ARG(groups && n_groups >= 1 && n_groups <= MAX_GROUPS, "optim_step_groups_avg: n_groups must be 1 .. 32 (got %d) with a table", n_groups);
+  UCHECK_ARG(step >= 1, "optim_step_groups_avg: step must be >= 1");
+  GroupTable t;
+  t.n = n_groups;
+  for (int k = 0; k < MAX_GROUPS; ++k) {
+    const uniter_optim_group_t& g = groups[k < n_groups ? k : 0];
+    const double bc1 = 1.0 - pow((double)g.beta1, (double)step);      // (as uniter_optim_step_groups forms them)
+    const double bc2 = 1.0 - pow((double)g.beta2, (double)step);
+    t.row[k] = GroupRow{g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, (float)((double)g.lr / bc1), (float)(1.0 / sqrt(bc2)), 0.f};
+  }
+  const AvgArgs e = {avg, avg_weight};
+  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
+                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, 0.f, 0.f, 0.f, 0.f, 0.f, step,
+                        kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element,
+                        stream, &t, &e);
 }

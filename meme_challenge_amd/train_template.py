@@ -26,6 +26,7 @@ The loop itself is this package's own:
     (trainer.FusedAdam / FusedAdamax / FusedSGD: one kernel family, uniter_optim_step) with the overlap, the clip norm
     taken during the backward pass and the weight mirror written by the update itself.
 """
+import contextlib
 import datetime
 import json
 import logging
@@ -79,12 +80,27 @@ class ModelSaver(object):
     def __init__(self, output_path):
         self.output_path = output_path
 
-    def save(self, model, optimizer=None):
+    def save(self, model, optimizer=None, with_optimizer=False):
+        """with_optimizer: add 'optimizer_state_dict' (utils/save.py:60-61; CPU tensors) -- the moments are twice the model, so
+        the checkpoint stays what it was unless asked (--save_optimizer_state)"""
         if optimizer is not None and hasattr(optimizer, 'join'):
             optimizer.join()                 # an update overlapped with the next forward may still be running
         tensors = {k: (v.detach().cpu().clone() if isinstance(v, torch.Tensor) else v)
                    for k, v in model.state_dict().items()}
-        torch.save({'model_state_dict': tensors}, self.output_path)
+        dump = {'model_state_dict': tensors}
+        if with_optimizer and optimizer is not None:
+            dump['optimizer_state_dict'] = _to_cpu(optimizer.state_dict())
+        torch.save(dump, self.output_path)
+
+
+def _to_cpu(obj):
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
 
 
 class EpochLog(object):
@@ -262,9 +278,19 @@ class TrainerTemplate(object):
                 step(iters, batch)
         self._ids = None
 
+    def _averaged(self):
+        """--ema_decay: the block runs on the optimizer's averaged weights (evaluation passes, prediction exports, the
+        best-checkpoint save); a no-op without averaging, inside such a block already, and once the best checkpoint -- which
+        holds the averaged weights its score was measured on -- has been reloaded for the final evaluation."""
+        opt = getattr(self, 'optimizer', None)
+        if getattr(opt, 'ema_decay', None) and not opt._exchanged and not getattr(self, '_best_reloaded', False):
+            return opt.averaged_parameters()
+        return contextlib.nullcontext()
+
     def eval_model(self, test=False, test_idx=0):
         loader = self.config['test_loader'][test_idx] if test else self.config['val_loader']
-        self._pass(loader, lambda iters, batch: self.eval_iter_step(iters, batch, test=test))
+        with self._averaged():
+            self._pass(loader, lambda iters, batch: self.eval_iter_step(iters, batch, test=test))
         self.eval_probs, self.eval_labels, loss, self.eval_ids = self.log.collect(with_ids=True)
         return standard_metrics(self.eval_probs, self.eval_labels, add_optimal_acc=True), loss
 
@@ -285,10 +311,11 @@ class TrainerTemplate(object):
             "Can only export test results if the IDs are returned in the test dataset."
         self.model.eval()
         ids, probs = [], []
-        for batch in loader:
-            batch = self.batch_to_device(batch)
-            ids.append(batch['ids'])
-            probs.append(torch.sigmoid(self.test_iter_step(batch).reshape(-1)))
+        with self._averaged():
+            for batch in loader:
+                batch = self.batch_to_device(batch)
+                ids.append(batch['ids'])
+                probs.append(torch.sigmoid(self.test_iter_step(batch).reshape(-1)))
         self._write_predictions(loader.dataset.name, torch.cat(ids).cpu(), torch.cat(probs).cpu(), threshold)
 
     @torch.no_grad()
@@ -368,7 +395,9 @@ class TrainerTemplate(object):
             LOGGER.info("New High Score! Saving model...")
             self.best_val_metrics, self.best_val_loss = self.val_metrics, self.val_loss
             if not self.config['no_model_checkpoints'] and _is_main():
-                self.model_saver.save(self.model, self.optimizer)
+                with self._averaged():       # the checkpoint holds the weights its validation score was measured on
+                    self.model_saver.save(self.model, self.optimizer, **(
+                        {'with_optimizer': True} if self.config.get('save_optimizer_state') else {}))
         LOGGER.info("current patience: {}".format(self.plateau.stale))
         self.terminate_training = stop
 
@@ -378,6 +407,7 @@ class TrainerTemplate(object):
             raise ValueError("No Saved model state_dict found for the chosen model...!!! \n"
                              "Aborting evaluation on test set...")
         self.load_model()
+        self._best_reloaded = True
         self.model.to(self.device)
         self.export_val_predictions()
         threshold = find_optimal_threshold(self.eval_probs, self.eval_labels, metric="accuracy")
@@ -486,7 +516,10 @@ class TrainerTemplate(object):
              ('weight_decay', float, 1e-3), ('max_epoch', int, 20), ('lr_decay_step', float, 3),
              ('lr_decay_factor', float, 0.8), ('patience', float, 5), ('early_stop_thresh', float, 1e-3),
              ('seed', int, 42), ('log_every', int, 2000), ('parallel_computing', bool, False),
-             ('deterministic', None, False))      # additive: bit-reproducible steps (UniterModel.deterministic)
+             ('deterministic', None, False),      # additive: bit-reproducible steps (UniterModel.deterministic)
+             # additive: evaluate and checkpoint an exponential moving average of the weights, kept by the fused step (0 = off);
+             # add optimizer_state_dict to the checkpoint (utils/save.py:60-61)
+             ('ema_decay', float, 0.0), ('save_optimizer_state', None, False))
 
     @classmethod
     def add_default_argparse(cls, parser, defaults=dict()):

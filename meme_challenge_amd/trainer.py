@@ -14,6 +14,7 @@ zero_grad) is ONE fused kernel over the flat parameter buffer
 iteration needs no host synchronisation (the reference does `.item()` /
 `.cpu()` every iteration, train_template.py:121-124).
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -220,6 +221,95 @@ def optim_schedule(numel, plan, rows_ahead, has_grad_ready, overlap_wgs, sw, tra
     return out
 
 
+def ema_weight(decay, steps, warmup=True):
+    """The weight w = 1 - d_t of the parameters in the averaging step that follows `steps` earlier ones (a' = a + w (p' - a)):
+    d_t = min(decay, (1 + t) / (10 + t)) with warm-up -- the average forgets its start (a copy of the initial weights) at the rate
+    the run can afford: w = 0.9, 0.82, 0.75, .. until 1 - decay takes over -- else d_t = decay.  Formed in double; the launch takes
+    its fp32 value."""
+    d = min(float(decay), (1.0 + steps) / (10.0 + steps)) if warmup else float(decay)
+    return 1.0 - d
+
+
+# state_dict()['state'] in torch's layout, on plain values: `order` = [(name, shape)] of the parameters in param_groups order (None
+# in the place of a name: a parameter without state -- frozen), offsets: name -> first element in the flat buffers, `flat`: key ->
+# flat tensor.  The keys per rule, in torch's spelling (KIND None / 2 / 3):
+STATE_KEYS = {None: ('exp_avg', 'exp_avg_sq'), 2: ('exp_avg', 'exp_inf'), 3: ('momentum_buffer',)}
+
+
+def _numel(shape):
+    return int(math.prod(shape))
+
+
+def pack_optim_state(order, offsets, flat, keys, step_count):
+    """-> {i: {'step': 0-dim fp32 tensor (rules with a counter), key: clone shaped like parameter i}} for every named entry of
+    `order`; flat: the flat tensors in the order of `keys`.  Before the first step there is no state (torch's own behaviour)."""
+    if step_count < 1:
+        return {}
+    out = {}
+    for i, (name, shape) in enumerate(order):
+        if name is None:
+            continue
+        o, k = offsets[name], _numel(shape)
+        entry = {} if keys == STATE_KEYS[3] else {'step': torch.tensor(float(step_count), dtype=torch.float32)}
+        for key, buf in zip(keys, flat):
+            entry[key] = buf[o:o + k].detach().clone().reshape(shape)
+        out[i] = entry
+    return out
+
+
+def unpack_optim_state(state, order, offsets, flat, keys):
+    """Copy a torch-layout `state` into the flat tensors (in place, in the order of `keys`) -> the step counter it carries (None:
+    the rule has none, or the dict holds no state).  Entries are looked up by index; a parameter without an entry keeps what the
+    flat tensors hold; a missing momentum_buffer is zeros (torch leaves it None until the parameter's first gradient).  A count
+    or shape mismatch raises ValueError; `step` values that differ raise UniterHipError (ONE counter for every parameter)."""
+    if any((not isinstance(i, int)) or i < 0 or i >= len(order) for i in state):
+        raise ValueError('optimizer state names parameter(s) %r: this optimizer holds %d' % (sorted(state, key=str)[-1], len(order)))
+    steps, copies = set(), []
+    for i, entry in state.items():          # everything is checked before anything is written
+        name, shape = order[i]
+        if name is None:
+            if entry:
+                raise ValueError('optimizer state holds an entry for parameter %d, which is frozen here' % i)
+            continue
+        o, k = offsets[name], _numel(shape)
+        for key, buf in zip(keys, flat):
+            t = entry.get(key)
+            if t is None and key != 'momentum_buffer':
+                raise ValueError('optimizer state of parameter %d (%s) lacks %r' % (i, name, key))
+            if t is not None and tuple(t.shape) != tuple(shape):
+                raise ValueError('optimizer state %r of parameter %d (%s) has shape %s, the parameter %s'
+                                 % (key, i, name, tuple(t.shape), tuple(shape)))
+            copies.append((buf[o:o + k], t))
+        if 'step' in entry:
+            steps.add(float(entry['step']))
+    if len(steps) > 1:
+        raise UniterHipError('the optimizer state carries different step counters (%s): the fused step keeps ONE counter for '
+                             'every parameter (step_count), as if each had received a gradient in every step'
+                             % ', '.join('%g' % v for v in sorted(steps)))
+    for dst, t in copies:
+        if t is None:
+            dst.zero_()
+        else:
+            dst.copy_(t.detach().reshape(-1).to(dst.dtype))
+    return int(steps.pop()) if steps else None
+
+
+def pack_averaged(order, offsets, avg):
+    """top-level 'averaged' of the state dict: {i: clone of the average shaped like parameter i}, frozen parameters left out"""
+    return {i: avg[offsets[name]:offsets[name] + _numel(shape)].detach().clone().reshape(shape)
+            for i, (name, shape) in enumerate(order) if name is not None}
+
+
+def unpack_averaged(averaged, order, offsets, avg):
+    for i, t in averaged.items():
+        if (not isinstance(i, int)) or i < 0 or i >= len(order) or order[i][0] is None:
+            raise ValueError("'averaged' names parameter %r, which this optimizer does not average" % (i,))
+        name, shape = order[i]
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("'averaged' of parameter %d (%s) has shape %s, the parameter %s" % (i, name, tuple(t.shape), tuple(shape)))
+        avg[offsets[name]:offsets[name] + _numel(shape)].copy_(t.detach().reshape(-1).to(avg.dtype))
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam (coupled L2) / AdamW over the model's flat buffers.
 
@@ -240,7 +330,10 @@ class FusedAdam(torch.optim.Optimizer):
     KIND = None             # None: torch.optim.Adam / AdamW through uniter_adam_step_x3p; 2 / 3: uniter_optim_step's Adamax / SGD
     SECOND_STATE = True     # the rule keeps exp_avg_sq (Adam's second moment, Adamax's infinity norm)
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False, defaults=None, group_param_func=None, layout=None):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3, adamw=False, defaults=None, group_param_func=None, layout=None,
+                 ema_decay=None, ema_warmup=True):
+        if ema_decay and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError('ema_decay must lie in (0, 1) (0 / None: no averaging), got %r' % (ema_decay,))
         self.model = model
         self.store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
         if layout is None:      # (get_optimizer passes the layout it already built: `group_param_func` is called once)
@@ -295,6 +388,18 @@ class FusedAdam(torch.optim.Optimizer):
         # launch takes from the forward pass it runs beside, and behind the table the next forward's own first kernels bound the head)
         # (Adam / AdamW only: uniter_adam_step_rows knows no other rule, FusedAdamax / FusedSGD never split)
         self.split_word_rows = self.KIND is None and sw.word_rows
+        # An exponential moving average of the parameters kept by the step's own launches (uniter_optim_step_avg: 8 bytes per
+        # parameter inside the kernel that has the new value in registers; a separate lerp_ pass would have to join() the
+        # overlapped update first and stream 12).  avg starts as a copy of the parameters; a parameter a step skips (no gradient,
+        # or frozen) keeps its average -- torch.optim.swa_utils would go on averaging it -- so a frozen tensor's average is
+        # always the tensor.  averaged_parameters() evaluates and checkpoints on it.  No row-split form of the word table's update
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        self.ema_warmup = bool(ema_warmup)
+        self.avg = st.flat_params.detach().clone() if self.ema_decay else None
+        self.avg_steps = 0
+        self._exchanged = False
+        if self.ema_decay:
+            self.split_word_rows = False
         self._rowmask = None        # one byte per row of the table: 1 = a token of the micro-batches since the last step looks it up
         self._rows_noted = False    # every micro-batch since the last step announced its ids (none had a dense table gradient)
         self._early = None          # the rows without a gradient were updated ahead: (the Hyper of that launch, the event behind it)
@@ -629,14 +734,20 @@ class FusedAdam(torch.optim.Optimizer):
             check(lib.uniter_sumsq_combine(ptr(self._parts), len(pieces), ptr(self._sumsq), _lib.cur_stream()), 'uniter_sumsq_combine')
         return True
 
-    def _execute(self, sched, wt, early_ev, grad_ready, h, scale, flags, grad_bf16, layers, blocks=None):
+    def _execute(self, sched, wt, early_ev, grad_ready, h, scale, flags, grad_bf16, layers, blocks=None, avg_w=None):
         """Issue optim_schedule's launches.  wt: the word table of a 'rows' launch; early_ev: what the main stream waits for first;
-        blocks: the plan's blocks when launches may have been dropped from `sched` (frozen parameters), else None"""
+        blocks: the plan's blocks when launches may have been dropped from `sched` (frozen parameters), else None; avg_w: the
+        average's weight of this step when averaging is on"""
         lib = _lib.lib()
         flat, kind, what = (lib.uniter_adam_step_x3p, (), 'uniter_adam_step') if self.KIND is None else \
             (lib.uniter_optim_step, (self.KIND,), 'uniter_optim_step')
         if isinstance(h, GroupHyper):       # every 'flat' launch with its chunks' own hyper-parameters
             flat, kind, what = lib.uniter_optim_step_groups, (int(self.adamw) if self.KIND is None else self.KIND,), 'uniter_optim_step_groups'
+        if avg_w is not None:               # .. and with the average's stream: the same launches through the _avg entry points
+            if isinstance(h, GroupHyper):
+                flat, what = lib.uniter_optim_step_groups_avg, 'uniter_optim_step_groups_avg'
+            else:
+                flat, kind, what = lib.uniter_optim_step_avg, (int(self.adamw) if self.KIND is None else self.KIND,), 'uniter_optim_step_avg'
         streams = {'main': self._stream('main')}
         events, by_range = {'block': [], 'word': []}, {}
         for r in sched:
@@ -655,7 +766,10 @@ class FusedAdam(torch.optim.Optimizer):
             if r.kind == 'rows':
                 check(lib.uniter_adam_step_rows(*self._rows_args(wt, h, ptr(self._sumsq), scale, 1, r.max_wgs, sp)), 'uniter_adam_step_rows')
             else:
-                check(flat(*kind, *self._range_args(r.lo, r.hi, r.max_wgs, sp, h, scale, flags, grad_bf16, layers)), what)
+                args = self._range_args(r.lo, r.hi, r.max_wgs, sp, h, scale, flags, grad_bf16, layers)
+                if avg_w is not None:       # (avg, avg_weight) in front of max_workgroups
+                    args = args[:-2] + (self.avg.data_ptr() + 4 * r.lo, avg_w) + args[-2:]
+                check(flat(*kind, *args), what)
             if r.clear_mask:
                 with torch.cuda.stream(s):
                     self._rowmask.zero_()
@@ -697,6 +811,8 @@ class FusedAdam(torch.optim.Optimizer):
         st = self.store
         if not st.is_current():
             raise UniterHipError('model parameters were moved after the optimizer was built')
+        if self._exchanged:
+            raise UniterHipError('%s.step inside averaged_parameters(): the parameters hold the averaged weights' % type(self).__name__)
         grouped = not self._uniform()
         sw = optim_switches()
         lazy = bool(zero_grads) and self.lazy_zero_encoder is not None and sw.lazy_zero
@@ -720,8 +836,12 @@ class FusedAdam(torch.optim.Optimizer):
         trainable = self._trainable_ranges()
         sched = optim_schedule(st.numel, plan, wt, grad_ready is not None, self.overlap_workgroups, sw,
                                **({} if trainable is None else {'trainable': trainable}))
+        more = {} if trainable is None or plan is None else {'blocks': plan[1]}
+        if self.ema_decay:
+            more['avg_w'] = float(ema_weight(self.ema_decay, self.avg_steps, self.ema_warmup))
+            self.avg_steps += 1
         self._execute(sched, wt, early[1] if early is not None and plan is None else None, grad_ready, h, scale, flags, grad_bf16, layers,
-                      **({} if trainable is None or plan is None else {'blocks': plan[1]}))
+                      **more)
         if early is not None or self._rows_noted is not False:
             # the row mask belongs to the micro-batches of THIS step: clear it behind its last reader
             if self._rowmask is not None and not (plan is not None and early is not None):
@@ -737,6 +857,92 @@ class FusedAdam(torch.optim.Optimizer):
         self.store.zero_grads()
         self._flags_key = None
 
+    # -- the averaged weights -------------------------------------------------------------------------------------------
+    def _exchange(self):
+        p, a = self.store.flat_params, self.avg
+        with torch.no_grad():
+            t = p.detach().clone()
+            p.copy_(a)          # in place: the version counter moves, ParamStore.ensure_mirror rebuilds the bf16 / x3 mirror
+            a.copy_(t)
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """Inside the block the model's parameters ARE the averaged weights (evaluation, the checkpoint's model_state_dict): waits
+        for an overlapped update, exchanges the contents of the flat parameter buffer and `avg` in place -- the weight mirror of the
+        bf16 / fp32x3 modes is rebuilt at the next forward pass -- and exchanges them back on the way out: the raw weights return
+        bit for bit.  Nesting and step() inside the block raise."""
+        if self.avg is None:
+            raise UniterHipError('averaged_parameters(): this optimizer keeps no average (ema_decay is off)')
+        if self._exchanged:
+            raise UniterHipError('averaged_parameters() does not nest')
+        self.join()
+        self._exchange()
+        self._exchanged = True
+        try:
+            yield self
+        finally:
+            self.join()
+            self._exchange()
+            self._exchanged = False
+
+    # -- state_dict in torch's layout -----------------------------------------------------------------------------------
+    def _state_order(self):
+        """[(store name or None (frozen), shape)] of the parameters in param_groups order; the flat tensors and torch's keys"""
+        by_id = {id(p): n for n, p in self.store.params.items()}
+        order = []
+        for g in self.param_groups:
+            for p in g['params']:
+                n = by_id.get(id(p))
+                order.append((None if n is None or n in self._frozen else n, tuple(p.shape)))
+        flat = (self.exp_avg, self.exp_avg_sq) if self.SECOND_STATE else (self.exp_avg,)
+        return order, flat, STATE_KEYS[self.KIND]
+
+    def state_dict(self):
+        """torch.optim's layout: {'state': {i: {'step', 'exp_avg', ..}}, 'param_groups': [..]} with the i-th parameter in param_groups
+        order -- loadable by the torch optimizer of the same rule over the same parameters -- plus, with averaging on, top-level
+        'averaged' ({i: tensor}) and 'averaged_steps', which torch's loader ignores.  Waits for an overlapped step first."""
+        self.join()
+        groups = super().state_dict()['param_groups']
+        order, flat, keys = self._state_order()
+        out = {'state': pack_optim_state(order, self.store.offsets, flat, keys, self.step_count), 'param_groups': groups}
+        if self.avg is not None:
+            # (inside averaged_parameters() the two buffers are exchanged: the average sits in the parameters' place)
+            out['averaged'] = pack_averaged(order, self.store.offsets, self.store.flat_params if self._exchanged else self.avg)
+            out['averaged_steps'] = self.avg_steps
+        return out
+
+    def load_state_dict(self, state_dict):
+        """Takes this class's dicts and those of torch.optim.Adam / AdamW / Adamax / SGD over the same parameters in the same order:
+        the moments go into the flat buffers, the hyper-parameters ('initial_lr' included) come from the dict's groups as torch
+        takes them, step_count from the entries' `step` (they must agree).  Without 'averaged' while averaging is on, the average
+        restarts from the current parameters."""
+        self.join()
+        if self._exchanged:
+            raise UniterHipError('load_state_dict() inside averaged_parameters()')
+        groups, state = state_dict['param_groups'], state_dict.get('state', {})
+        if len(groups) != len(self.param_groups):
+            raise ValueError('loaded state dict has %d parameter groups, this optimizer %d' % (len(groups), len(self.param_groups)))
+        for k, (mine, theirs) in enumerate(zip(self.param_groups, groups)):
+            if len(mine['params']) != len(theirs['params']):
+                raise ValueError('parameter group %d holds %d parameters in the loaded state dict, %d here'
+                                 % (k, len(theirs['params']), len(mine['params'])))
+        order, flat, keys = self._state_order()
+        with torch.no_grad():
+            step = unpack_optim_state(state, order, self.store.offsets, flat, keys)
+            for mine, theirs in zip(self.param_groups, groups):
+                mine.update({k: v for k, v in theirs.items() if k != 'params'})
+            if step is not None:
+                self.step_count = step
+            elif not state:
+                self.step_count = 0
+            if self.avg is not None:
+                if state_dict.get('averaged') is not None:
+                    unpack_averaged(state_dict['averaged'], order, self.store.offsets, self.avg)
+                    self.avg_steps = int(state_dict.get('averaged_steps', 0))
+                else:
+                    self.avg.copy_(self.store.flat_params)
+                    self.avg_steps = 0
+
 
 class FusedAdamax(FusedAdam):
     """torch.optim.Adamax (coupled L2; utils/optim_utils.py:36-37) over the flat buffers: FusedAdam's launch with the Adamax rule
@@ -750,9 +956,10 @@ class FusedAdamax(FusedAdam):
 
     KIND = 2
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, group_param_func=None, layout=None):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, group_param_func=None, layout=None,
+                 ema_decay=None, ema_warmup=True):
         super().__init__(model, lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=False, group_param_func=group_param_func,
-                         layout=layout)
+                         layout=layout, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
 
 class FusedSGD(FusedAdam):
@@ -767,10 +974,10 @@ class FusedSGD(FusedAdam):
     KIND = 3
     SECOND_STATE = False
 
-    def __init__(self, model, lr, momentum=0.0, weight_decay=0.0, group_param_func=None, layout=None):
+    def __init__(self, model, lr, momentum=0.0, weight_decay=0.0, group_param_func=None, layout=None, ema_decay=None, ema_warmup=True):
         super().__init__(model, lr, weight_decay=weight_decay, adamw=False,
                          defaults=dict(lr=lr, momentum=momentum, weight_decay=weight_decay), group_param_func=group_param_func,
-                         layout=layout)
+                         layout=layout, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     def _rule_args(self, group):
         return float(group['momentum']), 0.0, 0.0
@@ -819,9 +1026,12 @@ def get_optimizer(model, config, group_param_func=None, fused=True):
     decay and a no-decay group (weight decay off for biases and LayerNorm) -- then the optimizer by name.  All four run as the
     fused HIP step; fused=False runs adamax / sgd as torch.optim's own update (TorchOptimizerStep)."""
     name = config['optimizer']
+    ema = dict(ema_decay=config.get('ema_decay') or None, ema_warmup=config.get('ema_warmup', True))
+    if ema['ema_decay'] and not fused:
+        raise ValueError('ema_decay needs the fused step (the average is kept by its kernel): fused=False keeps none')
     if name in ('adam', 'adamw'):
         return FusedAdam(model, lr=config['lr'], betas=(config['beta1'], config['beta2']),
-                         weight_decay=config['weight_decay'], adamw=(name == 'adamw'), group_param_func=group_param_func)
+                         weight_decay=config['weight_decay'], adamw=(name == 'adamw'), group_param_func=group_param_func, **ema)
     if name not in ('adamax', 'sgd'):
         raise ValueError('invalid optimizer %r' % name)
     store = model.param_store() if hasattr(model, 'param_store') else ensure_store(model)
@@ -841,8 +1051,8 @@ def get_optimizer(model, config, group_param_func=None, fused=True):
     # the torch optimizer carries the reference's hyper-parameters (its defaults where the reference passes none)
     d = inner.defaults
     if name == 'adamax':
-        return FusedAdamax(model, lr=d['lr'], betas=tuple(d['betas']), eps=d['eps'], weight_decay=config['weight_decay'], layout=layout)
-    return FusedSGD(model, lr=d['lr'], momentum=d['momentum'], weight_decay=config['weight_decay'], layout=layout)
+        return FusedAdamax(model, lr=d['lr'], betas=tuple(d['betas']), eps=d['eps'], weight_decay=config['weight_decay'], layout=layout, **ema)
+    return FusedSGD(model, lr=d['lr'], momentum=d['momentum'], weight_decay=config['weight_decay'], layout=layout, **ema)
 
 
 # --------------------------------------------------------------------------- #
