@@ -341,6 +341,16 @@ size_t uniter_ln_bwd_ws_bytes(int M, int H);
  *   attn_mask : [B, L] 1 = attend, 0 = padded (additive (1-m)*-10000 as model/model.py:345)
  *   ctx : [B*L, H] merged heads;  lse : [B, nh, L] log-sum-exp of the scaled+masked scores
  * head_dim must be 64.
+ * Every family below (fp32, x3, bf16):
+ *  - qkv, ctx, dctx, dqkv, their bf16 / piece copies and the workspace are 16-byte aligned -- no more than that; the
+ *    uniter_attn_x3_* and uniter_attn_b16x_* entry points check it (UNITER_E_ARG), the others rely on it; keep_bits 4-byte;
+ *  - the mask is 0 / 1 and every sample has at least one row; in the mask form a padded QUERY is an ordinary query: its
+ *    ctx / lse / dqkv / delta are computed and bias_part sums all L rows of a sample;
+ *  - with cu_seqlens, lse and delta stay [B, nh, Lmax] and only the positions below a sample's length exist: no forward pass
+ *    writes lse, and no backward pass writes delta or reads lse, at or beyond it -- those elements are left untouched;
+ *  - a piece copy (ctx_x3, dqkv_x3) is the exact three-piece split of the fp32 value from |x| >= 2^-102 on; below that a
+ *    piece would be a bf16 subnormal, which is flushed to zero: the pieces then sum to x within 2^-126.
+ * (tests/test_attention_f64_gpu.py holds every family to these.)
  * ------------------------------------------------------------------------- */
 int uniter_attn_fwd(const float* qkv, const float* attn_mask, float* ctx, float* lse,
                     int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
