@@ -571,6 +571,48 @@ int uniter_img_embed_bwd_det(const float* dcat, const float* imgfc, const float*
 size_t uniter_embed_bwd_det_ws_bytes(int txt_rows, int img_rows, int H);
 
 /* ------------------------------------------------------------------------- *
+ * Gradients with respect to the INPUTS (csrc/input_grads.hip) -- what autograd gives the reference for
+ * img_feat.requires_grad_() and for a perturbation added to the word embeddings (the FreeLB / VILLA recipes on top of
+ * UniterTextEmbeddings.forward model/model.py:232-245 and UniterImageEmbeddings.forward :261-272; the reference's own
+ * inspection tool, utils/misclassification.py, stops at the predictions).  No float atomics: every output element has one
+ * writer and is overwritten, so the results are a function of the inputs alone (nothing to switch for
+ * uniter_model_set_deterministic).  H % 4 == 0 and H <= 1024, UNITER_E_SHAPE beyond.
+ * ------------------------------------------------------------------------- */
+/* uniter_txt_embed_fwd with a perturbation of the word rows (model/model.py:238-243 with words_embeddings + delta):
+ *   cat[b, t] = dropout(LN(((word[ids] + delta[b, t]) + pos[position_ids]) + type[type_ids or 0]))
+ * delta [B, T, H] fp32, 16-byte aligned; delta == NULL is uniter_txt_embed_fwd itself (the same kernel). */
+int uniter_txt_embed_fwd_delta(const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                               const float* word, const float* pos, const float* type, const float* gamma, const float* beta,
+                               const float* delta /*NULL = none*/, float* cat, int B, int T, int S, int H,
+                               int vocab, int max_pos, int type_vocab, int pos_bcast,
+                               float p_drop, uint64_t seed, uint32_t offset, void* stream);
+/* d_rows[b, t] = gradient of the sum that enters that LayerNorm (model/model.py:243-244 backwards: dropout replayed from
+ * (seed, offset), then the LayerNorm's backward) -- one quantity, the gradient of the word row, of the position row and of
+ * delta[b, t] alike.  dcat as in uniter_txt_embed_bwd; delta as the forward pass had it (NULL = none).  Plain stores: d_rows
+ * [B, T, H] is overwritten whatever it held, a row whose id is 0 (padding_idx) included -- only the TABLE's row 0 is exempt in
+ * the reference, and no table is touched here.  The arithmetic is the row pass of uniter_txt_embed_bwd_det, so d_rows[b, t] is
+ * bit for bit what that call adds to a table row which this row alone reads. */
+int uniter_txt_embed_bwd_rows(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
+                              const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                              const float* gamma, const float* delta /*NULL = none*/, float* d_rows,
+                              int B, int T, int S, int H, int vocab, int max_pos, int type_vocab, int pos_bcast,
+                              float p_drop, uint64_t seed, uint32_t offset, void* stream);
+/* d_pos7[rows, 7] = d_posfc[rows, H] @ Wp[H, 7]: the gradient of img_pos_feat through pos_linear (model/model.py:268), d_posfc
+ * as uniter_img_embed_bwd leaves it.  One wave per row. */
+int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, int rows, int H, void* stream);
+/* One ascent step of an adversarial perturbation and its projection onto the L2 ball, per sample b over its n contiguous
+ * floats (n % 4 == 0, delta and grad [B, n], 16-byte aligned):
+ *   delta_b <- delta_b + step_size * g_b / |g_b|_2      (|g_b| = 0: nothing is added)
+ *   delta_b <- delta_b * min(1, max_norm / |delta_b|_2) (max_norm <= 0: no projection)
+ * A sample with g_b = 0 that lies inside the ball keeps its bits.  Two launches of ceil(n / 4096) workgroups per sample: the
+ * sample's sums g.g, delta.g, delta.delta as double partials in ws (one writer each), folded in ascending order by every
+ * workgroup of the second launch; the norm of the stepped perturbation is formed from the three sums.  Bit-reproducible.
+ * ws: uniter_adv_delta_ws_bytes(B, n) bytes, 8-byte aligned. */
+int uniter_adv_delta_step(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
+                          void* stream);
+size_t uniter_adv_delta_ws_bytes(int B, int n);
+
+/* ------------------------------------------------------------------------- *
  * Pooler + classification head (replaces BertPooler.forward model/layer.py:179-185
  * and MemeUniter.linear model/meme_uniter.py:19-20) and the loss
  * (nn.BCEWithLogitsLoss(pos_weight), train_template.py:65,98-99).
@@ -900,6 +942,21 @@ int uniter_ln_set_next_keep_bits(const void* site_bits);
  * for that forward's plan) returns 0 when the current precision / switches / plan have no such riders: the caller
  * then reduces the bucket itself (uniter_grad_sumsq_part). */
 int uniter_model_set_norm_partials(uniter_model_t* m, double* parts, size_t stride_doubles);
+/* Input gradients and a text perturbation for the NEXT forward pass and its backward pass, a setting on the handle:
+ *   txt_delta      [B, T, H]  read by the next uniter_model_forward: added to the word rows (uniter_txt_embed_fwd_delta)
+ *   d_txt_rows     [B, T, H]  uniter_txt_embed_bwd_rows of that pass (the gradient of txt_delta and of the word rows)
+ *   d_img_feat     [B, R, D]  d_imgfc @ W_img: the gradient of img_feat (and of img_feat + mask_embedding[img_masks])
+ *   d_img_pos_feat [B, R, 7]  uniter_pos_feat_dgrad
+ * With txt_delta the text embeddings' own backward recomputes its LayerNorm input with it (the kernels of uniter_txt_embed_bwd /
+ * _det, instantiated with the perturbation), so every parameter gradient is that of the perturbed forward pass.
+ * uniter_model_backward_embed writes whichever outputs are non-NULL (overwriting them) behind the embedding backward of their
+ * branch -- the text one on the auxiliary stream when that branch runs there, the image ones on the main stream -- all of it
+ * finished when uniter_model_backward_end joins; the backward pass (or an inference forward) then forgets all four pointers.
+ * All NULL, or never called: exactly the launches without it.  The forward pass refuses (UNITER_E_ARG, and forgets the setting)
+ * txt_delta / d_txt_rows on a batch without text, the image outputs on a batch without regions, and outputs with train == 0.
+ * A backward pass that stops above a frozen prefix (uniter_model_backward_end in place of _embed) writes nothing. */
+int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_delta, float* d_txt_rows, float* d_img_feat,
+                                 float* d_img_pos_feat);
 /* A stream for launches of the forward pass that depend on nothing the step computes -- the dropout keep flags of the attention
  * probabilities (a function of seed and offset alone: 60 us of Philox rounds for twelve layers) -- so that they run BESIDE the head
  * of the forward pass instead of in front of it; the first attention kernel waits for them.  NULL (default): on `stream`. */

@@ -67,29 +67,39 @@ struct TxtArgs {
   DropCfg drop;
 };
 
-template <int NV>
-__device__ __forceinline__ void txt_row_sum(const TxtArgs& a, int row, int t, f32x4 (&e)[NV], int& id, int& pid,
-                                            int& tt, int H4, int lane) {
+// DELTA: an additive perturbation of the word row, delta[row][H] (uniter_txt_embed_fwd_delta, and the backward pass of such a forward,
+// which recomputes the LayerNorm's input): (word + delta) + pos + type
+struct TxtDeltaArgs : TxtArgs { const float* delta; };
+
+template <int NV, bool DELTA = false>
+__device__ __forceinline__ void txt_row_sum(const TxtArgs& a, const float* __restrict__ delta, int row, int t, f32x4 (&e)[NV],
+                                            int& id, int& pid, int& tt, int H4, int lane) {
   id = clampi(a.ids[row], a.vocab);
   pid = clampi(a.pos_ids[a.pos_bcast ? t : row], a.max_pos);
   tt = a.type_ids ? clampi(a.type_ids[row], a.type_vocab) : 0;
   f32x4 w[NV];
   row_load<NV>(e, a.word + (size_t)id * a.H, H4, lane);
+  if constexpr (DELTA) {
+    row_load<NV>(w, delta + (size_t)row * a.H, H4, lane);
+    row_add<NV>(e, w);
+  }
   row_load<NV>(w, a.pos + (size_t)pid * a.H, H4, lane);
   row_add<NV>(e, w);
   row_load<NV>(w, a.type + (size_t)tt * a.H, H4, lane);
   row_add<NV>(e, w);
 }
 
-template <int NV>
-__global__ __launch_bounds__(256) void txt_embed_fwd_kernel(const TxtArgs a) {
+template <int NV, bool DELTA = false>
+__global__ __launch_bounds__(256) void txt_embed_fwd_kernel(const std::conditional_t<DELTA, TxtDeltaArgs, TxtArgs> a) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.T) return;
   const int b = row / a.T, t = row - b * a.T, H4 = a.H >> 2;
   f32x4 e[NV];
   int id, pid, tt;
-  txt_row_sum<NV>(a, row, t, e, id, pid, tt, H4, lane);
+  const float* delta = nullptr;
+  if constexpr (DELTA) delta = a.delta;
+  txt_row_sum<NV, DELTA>(a, delta, row, t, e, id, pid, tt, H4, lane);
   float mean, rstd;
   row_stats<NV>(e, a.H, H4, lane, mean, rstd);
   row_affine<NV>(e, a.gamma, a.beta, mean, rstd, H4, lane);
@@ -114,9 +124,12 @@ __device__ __forceinline__ void row_atomic_add(const f32x4 (&v)[NV], float* buf,
 
 // DET: the row's table gradient goes to the workspace drow[row][H] with plain 16-byte stores instead of the atomic scatter
 struct TxtDetArgs : TxtArgs { float* drow; };
+struct TxtDetDeltaArgs : TxtDetArgs { const float* delta; };
+template <bool DET, bool DELTA>
+using TxtBwdArgs = std::conditional_t<DELTA, std::conditional_t<DET, TxtDetDeltaArgs, TxtDeltaArgs>, std::conditional_t<DET, TxtDetArgs, TxtArgs>>;
 
-template <int NV, bool DET = false>
-__global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const std::conditional_t<DET, TxtDetArgs, TxtArgs> a) {
+template <int NV, bool DET = false, bool DELTA = false>
+__global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const TxtBwdArgs<DET, DELTA> a) {
   __shared__ __attribute__((aligned(16))) float red[4 * NV * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, H4 = a.H >> 2;
   float* abuf = red + wave * NV * 256;   // per-wave staging for atomics (reused for the reduce)
@@ -131,7 +144,9 @@ __global__ __launch_bounds__(256) void txt_embed_bwd_kernel(const std::condition
     row_load<NV>(d, a.dcat + ((size_t)b * a.S + t) * a.H, H4, lane);
     if (a.drop.active) row_dropout<NV>(d, a.drop, (uint64_t)row * H4, H4, lane);
     int id, pid, tt;
-    txt_row_sum<NV>(a, row, t, e, id, pid, tt, H4, lane);
+    const float* delta = nullptr;
+    if constexpr (DELTA) delta = a.delta;
+    txt_row_sum<NV, DELTA>(a, delta, row, t, e, id, pid, tt, H4, lane);
     float mean, rstd;
     row_stats<NV>(e, a.H, H4, lane, mean, rstd);
     row_ln_bwd<NV>(d, e, g, mean, rstd, dg, db, a.H, H4, lane);     // d <- d(sum of the three lookups)
@@ -532,6 +547,17 @@ int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int r
              return UNITER_E_SHAPE;                                                            \
   }
 
+// KERNEL<NV, further template arguments>
+#define NV_DISPATCH_T(KERNEL, GRID, ARG, ...)                                                           \
+  switch ((H / 4 + 63) / 64) {                                                                          \
+    case 1: hipLaunchKernelGGL((KERNEL<1, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
+    case 2: hipLaunchKernelGGL((KERNEL<2, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
+    case 3: hipLaunchKernelGGL((KERNEL<3, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
+    case 4: hipLaunchKernelGGL((KERNEL<4, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
+    default: uniter_set_error("embed: hidden size %d unsupported (max 1024)", H);                       \
+             return UNITER_E_SHAPE;                                                                     \
+  }
+
 extern "C" size_t uniter_embed_bwd_ws_bytes(int rows, int H) {
   return (size_t)bwd_blocks(rows) * 7 * H * sizeof(float);
 }
@@ -562,12 +588,24 @@ extern "C" int uniter_txt_embed_bwd(const float* dcat, const int64_t* input_ids,
                                     float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H,
                                     int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop,
                                     uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
+  return txt_embed_bwd_run(dcat, input_ids, position_ids, type_ids, word, pos, type, gamma, nullptr, dword, dpos, dtype, dgamma, dbeta, B, T,
+                           S, H, vocab, max_pos, type_vocab, pos_bcast, p_drop, seed, offset, ws, ws_bytes, stream);
+}
+
+// uniter_txt_embed_bwd behind a forward pass that had `delta` added to the word rows (uniter_txt_embed_fwd_delta): the LayerNorm's
+// input is recomputed with it.  delta == NULL: the kernels uniter_txt_embed_bwd always ran
+int txt_embed_bwd_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                      const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
+                      float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
+                      int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
+                      void* stream) {
   UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && dword && dpos && dtype &&
              dgamma && dbeta && ws, "txt_embed_bwd: null pointer");
   UCHECK_SHAPE(H % 4 == 0 && T <= S, "txt_embed_bwd: bad shape");
   UCHECK_ARG(ws_bytes >= uniter_embed_bwd_ws_bytes(B * T, H), "txt_embed_bwd: workspace too small");
   if (B * T <= 0) return 0;
-  TxtArgs a = {};
+  TxtDeltaArgs a = {};
+  a.delta = delta;
   a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
   a.type = type; a.gamma = gamma; a.dcat = dcat; a.dword = dword; a.dpos = dpos; a.dtype = dtype;
   a.part = (float*)ws; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
@@ -575,7 +613,12 @@ extern "C" int uniter_txt_embed_bwd(const float* dcat, const int64_t* input_ids,
   a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
   hipStream_t st = (hipStream_t)stream;
   const int nblk = bwd_blocks(B * T);
-  NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), a);
+  if (delta) {
+    NV_DISPATCH_T(txt_embed_bwd_kernel, dim3(nblk), a, false, true);
+  } else {
+    const TxtArgs& plain = a;
+    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), plain);
+  }
   UCHECK_LAUNCH();
   float* outs[3] = {dgamma, dbeta, type_ids ? nullptr : dtype};
   return finalize_partials_multi(a.part, nblk, (size_t)3 * H, outs, 3, H, st);
@@ -645,6 +688,31 @@ extern "C" int uniter_img_embed_bwd(const float* dcat, const float* imgfc, const
              return UNITER_E_SHAPE;                                                            \
   }
 
+// uniter_txt_embed_fwd with delta[B][T][H] added to the word rows (include/uniter_hip.h); delta == NULL is that call itself
+extern "C" int uniter_txt_embed_fwd_delta(const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                                          const float* word, const float* pos, const float* type, const float* gamma,
+                                          const float* beta, const float* delta, float* cat, int B, int T, int S, int H, int vocab,
+                                          int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset,
+                                          void* stream) {
+  if (!delta)
+    return uniter_txt_embed_fwd(input_ids, position_ids, type_ids, word, pos, type, gamma, beta, cat, B, T, S, H, vocab, max_pos,
+                                type_vocab, pos_bcast, p_drop, seed, offset, stream);
+  UCHECK_ARG(input_ids && position_ids && word && pos && type && gamma && beta && cat, "txt_embed_fwd_delta: null pointer");
+  UCHECK_ARG(((uintptr_t)delta & 15) == 0, "txt_embed_fwd_delta: delta must be 16-byte aligned");
+  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_fwd_delta: bad shape (H %% 4, H <= 1024, T <= S)");
+  if (B * T <= 0) return 0;
+  TxtDeltaArgs a = {};
+  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
+  a.type = type; a.gamma = gamma; a.beta = beta; a.cat = cat; a.B = B; a.T = T; a.S = S; a.H = H;
+  a.vocab = vocab; a.max_pos = max_pos; a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
+  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
+  a.delta = delta;
+  hipStream_t st = (hipStream_t)stream;
+  NV_DISPATCH_T(txt_embed_fwd_kernel, dim3((B * T + 3) / 4), a, true);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
 namespace {
 
 // the workspace of one _det call: column partials | drow | per table: order, skey, pieces | position-projection partials
@@ -699,6 +767,16 @@ extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_
                                         float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H,
                                         int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop,
                                         uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
+  return txt_embed_bwd_det_run(dcat, input_ids, position_ids, type_ids, word, pos, type, gamma, nullptr, dword, dpos, dtype, dgamma, dbeta,
+                               B, T, S, H, vocab, max_pos, type_vocab, pos_bcast, p_drop, seed, offset, ws, ws_bytes, stream);
+}
+
+// uniter_txt_embed_bwd_det with the forward pass's perturbation, as txt_embed_bwd_run
+int txt_embed_bwd_det_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                          const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
+                          float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
+                          int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
+                          void* stream) {
   UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && dword && dpos && dtype &&
              dgamma && dbeta && ws, "txt_embed_bwd_det: null pointer");
   UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_bwd_det: bad shape (H %% 4, H <= 1024, T <= S)");
@@ -708,7 +786,8 @@ extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_
   const int rows = B * T;
   UCHECK_ARG(ws_bytes >= uniter_embed_bwd_det_ws_bytes(rows, 0, H), "txt_embed_bwd_det: workspace too small");
   const DetWs w = det_carve(ws, rows, H, 3, 3, false);
-  TxtDetArgs a = {};
+  TxtDetDeltaArgs a = {};
+  a.delta = delta;
   a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
   a.type = type; a.gamma = gamma; a.dcat = dcat; a.dword = dword; a.dpos = dpos; a.dtype = dtype;
   a.part = w.part; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
@@ -717,7 +796,12 @@ extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_
   a.drow = w.drow;
   hipStream_t st = (hipStream_t)stream;
   const int nblk = bwd_blocks(rows);
-  NV_DISPATCH_DET(txt_embed_bwd_kernel, dim3(nblk), a);
+  if (delta) {
+    NV_DISPATCH_T(txt_embed_bwd_kernel, dim3(nblk), a, true, true);
+  } else {
+    const TxtDetArgs& plain = a;
+    NV_DISPATCH_DET(txt_embed_bwd_kernel, dim3(nblk), plain);
+  }
   UCHECK_LAUNCH();
   float* outs[3] = {dgamma, dbeta, type_ids ? nullptr : dtype};
   UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)3 * H, outs, 3, H, st));

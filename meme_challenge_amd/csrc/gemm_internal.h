@@ -78,6 +78,18 @@ int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float* res, 
 int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean, const float* rstd,
                     const float* gamma, float* dz, float* dx, void* dx_copy, int pieces, int want_dbias, int M, int H, float p_drop,
                     uint64_t seed, uint32_t offset, uint32_t site, const unsigned char* keep_bits, void* ws, size_t ws_bytes, void* stream);
+// the text embedding backward (uniter_txt_embed_bwd / _det) behind a forward pass with a perturbation of the word rows: delta [B, T, H]
+// as uniter_txt_embed_fwd_delta had it, NULL = none (the public entry points)
+int txt_embed_bwd_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                      const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
+                      float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
+                      int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
+                      void* stream);
+int txt_embed_bwd_det_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                          const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
+                          float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
+                          int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
+                          void* stream);
 int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int rows, int D, hipStream_t st);
 
 // ---- attention backward: attention_f32.hip, attention_x3.hip, attention_bf16.hip ----

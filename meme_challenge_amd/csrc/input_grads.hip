@@ -1,0 +1,239 @@
+// Gradients with respect to the model's INPUTS, and the update of an adversarial perturbation (FreeLB):
+//   uniter_txt_embed_bwd_rows  per-token gradient of the sum that enters the text embeddings' LayerNorm
+//                              (autograd of model/model.py:232-245 with respect to words_embeddings)
+//   uniter_pos_feat_dgrad      d_pos7 = d_posfc @ Wp (autograd of pos_linear, model/model.py:268, with respect to img_pos_feat)
+//   uniter_adv_delta_step      delta <- project(delta + step * g / |g|) per sample
+// The region-feature gradient is the schedule's own dense product (model.cpp); the perturbed text forward is an instantiation of
+// the text row kernel (embed.hip).
+//
+// Row kernels in the style of embed.hip: one wave per row, 16-byte accesses, H % 4 == 0, H <= 1024.  No float atomics anywhere:
+// every result is a function of the inputs alone, every output element has one writer and is overwritten.
+#include "common.h"
+#include "gemm_internal.h"
+#include "philox.h"
+#include "rowops.h"
+
+namespace {
+
+__device__ __forceinline__ int clampi(long long v, int hi) { return v < 0 ? 0 : (v >= hi ? hi - 1 : (int)v); }
+
+struct RowsArgs {
+  const float* dcat; const int64_t* ids; const int64_t* pos_ids; const int64_t* type_ids;
+  const float* word; const float* pos; const float* type; const float* gamma; const float* delta;
+  float* d_rows;
+  int B, T, S, H, vocab, max_pos, type_vocab, pos_bcast;
+  DropCfg drop;
+};
+
+// The row pass of txt_embed_bwd_kernel (embed.hip), statement for statement, with the row's gradient stored to d_rows[row] and
+// nothing else kept: the same operations in the same order, so d_rows[row] is bit for bit what the deterministic backward adds to a
+// table row that this row alone reads.
+template <int NV>
+__global__ __launch_bounds__(256) void txt_embed_bwd_rows_kernel(const RowsArgs a) {
+  const int lane = threadIdx.x & 63, H4 = a.H >> 2;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.B * a.T) return;
+  const int b = row / a.T, t = row - b * a.T;
+  f32x4 g[NV], dg[NV], db[NV], d[NV], e[NV], w[NV];
+  row_load<NV>(g, a.gamma, H4, lane);
+#pragma unroll
+  for (int k = 0; k < NV; ++k) { dg[k] = f32x4{0, 0, 0, 0}; db[k] = dg[k]; }
+  row_load<NV>(d, a.dcat + ((size_t)b * a.S + t) * a.H, H4, lane);
+  if (a.drop.active) row_dropout<NV>(d, a.drop, (uint64_t)row * H4, H4, lane);
+  const int id = clampi(a.ids[row], a.vocab);
+  const int pid = clampi(a.pos_ids[a.pos_bcast ? t : row], a.max_pos);
+  const int tt = a.type_ids ? clampi(a.type_ids[row], a.type_vocab) : 0;
+  row_load<NV>(e, a.word + (size_t)id * a.H, H4, lane);
+  if (a.delta) {                                                  // (uniform per launch)
+    row_load<NV>(w, a.delta + (size_t)row * a.H, H4, lane);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) e[k] += w[k];
+  }
+  row_load<NV>(w, a.pos + (size_t)pid * a.H, H4, lane);
+#pragma unroll
+  for (int k = 0; k < NV; ++k) e[k] += w[k];
+  row_load<NV>(w, a.type + (size_t)tt * a.H, H4, lane);
+#pragma unroll
+  for (int k = 0; k < NV; ++k) e[k] += w[k];
+  float mean, rstd;
+  row_stats<NV>(e, a.H, H4, lane, mean, rstd);
+  row_ln_bwd<NV>(d, e, g, mean, rstd, dg, db, a.H, H4, lane);     // d <- d(sum of the lookups and the perturbation)
+  row_store<NV>(d, a.d_rows + (size_t)row * a.H, H4, lane);
+}
+
+// d_pos7[row][k] = sum_c d_posfc[row][c] * Wp[c][k].  One wave per row; lane l owns the 16-byte chunks l, l + 64, ... of the row and
+// the 7 x 4 weights that belong to each (112 contiguous bytes, seven 16-byte loads).  The chunk loop has NV trips for EVERY lane -- the
+// bound is the template parameter, the row's end is a predicate inside -- and the seven wave sums follow it, outside any loop: no
+// shuffle runs under a trip count that differs between lanes.
+template <int NV>
+__global__ __launch_bounds__(256) void pos_feat_dgrad_kernel(const float* __restrict__ d_posfc, const float* __restrict__ Wp,
+                                                             float* __restrict__ d_pos7, int rows, int H) {
+  const int lane = threadIdx.x & 63, H4 = H >> 2;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                                        // (whole waves leave: the row index is uniform in a wave)
+  f32x4 d[NV];
+  row_load<NV>(d, d_posfc + (size_t)row * H, H4, lane);
+  float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kk = 0; kk < NV; ++kk) {
+    const int c4 = lane + 64 * kk;
+    if (c4 < H4) {
+      const f32x4* wp = reinterpret_cast<const f32x4*>(Wp + (size_t)c4 * 28);
+      float w[28];
+#pragma unroll
+      for (int q = 0; q < 7; ++q) {
+        const f32x4 v = wp[q];
+        w[4 * q] = v[0]; w[4 * q + 1] = v[1]; w[4 * q + 2] = v[2]; w[4 * q + 3] = v[3];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) s[k] += d[kk][e] * w[e * 7 + k];
+    }
+  }
+  float o = 0.f;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    const float t = wave_sum(s[k]);
+    if (lane == k) o = t;
+  }
+  if (lane < 7) d_pos7[(size_t)row * 7 + lane] = o;
+}
+
+// ---- uniter_adv_delta_step ----
+constexpr int ADV_CHUNK = 4096;      // floats of a sample one workgroup owns: 256 threads x 4 x 16 bytes
+
+// sum of a double over the workgroup in a fixed order: lanes by the shuffle tree, then the four waves in ascending index
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// grid (P, B): part[b][p] = {g.g, delta.g, delta.delta} over the chunk, in double (a product of two floats is exact there)
+__global__ __launch_bounds__(256) void adv_partials_kernel(const float* __restrict__ delta, const float* __restrict__ grad,
+                                                           double* __restrict__ part, int n4) {
+  __shared__ double red[4][3];
+  const int p = blockIdx.x, b = blockIdx.y, P = gridDim.x;
+  const f32x4* d4 = reinterpret_cast<const f32x4*>(delta) + (size_t)b * n4;
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(grad) + (size_t)b * n4;
+  double gg = 0.0, dg = 0.0, dd = 0.0;
+#pragma unroll
+  for (int j = 0; j < ADV_CHUNK / 1024; ++j) {
+    const int i = p * (ADV_CHUNK / 4) + j * 256 + (int)threadIdx.x;
+    if (i < n4) {
+      const f32x4 dv = d4[i], gv = g4[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double x = (double)dv[e], y = (double)gv[e];
+        gg += y * y; dg += x * y; dd += x * x;
+      }
+    }
+  }
+  gg = wave_sum_f64(gg); dg = wave_sum_f64(dg); dd = wave_sum_f64(dd);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[wave][0] = gg; red[wave][1] = dg; red[wave][2] = dd; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int k = threadIdx.x;
+    part[((size_t)b * P + p) * 3 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// grid (P, B), behind adv_partials_kernel: every thread folds the sample's P partials in ascending order (the same value in every
+// thread and workgroup), forms the step and the projection's factor from them, and updates its elements of the chunk:
+//   a = step / |g|;  |delta + a g|^2 = dd + 2 a dg + a^2 gg;  delta <- (delta + a g) * min(1, max_norm / |delta + a g|)
+__global__ __launch_bounds__(256) void adv_update_kernel(float* __restrict__ delta, const float* __restrict__ grad,
+                                                         const double* __restrict__ part, int n4, float step_size, float max_norm) {
+  const int p = blockIdx.x, b = blockIdx.y, P = gridDim.x;
+  const double* pp = part + (size_t)b * P * 3;
+  double gg = 0.0, dg = 0.0, dd = 0.0;
+  for (int q = 0; q < P; ++q) { gg += pp[3 * q]; dg += pp[3 * q + 1]; dd += pp[3 * q + 2]; }       // (P: uniform)
+  const double a = gg > 0.0 ? (double)step_size / sqrt(gg) : 0.0;
+  const float af = (float)a;
+  const double ad = (double)af;                                   // (the factor the elements are stepped with)
+  double n2 = dd + 2.0 * ad * dg + ad * ad * gg;
+  n2 = n2 > 0.0 ? n2 : 0.0;
+  const double nrm = sqrt(n2);
+  const float sf = (max_norm > 0.f && nrm > (double)max_norm) ? (float)((double)max_norm / nrm) : 1.0f;
+  if (af == 0.f && sf == 1.0f) return;                            // (uniform: the sample keeps its bits)
+  f32x4* d4 = reinterpret_cast<f32x4*>(delta) + (size_t)b * n4;
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(grad) + (size_t)b * n4;
+#pragma unroll
+  for (int j = 0; j < ADV_CHUNK / 1024; ++j) {
+    const int i = p * (ADV_CHUNK / 4) + j * 256 + (int)threadIdx.x;
+    if (i < n4) {
+      f32x4 dv = d4[i];
+      const f32x4 gv = g4[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dv[e] = (dv[e] + af * gv[e]) * sf;
+      d4[i] = dv;
+    }
+  }
+}
+
+inline int adv_parts(int n) { return (n + ADV_CHUNK - 1) / ADV_CHUNK; }
+
+}  // namespace
+
+#define IG_NV_DISPATCH(KERNEL, GRID, ...)                                                      \
+  switch ((H / 4 + 63) / 64) {                                                                 \
+    case 1: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(256), 0, st, __VA_ARGS__); break;       \
+    case 2: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(256), 0, st, __VA_ARGS__); break;       \
+    case 3: hipLaunchKernelGGL((KERNEL<3>), GRID, dim3(256), 0, st, __VA_ARGS__); break;       \
+    default: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, st, __VA_ARGS__); break;      \
+  }
+
+extern "C" int uniter_txt_embed_bwd_rows(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
+                                         const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                                         const float* gamma, const float* delta, float* d_rows, int B, int T, int S, int H,
+                                         int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed,
+                                         uint32_t offset, void* stream) {
+  UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && d_rows, "txt_embed_bwd_rows: null pointer");
+  UCHECK_ARG((((uintptr_t)delta | (uintptr_t)d_rows) & 15) == 0, "txt_embed_bwd_rows: delta and d_rows must be 16-byte aligned");
+  UCHECK_SHAPE(H > 0 && H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_bwd_rows: bad shape (H %% 4, H <= 1024, T <= S)");
+  if (B * T <= 0) return 0;
+  RowsArgs a = {};
+  a.dcat = dcat; a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos; a.type = type;
+  a.gamma = gamma; a.delta = delta; a.d_rows = d_rows; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
+  a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
+  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
+  hipStream_t st = (hipStream_t)stream;
+  IG_NV_DISPATCH(txt_embed_bwd_rows_kernel, dim3((B * T + 3) / 4), a);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, int rows, int H, void* stream) {
+  UCHECK_ARG(d_posfc && Wp && d_pos7, "pos_feat_dgrad: null pointer");
+  UCHECK_ARG((((uintptr_t)d_posfc | (uintptr_t)Wp) & 15) == 0, "pos_feat_dgrad: d_posfc and Wp must be 16-byte aligned");
+  UCHECK_SHAPE(H > 0 && H % 4 == 0 && H <= 1024, "pos_feat_dgrad: bad shape (H %% 4, H <= 1024)");
+  if (rows <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  IG_NV_DISPATCH(pos_feat_dgrad_kernel, dim3((rows + 3) / 4), d_posfc, Wp, d_pos7, rows, H);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t uniter_adv_delta_ws_bytes(int B, int n) {
+  if (B <= 0 || n <= 0) return 0;
+  return (size_t)B * adv_parts(n) * 3 * sizeof(double);
+}
+
+extern "C" int uniter_adv_delta_step(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
+                                     void* stream) {
+  UCHECK_ARG(delta && grad && ws, "adv_delta_step: null pointer");
+  UCHECK_ARG((((uintptr_t)delta | (uintptr_t)grad) & 15) == 0 && ((uintptr_t)ws & 7) == 0,
+             "adv_delta_step: delta and grad must be 16-byte aligned, the workspace 8-byte");
+  UCHECK_ARG(step_size == step_size && max_norm == max_norm, "adv_delta_step: step_size / max_norm is NaN");
+  UCHECK_SHAPE(B >= 0 && n >= 0 && n % 4 == 0, "adv_delta_step: n must be a multiple of 4 (got %d)", n);
+  UCHECK_SHAPE(B <= 65535, "adv_delta_step: at most 65535 samples (got %d)", B);
+  if (B == 0 || n == 0) return 0;
+  const dim3 grid(adv_parts(n), B);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adv_partials_kernel, grid, dim3(256), 0, st, delta, grad, (double*)ws, n / 4);
+  UCHECK_LAUNCH();
+  hipLaunchKernelGGL(adv_update_kernel, grid, dim3(256), 0, st, delta, grad, (const double*)ws, n / 4, step_size, max_norm);
+  UCHECK_LAUNCH();
+  return 0;
+}

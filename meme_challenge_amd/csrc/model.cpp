@@ -166,6 +166,10 @@ struct uniter_model {
   double* norm_parts = nullptr;   // uniter_model_set_norm_partials: layer l's clip-norm partial sums at norm_parts + l * norm_stride
   size_t norm_stride = 0;
   bool wg_overwrite = false; // the next backward pass overwrites the encoder's weight gradients (uniter_model_set_wgrad_overwrite)
+  // uniter_model_set_input_grads: the perturbation the next forward pass reads and the input gradients its backward pass writes
+  struct InputGrads { const float* txt_delta = nullptr; float* d_txt_rows = nullptr; float* d_img_feat = nullptr; float* d_img_pos_feat = nullptr;
+                      bool outputs() const { return d_txt_rows || d_img_feat || d_img_pos_feat; } };
+  InputGrads ig_next, ig;    // as set / as the latest forward pass took it over (its backward pass reads ig)
   uint64_t generation = 0;   // bumped by every forward: a backward must belong to the LATEST forward (one plan / workspace per model)
 
   float* P(int i) const { return p[i]; }
@@ -736,6 +740,18 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     UCHECK_SHAPE(b->L <= uniter_attn_varlen_max_len(), "model_forward: packed mode supports L <= %d (got %d)",
                  uniter_attn_varlen_max_len(), b->L);
   }
+  const uniter_model::InputGrads ig = m->ig_next;      // uniter_model_set_input_grads: this pass's, whatever becomes of it
+  m->ig_next = m->ig = uniter_model::InputGrads();
+  if (ig.txt_delta || ig.outputs()) {
+    UCHECK_ARG(has_txt || !(ig.txt_delta || ig.d_txt_rows), "model_forward: txt_delta / d_txt_rows set (uniter_model_set_input_grads) on a batch without text");
+    UCHECK_ARG(has_img || !(ig.d_img_feat || ig.d_img_pos_feat), "model_forward: d_img_feat / d_img_pos_feat set (uniter_model_set_input_grads) on a batch without regions");
+    UCHECK_ARG(train != 0 || !ig.outputs(), "model_forward: input gradients set (uniter_model_set_input_grads) for an inference forward (train = 0)");
+    UCHECK_ARG((((uintptr_t)ig.txt_delta | (uintptr_t)ig.d_txt_rows | (uintptr_t)ig.d_img_feat) & 15) == 0,
+               "model_forward: txt_delta, d_txt_rows and d_img_feat must be 16-byte aligned");
+    UCHECK_SHAPE(!(ig.txt_delta || ig.d_txt_rows || ig.d_img_pos_feat) || (c.hidden_size % 4 == 0 && c.hidden_size <= 1024),
+                 "model_forward: input gradients need hidden_size %% 4 == 0 and <= 1024 (got %d)", c.hidden_size);
+    m->ig = ig;
+  }
   make_plan(m, pl, ws, b->B, b->T, b->R, b->L, has_txt, has_img, b->img_masks != nullptr, train,
             packed ? b->Mp : -1);
   if (pl.total > ws_bytes) {
@@ -839,11 +855,18 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   }
   if (has_txt) {
     if (word_split) UCHECK_HIP(hipStreamWaitEvent(st, m->ready[nl + 1], 0));
+    if (m->ig.txt_delta)
+      UCHECK_RC(uniter_txt_embed_fwd_delta(b->input_ids, b->position_ids, b->txt_type_ids, m->P(P_WORD), m->P(P_POS),
+                                           m->P(P_TYPE), m->P(P_ELN_G), m->P(P_ELN_B), m->ig.txt_delta, pl.cat, B, T, S, H,
+                                           c.vocab_size, c.max_position_embeddings, c.type_vocab_size, b->pos_bcast,
+                                           ph, seed, offset, st));
+    else
     UCHECK_RC(uniter_txt_embed_fwd(b->input_ids, b->position_ids, b->txt_type_ids, m->P(P_WORD), m->P(P_POS),
                                    m->P(P_TYPE), m->P(P_ELN_G), m->P(P_ELN_B), pl.cat, B, T, S, H,
                                    c.vocab_size, c.max_position_embeddings, c.type_vocab_size, b->pos_bcast,
                                    ph, seed, offset, st));
   }
+  if (!save) m->ig = uniter_model::InputGrads();      // an inference forward: no backward pass follows
   const bool joint = has_txt && has_img;
   // (round 6) the joint rows and their operand copy for layer 0's first product in ONE launch: this chain -- text embeddings, gather,
   // split -- is what the first encoder product waits for behind the optimizer's update of the word table
@@ -1192,11 +1215,16 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
     UCHECK_HIP(hipStreamWaitEvent(ax, m->ev_emb0, 0));
   }
   if (pl.has_txt)
-    UCHECK_RC((pl.det ? uniter_txt_embed_bwd_det : uniter_txt_embed_bwd)(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD),
-                                   m->P(P_POS), m->P(P_TYPE), m->P(P_ELN_G), m->G(P_WORD), m->G(P_POS),
+    // (m->ig.txt_delta: the forward pass's perturbation of the word rows, NULL = none -- then the public entry points' launches)
+    UCHECK_RC((pl.det ? txt_embed_bwd_det_run : txt_embed_bwd_run)(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD),
+                                   m->P(P_POS), m->P(P_TYPE), m->P(P_ELN_G), m->ig.txt_delta, m->G(P_WORD), m->G(P_POS),
                                    m->G(P_TYPE), m->G(P_ELN_G), m->G(P_ELN_B), B, T, S, H, c.vocab_size,
                                    c.max_position_embeddings, c.type_vocab_size, b.pos_bcast, ph, m->seed,
                                    m->offset, ax ? pl.emb_ws2 : pl.emb_ws, pl.emb_ws_bytes, ax ? ax : st));
+  if (pl.has_txt && m->ig.d_txt_rows)      // the per-token gradient: its own launch behind the text branch, on that branch's stream
+    UCHECK_RC(uniter_txt_embed_bwd_rows(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD), m->P(P_POS), m->P(P_TYPE),
+                                        m->P(P_ELN_G), m->ig.txt_delta, m->ig.d_txt_rows, B, T, S, H, c.vocab_size,
+                                        c.max_position_embeddings, c.type_vocab_size, b.pos_bcast, ph, m->seed, m->offset, ax ? ax : st));
   if (pl.has_img) {
     UCHECK_RC((pl.det ? uniter_img_embed_bwd_det : uniter_img_embed_bwd)(pl.dcat, pl.imgfc, b.img_pos_feat, b.img_type_ids, m->P(P_POSL_W),
                                    m->P(P_POSL_B), m->P(P_TYPE), m->P(P_ILN_G), m->P(P_ILN_B), m->P(P_PLN_G),
@@ -1214,12 +1242,15 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
     UCHECK_RC(gemm(m, UNITER_K_GEMM_WGRAD, st, 1, 1, H, c.img_dim, B * R, pl.d_imgfc, H, feat, c.img_dim,
                    m->G(P_IMG_W), c.img_dim, UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 1));
     if (!ax) UCHECK_RC(uniter_colsum_f32(pl.d_imgfc, B * R, H, H, m->G(P_IMG_B), 1, pl.emb_ws, pl.emb_ws_bytes, st));
-    if (b.img_masks) {
-      // d(img_feat + mask_emb[img_masks]) = d_imgfc @ W_img; row 1 of mask_embedding sums the masked rows
+    if (b.img_masks || m->ig.d_img_feat) {
+      // d(img_feat + mask_emb[img_masks]) = d_imgfc @ W_img; row 1 of mask_embedding sums the masked rows.  The same product is the
+      // gradient of img_feat: formed once, in the caller's buffer when it asked for it (uniter_model_set_input_grads)
+      float* d_feat = m->ig.d_img_feat ? m->ig.d_img_feat : pl.d_feat;
       UCHECK_RC(gemm(m, UNITER_K_GEMM_DGRAD, st, 0, 1, B * R, c.img_dim, H, pl.d_imgfc, H, m->P(P_IMG_W),
-                     c.img_dim, pl.d_feat, c.img_dim, UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 0));
-      UCHECK_RC(launch_masked_rowsum(pl.d_feat, b.img_masks, m->G(P_MASK_EMB) + c.img_dim, B * R, c.img_dim, st));
+                     c.img_dim, d_feat, c.img_dim, UNITER_EPI_NONE, nullptr, nullptr, nullptr, 0, 0));
+      if (b.img_masks) UCHECK_RC(launch_masked_rowsum(d_feat, b.img_masks, m->G(P_MASK_EMB) + c.img_dim, B * R, c.img_dim, st));
     }
+    if (m->ig.d_img_pos_feat) UCHECK_RC(uniter_pos_feat_dgrad(pl.d_posfc, m->P(P_POSL_W), m->ig.d_img_pos_feat, B * R, H, st));
   }
   if (ax) {           // join the auxiliary stream's branch
     UCHECK_HIP(hipEventRecord(m->ev_emb2, ax));
@@ -1241,6 +1272,7 @@ extern "C" int uniter_model_backward_end(uniter_model_t* m) {
   }
   m->bwd_open = false;
   m->wg_overwrite = false;       // one backward pass: the next one accumulates again
+  m->ig = uniter_model::InputGrads();      // ... and the input gradients were this pass's (uniter_model_set_input_grads)
   return 0;
 }
 
@@ -1280,6 +1312,14 @@ extern "C" int uniter_model_set_norm_partials(uniter_model_t* m, double* parts, 
   UCHECK_ARG(m && (parts == nullptr || stride_doubles > 0), "set_norm_partials: bad argument");
   m->norm_parts = parts;
   m->norm_stride = parts ? stride_doubles : 0;
+  return 0;
+}
+
+extern "C" int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_delta, float* d_txt_rows, float* d_img_feat,
+                                            float* d_img_pos_feat) {
+  UCHECK_ARG(m, "set_input_grads: null model");
+  m->ig_next.txt_delta = txt_delta; m->ig_next.d_txt_rows = d_txt_rows; m->ig_next.d_img_feat = d_img_feat;
+  m->ig_next.d_img_pos_feat = d_img_pos_feat;
   return 0;
 }
 

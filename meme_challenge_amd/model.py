@@ -664,7 +664,9 @@ class HipLinear(nn.Module):
 # --------------------------------------------------------------------------- #
 class _UniterFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, model, batch, keep, all_layers, mode, seed, offset):
+    def forward(ctx, anchor, img_feat, img_pos_feat, txt_delta, model, batch, keep, all_layers, mode, seed, offset):
+        # img_feat / img_pos_feat / txt_delta: the prepared tensors batch's pointers name, here as inputs of the node so that
+        # autograd asks for their gradients (ctx.needs_input_grad) -- the library writes them in the backward pass
         lib = _lib.lib()
         cfg = model.config
         B, L = batch.B, batch.L
@@ -690,6 +692,15 @@ class _UniterFn(torch.autograd.Function):
             check(lib.uniter_model_set_aux_stream(model._handle, C.c_void_p(aux.cuda_stream)), 'uniter_model_set_aux_stream')
         else:
             check(lib.uniter_model_set_aux_stream(model._handle, None), 'uniter_model_set_aux_stream')
+        need = ctx.needs_input_grad
+        outs = [torch.empty_like(t) if (mode != 0 and t is not None and need[i]) else None
+                for i, t in ((1, img_feat), (2, img_pos_feat), (3, txt_delta))]
+        ctx.input_grads = outs if any(o is not None for o in outs) else None
+        ctx.txt_delta = txt_delta
+        if txt_delta is not None or ctx.input_grads is not None:
+            # a setting for THIS forward pass and its backward pass (the handle forgets it afterwards)
+            check(lib.uniter_model_set_input_grads(model._handle, ptr(txt_delta), ptr(outs[2]), ptr(outs[0]), ptr(outs[1])),
+                  'uniter_model_set_input_grads')
         check(lib.uniter_model_forward(model._handle, C.byref(batch), ptr(hidden), int(all_layers),
                                        mode, seed, offset, ptr(ws), nbytes, _lib.cur_stream()),
               'uniter_model_forward')
@@ -706,10 +717,12 @@ class _UniterFn(torch.autograd.Function):
                                  'keeps the activations of ONE forward per model: run backward before ANY further forward of '
                                  'this model (forwards under torch.no_grad() reuse the same plan and count as well)')
         d_hidden = d_hidden.contiguous()
+        outs = ctx.input_grads
         model._run_backward(ctx.batch, d_hidden, ctx.all_layers, ctx.seed, ctx.offset, ctx.ws,
-                            ctx.nbytes)
+                            ctx.nbytes, full=outs is not None)
         ctx.ws = None
-        return (None,) * 8
+        ctx.input_grads = ctx.txt_delta = None
+        return (None,) + (tuple(outs) if outs is not None else (None,) * 3) + (None,) * 7
 
 
 class UniterPreTrainedModel(nn.Module):
@@ -942,14 +955,14 @@ class UniterModel(UniterPreTrainedModel):
             self._ws_cache[0] = ws
         return ws
 
-    def _touched_names(self, batch):
+    def _touched_names(self, batch, floor=None):
         """Parameter names (in the root's namespace) that receive a gradient."""
         root = self._root()
         if self._prefix_names is None:
             ids = {id(p): n for n, p in root.named_parameters()}
             self._prefix_names = {n: ids[id(p)] for n, p in self.named_parameters()}
             self._touch_lists = {}
-        floor = self.backward_floor()
+        floor = self.backward_floor() if floor is None else floor
         key = (bool(batch.input_ids), bool(batch.img_feat), bool(batch.img_masks), floor)
         if key in self._touch_lists:
             return self._touch_lists[key]
@@ -971,7 +984,7 @@ class UniterModel(UniterPreTrainedModel):
         self._touch_lists[key] = out
         return out
 
-    def _run_backward(self, batch, d_hidden, all_layers, seed, offset, ws, nbytes):
+    def _run_backward(self, batch, d_hidden, all_layers, seed, offset, ws, nbytes, full=False):
         lib = _lib.lib()
         nl = self.config.num_hidden_layers
         st = _find_store(self._root())
@@ -1002,7 +1015,8 @@ class UniterModel(UniterPreTrainedModel):
             hook('begin', None, side or main)
         # a frozen prefix (freeze_prefix): nothing below layer `floor` holds a trainable parameter, so the pass ends above it --
         # no backward of those layers, none of the embeddings -- and the hooks see the layers that ran
-        floor = self.backward_floor()
+        # (`full`: an input's gradient is wanted -- the pass goes down to the embeddings whatever is frozen)
+        floor = 0 if full else self.backward_floor()
         for l in range(nl - 1, floor - 1, -1):
             check(lib.uniter_model_backward_layer(self._handle, l), 'uniter_model_backward_layer')
             if hook is not None:
@@ -1012,7 +1026,7 @@ class UniterModel(UniterPreTrainedModel):
             st.touch(self._touched_names(batch))
             return
         check(lib.uniter_model_backward_embed(self._handle), 'uniter_model_backward_embed')
-        st.touch(self._touched_names(batch))
+        st.touch(self._touched_names(batch, floor))
         if hook is not None:
             hook('embed', None, main)
 
@@ -1105,9 +1119,15 @@ class UniterModel(UniterPreTrainedModel):
     # -- the reference's public surface ---------------------------------------
     def forward(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask,
                 gather_index=None, img_masks=None, output_all_encoded_layers=True,
-                txt_type_ids=None, img_type_ids=None, seq_lens=None):
+                txt_type_ids=None, img_type_ids=None, seq_lens=None, txt_embed_delta=None):
         """Same signature / return as model/model.py:336-367: list of per-layer
         hidden states, or the last layer's [B, L, H] tensor.
+
+        ``txt_embed_delta`` (extension, [B, T, H] float32 on the model's device) is added to the word-embedding rows before
+        the text LayerNorm.  ``img_feat``, ``img_pos_feat`` and ``txt_embed_delta`` are differentiable inputs: with
+        ``requires_grad`` set their ``.grad`` is filled by ``backward()`` (the gradient of ``txt_embed_delta`` is the per-token
+        gradient of the word rows) -- also when every parameter is frozen.  Asking for one runs the full backward pass
+        (``backward_floor()`` does not apply) and changes no parameter gradient.
 
         ``seq_lens`` (extension, host list of tl+nbb per sample) is read (and required) only when
         ``self.pack_padded`` is set: the packed layout's row count sizes the workspace on the host."""
@@ -1140,6 +1160,10 @@ class UniterModel(UniterPreTrainedModel):
         img_masks = prep(img_masks, torch.int64, 'img_masks')
         attention_mask = prep(attention_mask, torch.float32, 'attention_mask')
         gather_index = prep(gather_index, torch.int64, 'gather_index')
+        txt_embed_delta = prep(txt_embed_delta, torch.float32, 'txt_embed_delta')
+        if txt_embed_delta is not None and input_ids is not None and tuple(txt_embed_delta.shape) != (
+                input_ids.shape[0], input_ids.shape[1], self.config.hidden_size):
+            raise ValueError('txt_embed_delta must be [B, T, hidden_size]')
         if input_ids is not None and img_feat is not None and gather_index is None:
             raise ValueError('joint text+image input needs gather_index (model/model.py:327-333)')
 
@@ -1175,16 +1199,19 @@ class UniterModel(UniterPreTrainedModel):
             self._pack(b, keep, attention_mask, gather_index, seq_lens)
 
         trainable = next((p for p in self.parameters() if p.requires_grad), None)
-        grad = torch.is_grad_enabled() and trainable is not None
+        # (prep's dtype / layout copies were made with autograd on: the prepared tensors are still linked to the caller's leaves)
+        wanted = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (img_feat, img_pos_feat, txt_embed_delta))
+        grad = torch.is_grad_enabled() and (trainable is not None or wanted)
         mode = 0 if not grad else (1 if self.training else 2)
         seed, offset = self._seed, self._offset
         if mode == 1:
             self._offset = (self._offset + 1) & 0xFFFFFFFF
         anchor = self.embeddings.LayerNorm.weight
-        if grad and not anchor.requires_grad:      # (frozen embeddings: any trainable parameter makes autograd call the backward pass)
+        if grad and not anchor.requires_grad and trainable is not None:      # (frozen embeddings: any trainable parameter makes autograd call the backward pass)
             anchor = trainable
-        anchor = anchor if grad else anchor.detach()
-        hidden = _UniterFn.apply(anchor, self, b, keep, bool(output_all_encoded_layers), mode, seed, offset)
+        anchor = anchor if grad else anchor.detach()      # (a fully frozen model: an input that requires a gradient is what calls it)
+        hidden = _UniterFn.apply(anchor, img_feat, img_pos_feat, txt_embed_delta, self, b, keep, bool(output_all_encoded_layers), mode,
+                                 seed, offset)
         if output_all_encoded_layers:
             return [hidden[i] for i in range(self.config.num_hidden_layers)]
         return hidden

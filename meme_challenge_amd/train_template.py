@@ -39,7 +39,7 @@ import torch.distributed as dist
 
 from . import dp
 from .metrics import standard_metrics, find_optimal_threshold
-from .trainer import bce_with_logits_loss, get_optimizer, get_scheduler, sync_step
+from .trainer import TrainStep, adv_config, bce_with_logits_loss, get_optimizer, get_scheduler, sync_step
 from .utils import set_seed
 
 LOGGER = logging.getLogger('TrainerLogger')
@@ -206,6 +206,8 @@ class TrainerTemplate(object):
         loss_func = self.config['loss_func']
         if loss_func not in ('bce_logits', 'bce', 'ce'):
             raise ValueError('invalid loss_func %r' % loss_func)
+        adv_config(self.config)          # --adv_*: an unknown adv_modality fails here, before anything is built
+        self._adv_step = None
         self.init_model()
         self.model.to(self.device)
         self.model_saver = ModelSaver(self.model_file)
@@ -264,6 +266,16 @@ class TrainerTemplate(object):
                 sync_step(self.optimizer, self.grad_sync, accum, self.config['max_grad_norm'])
                 self.scheduler.step()
         self.log.add(probs, batch_label, loss, ids=self._ids)
+
+    def adversarial_train_iter(self, batch):
+        """--adv_steps K > 0: one FreeLB micro-batch in place of forward + calculate_loss (trainer.TrainStep runs the K passes and
+        takes the step when the accumulation modulo says so); the epoch log gets the first, least perturbed pass."""
+        if self._adv_step is None:
+            self._adv_step = TrainStep(self.model, self.optimizer, self.scheduler, self.config, grad_sync=self.grad_sync)
+        self._adv_step.optimizer, self._adv_step.scheduler = self.optimizer, self.scheduler
+        loss = self._adv_step.train_iter(batch, iters=self.iters)
+        self.log.add(self._adv_step.last_probs, batch['labels'], loss, ids=self._ids)
+        return loss
 
     # --------------------------------------------------------------------- eval
     def _pass(self, loader, step):
@@ -517,6 +529,10 @@ class TrainerTemplate(object):
              ('lr_decay_factor', float, 0.8), ('patience', float, 5), ('early_stop_thresh', float, 1e-3),
              ('seed', int, 42), ('log_every', int, 2000), ('parallel_computing', bool, False),
              ('deterministic', None, False),      # additive: bit-reproducible steps (UniterModel.deterministic)
+             # additive: FreeLB adversarial fine-tuning (trainer.adv_config): K passes per batch with a perturbation of the word
+             # embeddings and / or the region features (0 = off), ascent step size, radius of the L2 ball, magnitude of the random start
+             ('adv_steps', int, 0), ('adv_lr', float, 1e-1), ('adv_max_norm', float, 1.0), ('adv_init_mag', float, 0.0),
+             ('adv_modality', str, 'both'),
              # additive: evaluate and checkpoint an exponential moving average of the weights, kept by the fused step (0 = off);
              # add optimizer_state_dict to the checkpoint (utils/save.py:60-61)
              ('ema_decay', float, 0.0), ('save_optimizer_state', None, False))

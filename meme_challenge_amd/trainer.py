@@ -1121,9 +1121,49 @@ def sync_step(optimizer, grad_sync, accum, max_grad_norm):
 
 
 
+ADV_MODALITIES = ('both', 'txt', 'img')
+AdvConfig = namedtuple('AdvConfig', 'steps lr max_norm init_mag modality')
+
+
+def adv_config(config):
+    """The FreeLB settings of a trainer config (adv_steps = 0, the default, switches the adversarial step off):
+    adv_steps K, adv_lr (ascent step size), adv_max_norm (radius of the L2 ball, <= 0: none), adv_init_mag (magnitude of the
+    random start, 0: start from zero), adv_modality ('both' | 'txt' | 'img': which inputs are perturbed)."""
+    adv = AdvConfig(int(config.get('adv_steps', 0) or 0), float(config.get('adv_lr', 0.0) or 0.0),
+                    float(config.get('adv_max_norm', 0.0) or 0.0), float(config.get('adv_init_mag', 0.0) or 0.0),
+                    config.get('adv_modality', 'both') or 'both')
+    if adv.modality not in ADV_MODALITIES:
+        raise ValueError("adv_modality must be one of %s, got %r" % (', '.join(repr(m) for m in ADV_MODALITIES), adv.modality))
+    if adv.steps < 0 or adv.lr < 0 or adv.init_mag < 0:
+        raise ValueError('adv_steps, adv_lr and adv_init_mag must not be negative')
+    return adv
+
+
+def adv_delta_step(delta, grad, step_size, max_norm):
+    """delta[b] <- project(delta[b] + step_size * grad[b] / |grad[b]|) onto the L2 ball of radius max_norm, per sample of the
+    leading dimension, in place (uniter_adv_delta_step; step_size = 0 projects only)."""
+    _lib.require_gpu_tensor(delta, torch.float32, 'delta')
+    _lib.require_gpu_tensor(grad, torch.float32, 'grad')
+    if delta.shape != grad.shape or not delta.is_contiguous() or not grad.is_contiguous():
+        raise UniterHipError('adv_delta_step: delta and grad must be contiguous and of one shape')
+    B = delta.shape[0]
+    n = delta.numel() // max(B, 1)
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.uniter_adv_delta_ws_bytes(B, n), 8), dtype=torch.uint8, device=delta.device)
+    check(lib.uniter_adv_delta_step(ptr(delta), ptr(grad), B, n, float(step_size), float(max_norm), ptr(ws), _lib.cur_stream()),
+          'uniter_adv_delta_step')
+    return delta
+
+
 class TrainStep(object):
     """`TrainerTemplate.calculate_loss` (train_template.py:95-126) + the forward of
     `TrainerUniter.train_iter_step` (train_uniter.py:67-72).
+
+    With ``adv_steps`` = K > 0 in the config a micro-batch is a FreeLB step (`adv_config`): K forward / backward passes on
+    the batch with a perturbation on the word-embedding rows and / or the region features, the perturbation taking one
+    normalised ascent step (projected onto the ball of radius ``adv_max_norm``) between two passes.  The parameter gradients
+    of the K passes accumulate as micro-batches do and the optimizer step divides by K on top of ``gradient_accumulation``.
+    The logged loss and probabilities are the first (least perturbed) pass's.
 
     Quirk kept on purpose: the modulo test is on the per-epoch iteration index
     starting at 0, so iteration 0 steps immediately with a single micro-batch whose
@@ -1143,6 +1183,70 @@ class TrainStep(object):
         self.iters = 0
         self.last_loss = None
         self.last_probs = None
+        self.adv = adv_config(config)
+        if self.adv.steps > 0 and grad_sync is not None:
+            # (the exchange's prepare(will_step=...) would have to be held back to the last of the K passes: not built, because it
+            # could not be checked without a multi-rank run)
+            raise UniterHipError('adv_steps > 0 (FreeLB) is built for the single-process step: not with a data-parallel gradient exchange')
+        self._adv_gen = None
+        self.last_adv_delta = None      # (delta_txt, delta_img) after the last FreeLB micro-batch's final ascent step
+
+    def _adv_start(self, batch, shape):
+        """delta_0 of one perturbation: uniform in [-1, 1] * adv_init_mag / sqrt(n) per sample (n = its elements per sample)
+        from a device generator seeded with the config's seed, projected onto the ball; zeros for adv_init_mag = 0"""
+        dev = batch['labels'].device
+        if self.adv.init_mag <= 0:
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+        if self._adv_gen is None or self._adv_gen.device != dev:
+            self._adv_gen = torch.Generator(device=dev)
+            self._adv_gen.manual_seed(int(self.config.get('seed', 0) or 0) + 0x5EED)
+        n = 1
+        for d in shape[1:]:
+            n *= int(d)
+        delta = (torch.rand(shape, generator=self._adv_gen, dtype=torch.float32, device=dev) * 2 - 1) * (self.adv.init_mag / n ** 0.5)
+        if self.adv.max_norm > 0:
+            adv_delta_step(delta, delta, 0.0, self.adv.max_norm)
+        return delta
+
+    def _train_iter_adv(self, batch, stepping, delta0=None):
+        """The K passes of a FreeLB micro-batch (class docstring).  delta0: {'txt': [B, T, H], 'img': [B, R, D]} to start from
+        (either may be missing) instead of the seeded random start."""
+        cfg, adv = self.config, self.adv
+        K = adv.steps
+        delta0 = delta0 or {}
+        d_txt = d_img = None
+        if adv.modality in ('both', 'txt') and batch.get('input_ids') is not None:
+            H = self.model.uniter_model.config.hidden_size
+            shape = tuple(batch['input_ids'].shape) + (H,)
+            d_txt = delta0['txt'].detach().clone().float().contiguous() if delta0.get('txt') is not None else self._adv_start(batch, shape)
+        if adv.modality in ('both', 'img') and batch.get('img_feat') is not None:
+            d_img = delta0['img'].detach().clone().float().contiguous() if delta0.get('img') is not None else \
+                self._adv_start(batch, tuple(batch['img_feat'].shape))
+        first = None
+        for k in range(K):
+            ascend = k < K - 1              # the last pass needs no gradient of the perturbation
+            kw = self.forward_kwargs(batch)
+            leaves = []
+            for key, d in (('txt_embed_delta', d_txt), ('img_feat', d_img)):
+                if d is None:
+                    continue
+                leaf = d.detach().requires_grad_(ascend)        # (shares d's memory)
+                leaves.append((d, leaf))
+                kw[key] = leaf if key == 'txt_embed_delta' else batch['img_feat'] + leaf
+            preds = self.model(**kw)
+            loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'], return_probs=True)
+            loss.backward(unit_gradient(loss.device))
+            if first is None:
+                first = (loss.detach(), probs)
+            if ascend:
+                for d, leaf in leaves:
+                    adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm)
+        self.last_adv_delta = (d_txt, d_img)
+        if stepping:
+            # the K passes' gradients were accumulated like K micro-batches: the step's grad_scale carries the extra 1 / K
+            sync_step(self.optimizer, None, cfg['gradient_accumulation'] * K, cfg['max_grad_norm'])
+            self.scheduler.step()
+        return first
 
     @staticmethod
     def forward_kwargs(batch):
@@ -1151,7 +1255,7 @@ class TrainStep(object):
                     attention_mask=batch['attn_mask'], gather_index=batch['gather_index'],
                     output_all_encoded_layers=False, seq_lens=batch.get('seq_lens'))
 
-    def train_iter(self, batch, iters=None):
+    def train_iter(self, batch, iters=None, adv_delta0=None):
         if iters is not None:
             self.iters = iters
         cfg = self.config
@@ -1164,6 +1268,10 @@ class TrainStep(object):
             opt.note_tokens(batch.get('input_ids'))
             if stepping:
                 opt.early_word_update()
+        if self.adv.steps > 0:
+            self.last_loss, self.last_probs = self._train_iter_adv(batch, stepping, adv_delta0)
+            self.iters += 1
+            return self.last_loss
         preds = self.model(**self.forward_kwargs(batch))
         loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'],
                                            return_probs=True)

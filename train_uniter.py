@@ -10,7 +10,9 @@ libuniter_hip.so.
 
 Additive flags (not in the reference): --synthetic N (write a synthetic dataset in the reference's
 on-disk format under --data_path and train on it), --hash_tokenizer (offline tokenizer), --deterministic (every sum of the
-step in a fixed order: same seed, same bits in every parameter; UniterModel.deterministic).
+step in a fixed order: same seed, same bits in every parameter; UniterModel.deterministic), --adv_steps K with --adv_lr / --adv_max_norm /
+--adv_init_mag / --adv_modality (FreeLB adversarial fine-tuning: K passes per batch with a perturbation of the word embeddings and the
+region features; trainer.TrainStep).
 """
 import argparse
 import json
@@ -94,6 +96,9 @@ class TrainerUniter(TrainerTemplate):
         self.calculate_loss(self._forward(batch), batch['labels'], grad_step=False)
 
     def train_iter_step(self):
+        if int(self.config.get('adv_steps', 0) or 0) > 0:      # --adv_steps: a FreeLB micro-batch (TrainerTemplate.adversarial_train_iter)
+            self.adversarial_train_iter(self.batch)
+            return
         self.preds = self._forward(self.batch)
         self.calculate_loss(self.preds, self.batch['labels'], grad_step=True)
         if self.config.get('deterministic') and not getattr(self, '_det_reported', False):
