@@ -465,6 +465,22 @@ int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const float* attn_mas
                          const float* ctx, const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16,
                          float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh, float p_drop,
                          uint64_t seed, uint32_t offset, uint32_t site, void* ws, size_t ws_bytes, void* stream);
+/* The attention probabilities as an OUTPUT (csrc/attn_probs.hip; softmax(QK^T / 8 + mask) of BertSelfAttention.forward,
+ * model/layer.py:85-95, BEFORE its dropout): the attention kernels above keep them in registers, this call recomputes them from the
+ * operands those kernels read.  qkv [rows, 3 nh 64], columns Q | K | V head-major, fp32 or (qkv_is_bf16 = 1) bf16, 16-byte aligned;
+ * exactly one of attn_mask [B, L] (padded form, rows = B L; every query row is an ordinary query) and cu_seqlens [B + 1] (packed
+ * form, L >= the longest sample; rows and columns at or beyond a sample's length are written as 0):
+ *   p_ij = exp(s_ij - lse_i),  s_ij = q_i . k_j / 8 + (1 - mask_j) * -10000,  lse_i = log sum_j exp(s_ij)
+ * in fp32, a function of qkv and the mask alone (no dropout, the forward pass's lse is not an input).  head_mean = 0: probs
+ * [B, nh, L, L]; head_mean = 1: probs [B, L, L], the mean over heads, the heads added in ascending order by one workgroup (nh <= 64).
+ * No atomics, every element written once: two runs give the same bits.  Any L >= 1; B, L or nh < 1: UNITER_E_SHAPE. */
+int uniter_attn_probs(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, float* probs,
+                      int B, int L, int nh, int head_mean, void* stream);
+/* Attention rollout (Abnar & Zuidema 2020) of nl layers' head-mean maps attn [nl, B, L, L], per sample in fp32:
+ *   A~_l = residual I + (1 - residual) A_l,   R_0 = A~_0,   R_l = A~_l R_{l-1},   rollout [B, L, L] = R_{nl-1}
+ * No renormalisation (the rows of A_l sum to 1 already).  residual in [0, 1].  tmp [B, L, L]: the caller's ping-pong space (may be
+ * NULL when nl == 1).  One launch per layer, every sum in ascending order.  attn, rollout and tmp must not overlap (UNITER_E_ARG). */
+int uniter_attn_rollout(const float* attn, float* rollout, float* tmp, int nl, int B, int L, float residual, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Embeddings (replace UniterTextEmbeddings.forward model/model.py:232-245,
@@ -957,6 +973,13 @@ int uniter_model_set_norm_partials(uniter_model_t* m, double* parts, size_t stri
  * A backward pass that stops above a frozen prefix (uniter_model_backward_end in place of _embed) writes nothing. */
 int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_delta, float* d_txt_rows, float* d_img_feat,
                                  float* d_img_pos_feat);
+/* Every layer's attention probabilities out of the NEXT forward pass, a setting on the handle like the one above: directly behind
+ * layer l's attention launch, on the same stream, the pass calls uniter_attn_probs on that layer's query|key|value buffer (bf16
+ * exactly when the bf16 attention kernels ran; cu_seqlens for a packed batch) with probs = out + l * layer_stride_elems:
+ * [B, L, L] per layer with head_mean = 1, [B, nh, L, L] with 0, L the batch's.  The values before dropout, whatever `train` is.
+ * The handle forgets the setting when that uniter_model_forward returns, with or without an error.  out = NULL, or never called:
+ * exactly the launches without it. */
+int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t layer_stride_elems, int head_mean);
 /* A stream for launches of the forward pass that depend on nothing the step computes -- the dropout keep flags of the attention
  * probabilities (a function of seed and offset alone: 60 us of Philox rounds for twelve layers) -- so that they run BESIDE the head
  * of the forward pass instead of in front of it; the first attention kernel waits for them.  NULL (default): on `stream`. */

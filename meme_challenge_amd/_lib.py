@@ -157,6 +157,10 @@ _SIGS = {
     'uniter_adv_delta_step': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
     'uniter_adv_delta_ws_bytes': (_SZ, [_I, _I]),
     'uniter_model_set_input_grads': (_I, [_P, _P, _P, _P, _P]),
+    # the attention probabilities as an output, and rollout on them (csrc/attn_probs.hip)
+    'uniter_attn_probs': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'uniter_attn_rollout': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
+    'uniter_model_set_attn_probs': (_I, [_P, _P, _SZ, _I]),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'uniter_pooler_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_linear_small_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

@@ -3,15 +3,34 @@
 The reference inspects its mistakes by listing them (utils/misclassification.py); the step from a wrong prediction to the
 regions and words behind it needs the gradient of the logit with respect to the image-region features and the word
 embeddings, which `UniterModel.forward` exposes (csrc/input_grads.hip: `img_feat.grad`, and the gradient of a zero
-`txt_embed_delta`, which is the per-token gradient of the word rows)."""
+`txt_embed_delta`, which is the per-token gradient of the word rows).
+
+And what does the encoder's attention look like?  `UniterModel.output_attentions` makes a forward pass leave every layer's
+probabilities softmax(QK^T / 8 + mask) (model/layer.py:85-95, before the dropout; csrc/attn_probs.hip) in `last_attentions`:
+`attention_maps` returns them for a batch, `attention_rollout` multiplies the head-mean maps through the layers (Abnar & Zuidema 2020,
+uniter_attn_rollout) and reads off what reaches [CLS], and `split_joint` maps scores over the joint sequence back to tokens and
+regions."""
 from collections import namedtuple
 
 import torch
 
 Saliency = namedtuple('Saliency', 'region_norm region_gxi token_norm token_gxi img_feat_grad img_pos_feat_grad txt_grad logits')
+AttentionMaps = namedtuple('AttentionMaps', 'probs logits')
+Rollout = namedtuple('Rollout', 'joint cls_token cls_region logits')
 
 MODEL_KEYS = ('input_ids', 'position_ids', 'img_feat', 'img_pos_feat', 'attention_mask', 'gather_index', 'img_masks',
               'txt_type_ids', 'img_type_ids', 'seq_lens')
+
+
+def _model_kwargs(batch):
+    """the keyword arguments of `MemeUniter.forward` out of a batch (``attn_mask`` is accepted for ``attention_mask``)"""
+    kw = {k: batch[k] for k in MODEL_KEYS if k in batch and batch[k] is not None}
+    if 'attention_mask' not in kw and batch.get('attn_mask') is not None:
+        kw['attention_mask'] = batch['attn_mask']
+    for k in ('input_ids', 'position_ids', 'img_feat', 'img_pos_feat'):
+        kw.setdefault(k, None)
+    kw['output_all_encoded_layers'] = False
+    return kw
 
 
 def input_saliency(model, batch, target=None):
@@ -33,12 +52,7 @@ def input_saliency(model, batch, target=None):
     backward."""
     from .model import ensure_store
     uniter = model.uniter_model
-    kw = {k: batch[k] for k in MODEL_KEYS if k in batch and batch[k] is not None}
-    if 'attention_mask' not in kw and batch.get('attn_mask') is not None:
-        kw['attention_mask'] = batch['attn_mask']
-    for k in ('input_ids', 'position_ids', 'img_feat', 'img_pos_feat'):
-        kw.setdefault(k, None)
-    kw['output_all_encoded_layers'] = False
+    kw = _model_kwargs(batch)
     store = ensure_store(model)
     saved = store.flat_grads.clone()
     saved_touched, saved_stale = set(store.touched), store.wgrad_stale
@@ -72,3 +86,63 @@ def input_saliency(model, batch, target=None):
     return Saliency(rn, rg, tn, tg, feat.grad if feat is not None else None, pos7.grad if pos7 is not None else None,
                     delta.grad if delta is not None else None, logits.detach())
 
+
+
+def attention_maps(model, batch, heads='mean'):
+    """Every layer's attention probabilities for ``batch`` (keys as for `input_saliency`): one eval-mode forward under ``no_grad`` with
+    ``UniterModel.output_attentions = heads``.  Returns `AttentionMaps`: ``probs`` [nl, B, L, L] (``heads='mean'``, the mean over
+    heads) or [nl, B, nh, L, L] (``'all'``), row i = what joint position i attends to, and the detached ``logits``.  The model's
+    train / eval mode and ``output_attentions`` are restored.  Like any forward, this call must not sit between another forward and
+    its backward."""
+    if heads not in ('mean', 'all'):
+        raise ValueError("heads must be 'mean' or 'all'")
+    uniter = model.uniter_model
+    kw = _model_kwargs(batch)
+    was_training, was_output = model.training, uniter.output_attentions
+    model.eval()
+    uniter.output_attentions = heads
+    try:
+        with torch.no_grad():
+            logits = model(**kw)
+        probs = uniter.last_attentions
+    finally:
+        uniter.output_attentions = was_output
+        model.train(was_training)
+    return AttentionMaps(probs, logits.detach())
+
+
+def attention_rollout(model, batch, residual=0.5, start_layer=0):
+    """Attention rollout of the head-mean maps of layers ``start_layer`` .. nl - 1: R = A~_(nl-1) ... A~_(start_layer) with
+    A~_l = residual I + (1 - residual) A_l per sample (uniter_attn_rollout; fp32, no renormalisation: the rows of A_l sum to 1).
+    Returns `Rollout`: ``joint`` [B, L, L]; ``cls_token`` [B, T] and ``cls_region`` [B, R], row 0 of ``joint`` -- how much of each
+    input position reaches [CLS] -- mapped back to tokens and regions with `split_joint` (None for a modality the batch lacks);
+    the detached ``logits``."""
+    from . import _lib
+    maps = attention_maps(model, batch, 'mean')
+    probs = maps.probs
+    nl, B, L = probs.shape[0], probs.shape[1], probs.shape[2]
+    if not 0 <= int(start_layer) < nl:
+        raise ValueError('start_layer must lie in [0, %d)' % nl)
+    attn = probs[int(start_layer):].contiguous()
+    joint, tmp = torch.empty_like(attn[0]), torch.empty_like(attn[0])
+    _lib.check(_lib.lib().uniter_attn_rollout(_lib.ptr(attn), _lib.ptr(joint), _lib.ptr(tmp), attn.shape[0], B, L, float(residual),
+                                              _lib.cur_stream()), 'uniter_attn_rollout')
+    kw = _model_kwargs(batch)
+    T = kw['input_ids'].shape[1] if kw['input_ids'] is not None else 0
+    R = kw['img_feat'].shape[1] if kw['img_feat'] is not None else 0
+    tok, reg = split_joint(joint[:, 0], kw.get('gather_index') if T and R else None, kw['attention_mask'], T, R)
+    return Rollout(joint, tok if T else None, reg if R else None, maps.logits)
+
+
+def split_joint(scores, gather_index, attention_mask, T, R):
+    """Scores over the joint sequence ``scores`` [B, L] back to the inputs: ([B, T], [B, R]).  Joint position l of sample b is token
+    ``gather_index[b, l]`` when that is < T, else region ``gather_index[b, l] - T`` (model/model.py:327-333); positions whose
+    ``attention_mask`` is 0 are dropped, and a token or region no position maps to gets 0.  ``gather_index=None`` (text only or
+    regions only) is the identity: position l is token l, or region l - T.  Pure torch, any device."""
+    B, L = scores.shape
+    gi = gather_index if gather_index is not None else torch.arange(L, device=scores.device).unsqueeze(0).expand(B, L)
+    gi = gi.to(torch.int64)
+    valid = (attention_mask != 0) & (gi >= 0) & (gi < T + R)
+    out = torch.zeros(B, T + R + 1, dtype=scores.dtype, device=scores.device)
+    out.scatter_(1, torch.where(valid, gi, torch.full_like(gi, T + R)), torch.where(valid, scores, torch.zeros_like(scores)))
+    return out[:, :T], out[:, T:T + R]

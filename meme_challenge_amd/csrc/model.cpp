@@ -170,6 +170,9 @@ struct uniter_model {
   struct InputGrads { const float* txt_delta = nullptr; float* d_txt_rows = nullptr; float* d_img_feat = nullptr; float* d_img_pos_feat = nullptr;
                       bool outputs() const { return d_txt_rows || d_img_feat || d_img_pos_feat; } };
   InputGrads ig_next, ig;    // as set / as the latest forward pass took it over (its backward pass reads ig)
+  // uniter_model_set_attn_probs: where the next forward pass leaves every layer's attention probabilities (out == nullptr: nowhere)
+  struct AttnProbs { float* out = nullptr; size_t stride = 0; int head_mean = 0; };
+  AttnProbs ap_next;
   uint64_t generation = 0;   // bumped by every forward: a backward must belong to the LATEST forward (one plan / workspace per model)
 
   float* P(int i) const { return p[i]; }
@@ -724,6 +727,8 @@ extern "C" size_t uniter_model_ws_bytes(const uniter_model_t* m, int B, int T, i
 extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, float* hidden_out,
                                     int all_layers, int train, uint64_t seed, uint32_t offset, void* ws,
                                     size_t ws_bytes, void* stream) {
+  uniter_model::AttnProbs ap;      // uniter_model_set_attn_probs: this pass's, forgotten whatever becomes of the pass
+  if (m) { ap = m->ap_next; m->ap_next = uniter_model::AttnProbs(); }
   UCHECK_ARG(m && hidden_out && ws, "model_forward: null pointer");
   m->launch_reserve = 0;      // (no collective of this step is in flight during its forward pass: the reserve is the backward pass's)
   UCHECK_ARG(train >= 0 && train <= 2, "model_forward: train must be 0, 1 or 2");
@@ -923,6 +928,10 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
         break;
       }
     }
+    // the probabilities as an output (uniter_model_set_attn_probs): here, because only between this layer's attention launch and the
+    // next layer's query|key|value product does lb.qkv hold layer l's values in a pass that saves nothing
+    if (ap.out)
+      UCHECK_RC(uniter_attn_probs(lb.qkv, attn_b16 ? 1 : 0, mask, cu_seqlens, ap.out + (size_t)l * ap.stride, B, L, nh, ap.head_mean, st));
     // the context's operand copy: operand of the projection below and of its weight gradient
     const Act ctx = {lb.ctx, lb.ctxb}, y1 = {lb.y1, lb.y1b}, hact = {lb.hact, lb.hactb};
     if (ctx_copy) UCHECK_RC(operand_copy(pl, ctx, M, H, st));
@@ -1320,6 +1329,13 @@ extern "C" int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_
   UCHECK_ARG(m, "set_input_grads: null model");
   m->ig_next.txt_delta = txt_delta; m->ig_next.d_txt_rows = d_txt_rows; m->ig_next.d_img_feat = d_img_feat;
   m->ig_next.d_img_pos_feat = d_img_pos_feat;
+  return 0;
+}
+
+extern "C" int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t layer_stride_elems, int head_mean) {
+  UCHECK_ARG(m, "set_attn_probs: null model");
+  UCHECK_ARG(((uintptr_t)out & 3) == 0, "set_attn_probs: out must be 4-byte aligned");
+  m->ap_next.out = out; m->ap_next.stride = out ? layer_stride_elems : 0; m->ap_next.head_mean = head_mean ? 1 : 0;
   return 0;
 }
 

@@ -701,6 +701,11 @@ class _UniterFn(torch.autograd.Function):
             # a setting for THIS forward pass and its backward pass (the handle forgets it afterwards)
             check(lib.uniter_model_set_input_grads(model._handle, ptr(txt_delta), ptr(outs[2]), ptr(outs[0]), ptr(outs[1])),
                   'uniter_model_set_input_grads')
+        attn = model.__dict__.pop('_attn_next', None)
+        if attn is not None:
+            # UniterModel.output_attentions: a setting for THIS forward pass alone (the handle forgets it when the pass returns)
+            check(lib.uniter_model_set_attn_probs(model._handle, ptr(attn), attn[0].numel(), int(attn.dim() == 4)),
+                  'uniter_model_set_attn_probs')
         check(lib.uniter_model_forward(model._handle, C.byref(batch), ptr(hidden), int(all_layers),
                                        mode, seed, offset, ptr(ws), nbytes, _lib.cur_stream()),
               'uniter_model_forward')
@@ -813,6 +818,12 @@ class UniterModel(UniterPreTrainedModel):
         # fp32 master weights / LayerNorm / softmax / optimizer; 'bf16_hybrid': bf16 MFMA, operands converted in flight
         self.precision = 'fp32'
         self.pack_padded = False     # True: compute the valid positions only (see _pack); padded outputs are 0
+        # None | 'mean' | 'all': a forward pass with it set leaves every layer's attention probabilities (before dropout, in train
+        # and eval mode alike; csrc/attn_probs.hip) in `last_attentions`, a detached fp32 tensor [nl, B, L, L] (the mean over
+        # heads) or [nl, B, nh, L, L]; in a packed batch rows and columns beyond a sample's length are 0.  None: last_attentions
+        # = None and not one more launch
+        self.output_attentions = None
+        self.last_attentions = None
 
     # -- plumbing ------------------------------------------------------------
     @property
@@ -1210,8 +1221,20 @@ class UniterModel(UniterPreTrainedModel):
         if grad and not anchor.requires_grad and trainable is not None:      # (frozen embeddings: any trainable parameter makes autograd call the backward pass)
             anchor = trainable
         anchor = anchor if grad else anchor.detach()      # (a fully frozen model: an input that requires a gradient is what calls it)
-        hidden = _UniterFn.apply(anchor, img_feat, img_pos_feat, txt_embed_delta, self, b, keep, bool(output_all_encoded_layers), mode,
-                                 seed, offset)
+        self.last_attentions = attn = None
+        if self.output_attentions is not None:
+            if self.output_attentions not in ('mean', 'all'):
+                raise ValueError("output_attentions must be None, 'mean' or 'all'")
+            nl, nh = self.config.num_hidden_layers, self.config.num_attention_heads
+            attn = torch.empty((nl, B, b.L, b.L) if self.output_attentions == 'mean' else (nl, B, nh, b.L, b.L),
+                               dtype=torch.float32, device=dev)
+            self._attn_next = attn
+        try:
+            hidden = _UniterFn.apply(anchor, img_feat, img_pos_feat, txt_embed_delta, self, b, keep, bool(output_all_encoded_layers),
+                                     mode, seed, offset)
+        finally:
+            self.__dict__.pop('_attn_next', None)
+        self.last_attentions = attn
         if output_all_encoded_layers:
             return [hidden[i] for i in range(self.config.num_hidden_layers)]
         return hidden
