@@ -481,6 +481,27 @@ int uniter_attn_probs(const void* qkv, int qkv_is_bf16, const float* attn_mask, 
  * No renormalisation (the rows of A_l sum to 1 already).  residual in [0, 1].  tmp [B, L, L]: the caller's ping-pong space (may be
  * NULL when nl == 1).  One launch per layer, every sum in ascending order.  attn, rollout and tmp must not overlap (UNITER_E_ARG). */
 int uniter_attn_rollout(const float* attn, float* rollout, float* tmp, int nl, int B, int L, float residual, void* stream);
+/* Gradient-weighted attention (csrc/attn_grad.hip): g_ij = p_ij dP_ij per (sample, head), p as uniter_attn_probs computes it (lse
+ * recomputed from qkv, no dropout) and dP_ij = dO_i . v_j, dO the gradient of the attention context.  qkv, attn_mask / cu_seqlens as
+ * for uniter_attn_probs; dctx fp32 [rows, nh 64], rows laid out as qkv's, 16-byte aligned, given as n_slabs >= 1 slabs slab_stride
+ * ELEMENTS apart (slab_stride % 4 == 0) that are summed in ascending order.
+ *   reduce = 0: out [B, nh, L, L] = g (signed)
+ *   reduce = 1: out [B, L, L] = (1 / nh) sum_h max(g, 0), heads in ascending order (nh <= 64) -- Chefer, Gur & Wolf 2021
+ *   head_sums [B, nh] or NULL: sum_ij g_ij (signed) = the gradient with respect to a gate on the head (Michel et al. 2019); it goes
+ *   through one partial sum per workgroup in ws (uniter_attn_grad_ws_bytes(B, L, nh) bytes), added in ascending tile order.
+ * fp32, any L >= 1, no atomics, every element written once: two runs give the same bits.  In the packed form rows and columns at or
+ * beyond a sample's length are 0; a masked key has p = 0 and therefore g = 0.  UNITER_E_ARG: a null pointer, both or neither of
+ * attn_mask / cu_seqlens, alignment, n_slabs < 1, head_sums without a large enough ws, an output overlapping an input or another
+ * output (in the packed form, whose row count is on the device, the first row of qkv and of each slab); UNITER_E_SHAPE: B, L or nh < 1, B or nh > 65535, reduce with nh > 64. */
+size_t uniter_attn_grad_ws_bytes(int B, int L, int nh);
+int uniter_attn_grad(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* dctx,
+                     int n_slabs, size_t slab_stride, float* out, float* head_sums, void* ws, size_t ws_bytes, int B, int L, int nh,
+                     int reduce, void* stream);
+/* Relevance propagation over nl layers' maps [nl, B, L, L] (the reduce = 1 output above), per sample in fp32:
+ *   R_0 = I + A_0,   R_l = R_{l-1} + A_l R_{l-1},   out [B, L, L] = R_{nl-1}
+ * tmp [B, L, L]: the caller's ping-pong space (may be NULL when nl == 1).  One launch per layer, the L terms of every element's
+ * product added by fmaf in ascending k, then the element of R_{l-1}.  maps, out and tmp must not overlap (UNITER_E_ARG). */
+int uniter_attn_relevance(const float* maps, float* out, float* tmp, int nl, int B, int L, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Embeddings (replace UniterTextEmbeddings.forward model/model.py:232-245,
@@ -980,6 +1001,17 @@ int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_delta, floa
  * The handle forgets the setting when that uniter_model_forward returns, with or without an error.  out = NULL, or never called:
  * exactly the launches without it. */
 int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t layer_stride_elems, int head_mean);
+/* Every layer's gradient-weighted attention out of the backward pass of the NEXT forward pass, a setting on the handle held like
+ * uniter_model_set_input_grads: the forward pass takes it over, uniter_model_backward_layer(l) calls uniter_attn_grad on the main
+ * stream between the product that writes the context's gradient and the attention backward launch (qkv bf16 exactly when the bf16
+ * attention kernels run; the gradient's k-piece slabs summed; cu_seqlens for a packed batch) with out + l * layer_stride_elems,
+ * `reduce` as there, head_sums + l * B * nh ([nl, B, nh], or NULL) and the workspace ws (uniter_attn_grad_ws_bytes, shared by the
+ * layers); uniter_model_backward_end, or the next forward pass, forgets it.  The forward pass refuses it (UNITER_E_ARG, and forgets
+ * it) with train = 0, and with train = 1 when attention_probs_dropout_prob > 0: the quantity is defined on the undropped
+ * probabilities.  A layer the backward pass does not visit (a frozen prefix) is not written.  out = NULL, or never called: exactly
+ * the launches without it. */
+int uniter_model_set_attn_grads(uniter_model_t* m, float* out, size_t layer_stride_elems, int reduce, float* head_sums, void* ws,
+                                size_t ws_bytes);
 /* A stream for launches of the forward pass that depend on nothing the step computes -- the dropout keep flags of the attention
  * probabilities (a function of seed and offset alone: 60 us of Philox rounds for twelve layers) -- so that they run BESIDE the head
  * of the forward pass instead of in front of it; the first attention kernel waits for them.  NULL (default): on `stream`. */

@@ -161,6 +161,11 @@ _SIGS = {
     'uniter_attn_probs': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_attn_rollout': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     'uniter_model_set_attn_probs': (_I, [_P, _P, _SZ, _I]),
+    # gradient-weighted attention, relevance and head sums (csrc/attn_grad.hip)
+    'uniter_attn_grad_ws_bytes': (_SZ, [_I, _I, _I]),
+    'uniter_attn_grad': (_I, [_P, _I, _P, _P, _P, _I, _SZ, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
+    'uniter_attn_relevance': (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    'uniter_model_set_attn_grads': (_I, [_P, _P, _SZ, _I, _P, _P, _SZ]),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'uniter_pooler_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_linear_small_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

@@ -9,7 +9,13 @@ And what does the encoder's attention look like?  `UniterModel.output_attentions
 probabilities softmax(QK^T / 8 + mask) (model/layer.py:85-95, before the dropout; csrc/attn_probs.hip) in `last_attentions`:
 `attention_maps` returns them for a batch, `attention_rollout` multiplies the head-mean maps through the layers (Abnar & Zuidema 2020,
 uniter_attn_rollout) and reads off what reaches [CLS], and `split_joint` maps scores over the joint sequence back to tokens and
-regions."""
+regions.
+
+And which of that attention moved THIS logit?  `UniterModel.output_attention_grads` makes the backward pass leave every layer's
+gradient-weighted attention g = p * d target / d p (csrc/attn_grad.hip) in `last_attention_grads` and every head's sum of g in
+`last_head_grads`: `attention_gradients` returns them for a batch, `attention_relevance` propagates the head means of max(g, 0)
+through the layers (Chefer, Gur & Wolf 2021, uniter_attn_relevance) and reads off row [CLS], and `head_importance` turns the head sums
+of many batches into Michel et al.'s (2019) importance score per head."""
 from collections import namedtuple
 
 import torch
@@ -17,6 +23,8 @@ import torch
 Saliency = namedtuple('Saliency', 'region_norm region_gxi token_norm token_gxi img_feat_grad img_pos_feat_grad txt_grad logits')
 AttentionMaps = namedtuple('AttentionMaps', 'probs logits')
 Rollout = namedtuple('Rollout', 'joint cls_token cls_region logits')
+AttentionGrads = namedtuple('AttentionGrads', 'maps head_grads logits')
+Relevance = namedtuple('Relevance', 'joint cls_token cls_region logits')
 
 MODEL_KEYS = ('input_ids', 'position_ids', 'img_feat', 'img_pos_feat', 'attention_mask', 'gather_index', 'img_masks',
               'txt_type_ids', 'img_type_ids', 'seq_lens')
@@ -31,6 +39,50 @@ def _model_kwargs(batch):
         kw.setdefault(k, None)
     kw['output_all_encoded_layers'] = False
     return kw
+
+
+class _Run:
+    feat = pos7 = delta = words = logits = None
+
+
+def _eval_backward(model, batch, target, attention_grads=None):
+    """One eval-mode forward with gradients and one backward of the logits' sum (or of ``target(logits)``) with the batch's inputs
+    as differentiable leaves -- what `input_saliency` and `attention_gradients` share.  Returns a `_Run` (the leaves, the word rows,
+    the detached logits).  Whatever happens, the flat gradient buffer is restored bit for bit afterwards, with the store's
+    bookkeeping (which tensors were touched, the lazy zero_grad's flag), and so are the model's train / eval mode and
+    ``output_attention_grads`` (set to ``attention_grads`` for the pass)."""
+    from .model import ensure_store
+    uniter = model.uniter_model
+    kw = _model_kwargs(batch)
+    store = ensure_store(model)
+    saved = store.flat_grads.clone()
+    saved_touched, saved_stale = set(store.touched), store.wgrad_stale
+    was_training, was_setting = model.training, uniter.output_attention_grads
+    model.eval()
+    uniter.output_attention_grads = attention_grads
+    run = _Run()
+    try:
+        with torch.enable_grad():
+            if kw['img_feat'] is not None:
+                run.feat = kw['img_feat'].detach().float().requires_grad_(True)
+                run.pos7 = kw['img_pos_feat'].detach().float().requires_grad_(True)
+                kw['img_feat'], kw['img_pos_feat'] = run.feat, run.pos7
+            if kw['input_ids'] is not None:
+                run.words = uniter.embeddings.word_embeddings.weight.detach()[kw['input_ids']]
+                run.delta = torch.zeros_like(run.words).requires_grad_(True)
+                kw['txt_embed_delta'] = run.delta
+            logits = model(**kw)
+            out = logits.sum() if target is None else target(logits)
+            out.backward()
+            run.logits = logits.detach()
+    finally:
+        store.flat_grads.copy_(saved)
+        store.touched.clear()
+        store.touched.update(saved_touched)
+        store.wgrad_stale = saved_stale
+        uniter.output_attention_grads = was_setting
+        model.train(was_training)
+    return run
 
 
 def input_saliency(model, batch, target=None):
@@ -50,41 +102,15 @@ def input_saliency(model, batch, target=None):
     store's bookkeeping (which tensors were touched, the lazy zero_grad's flag).  The model's train / eval mode is restored.
     The library keeps the activations of one forward per model, so this call must not sit between another forward and its
     backward."""
-    from .model import ensure_store
-    uniter = model.uniter_model
-    kw = _model_kwargs(batch)
-    store = ensure_store(model)
-    saved = store.flat_grads.clone()
-    saved_touched, saved_stale = set(store.touched), store.wgrad_stale
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.enable_grad():
-            feat = pos7 = delta = words = None
-            if kw['img_feat'] is not None:
-                feat = kw['img_feat'].detach().float().requires_grad_(True)
-                pos7 = kw['img_pos_feat'].detach().float().requires_grad_(True)
-                kw['img_feat'], kw['img_pos_feat'] = feat, pos7
-            if kw['input_ids'] is not None:
-                words = uniter.embeddings.word_embeddings.weight.detach()[kw['input_ids']]
-                delta = torch.zeros_like(words).requires_grad_(True)
-                kw['txt_embed_delta'] = delta
-            logits = model(**kw)
-            out = logits.sum() if target is None else target(logits)
-            out.backward()
-    finally:
-        store.flat_grads.copy_(saved)
-        store.touched.clear()
-        store.touched.update(saved_touched)
-        store.wgrad_stale = saved_stale
-        model.train(was_training)
+    run = _eval_backward(model, batch, target)
+    feat, pos7, delta, words, logits = run.feat, run.pos7, run.delta, run.words, run.logits
 
     def scores(g, x):
         return (None, None) if g is None else (g.norm(dim=-1), (g * x.detach()).sum(dim=-1))
     rn, rg = scores(feat.grad if feat is not None else None, feat)
     tn, tg = scores(delta.grad if delta is not None else None, words)
     return Saliency(rn, rg, tn, tg, feat.grad if feat is not None else None, pos7.grad if pos7 is not None else None,
-                    delta.grad if delta is not None else None, logits.detach())
+                    delta.grad if delta is not None else None, logits)
 
 
 
@@ -127,11 +153,70 @@ def attention_rollout(model, batch, residual=0.5, start_layer=0):
     joint, tmp = torch.empty_like(attn[0]), torch.empty_like(attn[0])
     _lib.check(_lib.lib().uniter_attn_rollout(_lib.ptr(attn), _lib.ptr(joint), _lib.ptr(tmp), attn.shape[0], B, L, float(residual),
                                               _lib.cur_stream()), 'uniter_attn_rollout')
+    tok, reg = _split_cls(joint, batch)
+    return Rollout(joint, tok, reg, maps.logits)
+
+
+def _split_cls(joint, batch):
+    """row [CLS] of ``joint`` [B, L, L] as ([B, T] or None, [B, R] or None)"""
     kw = _model_kwargs(batch)
     T = kw['input_ids'].shape[1] if kw['input_ids'] is not None else 0
     R = kw['img_feat'].shape[1] if kw['img_feat'] is not None else 0
     tok, reg = split_joint(joint[:, 0], kw.get('gather_index') if T and R else None, kw['attention_mask'], T, R)
-    return Rollout(joint, tok if T else None, reg if R else None, maps.logits)
+    return tok if T else None, reg if R else None
+
+
+def attention_gradients(model, batch, target=None, heads='relu_mean'):
+    """Every layer's gradient-weighted attention for ``batch`` (keys as for `input_saliency`): one eval-mode forward with gradients and
+    one backward of the logits' sum (or of ``target(logits)``, a scalar) with ``UniterModel.output_attention_grads = heads``.
+    Returns `AttentionGrads`: ``maps`` -- g = p * d target / d p per head [nl, B, nh, L, L] (``heads='all'``, signed), or the mean
+    over heads of max(g, 0) [nl, B, L, L] (``'relu_mean'``, the layer maps of Chefer et al. 2021); ``head_grads`` [nl, B, nh], the
+    sum of g over each head's map = d target / d (a gate on that head); the detached ``logits``.  The flat gradient buffer and the
+    store's bookkeeping are restored bit for bit, and so are the train / eval mode and ``output_attention_grads``.  Like any
+    forward, this call must not sit between another forward and its backward."""
+    if heads not in ('relu_mean', 'all'):
+        raise ValueError("heads must be 'relu_mean' or 'all'")
+    uniter = model.uniter_model
+    run = _eval_backward(model, batch, target, heads)
+    return AttentionGrads(uniter.last_attention_grads, uniter.last_head_grads, run.logits)
+
+
+def attention_relevance(model, batch, target=None, start_layer=0):
+    """Relevance of every joint position for the target (Chefer, Gur & Wolf 2021, the single-stream rule): with A_l the 'relu_mean'
+    map of layer l, R = I, then R <- R + A_l R for l = ``start_layer`` .. nl - 1 per sample (uniter_attn_relevance; fp32).
+    Returns `Relevance`: ``joint`` [B, L, L]; ``cls_token`` [B, T] and ``cls_region`` [B, R], row 0 of ``joint`` -- the relevance of
+    each input position for what [CLS] holds -- mapped back to tokens and regions with `split_joint` (None for a modality the batch
+    lacks); the detached ``logits``.  ``joint`` includes the identity R started from: entry [0, 0] of every sample carries [CLS]'s
+    own 1, and so does ``cls_token[:, 0]``; subtract it (or drop that position) before ranking the tokens."""
+    from . import _lib
+    grads = attention_gradients(model, batch, target, 'relu_mean')
+    nl, B, L = grads.maps.shape[:3]
+    if not 0 <= int(start_layer) < nl:
+        raise ValueError('start_layer must lie in [0, %d)' % nl)
+    maps = grads.maps[int(start_layer):].contiguous()
+    joint, tmp = torch.empty_like(maps[0]), torch.empty_like(maps[0])
+    _lib.check(_lib.lib().uniter_attn_relevance(_lib.ptr(maps), _lib.ptr(joint), _lib.ptr(tmp), maps.shape[0], B, L, _lib.cur_stream()),
+               'uniter_attn_relevance')
+    tok, reg = _split_cls(joint, batch)
+    return Relevance(joint, tok, reg, grads.logits)
+
+
+def head_importance(model, batches, target=None, normalize=True):
+    """Michel, Levy & Neubig (2019): the importance of head h of layer l is |E_x d target / d gate_lh|, the expectation over the
+    samples of ``batches`` (an iterable of batches) of `attention_gradients`' ``head_grads``.  Returns [nl, nh]; with ``normalize``
+    each layer is divided by its L2 norm (their section 4), a layer of zeros staying zeros."""
+    total, count = None, 0
+    for batch in batches:
+        hg = attention_gradients(model, batch, target, 'relu_mean').head_grads.double()
+        total = hg.sum(1) if total is None else total + hg.sum(1)
+        count += hg.shape[1]
+    if total is None:
+        raise ValueError('head_importance needs at least one batch')
+    imp = (total / count).abs()
+    if normalize:
+        norm = imp.norm(dim=1, keepdim=True)
+        imp = imp / torch.where(norm > 0, norm, torch.ones_like(norm))
+    return imp.float()
 
 
 def split_joint(scores, gather_index, attention_mask, T, R):

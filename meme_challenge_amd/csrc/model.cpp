@@ -173,6 +173,10 @@ struct uniter_model {
   // uniter_model_set_attn_probs: where the next forward pass leaves every layer's attention probabilities (out == nullptr: nowhere)
   struct AttnProbs { float* out = nullptr; size_t stride = 0; int head_mean = 0; };
   AttnProbs ap_next;
+  // uniter_model_set_attn_grads: where the backward pass of the next forward pass leaves every layer's gradient-weighted attention
+  // (out == nullptr: nowhere)
+  struct AttnGrads { float* out = nullptr; size_t stride = 0; int reduce = 0; float* head_sums = nullptr; void* ws = nullptr; size_t ws_bytes = 0; };
+  AttnGrads ag_next, ag;     // as set / as the latest forward pass took it over (its backward pass reads ag)
   uint64_t generation = 0;   // bumped by every forward: a backward must belong to the LATEST forward (one plan / workspace per model)
 
   float* P(int i) const { return p[i]; }
@@ -757,6 +761,15 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
                  "model_forward: input gradients need hidden_size %% 4 == 0 and <= 1024 (got %d)", c.hidden_size);
     m->ig = ig;
   }
+  const uniter_model::AttnGrads ag = m->ag_next;       // uniter_model_set_attn_grads: this pass's, whatever becomes of it
+  m->ag_next = m->ag = uniter_model::AttnGrads();
+  if (ag.out) {
+    UCHECK_ARG(train != 0, "model_forward: attention gradients set (uniter_model_set_attn_grads) for an inference forward (train = 0)");
+    UCHECK_ARG(train != 1 || !(c.attention_probs_dropout_prob > 0.f),
+               "model_forward: attention gradients set (uniter_model_set_attn_grads) for a training forward with attention dropout: "
+               "they are defined on the undropped probabilities");
+    m->ag = ag;
+  }
   make_plan(m, pl, ws, b->B, b->T, b->R, b->L, has_txt, has_img, b->img_masks != nullptr, train,
             packed ? b->Mp : -1);
   if (pl.total > ws_bytes) {
@@ -1064,6 +1077,14 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // (two k-pieces when the x3 attention backward follows: it sums the slabs while it reads them -- 126 tiles do not fill the chip)
   UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, H, l, L_OW, g1, Act{lb.dctx, nullptr}, ns_dctx, UNITER_EPI_NONE, nullptr, nullptr,
                    nullptr));
+  // the gradient-weighted attention as an output (uniter_model_set_attn_grads): here, because only between the product that wrote
+  // dctx and the attention backward that consumes it do this layer's qkv and dctx both hold what the pass computed
+  if (m->ag.out) {
+    const uniter_model::AttnGrads& ag = m->ag;
+    UCHECK_RC(uniter_attn_grad(lb.qkv, attn_b16 ? 1 : 0, pl.packed ? nullptr : m->batch.attention_mask, pl.packed ? m->batch.cu_seqlens : nullptr,
+                               lb.dctx, ns_dctx, MH, ag.out + (size_t)l * ag.stride,
+                               ag.head_sums ? ag.head_sums + (size_t)l * B * nh : nullptr, ag.ws, ag.ws_bytes, B, L, nh, ag.reduce, st));
+  }
   {
     ProfScope ps(m, UNITER_K_ATTN_BWD, st);
     const float* mask = pl.packed ? nullptr : m->batch.attention_mask;
@@ -1282,6 +1303,7 @@ extern "C" int uniter_model_backward_end(uniter_model_t* m) {
   m->bwd_open = false;
   m->wg_overwrite = false;       // one backward pass: the next one accumulates again
   m->ig = uniter_model::InputGrads();      // ... and the input gradients were this pass's (uniter_model_set_input_grads)
+  m->ag = uniter_model::AttnGrads();       // ... and so was the attention-gradient capture (uniter_model_set_attn_grads)
   return 0;
 }
 
@@ -1336,6 +1358,20 @@ extern "C" int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t
   UCHECK_ARG(m, "set_attn_probs: null model");
   UCHECK_ARG(((uintptr_t)out & 3) == 0, "set_attn_probs: out must be 4-byte aligned");
   m->ap_next.out = out; m->ap_next.stride = out ? layer_stride_elems : 0; m->ap_next.head_mean = head_mean ? 1 : 0;
+  return 0;
+}
+
+extern "C" int uniter_model_set_attn_grads(uniter_model_t* m, float* out, size_t layer_stride_elems, int reduce, float* head_sums, void* ws,
+                                           size_t ws_bytes) {
+  UCHECK_ARG(m, "set_attn_grads: null model");
+  UCHECK_ARG((((uintptr_t)out | (uintptr_t)head_sums | (uintptr_t)ws) & 3) == 0, "set_attn_grads: out, head_sums and ws must be 4-byte aligned");
+  UCHECK_ARG(out || !head_sums, "set_attn_grads: head_sums without out");
+  UCHECK_ARG(!head_sums || ws, "set_attn_grads: head_sums needs a workspace (uniter_attn_grad_ws_bytes)");
+  m->ag_next = uniter_model::AttnGrads();
+  if (out) {
+    m->ag_next.out = out; m->ag_next.stride = layer_stride_elems; m->ag_next.reduce = reduce ? 1 : 0;
+    m->ag_next.head_sums = head_sums; m->ag_next.ws = ws; m->ag_next.ws_bytes = ws_bytes;
+  }
   return 0;
 }
 

@@ -706,6 +706,11 @@ class _UniterFn(torch.autograd.Function):
             # UniterModel.output_attentions: a setting for THIS forward pass alone (the handle forgets it when the pass returns)
             check(lib.uniter_model_set_attn_probs(model._handle, ptr(attn), attn[0].numel(), int(attn.dim() == 4)),
                   'uniter_model_set_attn_probs')
+        ctx.attn_grads = ag = model.__dict__.pop('_attn_grads_next', None)
+        if ag is not None:
+            # UniterModel.output_attention_grads: a setting for THIS forward pass and its backward pass (maps, head sums, workspace)
+            check(lib.uniter_model_set_attn_grads(model._handle, ptr(ag[0]), ag[0][0].numel(), int(ag[0].dim() == 4), ptr(ag[1]),
+                                                  ptr(ag[2]), ag[2].numel() * 4), 'uniter_model_set_attn_grads')
         check(lib.uniter_model_forward(model._handle, C.byref(batch), ptr(hidden), int(all_layers),
                                        mode, seed, offset, ptr(ws), nbytes, _lib.cur_stream()),
               'uniter_model_forward')
@@ -722,10 +727,13 @@ class _UniterFn(torch.autograd.Function):
                                  'keeps the activations of ONE forward per model: run backward before ANY further forward of '
                                  'this model (forwards under torch.no_grad() reuse the same plan and count as well)')
         d_hidden = d_hidden.contiguous()
-        outs = ctx.input_grads
+        outs, ag = ctx.input_grads, ctx.attn_grads
+        # (full: an input's gradient or every layer's attention gradient is wanted -- a frozen prefix must not cut layers off)
         model._run_backward(ctx.batch, d_hidden, ctx.all_layers, ctx.seed, ctx.offset, ctx.ws,
-                            ctx.nbytes, full=outs is not None)
-        ctx.ws = None
+                            ctx.nbytes, full=outs is not None or ag is not None)
+        if ag is not None:
+            model.last_attention_grads, model.last_head_grads = ag[0], ag[1]
+        ctx.ws = ctx.attn_grads = None
         ctx.input_grads = ctx.txt_delta = None
         return (None,) + (tuple(outs) if outs is not None else (None,) * 3) + (None,) * 7
 
@@ -824,6 +832,15 @@ class UniterModel(UniterPreTrainedModel):
         # = None and not one more launch
         self.output_attentions = None
         self.last_attentions = None
+        # None | 'all' | 'relu_mean': the backward pass of a forward pass with it set leaves every layer's gradient-weighted attention
+        # g = p * d target / d p (p before dropout; csrc/attn_grad.hip) in `last_attention_grads`, a detached fp32 tensor
+        # [nl, B, nh, L, L] ('all', signed) or [nl, B, L, L] ('relu_mean': the mean over heads of max(g, 0)), and every head's sum of g
+        # in `last_head_grads` [nl, B, nh].  Both are None until that backward pass has run and are reset by the next forward; the pass
+        # visits every layer whatever is frozen.  A forward without gradients captures nothing; a train-mode forward with
+        # attention dropout raises ValueError (the quantity is defined on the undropped probabilities).  None: not one more launch
+        self.output_attention_grads = None
+        self.last_attention_grads = None
+        self.last_head_grads = None
 
     # -- plumbing ------------------------------------------------------------
     @property
@@ -1214,6 +1231,14 @@ class UniterModel(UniterPreTrainedModel):
         wanted = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (img_feat, img_pos_feat, txt_embed_delta))
         grad = torch.is_grad_enabled() and (trainable is not None or wanted)
         mode = 0 if not grad else (1 if self.training else 2)
+        self.last_attention_grads = self.last_head_grads = None
+        ag_kind = self.output_attention_grads
+        if ag_kind is not None:
+            if ag_kind not in ('all', 'relu_mean'):
+                raise ValueError("output_attention_grads must be None, 'all' or 'relu_mean'")
+            if mode == 1 and self.config.attention_probs_dropout_prob > 0:      # (before any launch, and before the dropout offset moves)
+                raise ValueError('output_attention_grads needs the undropped attention probabilities: call eval() (or set '
+                                 'attention_probs_dropout_prob = 0) for this forward pass')
         seed, offset = self._seed, self._offset
         if mode == 1:
             self._offset = (self._offset + 1) & 0xFFFFFFFF
@@ -1229,11 +1254,18 @@ class UniterModel(UniterPreTrainedModel):
             attn = torch.empty((nl, B, b.L, b.L) if self.output_attentions == 'mean' else (nl, B, nh, b.L, b.L),
                                dtype=torch.float32, device=dev)
             self._attn_next = attn
+        if ag_kind is not None and mode != 0:
+            nl, nh = self.config.num_hidden_layers, self.config.num_attention_heads
+            ws_bytes = _lib.lib().uniter_attn_grad_ws_bytes(B, b.L, nh)
+            self._attn_grads_next = (torch.empty((nl, B, nh, b.L, b.L) if ag_kind == 'all' else (nl, B, b.L, b.L), dtype=torch.float32, device=dev),
+                                     torch.empty((nl, B, nh), dtype=torch.float32, device=dev),
+                                     torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev))
         try:
             hidden = _UniterFn.apply(anchor, img_feat, img_pos_feat, txt_embed_delta, self, b, keep, bool(output_all_encoded_layers),
                                      mode, seed, offset)
         finally:
             self.__dict__.pop('_attn_next', None)
+            self.__dict__.pop('_attn_grads_next', None)
         self.last_attentions = attn
         if output_all_encoded_layers:
             return [hidden[i] for i in range(self.config.num_hidden_layers)]
