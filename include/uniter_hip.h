@@ -1096,6 +1096,45 @@ int uniter_prof_stamps_union(uniter_model_t* m, unsigned kind_mask, double* unio
  * microseconds since the first stamped launch's start -- where on the step's time axis each GEMM ran (synchronises). */
 int uniter_prof_stamp_spans(uniter_model_t* m, int* kinds, double* start_us, double* end_us, int cap, int* n);
 
+/* ------------------------------------------------------------------------- *
+ * Collate on the device (csrc/collate.hip; data.DeviceLoader).
+ * ------------------------------------------------------------------------- */
+/* A dataset resident in device memory.  The struct itself is HOST memory, copied into the launch's arguments
+ * (as uniter_optim_group_t is).  Sample s owns rows [row_start[s], row_start[s] + row_cnt[s]) of the pool;
+ * rows of different samples may lie in any order in the pool and may be shared between samples. */
+typedef struct {
+  const float*   feat;            /* [pool_rows, D]  region features, 16-byte aligned, D % 4 == 0 */
+  const float*   pos;             /* [pool_rows, 7]  box features as data.load_img_feature computes them */
+  const int64_t* row_start;       /* [N] */
+  const int32_t* row_cnt;         /* [N] */
+  const int64_t* input_ids;       /* [N, T]  as the tokenizer padded them (padding='max_length') */
+  const int64_t* token_type_ids;  /* [N, T] or NULL */
+  const int32_t* txt_len;         /* [N]     the tokenizer's `length` */
+  const int64_t* labels;          /* [N] */
+  const int64_t* ids;             /* [N] */
+  int64_t N, pool_rows; int32_t D, T;
+} uniter_dataset_t;
+
+/* One batch, as data.MemeDataset.get_collate_fn() (compact_batch = True) builds it for the samples sel[0..B), bit for bit:
+ * R and L_out are the caller's (host) values max_b row_cnt and max_b (txt_len + img_len); flags bit 0 =
+ * ragged_regions (img_len_b = row_cnt, else img_len_b = R for every b).  With s = sel[b], n = row_cnt[s], tl = txt_len[s]:
+ *   img_feat[b,r,:] = feat[row_start[s] + r,:] for r < n, else 0 (img_pos_feat likewise);  input_ids[b,:] = input_ids[s,:]
+ *   (token_type_ids likewise where both pointers are non-NULL);  position_ids[b,t] = t;  attn_mask[b,j] = j < tl + img_len;
+ *   gather_index[b,j] = tl <= j < tl + img_len ? j - tl + T : j;  labels[b] = labels[s];  ids[b] = ids[s].
+ * ONE launch on `stream`, no host synchronisation, copy or allocation; every output element is written exactly once (the zero
+ * padding too: the outputs may be uninitialised), nothing else is touched, no atomics.  Offsets into feat / img_feat are 64-bit.
+ * For memory safety only -- the host validates its own order -- a sel value outside [0, N) is clamped into range, row_cnt is
+ * clamped to [0, R], and a pool row outside [0, pool_rows) reads as padding.  R == 0 (img_feat / img_pos_feat have no elements
+ * and may be NULL) and B == 1 are legal; feat / pos may be NULL only when pool_rows == 0.
+ * UNITER_E_ARG: a NULL required pointer, feat or img_feat not 16-byte aligned, N < 1;  UNITER_E_SHAPE: D % 4 != 0, B, T or
+ * L_out <= 0, R < 0, L_out > T + R.  A refusal sets the message and launches nothing. */
+int uniter_collate_batch(const uniter_dataset_t* ds, const int64_t* sel /* device */, int B, int R, int L_out, int flags,
+                         float* img_feat /* [B,R,D] */, float* img_pos_feat /* [B,R,7] */,
+                         int64_t* input_ids /* [B,T] */, int64_t* position_ids /* [B,T] */,
+                         int64_t* token_type_ids /* [B,T] or NULL */, float* attn_mask /* [B,L_out] */,
+                         int64_t* gather_index /* [B,L_out] */, int64_t* labels /* [B] */, int64_t* ids /* [B] */,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

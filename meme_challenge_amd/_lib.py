@@ -39,6 +39,13 @@ class OptimGroupC(C.Structure):
     _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float)]
 
 
+class UniterDatasetC(C.Structure):
+    """uniter_dataset_t (include/uniter_hip.h): a dataset resident in device memory, the source of uniter_collate_batch"""
+    _fields_ = [('feat', C.c_void_p), ('pos', C.c_void_p), ('row_start', C.c_void_p), ('row_cnt', C.c_void_p),
+                ('input_ids', C.c_void_p), ('token_type_ids', C.c_void_p), ('txt_len', C.c_void_p), ('labels', C.c_void_p),
+                ('ids', C.c_void_p), ('N', C.c_int64), ('pool_rows', C.c_int64), ('D', C.c_int32), ('T', C.c_int32)]
+
+
 class UniterBatchC(C.Structure):
     _fields_ = [('input_ids', C.c_void_p), ('position_ids', C.c_void_p),
                 ('txt_type_ids', C.c_void_p), ('img_feat', C.c_void_p),
@@ -166,6 +173,8 @@ _SIGS = {
     'uniter_attn_grad': (_I, [_P, _I, _P, _P, _P, _I, _SZ, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
     'uniter_attn_relevance': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'uniter_model_set_attn_grads': (_I, [_P, _P, _SZ, _I, _P, _P, _SZ]),
+    # a batch collated on the device from a resident dataset (csrc/collate.hip)
+    'uniter_collate_batch': (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 10),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'uniter_pooler_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_linear_small_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

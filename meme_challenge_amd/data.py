@@ -227,6 +227,7 @@ class MemeDataset(data.Dataset):
             labels=torch.LongTensor([j.get("label", -1) for j in js]),
             text=[j["text"] for j in js],
             imgs=[os.path.join(os.path.dirname(filepath), j.get("img", "")) for j in js])
+        self.feature_shard = feature_shard if not text_only else None
         self.shard = FeatureShard(feature_shard) if (feature_shard and not text_only) else None
         if not text_only:
             for i in self.data.ids.tolist():
@@ -378,3 +379,245 @@ def write_synthetic_dataset(root, n=64, num_bb=(10, 36), img_dim=2048, seed=0, s
                 f.write(json.dumps({'id': idx, 'img': 'img/%s.png' % expand_id(idx), 'label': label, 'text': text}) + '\n')
                 idx += 1
     return feat_dir
+
+
+# ---- device-resident dataset: batches collated on the GPU from HBM (csrc/collate.hip) ------------------------------
+# Fifteen cross-validation folds of up to 30 epochs read the same ~10 000 memes; at --max_bb 100 every region feature of
+# train + dev + test together is under 9 GB of fp32.  Held in HBM once per process, a batch is ONE launch from a device-side
+# list of sample indices: no per-step host tensor work, no host -> device copy, no background thread, no worker processes.
+# The batch is bit-identical to MemeDataset.get_collate_fn()'s for the same samples (tests/test_device_dataset_gpu.py).
+_GB = float(1 << 30)
+
+
+class DeviceFeaturePool(object):
+    """The process-wide store of region rows on `device`: feat [rows, D] and pos [rows, 7], fp32, growing.  A sample is
+    keyed by (feature source, image id, confidence threshold), so datasets that share images -- the fold files of a
+    cross-validation run -- upload every image once."""
+
+    CHUNK_BYTES = 256 << 20          # host rows gathered before one upload (and one budget check)
+
+    def __init__(self, device, max_gb=32.0):
+        self.device = torch.device(device)
+        self.max_bytes = int(float(max_gb) * _GB)
+        self.feat = self.pos = None          # [capacity, D] / [capacity, 7]; rows [0, self.rows) are in use
+        self.rows, self.dim = 0, None
+        self._where = {}                     # key -> (row_start, row_cnt)
+
+    @property
+    def resident_bytes(self):
+        return 0 if self.dim is None else self.rows * (self.dim + 7) * 4
+
+    @staticmethod
+    def source_of(dataset):
+        src = getattr(dataset, 'feature_shard', None) or dataset.feature_dir
+        return os.path.abspath(str(src))
+
+    def _reserve(self, rows):
+        cap = -1 if self.feat is None else self.feat.shape[0]
+        if rows <= cap:
+            return
+        new_cap = max(rows, cap + cap // 2)
+        feat = torch.empty((new_cap, self.dim), dtype=torch.float32, device=self.device)
+        pos = torch.empty((new_cap, 7), dtype=torch.float32, device=self.device)
+        if self.rows:
+            feat[:self.rows].copy_(self.feat[:self.rows])
+            pos[:self.rows].copy_(self.pos[:self.rows])
+        self.feat, self.pos = feat, pos      # (the old buffers go back to torch's allocator, in stream order)
+
+    def _upload(self, feats, poss, pending):
+        """append the host rows to the device buffers; the budget is checked before anything is allocated"""
+        n = sum(int(f.shape[0]) for f in feats)
+        need = (self.rows + n) * (self.dim + 7) * 4
+        if need > self.max_bytes:
+            raise ValueError('device dataset: %d bytes of region features needed, %d allowed (--device_dataset_max_gb %.3g)'
+                             % (need, self.max_bytes, self.max_bytes / _GB))
+        self._reserve(self.rows + n)
+        if n:
+            self.feat[self.rows:self.rows + n].copy_(torch.cat(feats))
+            self.pos[self.rows:self.rows + n].copy_(torch.cat(poss))
+        self.rows += n
+        self._where.update(pending)          # resident from here on
+
+    def add(self, dataset):
+        """Make every sample of `dataset` resident (each not-yet-resident one is read ONCE, through dataset[idx]: the host path's
+        feature directory, shard and confidence threshold) -> (row_start int64 [N], row_cnt int32 [N]) numpy arrays."""
+        src, thr = self.source_of(dataset), float(dataset.confidence_threshold)
+        ids = dataset.data.ids.tolist()
+        row_start, row_cnt = np.zeros(len(ids), dtype=np.int64), np.zeros(len(ids), dtype=np.int32)
+        feats, poss, pending, held, at = [], [], {}, 0, self.rows
+        for idx, img in enumerate(ids):
+            key = (src, int(img), thr)
+            if key not in self._where and key not in pending:
+                s = dataset[idx]
+                f, p = s['img_feat'].float().contiguous(), s['img_pos_feat'].float().contiguous()
+                if self.dim is None:
+                    self.dim = int(f.shape[1])
+                if int(f.shape[1]) != self.dim or tuple(p.shape) != (int(f.shape[0]), 7):
+                    raise ValueError('device dataset: image %d has features %s / %s, the pool holds rows of %d'
+                                     % (int(img), tuple(f.shape), tuple(p.shape), self.dim))
+                pending[key] = (at, int(f.shape[0]))
+                at += int(f.shape[0])
+                feats.append(f); poss.append(p)
+                held += f.numel() * 4
+                if held >= self.CHUNK_BYTES:
+                    self._upload(feats, poss, pending)
+                    feats, poss, pending, held = [], [], {}, 0
+            row_start[idx], row_cnt[idx] = self._where[key] if key in self._where else pending[key]
+        if self.dim is not None:
+            self._upload(feats, poss, pending)
+        return row_start, row_cnt
+
+
+class DeviceMemeDataset(object):
+    """A MemeDataset whose samples live on the device: region rows in `pool`, the tokenised texts, lengths, labels and ids
+    as device tensors.  Texts are tokenised once with the dataset's own `text_padding` (in chunks), which must pad to a fixed
+    length (padding='max_length') as the CLI's does: T and `length` are the tokenizer's own."""
+
+    TEXT_CHUNK = 1024
+
+    def __init__(self, dataset, pool):
+        if dataset.text_only:
+            raise ValueError('device dataset: text_only datasets are not built (there is no region pool to keep resident)')
+        if not dataset.compact_batch:
+            raise ValueError('device dataset: compact_batch=False is not built (the kernel writes the compact mask and gather index)')
+        self.dataset, self.pool = dataset, pool
+        self.name, self.return_ids, self.data = dataset.name, dataset.return_ids, dataset.data
+        self.ragged_regions = bool(dataset.ragged_regions)
+        row_start, self.row_cnt = pool.add(dataset)               # raises before any allocation when over budget
+        ids, tts, lens = [], [], []
+        for a in range(0, len(dataset), self.TEXT_CHUNK):
+            texts = dataset.text_padding(dataset.data.text[a:a + self.TEXT_CHUNK])
+            ids.append(texts['input_ids'])
+            tts.append(texts.get('token_type_ids') if hasattr(texts, 'get') else None)
+            ln = texts['length']
+            lens += [int(x) for x in (ln.tolist() if torch.is_tensor(ln) else ln)]
+            if ids[-1].shape[1] != ids[0].shape[1]:
+                raise ValueError('device dataset: text_padding must pad every text to one length (padding="max_length"); got %d and %d'
+                                 % (ids[0].shape[1], ids[-1].shape[1]))
+        if not ids:
+            raise ValueError('device dataset: %s is empty' % dataset.name)
+        self.txt_len = np.asarray(lens, dtype=np.int32)
+        dev = pool.device
+        self.T = int(ids[0].shape[1])
+        self.d_input_ids = torch.cat(ids).long().contiguous().to(dev)
+        self.d_token_type_ids = None if any(t is None for t in tts) else torch.cat(tts).long().contiguous().to(dev)
+        self.d_txt_len = torch.from_numpy(self.txt_len).to(dev)
+        self.d_row_start = torch.from_numpy(row_start).to(dev)
+        self.d_row_cnt = torch.from_numpy(self.row_cnt).to(dev)
+        self.d_labels = dataset.data.labels.long().contiguous().to(dev)
+        self.d_ids = dataset.data.ids.long().contiguous().to(dev)
+
+    def __len__(self):
+        return len(self.dataset)
+
+
+def plan_batches(order, batch_size, txt_len, row_cnt, ragged_regions):
+    """The host side of a DeviceLoader epoch, from the numpy length arrays alone: [(first, last, R, L_out, seq_lens)] over
+    `order` in batches of batch_size (the last may be short).  R, L_out and seq_lens are what the host collate derives: the
+    batch's largest region count, its longest text + image length, and the per-sample lengths as a list of ints."""
+    order = np.asarray(order, dtype=np.int64)
+    out = []
+    for a in range(0, len(order), batch_size):
+        sel = order[a:a + batch_size]
+        n, tl = row_cnt[sel].astype(np.int64), txt_len[sel].astype(np.int64)
+        R = int(n.max())
+        seq = tl + (n if ragged_regions else R)
+        out.append((a, a + len(sel), R, int(seq.max()), [int(x) for x in seq]))
+    return out
+
+
+def collate_batch(sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids, R, L_out,
+                  ragged_regions=False, out=None):
+    """uniter_collate_batch (include/uniter_hip.h) on the current stream: the batch of the samples `sel` (int64, device) of a
+    dataset given by its device tensors -> dict with the host collate's tensor keys.  `out`: the same dict of preallocated
+    outputs to write into (tests); default: fresh tensors from torch's allocator."""
+    import ctypes as C
+    from . import _lib
+    i64, i32, f32 = torch.int64, torch.int32, torch.float32
+    for name, t, dt in (('sel', sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('row_start', row_start, i64), ('row_cnt', row_cnt, i32),
+                        ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64), ('txt_len', txt_len, i32),
+                        ('labels', labels, i64), ('ids', ids, i64)):
+        if t is None and name != 'token_type_ids':
+            raise _lib.UniterHipError('collate_batch: %s is missing' % name)
+        _lib.require_gpu_tensor(t, dt, name)
+    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
+    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
+        raise _lib.UniterHipError('collate_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s' % (tuple(feat.shape), tuple(pos.shape)))
+    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
+                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()):
+        if tuple(t.shape) != shape:
+            raise _lib.UniterHipError('collate_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
+    R, L_out = int(R), int(L_out)
+    dev = sel.device
+    shapes = {'img_feat': ((B, max(R, 0), D), f32), 'img_pos_feat': ((B, max(R, 0), 7), f32), 'input_ids': ((B, T), i64),
+              'position_ids': ((B, T), i64), 'token_type_ids': ((B, T), i64), 'attn_mask': ((B, max(L_out, 0)), f32),
+              'gather_index': ((B, max(L_out, 0)), i64), 'labels': ((B,), i64), 'ids': ((B,), i64)}
+    if out is None:
+        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
+               for k, (s, dt) in shapes.items()}
+    else:
+        for k, (s, dt) in shapes.items():
+            t = out.get(k)
+            if t is None and k == 'token_type_ids':
+                continue
+            if t is None or tuple(t.shape) != s:
+                raise _lib.UniterHipError('collate_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
+            _lib.require_gpu_tensor(t, dt, 'output ' + k)
+    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
+                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
+                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+    for t in (sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
+        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
+    o = lambda k: None if out.get(k) is None else C.c_void_p(out[k].data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().uniter_collate_batch(
+            C.byref(ds), C.c_void_p(sel.data_ptr()), B, R, L_out, 1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'),
+            o('input_ids'), o('position_ids'), o('token_type_ids'), o('attn_mask'), o('gather_index'), o('labels'), o('ids'),
+            _lib.cur_stream()), 'uniter_collate_batch')
+    return out
+
+
+class DeviceLoader(object):
+    """Iterates a DeviceMemeDataset in batches built on the device.  Per epoch: the sampler's order (or range(N)), validated
+    and uploaded once as one int64 tensor on the current stream; per batch: R, L_out and seq_lens from the host length arrays,
+    fresh outputs from torch's allocator and one uniter_collate_batch launch on the current stream.  Yields the host collate's
+    dict (tensors on the device, `token_type_ids` None when the tokenizer gives none, `seq_lens` the same Python list).  No
+    thread, no side stream, and the loader never touches a yielded tensor's memory again."""
+
+    def __init__(self, device_dataset, batch_size, sampler=None):
+        if int(batch_size) < 1:
+            raise ValueError('DeviceLoader: batch_size must be positive')
+        self.dataset, self.batch_size, self.sampler = device_dataset, int(batch_size), sampler
+        self.epoch_order = None              # the last epoch's order as the device tensor (kept alive while its batches are built)
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.dataset)
+        return (n + self.batch_size - 1) // self.batch_size
+
+    def order(self):
+        """One epoch's sample order as a validated int64 numpy array (draws from the sampler)."""
+        n = len(self.dataset)
+        order = np.asarray(list(self.sampler) if self.sampler is not None else range(n), dtype=np.int64).reshape(-1)
+        if order.size and (order.min() < 0 or order.max() >= n):
+            raise ValueError('DeviceLoader: the sampler drew an index outside [0, %d)' % n)
+        return order
+
+    def plan(self, order):
+        d = self.dataset
+        return plan_batches(order, self.batch_size, d.txt_len, d.row_cnt, d.ragged_regions)
+
+    def __iter__(self):
+        d = self.dataset
+        order = self.order()
+        if order.size == 0:
+            return
+        self.epoch_order = dev_order = torch.from_numpy(order).to(d.pool.device)      # the epoch's one host -> device copy
+        for a, b, R, L_out, seq_lens in self.plan(order):
+            if L_out < 1:
+                raise ValueError('DeviceLoader: a batch without a single valid position')
+            pool = d.pool                    # (its buffers may have grown since the last batch: another dataset's add)
+            batch = collate_batch(dev_order[a:b], pool.feat[:pool.rows], pool.pos[:pool.rows], d.d_row_start, d.d_row_cnt,
+                                  d.d_input_ids, d.d_token_type_ids, d.d_txt_len, d.d_labels, d.d_ids, R, L_out,
+                                  ragged_regions=d.ragged_regions)
+            batch['seq_lens'] = seq_lens
+            yield batch

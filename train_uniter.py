@@ -12,7 +12,8 @@ Additive flags (not in the reference): --synthetic N (write a synthetic dataset 
 on-disk format under --data_path and train on it), --hash_tokenizer (offline tokenizer), --deterministic (every sum of the
 step in a fixed order: same seed, same bits in every parameter; UniterModel.deterministic), --adv_steps K with --adv_lr / --adv_max_norm /
 --adv_init_mag / --adv_modality (FreeLB adversarial fine-tuning: K passes per batch with a perturbation of the word embeddings and the
-region features; trainer.TrainStep).
+region features; trainer.TrainStep), --device_dataset with --device_dataset_max_gb (every split resident in device memory, each batch
+collated there by one launch: data.DeviceLoader).
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ import torch
 from torch.utils import data
 
 from meme_challenge_amd.data import (MemeDataset, ConfounderSampler, HashTokenizer, write_synthetic_dataset,
-                                     build_feature_shard, DevicePrefetcher)
+                                     build_feature_shard, DevicePrefetcher, DeviceFeaturePool, DeviceMemeDataset, DeviceLoader)
 from meme_challenge_amd.meme_uniter import MemeUniter
 from meme_challenge_amd.model import UniterModel, UniterConfig, resolve_config
 from meme_challenge_amd.train_template import TrainerTemplate, LOGGER
@@ -139,6 +140,11 @@ def build_parser():
                         help="GEMM arithmetic: fp32x3 (default, the path bench.py times: the reference's fp32 results from six bf16 "
                              "MFMA products per block on three bf16 pieces per value -- no less accurate than the fp32 MFMA kernels, "
                              "~30 %% faster steps), fp32 (native fp32 MFMA kernels), bf16 (bf16-resident operands) or bf16_hybrid")
+    parser.add_argument('--device_dataset', action='store_true',
+                        help='keep every split in device memory (region features once per image and process) and collate each batch '
+                             'on the GPU with one launch: no host collate, no host -> device copy, no prefetch thread, no workers')
+    parser.add_argument('--device_dataset_max_gb', type=float, default=32.0,
+                        help='--device_dataset: the most region-feature memory to hold on the device (fp32; an error beyond it)')
     return parser
 
 
@@ -163,6 +169,23 @@ def main(argv=None):
 
 
 def _main(argv=None):
+    config, make = _setup(argv)
+    if config['num_folds'] == 0:
+        config['train_loader'] = make('train.jsonl', train=True)
+        config['val_loader'] = make('dev_seen.jsonl')
+        return TrainerUniter(config).train_main()
+    # --num_folds k (-1 = all): one run per cross-validation fold, then the ensemble of the folds' predictions
+    # (train_uniter.py:183-188 -> utils/crossval.py:132-215 in the reference)
+    from meme_challenge_amd.crossval import train_crossval
+    split = lambda path: os.path.relpath(path, config['data_path'])
+    funcs = {'train': lambda path: make(split(path), train=True), 'val': lambda path: make(split(path)),
+             'test': lambda path: make(split(path), ids=True)}
+    return train_crossval(TrainerUniter, config, funcs, num_folds=config['num_folds'],
+                          dev_size=config['crossval_dev_size'], use_dev_set=config['crossval_use_dev'])
+
+
+def _setup(argv=None):
+    """Parse the flags -> (config with its test loaders, make(fname, train=False, ids=False) -> loader of one jsonl file)."""
     args, _ = build_parser().parse_known_args(argv)
     config = args.__dict__
     if config['parallel_computing'] and 'RANK' in os.environ and not torch.distributed.is_initialized():
@@ -195,6 +218,11 @@ def _main(argv=None):
     tokenizer_func = partial(tokenizer, max_length=config['max_txt_len'], padding='max_length', truncation=True,
                              return_tensors='pt', return_length=True)
 
+    pool = None
+    if config['device_dataset']:
+        pool = DeviceFeaturePool(config['device'], max_gb=config['device_dataset_max_gb'])      # one per process: folds share images
+        LOGGER.info('--device_dataset: batches are built on the device; --num_workers and --no_prefetch are ignored')
+
     def make(fname, train=False, ids=False):
         path = os.path.join(config['data_path'], fname)
         shard = None
@@ -208,6 +236,13 @@ def _main(argv=None):
         ds = MemeDataset(filepath=path, feature_dir=config['feature_path'], feature_shard=shard,
                          text_padding=tokenizer_func, return_ids=ids, confidence_threshold=config['object_conf_thresh'],
                          ragged_regions=config['ragged_regions'])
+        if pool is not None:
+            sampler = None
+            if train:                    # the order stays the host sampler's
+                sampler = ConfounderSampler(ds, config['confounder_repeat'])
+                if ddp:
+                    sampler = RankShard(sampler, rank, world)
+            return DeviceLoader(DeviceMemeDataset(ds, pool), config['batch_size'], sampler=sampler)
         kw = dict(batch_size=config['batch_size'], num_workers=config['num_workers'], collate_fn=ds.get_collate_fn(),
                   pin_memory=True)
         if config['num_workers'] > 0:
@@ -226,18 +261,7 @@ def _main(argv=None):
     config['test_loader'] = [make(f, ids=True) for f in ('test_seen.jsonl', 'test_unseen.jsonl', 'dev_seen.jsonl',
                                                         'dev_unseen.jsonl')
                              if os.path.isfile(os.path.join(config['data_path'], f))]
-    if config['num_folds'] == 0:
-        config['train_loader'] = make('train.jsonl', train=True)
-        config['val_loader'] = make('dev_seen.jsonl')
-        return TrainerUniter(config).train_main()
-    # --num_folds k (-1 = all): one run per cross-validation fold, then the ensemble of the folds' predictions
-    # (train_uniter.py:183-188 -> utils/crossval.py:132-215 in the reference)
-    from meme_challenge_amd.crossval import train_crossval
-    split = lambda path: os.path.relpath(path, config['data_path'])
-    funcs = {'train': lambda path: make(split(path), train=True), 'val': lambda path: make(split(path)),
-             'test': lambda path: make(split(path), ids=True)}
-    return train_crossval(TrainerUniter, config, funcs, num_folds=config['num_folds'],
-                          dev_size=config['crossval_dev_size'], use_dev_set=config['crossval_use_dev'])
+    return config, make
 
 
 if __name__ == '__main__':
