@@ -1135,6 +1135,79 @@ int uniter_collate_batch(const uniter_dataset_t* ds, const int64_t* sel /* devic
                          int64_t* gather_index /* [B,L_out] */, int64_t* labels /* [B] */, int64_t* ids /* [B] */,
                          void* stream);
 
+/* Pretraining batches from the same resident dataset (data.DevicePretrainLoader): the copy of uniter_collate_batch plus the
+ * masks of masked language modelling (MLM), masked region feature regression (MRFR) and the targets of image-text matching
+ * (ITM), drawn on the device, in ONE launch on `stream` with no host synchronisation, allocation or workspace.
+ *
+ * Text comes from sample ts = txt_sel[b] (txt_sel NULL: ts = sel[b]): input_ids, token_type_ids and tl = txt_len[ts].  Regions,
+ * labels and ids come from s = sel[b].  attn_mask, gather_index, position_ids and the zero padding are uniter_collate_batch's
+ * with that tl.  txt_sel is clamped into [0, N) as sel is (memory safety only).
+ *
+ * Random stream (Philox4x32-10 as the dropout sites': oracle/philox.py, csrc/philox.h):
+ *   w = philox4x32_10(c0 = position, c1 = lo32(sample), c2 = stream id, c3 = cfg.draw, key = (lo32(cfg.seed), hi32(cfg.seed)))
+ * with the four words called w.x, w.y, w.z, w.w.  `sample` is the DATASET index that owns the position: ts for a token, s for a
+ * region.  A sample's mask therefore depends on (seed, draw, sample, position) alone -- never on the batch it lands in or on its
+ * slot there.  The stream ids are the three constants below; no dropout site (0, 1, 2 + 4l .. 4 + 4l for layer l) reaches them.
+ * "With probability p" is  p >= 1 || word < floor((double)p * 2^32)  -- make_drop's floor and clamp (csrc/philox.h) in the
+ * opposite sense; cfg.prob is a float and is widened exactly.  Only the distribution is the reference's (its Python `random`
+ * stream cannot be reproduced, as for dropout).
+ *
+ * UNITER_TASK_MLM (T >= 2).  Token t of input_ids[ts] is eligible iff it is none of cfg.cls, cfg.sep, cfg.pad; an eligible
+ *   token is selected with probability cfg.prob on w.x.  A selected token becomes cfg.mask_token if w.y < UNITER_MASK_KEEP80,
+ *   else cfg.vocab_lo + (((uint64)w.z * (uint64)(cfg.vocab_hi - cfg.vocab_lo)) >> 32) if w.y < UNITER_MASK_KEEP90, else stays.
+ *   txt_labels[b,t] is the original id where selected and -1 elsewhere.  A sample without a single selected token takes
+ *   position 1 (whatever it holds, [SEP] included): label = the original id, token = cfg.mask_token.
+ * UNITER_TASK_MRFR.  With n = row_cnt[s] (the sample's own count, in the ragged and the non-ragged mode alike), region r < n is
+ *   selected with probability cfg.prob on w.x; when none is and n > 0, region ((uint64)w'.x * n) >> 32 is, w' being the draw at
+ *   c0 = 0xFFFFFFFF.  img_masks[b,r] = 1 / 0;  img_mask_tgt[b, tl + r] = selected (0 everywhere else, entries at or beyond L_out
+ *   do not exist);  the img_feat rows of selected regions are zero;  feat_targets holds their original rows.
+ * UNITER_TASK_ITM.  targets[b] = (txt_sel == NULL || txt_sel[b] == sel[b]) ? 1 : 0.  Nothing is drawn: the pairing is the host's
+ *   decision (data.itm_pairs), because L_out depends on it.  cfg may be NULL.
+ *
+ * Compaction (MLM, MRFR).  masked_positions[i] = (b, position) of the i-th selected entry in row-major (b, position) order,
+ * position = t for MLM and tl + r for MRFR;  feat_targets[i,:] (MRFR) is that entry's row;  *n_masked = their number.  The
+ * capacity of both is B * T rows (MLM) or B * R rows (MRFR); rows at and beyond *n_masked are not written.  The order is fixed
+ * and no workgroup waits for another: whoever needs the number of entries selected before its own draws them again -- the
+ * workgroup of sample b re-draws the b * T tokens in front of it (spread over its 256 lanes), a wave moving a selected region
+ * row re-draws the regions of the samples in front of it (one sample per lane) -- and the workgroup of the last sample writes
+ * *n_masked.  That recomputation grows with B^2 (B = 32, T = 128: at most 16 draws per lane; B = 256: at most 128).
+ * Every dense output element, and every element of the first *n_masked rows of masked_positions / feat_targets, has exactly
+ * one writer; plain vector stores only, no atomics; nothing outside the extents is touched.
+ *
+ * Outputs a task does not produce are ignored and may be NULL (MLM: txt_labels, masked_positions, n_masked; MRFR: img_masks,
+ * img_mask_tgt, feat_targets, masked_positions, n_masked; ITM: targets).  With R == 0 the arrays of B * R rows have no
+ * elements and may be NULL, as img_feat may; MRFR then writes *n_masked = 0.
+ * UNITER_E_ARG: an unknown task, a NULL pointer the task requires (cfg for MLM and MRFR), cfg.prob outside [0, 1] (NaN too),
+ * cfg.vocab_hi <= cfg.vocab_lo or a vocabulary range of more than 2^32 ids (MLM), feat_targets not 16-byte aligned, and
+ * uniter_collate_batch's;  UNITER_E_SHAPE: T < 2 for MLM, and uniter_collate_batch's.  A refusal sets the message and launches
+ * nothing. */
+#define UNITER_TASK_MLM  0
+#define UNITER_TASK_MRFR 1
+#define UNITER_TASK_ITM  2
+#define UNITER_STREAM_MLM         0xFFFF0001u   /* c2 of a token's draw */
+#define UNITER_STREAM_MRFR        0xFFFF0002u   /* c2 of a region's draw (and of the forced one at c0 = 0xFFFFFFFF) */
+#define UNITER_STREAM_ITM         0xFFFF0003u   /* reserved for the pairing: nothing on the device draws from it */
+#define UNITER_MASK_KEEP80        3435973836u   /* floor(0.8 * 2^32) */
+#define UNITER_MASK_KEEP90        3865470566u   /* floor(0.9 * 2^32) */
+typedef struct {
+  uint64_t seed;
+  uint32_t draw;                  /* c3: the task's epoch index in data.DevicePretrainLoader */
+  float    prob;
+  int64_t  cls, sep, pad, mask_token, vocab_lo, vocab_hi;     /* random tokens come from [vocab_lo, vocab_hi) */
+} uniter_mask_cfg_t;              /* HOST memory, copied into the launch's arguments */
+
+int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const int64_t* sel /* device [B] */,
+                                  const int64_t* txt_sel /* device [B] or NULL */, int task, const uniter_mask_cfg_t* cfg,
+                                  int B, int R, int L_out, int flags,
+                                  float* img_feat /* [B,R,D] */, float* img_pos_feat /* [B,R,7] */,
+                                  int64_t* input_ids /* [B,T] */, int64_t* position_ids /* [B,T] */,
+                                  int64_t* token_type_ids /* [B,T] or NULL */, float* attn_mask /* [B,L_out] */,
+                                  int64_t* gather_index /* [B,L_out] */, int64_t* labels /* [B] */, int64_t* ids /* [B] */,
+                                  int64_t* txt_labels /* [B,T] */, int64_t* img_masks /* [B,R] */,
+                                  unsigned char* img_mask_tgt /* [B,L_out] bool */, float* feat_targets /* [B*R,D] */,
+                                  int64_t* targets /* [B] */, int64_t* masked_positions /* [B*T or B*R, 2] */,
+                                  int32_t* n_masked /* device [1] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

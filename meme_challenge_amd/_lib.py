@@ -46,6 +46,15 @@ class UniterDatasetC(C.Structure):
                 ('ids', C.c_void_p), ('N', C.c_int64), ('pool_rows', C.c_int64), ('D', C.c_int32), ('T', C.c_int32)]
 
 
+class UniterMaskCfgC(C.Structure):
+    """uniter_mask_cfg_t (include/uniter_hip.h): the random stream and the special tokens of uniter_collate_pretrain_batch"""
+    _fields_ = [('seed', C.c_uint64), ('draw', C.c_uint32), ('prob', C.c_float), ('cls', C.c_int64), ('sep', C.c_int64),
+                ('pad', C.c_int64), ('mask_token', C.c_int64), ('vocab_lo', C.c_int64), ('vocab_hi', C.c_int64)]
+
+
+TASK_IDS = {'mlm': 0, 'mrfr': 1, 'itm': 2}       # UNITER_TASK_*
+
+
 class UniterBatchC(C.Structure):
     _fields_ = [('input_ids', C.c_void_p), ('position_ids', C.c_void_p),
                 ('txt_type_ids', C.c_void_p), ('img_feat', C.c_void_p),
@@ -175,6 +184,8 @@ _SIGS = {
     'uniter_model_set_attn_grads': (_I, [_P, _P, _SZ, _I, _P, _P, _SZ]),
     # a batch collated on the device from a resident dataset (csrc/collate.hip)
     'uniter_collate_batch': (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 10),
+    # the same with the MLM / MRFR masks and ITM targets of a pretraining batch: (ds, sel, txt_sel, task, cfg, B, R, L_out, flags, 16 outputs, stream)
+    'uniter_collate_pretrain_batch': (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I] + [_P] * 17),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'uniter_pooler_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_linear_small_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

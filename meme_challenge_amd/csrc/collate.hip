@@ -11,6 +11,7 @@
 //     label and the id.
 // Every output element has one writer and is written (padding rows as zeros); no atomics, no LDS, no workspace.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -128,6 +129,319 @@ extern "C" int uniter_collate_batch(const uniter_dataset_t* ds, const int64_t* s
   a.img_feat = img_feat; a.img_pos_feat = img_pos_feat; a.input_ids = input_ids; a.position_ids = position_ids;
   a.token_type_ids = token_type_ids; a.attn_mask = attn_mask; a.gather_index = gather_index; a.labels = labels; a.ids = ids;
   hipLaunchKernelGGL(collate_batch_kernel, dim3(a.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- pretraining batches: the same copy, plus the MLM / MRFR masks drawn here and their compaction -----------------------------
+// Same grid as above (region items, then one workgroup per sample); the specification of the random stream and of every output is
+// in include/uniter_hip.h.  What is new is the order of the compacted outputs (masked_positions, feat_targets): entry (b, position)
+// lands at [entries selected in samples < b] + [entries selected in sample b before position].  No workgroup waits for another: the
+// masks are a pure function of (seed, draw, sample, position), so whoever needs the first term draws those masks again.
+//   MLM   the workgroup of sample b: its four waves walk the samples in front of it (one sample per wave and trip, the lanes over
+//         its tokens), then the workgroup ranks its own tokens in chunks of 256 (ballot + popcount per wave, four wave totals
+//         through LDS).
+//   MRFR  a wave moving region row (b, r) draws its own sample's n <= R regions (lanes over regions); only when the row is selected
+//         does it count the samples in front (one sample per lane, serial over its regions).  The workgroup of sample b writes the
+//         dense img_masks / img_mask_tgt; the last one counts every sample (one per thread) for n_masked.
+namespace {
+
+struct PretrainArgs {
+  CollateArgs c;
+  const int64_t* txt_sel;
+  int task;
+  uint32_t k0, k1, draw, thresh;
+  int always;                            // prob >= 1
+  long long cls, sep, pad, mask_token, vocab_lo;
+  unsigned long long vocab_span;
+  int64_t* txt_labels;
+  int64_t* img_masks;
+  unsigned char* img_mask_tgt;
+  float* feat_targets;
+  int64_t* targets;
+  int64_t* masked_positions;
+  int32_t* n_masked;
+};
+
+__device__ __forceinline__ long long text_sample_of(const PretrainArgs& a, int b) {
+  if (!a.txt_sel) return sample_of(a.c, b);
+  long long s = a.txt_sel[b];
+  return s < 0 ? 0 : (s >= a.c.ds.N ? a.c.ds.N - 1 : s);
+}
+__device__ __forceinline__ bool hit(const PretrainArgs& a, uint32_t word) { return a.always || word < a.thresh; }
+
+// token t of dataset sample ts, holding `tok`: selected by its own draw?  (w: the draw, for the 80 / 10 / 10 split)
+__device__ __forceinline__ bool mlm_drawn(const PretrainArgs& a, long long ts, int t, long long tok, u32x4& w) {
+  w = philox4x32_10((uint32_t)t, (uint32_t)ts, UNITER_STREAM_MLM, a.draw, a.k0, a.k1);
+  return tok != a.cls && tok != a.sep && tok != a.pad && hit(a, w.x);
+}
+// selected tokens of sample ts, the forced one included; the whole wave calls it and every lane gets the result
+__device__ __forceinline__ int mlm_count_wave(const PretrainArgs& a, long long ts, int lane) {
+  const int T = a.c.ds.T;
+  const int64_t* src = a.c.ds.input_ids + (size_t)ts * T;
+  int cnt = 0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    u32x4 w;
+    const bool f = t < T && mlm_drawn(a, ts, t, src[t], w);
+    cnt += __popcll(__ballot(f));
+  }
+  return cnt > 0 ? cnt : 1;              // T >= 2: position 1 exists
+}
+
+__device__ __forceinline__ bool mrfr_drawn(const PretrainArgs& a, long long s, int r) {
+  return hit(a, philox4x32_10((uint32_t)r, (uint32_t)s, UNITER_STREAM_MRFR, a.draw, a.k0, a.k1).x);
+}
+// the region taken when none of the n > 0 regions of sample s was drawn
+__device__ __forceinline__ int mrfr_forced(const PretrainArgs& a, long long s, int n) {
+  const u32x4 w = philox4x32_10(0xFFFFFFFFu, (uint32_t)s, UNITER_STREAM_MRFR, a.draw, a.k0, a.k1);
+  return (int)(((unsigned long long)w.x * (unsigned long long)n) >> 32);
+}
+// selected regions of sample s, by ONE thread
+__device__ __forceinline__ int mrfr_count_serial(const PretrainArgs& a, long long s) {
+  const int n = regions_of(a.c, s);
+  int cnt = 0;
+  for (int r = 0; r < n; ++r) cnt += mrfr_drawn(a, s, r) ? 1 : 0;
+  return (cnt == 0 && n > 0) ? 1 : cnt;
+}
+
+__global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArgs a) {
+  __shared__ int sh[4];
+  const CollateArgs& c = a.c;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (blockIdx.x < c.region_blocks) {
+    const long long item = (long long)blockIdx.x * 4 + wave;
+    if (item >= c.region_items) return;
+    const long long row = item / c.pieces;             // b * R + r
+    const int piece = (int)(item - row * c.pieces);
+    const int b = (int)(row / c.R), r = (int)(row - (long long)b * c.R);
+    const long long s = sample_of(c, b);
+    const int n = regions_of(c, s);
+    const long long src_row = c.ds.row_start[s] + r;
+    const bool real = r < n && src_row >= 0 && src_row < c.ds.pool_rows;
+    // (everything up to `dest` is uniform over the wave)
+    bool masked = false;
+    long long dest = 0;                                // row of feat_targets / masked_positions
+    if (a.task == UNITER_TASK_MRFR && r < n) {
+      int before = 0, total = 0;
+      bool mine = false;
+      for (int base = 0; base < n; base += 64) {
+        const int rr = base + lane;
+        const unsigned long long bal = __ballot(rr < n && mrfr_drawn(a, s, rr));
+        total += __popcll(bal);
+        if (r >= base + 64) before += __popcll(bal);
+        else if (r >= base) {
+          before += __popcll(bal & ((1ull << (r - base)) - 1ull));
+          mine = (bal >> (r - base)) & 1ull;
+        }
+      }
+      if (total == 0) { masked = r == mrfr_forced(a, s, n); before = 0; }
+      else masked = mine;
+      if (masked) {
+        int front = 0;
+        for (int bp = lane; bp < b; bp += 64) front += mrfr_count_serial(a, sample_of(c, bp));
+        for (int o = 32; o > 0; o >>= 1) front += __shfl_xor(front, o, 64);
+        dest = (long long)front + before;              // < B * R: every sample contributes at most its n <= R
+      }
+    }
+    f32x4* dp = reinterpret_cast<f32x4*>(c.img_feat) + (size_t)row * c.D4;
+    const int c0 = piece * PIECE4 + lane;
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = zero;
+    if (real) {
+      const f32x4* sp = reinterpret_cast<const f32x4*>(c.ds.feat) + (size_t)src_row * c.D4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c0 + 64 * k < c.D4) v[k] = sp[c0 + 64 * k];
+    }
+    if (masked) {
+      f32x4* tp = reinterpret_cast<f32x4*>(a.feat_targets) + (size_t)dest * c.D4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c0 + 64 * k < c.D4) { tp[c0 + 64 * k] = v[k]; dp[c0 + 64 * k] = zero; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c0 + 64 * k < c.D4) dp[c0 + 64 * k] = v[k];
+    }
+    if (piece == 0 && lane < 7)
+      c.img_pos_feat[(size_t)row * 7 + lane] = real ? c.ds.pos[(size_t)src_row * 7 + lane] : 0.f;
+    if (piece == 0 && masked && lane == 0) {
+      a.masked_positions[2 * dest] = b;
+      a.masked_positions[2 * dest + 1] = (long long)c.ds.txt_len[text_sample_of(a, b)] + r;
+    }
+    return;
+  }
+
+  const int b = (int)(blockIdx.x - c.region_blocks);
+  const long long s = sample_of(c, b), ts = text_sample_of(a, b);
+  const int T = c.ds.T;
+  const long long tl = c.ds.txt_len[ts];
+  const int n = regions_of(c, s);
+  const long long il = c.ragged ? n : c.R;
+  const int64_t* src = c.ds.input_ids + (size_t)ts * T;
+
+  if (a.task == UNITER_TASK_MLM) {
+    // entries selected in the samples in front of this one
+    int acc = 0;
+    for (int bp = wave; bp < b; bp += 4) acc += mlm_count_wave(a, text_sample_of(a, bp), lane);
+    if (lane == 0) sh[wave] = acc;
+    __syncthreads();
+    const int front = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+    // this sample: is anything drawn at all?
+    int drawn = 0;
+    for (int base = 0; base < T; base += 256) {
+      const int t = base + (int)threadIdx.x;
+      u32x4 w;
+      drawn += __syncthreads_count(t < T && mlm_drawn(a, ts, t, src[t], w));
+    }
+    const bool forced = drawn == 0;
+    int run = 0;                                       // selected in the chunks already written
+    for (int base = 0; base < T; base += 256) {
+      const int t = base + (int)threadIdx.x;
+      long long tok = 0;
+      u32x4 w = u32x4{0u, 0u, 0u, 0u};
+      bool f = false;
+      if (t < T) {
+        tok = src[t];
+        f = mlm_drawn(a, ts, t, tok, w);
+        if (forced) f = t == 1;
+      }
+      const unsigned long long bal = __ballot(f);
+      if (lane == 0) sh[wave] = __popcll(bal);
+      __syncthreads();
+      int off = 0, chunk = 0;
+      for (int k = 0; k < 4; ++k) { off += k < wave ? sh[k] : 0; chunk += sh[k]; }
+      __syncthreads();
+      if (t < T) {
+        long long out_tok = tok;
+        if (f) {
+          if (forced || w.y < UNITER_MASK_KEEP80) out_tok = a.mask_token;
+          else if (w.y < UNITER_MASK_KEEP90) out_tok = a.vocab_lo + (long long)(((unsigned long long)w.z * a.vocab_span) >> 32);
+          const long long at = (long long)front + run + off + __popcll(bal & ((1ull << lane) - 1ull));      // < B * T
+          a.masked_positions[2 * at] = b;
+          a.masked_positions[2 * at + 1] = t;
+        }
+        c.input_ids[(size_t)b * T + t] = out_tok;
+        a.txt_labels[(size_t)b * T + t] = f ? tok : -1;
+      }
+      run += chunk;
+    }
+    if (b == c.B - 1 && threadIdx.x == 0) *a.n_masked = front + run;
+  } else {
+    for (int t = threadIdx.x; t < T; t += 256) c.input_ids[(size_t)b * T + t] = src[t];
+  }
+  for (int t = threadIdx.x; t < T; t += 256) {
+    c.position_ids[(size_t)b * T + t] = t;
+    if (c.token_type_ids) c.token_type_ids[(size_t)b * T + t] = c.ds.token_type_ids[(size_t)ts * T + t];
+  }
+  for (int j = threadIdx.x; j < c.L_out; j += 256) {
+    c.attn_mask[(size_t)b * c.L_out + j] = j < tl + il ? 1.0f : 0.0f;
+    c.gather_index[(size_t)b * c.L_out + j] = (tl <= j && j < tl + il) ? j - tl + T : j;
+  }
+  if (threadIdx.x == 0) {
+    c.labels[b] = c.ds.labels[s];
+    c.ids[b] = c.ds.ids[s];
+    if (a.task == UNITER_TASK_ITM) a.targets[b] = ts == s ? 1 : 0;
+  }
+  if (a.task == UNITER_TASK_MRFR) {
+    int any = 0;
+    for (int base = 0; base < n; base += 256) {
+      const int r = base + (int)threadIdx.x;
+      any |= __syncthreads_or(r < n && mrfr_drawn(a, s, r));
+    }
+    const int forced = (any || n == 0) ? -1 : mrfr_forced(a, s, n);
+    for (int r = threadIdx.x; r < c.R; r += 256)
+      a.img_masks[(size_t)b * c.R + r] = (r < n && (forced >= 0 ? r == forced : mrfr_drawn(a, s, r))) ? 1 : 0;
+    for (int j = threadIdx.x; j < c.L_out; j += 256) {
+      const long long r = j - tl;
+      a.img_mask_tgt[(size_t)b * c.L_out + j] = (r >= 0 && r < n && (forced >= 0 ? r == forced : mrfr_drawn(a, s, (int)r))) ? 1 : 0;
+    }
+    if (b == c.B - 1) {
+      int cnt = 0;
+      for (int bp = threadIdx.x; bp < c.B; bp += 256) cnt += mrfr_count_serial(a, sample_of(c, bp));
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if (lane == 0) sh[wave] = cnt;
+      __syncthreads();
+      if (threadIdx.x == 0) *a.n_masked = sh[0] + sh[1] + sh[2] + sh[3];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const int64_t* sel, const int64_t* txt_sel, int task,
+                                             const uniter_mask_cfg_t* cfg, int B, int R, int L_out, int flags, float* img_feat,
+                                             float* img_pos_feat, int64_t* input_ids, int64_t* position_ids, int64_t* token_type_ids,
+                                             float* attn_mask, int64_t* gather_index, int64_t* labels, int64_t* ids,
+                                             int64_t* txt_labels, int64_t* img_masks, unsigned char* img_mask_tgt, float* feat_targets,
+                                             int64_t* targets, int64_t* masked_positions, int32_t* n_masked, void* stream) {
+  UCHECK_ARG(task == UNITER_TASK_MLM || task == UNITER_TASK_MRFR || task == UNITER_TASK_ITM,
+             "collate_pretrain_batch: unknown task %d", task);
+  UCHECK_ARG(ds && sel, "collate_pretrain_batch: null dataset or selection");
+  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids,
+             "collate_pretrain_batch: null pointer in the dataset");
+  UCHECK_ARG(input_ids && position_ids && attn_mask && gather_index && labels && ids, "collate_pretrain_batch: null output pointer");
+  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "collate_pretrain_batch: dataset of %lld samples, %lld pool rows", (long long)ds->N,
+             (long long)ds->pool_rows);
+  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0,
+               "collate_pretrain_batch: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)", B, ds->T, L_out, R);
+  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "collate_pretrain_batch: L_out = %d exceeds T + R = %d + %d", L_out, ds->T, R);
+  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "collate_pretrain_batch: D = %d must be a positive multiple of 4 (rows move as 16-byte items)",
+               ds->D);
+  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "collate_pretrain_batch: null feat / pos with %lld pool rows",
+             (long long)ds->pool_rows);
+  UCHECK_ARG((img_feat && img_pos_feat) || R == 0, "collate_pretrain_batch: null img_feat / img_pos_feat with R = %d", R);
+  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "collate_pretrain_batch: feat is not 16-byte aligned");
+  UCHECK_ARG(((uintptr_t)img_feat & 15) == 0, "collate_pretrain_batch: img_feat is not 16-byte aligned");
+  PretrainArgs a;
+  a.k0 = a.k1 = a.draw = a.thresh = 0; a.always = 0;
+  a.cls = a.sep = a.pad = a.mask_token = a.vocab_lo = 0; a.vocab_span = 1;
+  if (task != UNITER_TASK_ITM) {
+    UCHECK_ARG(cfg, "collate_pretrain_batch: null mask configuration");
+    UCHECK_ARG(cfg->prob >= 0.0f && cfg->prob <= 1.0f, "collate_pretrain_batch: prob = %g is outside [0, 1]", (double)cfg->prob);
+    // (MRFR with R == 0: no region can be selected, masked_positions has no rows)
+    UCHECK_ARG((masked_positions || (task == UNITER_TASK_MRFR && R == 0)) && n_masked,
+               "collate_pretrain_batch: null masked_positions / n_masked");
+    a.k0 = (uint32_t)(cfg->seed & 0xffffffffu); a.k1 = (uint32_t)(cfg->seed >> 32); a.draw = cfg->draw;
+    const double t = (double)cfg->prob * 4294967296.0;       // make_drop's floor and clamp (philox.h)
+    a.always = cfg->prob >= 1.0f;
+    a.thresh = t >= 4294967295.0 ? 0xffffffffu : (t <= 0.0 ? 0u : (uint32_t)t);
+  }
+  if (task == UNITER_TASK_MLM) {
+    UCHECK_ARG(txt_labels, "collate_pretrain_batch: null txt_labels");
+    UCHECK_ARG(cfg->vocab_hi > cfg->vocab_lo && (unsigned long long)(cfg->vocab_hi - cfg->vocab_lo) <= (1ull << 32),
+               "collate_pretrain_batch: vocabulary range [%lld, %lld) is empty or holds more than 2^32 ids", (long long)cfg->vocab_lo,
+               (long long)cfg->vocab_hi);
+    UCHECK_SHAPE(ds->T >= 2, "collate_pretrain_batch: MLM needs T >= 2 (a sample without a drawn token takes position 1); T = %d", ds->T);
+    a.cls = cfg->cls; a.sep = cfg->sep; a.pad = cfg->pad; a.mask_token = cfg->mask_token; a.vocab_lo = cfg->vocab_lo;
+    a.vocab_span = (unsigned long long)(cfg->vocab_hi - cfg->vocab_lo);
+  } else if (task == UNITER_TASK_MRFR) {
+    UCHECK_ARG(img_mask_tgt && ((img_masks && feat_targets) || R == 0),
+               "collate_pretrain_batch: null img_masks / img_mask_tgt / feat_targets with R = %d", R);
+    UCHECK_ARG(((uintptr_t)feat_targets & 15) == 0, "collate_pretrain_batch: feat_targets is not 16-byte aligned");
+  } else {
+    UCHECK_ARG(targets, "collate_pretrain_batch: null targets");
+  }
+  CollateArgs& c = a.c;
+  c.ds = *ds;
+  if (!token_type_ids || !ds->token_type_ids) token_type_ids = nullptr;
+  c.sel = sel; c.B = B; c.R = R; c.L_out = L_out; c.ragged = flags & 1;
+  c.D4 = ds->D / 4;
+  c.pieces = (c.D4 + PIECE4 - 1) / PIECE4;
+  c.region_items = (long long)B * R * c.pieces;
+  const long long region_blocks = (c.region_items + 3) / 4;
+  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "collate_pretrain_batch: %lld region items exceed one launch", c.region_items);
+  c.region_blocks = (unsigned)region_blocks;
+  c.img_feat = img_feat; c.img_pos_feat = img_pos_feat; c.input_ids = input_ids; c.position_ids = position_ids;
+  c.token_type_ids = token_type_ids; c.attn_mask = attn_mask; c.gather_index = gather_index; c.labels = labels; c.ids = ids;
+  a.txt_sel = txt_sel; a.task = task;
+  a.txt_labels = txt_labels; a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.feat_targets = feat_targets;
+  a.targets = targets; a.masked_positions = masked_positions; a.n_masked = n_masked;
+  hipLaunchKernelGGL(collate_pretrain_kernel, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
 }

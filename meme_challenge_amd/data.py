@@ -506,6 +506,9 @@ class DeviceMemeDataset(object):
         self.d_row_cnt = torch.from_numpy(self.row_cnt).to(dev)
         self.d_labels = dataset.data.labels.long().contiguous().to(dev)
         self.d_ids = dataset.data.ids.long().contiguous().to(dev)
+        # the index of each sample's distinct text string (itm_pairs: a replaced text must differ from the sample's own)
+        seen = {}
+        self.text_class = np.asarray([seen.setdefault(str(t), len(seen)) for t in dataset.data.text], dtype=np.int32)
 
     def __len__(self):
         return len(self.dataset)
@@ -621,3 +624,227 @@ class DeviceLoader(object):
                                   ragged_regions=d.ragged_regions)
             batch['seq_lens'] = seq_lens
             yield batch
+
+
+# ---- pretraining batches from the resident dataset: MLM / MRFR masks and ITM targets drawn in the collate launch -------------------
+# Counterpart of data/pretrain_mlm.py:35-69, data/pretrain_mrfr.py:29-51, data/pretrain_itm.py:27-47 and of MetaLoader
+# (data/pretrain_meme_dataset.py:21-58).  The masks come from the Philox stream of include/uniter_hip.h (a function of seed, the
+# task's epoch, the dataset sample and the position -- not of the batch); what the host decides is what it must know without a
+# synchronisation: the order, the ITM pairing (the batch's L_out depends on it) and the task of every step.
+PRETRAIN_TASKS = ('mlm', 'mrfr', 'itm')
+
+
+def itm_pairs(order, text_class, replace_prob, rng):
+    """The text of every position of `order` for image-text matching -> txt_order (int64, like order).  With probability
+    replace_prob a position takes the text of a uniformly drawn sample whose text string differs from its own (rejection on
+    text_class, the index of each sample's distinct string), otherwise it keeps its own: txt_order[i] == order[i] is the ITM
+    target.  A dataset with one distinct text keeps all.  rng: a numpy Generator."""
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    text_class = np.asarray(text_class)
+    txt_order = order.copy()
+    if order.size == 0 or text_class.min() == text_class.max():
+        return txt_order
+    todo = np.flatnonzero(rng.random(order.size) < replace_prob)
+    while todo.size:
+        cand = rng.integers(0, len(text_class), todo.size)
+        ok = text_class[cand] != text_class[order[todo]]
+        txt_order[todo[ok]] = cand[ok]
+        todo = todo[~ok]
+    return txt_order
+
+
+def plan_pretrain_batches(order, txt_order, batch_size, txt_len, row_cnt, ragged_regions):
+    """plan_batches with the text lengths of txt_order (the samples the texts come from) and the region counts of order."""
+    order, txt_order = np.asarray(order, dtype=np.int64), np.asarray(txt_order, dtype=np.int64)
+    if order.shape != txt_order.shape:
+        raise ValueError('plan_pretrain_batches: order and txt_order differ in shape: %s / %s' % (order.shape, txt_order.shape))
+    out = []
+    for a in range(0, len(order), batch_size):
+        sel, tsel = order[a:a + batch_size], txt_order[a:a + batch_size]
+        n, tl = row_cnt[sel].astype(np.int64), txt_len[tsel].astype(np.int64)
+        R = int(n.max())
+        seq = tl + (n if ragged_regions else R)
+        out.append((a, a + len(sel), R, int(seq.max()), [int(x) for x in seq]))
+    return out
+
+
+def collate_pretrain_batch(task, sel, txt_sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids, R, L_out,
+                           ragged_regions=False, seed=0, draw=0, prob=0.15, cls_token=101, sep_token=102, pad_token=0, mask_token=103,
+                           vocab_range=(1000, 28996), out=None):
+    """uniter_collate_pretrain_batch (include/uniter_hip.h) on the current stream: the `task` ('mlm' / 'mrfr' / 'itm') batch of
+    the samples `sel` with the texts of `txt_sel` (None: their own) -> dict with the reference collates' keys (`attn_masks`, sic),
+    `labels` / `ids` / `token_type_ids` as collate_batch gives them, and for mlm / mrfr the compaction at full capacity:
+    `masked_positions` [B*T or B*R, 2], `n_masked` (int32 [1], on the device; the first n_masked rows are defined) and, for
+    mrfr, `feat_targets` [B*R, D].  `out`: the same dict of preallocated outputs to write into (tests)."""
+    import ctypes as C
+    from . import _lib
+    if task not in _lib.TASK_IDS:
+        raise ValueError('collate_pretrain_batch: unknown task %r (one of %s)' % (task, ', '.join(PRETRAIN_TASKS)))
+    i64, i32, f32 = torch.int64, torch.int32, torch.float32
+    for name, t, dt in (('sel', sel, i64), ('txt_sel', txt_sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('row_start', row_start, i64),
+                        ('row_cnt', row_cnt, i32), ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64),
+                        ('txt_len', txt_len, i32), ('labels', labels, i64), ('ids', ids, i64)):
+        if t is None and name not in ('token_type_ids', 'txt_sel'):
+            raise _lib.UniterHipError('collate_pretrain_batch: %s is missing' % name)
+        _lib.require_gpu_tensor(t, dt, name)
+    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
+    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
+        raise _lib.UniterHipError('collate_pretrain_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s'
+                                  % (tuple(feat.shape), tuple(pos.shape)))
+    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
+                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()) \
+            + ((('txt_sel', txt_sel, (B,)),) if txt_sel is not None else ()):
+        if tuple(t.shape) != shape:
+            raise _lib.UniterHipError('collate_pretrain_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
+    R, L_out = max(int(R), 0), max(int(L_out), 0)
+    dev = sel.device
+    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
+              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
+              'ids': ((B,), i64)}
+    if task == 'mlm':
+        shapes.update(txt_labels=((B, T), i64), masked_positions=((B * T, 2), i64), n_masked=((1,), i32))
+    elif task == 'mrfr':
+        shapes.update(img_masks=((B, R), i64), img_mask_tgt=((B, L_out), torch.bool), feat_targets=((B * R, D), f32),
+                      masked_positions=((B * R, 2), i64), n_masked=((1,), i32))
+    else:
+        shapes.update(targets=((B,), i64))
+    if out is None:
+        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
+               for k, (s, dt) in shapes.items()}
+    else:
+        for k, (s, dt) in shapes.items():
+            t = out.get(k)
+            if t is None and k == 'token_type_ids':
+                continue
+            if t is None or tuple(t.shape) != s:
+                raise _lib.UniterHipError('collate_pretrain_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
+            _lib.require_gpu_tensor(t, dt, 'output ' + k)
+    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
+                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
+                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+    cfg = _lib.UniterMaskCfgC(int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(prob), int(cls_token), int(sep_token),
+                              int(pad_token), int(mask_token), int(vocab_range[0]), int(vocab_range[1]))
+    for t in (sel, txt_sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
+        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
+    o = lambda k: None if out.get(k) is None else C.c_void_p(out[k].data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().uniter_collate_pretrain_batch(
+            C.byref(ds), C.c_void_p(sel.data_ptr()), None if txt_sel is None else C.c_void_p(txt_sel.data_ptr()), _lib.TASK_IDS[task],
+            C.byref(cfg), B, R, L_out, 1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'), o('input_ids'), o('position_ids'),
+            o('token_type_ids'), o('attn_masks'), o('gather_index'), o('labels'), o('ids'), o('txt_labels'), o('img_masks'),
+            o('img_mask_tgt'), o('feat_targets'), o('targets'), o('masked_positions'), o('n_masked'), _lib.cur_stream()),
+            'uniter_collate_pretrain_batch')
+    return out
+
+
+class DevicePretrainLoader(object):
+    """MetaLoader over a DeviceMemeDataset: an indefinite iterator of (task, batch).  Every `accum_steps` steps the task is drawn
+    from the ratio pool (`tasks`: (name, ratio) pairs) by a generator seeded from `seed`.  Every task walks its own epochs: its
+    own order per epoch (samplers[name], an iterable of sample indices as DeviceLoader's sampler; default: a permutation from the
+    task's own generator), for 'itm' its own pairing (itm_pairs), and its own `draw` counter -- the task's epoch index -- so that a
+    sample's mask changes from epoch to epoch and depends on nothing else.  Per batch: one uniter_collate_pretrain_batch launch
+    on the current stream; for mlm / mrfr the loader then reads n_masked -- the step's ONE host synchronisation, which waits for
+    the collate launch queued behind the previous step's tail -- and yields `masked_positions[:n]` / `feat_targets[:n]` as views
+    (UniterForPretraining uses masked_positions in place of its own nonzero).  Batches carry the reference collates' keys
+    (`attn_masks`; `txt_labels` | `img_masks`, `img_mask_tgt`, `feat_targets` | `targets`), `labels`, `ids`, `token_type_ids` and
+    the host list `seq_lens`.  len() is the sum of the tasks' batches per epoch."""
+
+    def __init__(self, device_dataset, batch_size, tasks=(('mlm', 1), ('mrfr', 1), ('itm', 1)), seed=0, mask_prob=0.15, replace_prob=0.5,
+                 accum_steps=1, samplers=None, cls_token=101, sep_token=102, pad_token=0, mask_token=103, vocab_range=(1000, 28996)):
+        if int(batch_size) < 1:
+            raise ValueError('DevicePretrainLoader: batch_size must be positive')
+        tasks = [(str(n), int(r)) for n, r in tasks]
+        if not tasks:
+            raise ValueError('DevicePretrainLoader: no task given')
+        for name, ratio in tasks:
+            if name not in PRETRAIN_TASKS:
+                raise ValueError('DevicePretrainLoader: unknown task %r (one of %s)' % (name, ', '.join(PRETRAIN_TASKS)))
+            if ratio < 1:
+                raise ValueError('DevicePretrainLoader: task %s has ratio %d; ratios are positive integers' % (name, ratio))
+        if len({n for n, _ in tasks}) != len(tasks):
+            raise ValueError('DevicePretrainLoader: a task is listed twice')
+        if not (0.0 <= float(mask_prob) <= 1.0 and 0.0 <= float(replace_prob) <= 1.0):
+            raise ValueError('DevicePretrainLoader: mask_prob and replace_prob are probabilities')
+        if int(accum_steps) < 1:
+            raise ValueError('DevicePretrainLoader: accum_steps must be positive')
+        self.dataset, self.batch_size, self.seed = device_dataset, int(batch_size), int(seed)
+        self.tasks = [n for n, _ in tasks]
+        self.sampling_pool = [n for n, r in tasks for _ in range(r)]
+        self.mask_prob, self.replace_prob, self.accum_steps = float(mask_prob), float(replace_prob), int(accum_steps)
+        self.samplers = dict(samplers or {})
+        for name in self.samplers:
+            if name not in self.tasks:
+                raise ValueError('DevicePretrainLoader: a sampler for %r, which is not among the tasks' % name)
+        self.tokens = dict(cls_token=int(cls_token), sep_token=int(sep_token), pad_token=int(pad_token), mask_token=int(mask_token),
+                           vocab_range=(int(vocab_range[0]), int(vocab_range[1])))
+        self.step = 0
+        self.epochs = {n: 0 for n in self.tasks}          # epochs begun per task: the next epoch's `draw`
+        self.epoch_orders = {}                            # task -> (order, txt_order) of its current epoch, numpy
+        self._task_rng = np.random.default_rng([self.seed, len(PRETRAIN_TASKS)])
+        self._rngs = {n: self.task_rng(self.seed, n) for n in self.tasks}
+        self._iters, self._dev_orders = {}, {}
+
+    @staticmethod
+    def task_rng(seed, task):
+        """the generator behind a task's default orders and ITM pairings"""
+        return np.random.default_rng([int(seed), PRETRAIN_TASKS.index(task)])
+
+    def _epoch_len(self, task):
+        s = self.samplers.get(task)
+        return len(s) if s is not None else len(self.dataset)
+
+    def __len__(self):
+        return sum((self._epoch_len(t) + self.batch_size - 1) // self.batch_size for t in self.tasks)
+
+    def order(self, task):
+        """One epoch's validated sample order of `task` (draws from its sampler or its generator)."""
+        n = len(self.dataset)
+        s = self.samplers.get(task)
+        order = np.asarray(list(s), dtype=np.int64).reshape(-1) if s is not None else self._rngs[task].permutation(n).astype(np.int64)
+        if order.size == 0:
+            raise ValueError('DevicePretrainLoader: the order of task %s is empty' % task)
+        if order.min() < 0 or order.max() >= n:
+            raise ValueError('DevicePretrainLoader: the sampler of task %s drew an index outside [0, %d)' % (task, n))
+        return order
+
+    def _epoch(self, task):
+        d = self.dataset
+        draw = self.epochs[task]
+        self.epochs[task] += 1
+        order = self.order(task)
+        txt_order = itm_pairs(order, d.text_class, self.replace_prob, self._rngs[task]) if task == 'itm' else order
+        self.epoch_orders[task] = (order, txt_order)
+        plan = plan_pretrain_batches(order, txt_order, self.batch_size, d.txt_len, d.row_cnt, d.ragged_regions)
+        if any(L_out < 1 for _, _, _, L_out, _ in plan):
+            raise ValueError('DevicePretrainLoader: a batch without a single valid position')
+        # the epoch's one host -> device copy (kept alive while its batches are built)
+        self._dev_orders[task] = dev = torch.from_numpy(np.stack([order, txt_order])).to(d.pool.device)
+        for a, b, R, L_out, seq_lens in plan:
+            pool = d.pool
+            batch = collate_pretrain_batch(task, dev[0, a:b], dev[1, a:b] if task == 'itm' else None, pool.feat[:pool.rows],
+                                           pool.pos[:pool.rows], d.d_row_start, d.d_row_cnt, d.d_input_ids, d.d_token_type_ids,
+                                           d.d_txt_len, d.d_labels, d.d_ids, R, L_out, ragged_regions=d.ragged_regions, seed=self.seed,
+                                           draw=draw, prob=self.mask_prob, **self.tokens)
+            if task != 'itm':
+                n = batch['n_masked'] = int(batch['n_masked'].item())          # the step's one host synchronisation
+                batch['masked_positions'] = batch['masked_positions'][:n]
+                if task == 'mrfr':
+                    batch['feat_targets'] = batch['feat_targets'][:n]
+            batch['seq_lens'] = seq_lens
+            yield batch
+
+    def __iter__(self):
+        """runs indefinitely; the tasks' epochs carry on where an earlier iteration left them"""
+        task = self.sampling_pool[0]
+        while True:
+            if self.step % self.accum_steps == 0:
+                task = self.sampling_pool[int(self._task_rng.integers(len(self.sampling_pool)))]
+            self.step += 1
+            if task not in self._iters:
+                self._iters[task] = self._epoch(task)
+            try:
+                batch = next(self._iters[task])
+            except StopIteration:
+                self._iters[task] = self._epoch(task)
+                batch = next(self._iters[task])
+            yield task, batch

@@ -424,15 +424,15 @@ class UniterForPretraining(UniterPreTrainedModel):
                   batch['attn_masks'], batch['gather_index'])
         self._seq_lens = batch['seq_lens']        # host lengths for token packing (UniterModel.pack_padded), when the batch has them
         if task == 'mlm':
-            return self.forward_mlm(*common, batch['txt_labels'], compute_loss)
+            return self.forward_mlm(*common, batch['txt_labels'], compute_loss, masked_positions=batch['masked_positions'])
         elif task == 'mrfr':
             return self.forward_mrfr(*common, batch['img_masks'], batch['img_mask_tgt'], batch['feat_targets'],
-                                     compute_loss)
+                                     compute_loss, masked_positions=batch['masked_positions'])
         elif task == 'itm':
             return self.forward_itm(*common, batch['targets'], batch['ot_inputs'], compute_loss)
         elif task.startswith('mrc'):
             return self.forward_mrc(*common, batch['img_masks'], batch['img_mask_tgt'], batch['label_targets'], task,
-                                    compute_loss)
+                                    compute_loss, masked_positions=batch['masked_positions'])
         raise ValueError('invalid task')
 
     @staticmethod
@@ -451,14 +451,24 @@ class UniterForPretraining(UniterPreTrainedModel):
         return torch.nonzero(mask.bool(), as_tuple=False)
 
     @staticmethod
+    def _given_positions(masked_positions):
+        """`batch['masked_positions']`: the [n, 2] int64 (sample, position) rows that _mask_positions would find, row-major,
+        already counted by whoever built the batch (data.DevicePretrainLoader: the collate launch compacts them and the loader
+        reads the count) -- no nonzero here, so the step's one host synchronisation stays the loader's."""
+        mp = masked_positions
+        if mp.dim() != 2 or mp.shape[1] != 2 or mp.dtype != torch.int64:
+            raise ValueError('masked_positions must be int64 [n, 2]; got %s %s' % (mp.dtype, tuple(mp.shape)))
+        return mp
+
+    @staticmethod
     def _rows_at(hidden, nz):
         L = hidden.shape[1]
         return _GatherRowsFn.apply(hidden, (nz[:, 0] * L + nz[:, 1]).contiguous())
 
     def forward_mlm(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
-                    txt_labels, compute_loss=True):
+                    txt_labels, compute_loss=True, masked_positions=None):
         self._sync_head_precision()
-        nz = self._mask_positions(txt_labels != -1)
+        nz = self._given_positions(masked_positions) if masked_positions is not None else self._mask_positions(txt_labels != -1)
         seq = self.uniter(input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
                           output_all_encoded_layers=False, seq_lens=getattr(self, '_seq_lens', None))
         T = input_ids.size(1)
@@ -471,9 +481,9 @@ class UniterForPretraining(UniterPreTrainedModel):
         return _CrossEntropyFn.apply(scores, txt_labels[nz[:, 0], nz[:, 1]])      # == txt_labels[txt_labels != -1]
 
     def forward_mrfr(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
-                     img_masks, img_mask_tgt, feat_targets, compute_loss=True):
+                     img_masks, img_mask_tgt, feat_targets, compute_loss=True, masked_positions=None):
         self._sync_head_precision()
-        nz = self._mask_positions(img_mask_tgt)
+        nz = self._given_positions(masked_positions) if masked_positions is not None else self._mask_positions(img_mask_tgt)
         seq = self.uniter(input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
                           output_all_encoded_layers=False, img_masks=img_masks, seq_lens=getattr(self, '_seq_lens', None))
         masked = self._rows_at(seq, nz)
@@ -483,11 +493,11 @@ class UniterForPretraining(UniterPreTrainedModel):
         return _MseFn.apply(pred, feat_targets)
 
     def forward_mrc(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
-                    img_masks, img_mask_tgt, label_targets, task, compute_loss=True):
+                    img_masks, img_mask_tgt, label_targets, task, compute_loss=True, masked_positions=None):
         """model/pretrain.py:205-233: region classification on the masked regions; 'mrc' trains against the most
         likely non-background detector class, 'mrc-kl' against the detector's soft labels."""
         self._sync_head_precision()
-        nz = self._mask_positions(img_mask_tgt)
+        nz = self._given_positions(masked_positions) if masked_positions is not None else self._mask_positions(img_mask_tgt)
         seq = self.uniter(input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
                           output_all_encoded_layers=False, img_masks=img_masks, seq_lens=getattr(self, '_seq_lens', None))
         masked = self._rows_at(seq, nz)

@@ -1,0 +1,265 @@
+"""uniter_collate_pretrain_batch (csrc/collate.hip) through data.collate_pretrain_batch against the numpy restatement
+tests/pretrain_collate_ref.py, bit for bit (torch.equal: the kernel copies values, does integer arithmetic and draws from the
+Philox stream the header specifies).  Every output lies inside a larger buffer, pre-filled with a sentinel byte between two guard
+bands: afterwards no sentinel is left in a dense extent or in the first n_masked rows of a compacted one, and every guard byte is
+unchanged."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from meme_challenge_amd import _lib
+from meme_challenge_amd.data import collate_pretrain_batch
+from pretrain_collate_ref import pretrain_collate_ref
+
+pytestmark = pytest.mark.gpu
+
+GUARD, GUARD_BYTE, SENTINEL_BYTE = 256, 0x5A, 0xCD      # GUARD % 16 == 0: img_feat / feat_targets stay 16-byte aligned
+ARRAY_KEYS = ('feat', 'pos', 'row_start', 'row_cnt', 'input_ids', 'token_type_ids', 'txt_len', 'labels', 'ids')
+COMMON = ('img_feat', 'img_pos_feat', 'input_ids', 'position_ids', 'token_type_ids', 'attn_masks', 'gather_index', 'labels', 'ids')
+DENSE = {'mlm': COMMON + ('txt_labels',), 'mrfr': COMMON + ('img_masks', 'img_mask_tgt'), 'itm': COMMON + ('targets',)}
+COMPACT = {'mlm': ('masked_positions',), 'mrfr': ('masked_positions', 'feat_targets'), 'itm': ()}
+ALL_OUT = COMMON + ('txt_labels', 'img_masks', 'img_mask_tgt', 'feat_targets', 'targets', 'masked_positions', 'n_masked')
+CLS, SEP = 101, 102
+N = 12
+
+
+def synth(D, R, T, token_types, seed=0):
+    """Twelve samples.  Region counts R, 0, 1 first, then min(2, R), R, 1 ..; texts [CLS] words [SEP] [PAD]..: sample 0 fills T,
+    sample 1 is [CLS] [SEP] alone, the others have every length in between.  Pool rows lie far apart and out of order, with rows
+    nobody owns between them."""
+    rng = np.random.default_rng(seed)
+    cnt = np.array([R, 0, 1, min(2, R), R, 1, 0, R, min(3, R), 1, R, min(2, R)], np.int32)
+    txt = np.array([T, 2] + [2 + (7 * i) % (T - 1) for i in range(N - 2)], np.int32)
+    place = [3, 5, 0, 11, 4, 2, 9, 1, 7, 10, 6, 8]
+    row_start, at = np.zeros(N, np.int64), 3
+    for s in place:
+        row_start[s] = at
+        at += int(cnt[s]) + 5
+    input_ids = np.zeros((N, T), np.int64)
+    for i, tl in enumerate(txt):
+        input_ids[i, :tl] = [CLS] + list(rng.integers(1000, 28996, tl - 2)) + [SEP]
+    return {'feat': rng.standard_normal((at, D)).astype(np.float32), 'pos': rng.random((at, 7)).astype(np.float32),
+            'row_start': row_start, 'row_cnt': cnt, 'input_ids': input_ids,
+            'token_type_ids': rng.integers(0, 2, (N, T)).astype(np.int64) if token_types else None, 'txt_len': txt,
+            'labels': rng.integers(0, 2, N).astype(np.int64), 'ids': rng.integers(0, 99999, N).astype(np.int64)}
+
+
+def to_device(a):
+    return {k: (None if v is None else torch.from_numpy(v).cuda()) for k, v in a.items()}
+
+
+class Guarded(object):
+    """an output tensor inside a larger byte buffer: [guard | extent, filled with the sentinel | guard]"""
+
+    def __init__(self, shape, dtype):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        self.nbytes = n
+        self.buf = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device='cuda')
+        self.buf[GUARD:GUARD + n] = SENTINEL_BYTE
+        self.t = self.buf[GUARD:GUARD + n].view(dtype).view(shape)
+
+    def check_guards(self, what):
+        b = self.buf.cpu()
+        assert bool((b[:GUARD] == GUARD_BYTE).all()) and bool((b[GUARD + self.nbytes:] == GUARD_BYTE).all()), '%s: a guard byte changed' % what
+
+    def untouched(self):
+        return bool((self.buf[GUARD:GUARD + self.nbytes] == SENTINEL_BYTE).all())
+
+
+def guarded_outputs(task, B, R, D, T, L_out, token_types, every=False):
+    i64, f32 = torch.int64, torch.float32
+    cap = B * T if task == 'mlm' else B * R
+    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
+              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
+              'ids': ((B,), i64), 'txt_labels': ((B, T), i64), 'img_masks': ((B, R), i64), 'img_mask_tgt': ((B, L_out), torch.bool),
+              'feat_targets': ((B * R, D), f32), 'targets': ((B,), i64), 'masked_positions': ((cap, 2), i64), 'n_masked': ((1,), torch.int32)}
+    keys = ALL_OUT if every else DENSE[task] + COMPACT[task] + (('n_masked',) if task != 'itm' else ())
+    return {k: Guarded(*shapes[k]) for k in keys if token_types or k != 'token_type_ids'}
+
+
+def sentinel_of(dtype):
+    return torch.full((1,), SENTINEL_BYTE, dtype=torch.uint8).repeat(8).view(dtype)[0]
+
+
+def launch(task, d, sel, txt_sel, R, L_out, ragged, cfg, g):
+    out = {k: v.t for k, v in g.items()}
+    dev = lambda x: None if x is None else torch.tensor(x, dtype=torch.int64, device='cuda')
+    return collate_pretrain_batch(task, dev(sel), dev(txt_sel), *[d[k] for k in ARRAY_KEYS], R=R, L_out=L_out, ragged_regions=ragged,
+                                  out=out, **cfg)
+
+
+def run_and_check(task, a, d, sel, txt_sel, ragged, prob, twice=False):
+    T, D = a['input_ids'].shape[1], a['feat'].shape[1]
+    ts = sel if txt_sel is None else txt_sel
+    R = int(a['row_cnt'][sel].max())
+    L_out = int((a['txt_len'][ts] + (a['row_cnt'][sel] if ragged else R)).max())
+    cfg = dict(seed=(5 << 32) + 17, draw=3, prob=prob)
+    want = pretrain_collate_ref(task, sel, txt_sel, *[a[k] for k in ARRAY_KEYS], R=R, L_out=L_out, ragged=ragged, cfg=cfg)
+    tt = a['token_type_ids'] is not None
+    g = guarded_outputs(task, len(sel), R, D, T, L_out, tt)
+    got = launch(task, d, sel, txt_sel, R, L_out, ragged, cfg, g)
+    torch.cuda.synchronize()
+    what = '%s sel %s txt_sel %s R %d ragged %s prob %g' % (task, list(sel), None if txt_sel is None else list(txt_sel), R, ragged, prob)
+    for k, v in g.items():
+        v.check_guards(k + ': ' + what)
+    for k in DENSE[task]:
+        if want[k] is None:
+            assert k not in g, what
+            continue
+        t = got[k].cpu()
+        if t.dtype == torch.bool:
+            assert bool((t.view(torch.uint8) <= 1).all()), '%s: %s holds bytes other than 0 / 1' % (k, what)
+        else:
+            assert not bool((t == sentinel_of(t.dtype)).any()), '%s: a sentinel is left inside the extent: %s' % (k, what)
+        assert torch.equal(t, torch.from_numpy(want[k])), '%s: %s' % (k, what)
+    if task != 'itm':
+        n = int(got['n_masked'].item())
+        assert n == want['n_masked'], what
+        for k in COMPACT[task]:
+            t = got[k][:n].cpu()
+            assert not bool((t == sentinel_of(t.dtype)).any()), '%s: a sentinel is left in the first n_masked rows: %s' % (k, what)
+            assert torch.equal(t, torch.from_numpy(want[k])), '%s: %s' % (k, what)
+        mp = got['masked_positions'][:n].cpu()
+        key = mp[:, 0] * (T + R + 1) + mp[:, 1]
+        assert bool((key[1:] > key[:-1]).all()), 'masked_positions is not strictly increasing: ' + what
+    if twice:                       # the same launch into fresh buffers: the same bytes, undefined rows (left as they were) included
+        g2 = guarded_outputs(task, len(sel), R, D, T, L_out, tt)
+        launch(task, d, sel, txt_sel, R, L_out, ragged, cfg, g2)
+        torch.cuda.synchronize()
+        for k in g:
+            assert torch.equal(g[k].buf, g2[k].buf), '%s differs between two identical launches: %s' % (k, what)
+    return want
+
+
+def mixed(sel):
+    """a txt_sel for sel: rotated by one, every third position kept (fixed points: the sample's own text)"""
+    sel = np.asarray(sel)
+    txt = np.roll(sel, 1)
+    txt[::3] = sel[::3]
+    return txt
+
+
+@pytest.mark.parametrize('token_types', [True, False])
+@pytest.mark.parametrize('T', [2, 16, 300])
+@pytest.mark.parametrize('R', [1, 5, 37])
+@pytest.mark.parametrize('D', [4, 260])
+def test_pretrain_batches_equal_the_restatement(D, R, T, token_types):
+    """D: one 16-byte item per row, one more than a wave's 64.  T = 300 is more than a workgroup's 256 threads: the "none selected"
+    count and the ranks span loop trips; T = 2 is [CLS] [SEP] everywhere (every sample forced).  B = 40: with R = 37 the rows in
+    front of a selected one (up to 39 x 37) are far more than a wave's lanes, and the four waves of a sample's workgroup walk ten
+    samples each.  Batches: region counts {R, 0, 1} together (both ragged modes x both text sources), B = 1 of each kind (its own
+    text and another sample's), 40 samples with repeats.  Each with prob 0, 0.15 and 1 for MLM and MRFR, and as ITM."""
+    a = synth(D, R, T, token_types, seed=D + R + T)
+    d = to_device(a)
+    rng = np.random.default_rng(R + T)
+    big = np.concatenate([rng.permutation(N), rng.integers(0, N, 40 - N)])
+    batches = [([0, 1, 2], True), ([0], False), ([1], False), ([2], False), (big, False)]
+    selected = 0
+    for sel, full in batches:
+        sel = np.asarray(sel)
+        if len(sel) == 1:
+            pairs = [(True, None), (False, np.array([(sel[0] + 1) % N]))]
+        else:
+            pairs = [(True, None), (False, mixed(sel))] + ([(False, None), (True, mixed(sel))] if full else [])
+        for ragged, txt_sel in pairs:
+            run_and_check('itm', a, d, sel, txt_sel, ragged, 0.0)
+            for task in ('mlm', 'mrfr'):
+                for prob in (0.0, 0.15, 1.0):
+                    want = run_and_check(task, a, d, sel, txt_sel, ragged, prob, twice=(prob == 0.15 and ragged))
+                    selected += want['n_masked'] if prob == 0.15 else 0
+    assert selected > 0
+
+
+def test_a_sample_is_masked_alike_in_every_batch_and_anew_in_every_epoch():
+    a = synth(8, 5, 16, False)
+    d = to_device(a)
+
+    def go(task, sel, draw):
+        sel = np.asarray(sel)
+        R = int(a['row_cnt'][sel].max())
+        L_out = int((a['txt_len'][sel] + a['row_cnt'][sel]).max())
+        dev = torch.tensor(sel, dtype=torch.int64, device='cuda')
+        return collate_pretrain_batch(task, dev, None, *[d[k] for k in ARRAY_KEYS], R=R, L_out=L_out, ragged_regions=True, seed=9,
+                                      draw=draw, prob=0.4)
+    one, two, later = go('mlm', [4, 7, 0, 10], 0), go('mlm', [10, 2, 4], 0), go('mlm', [4, 7, 0, 10], 1)
+    assert torch.equal(one['txt_labels'][0], two['txt_labels'][2]) and torch.equal(one['input_ids'][3], two['input_ids'][0])
+    assert not torch.equal(one['txt_labels'], later['txt_labels'])
+    one, two, later = go('mrfr', [4, 7, 0, 10], 0), go('mrfr', [10, 2, 4], 0), go('mrfr', [4, 7, 0, 10], 1)
+    assert torch.equal(one['img_masks'][0], two['img_masks'][2]) and torch.equal(one['img_masks'][3], two['img_masks'][0])
+    assert not torch.equal(one['img_masks'], later['img_masks'])
+
+
+# ---- refusals: an error code, a message, nothing launched ------------------------------------------------------------
+def raw_call(task, d, sel, outs, B, R, L_out, D=None, T=None, feat_ptr=None, drop=(), ds_null=False, sel_null=False, cfg_null=False,
+             ft_off=0, **cfg):
+    """the C call itself; drop: 'ds.<field>' / 'out.<name>' pointers passed as NULL"""
+    p = lambda t: None if t is None else t.data_ptr()
+    f = {k: (None if 'ds.' + k in drop else p(d[k])) for k in ARRAY_KEYS}
+    if feat_ptr is not None:
+        f['feat'] = feat_ptr
+    ds = _lib.UniterDatasetC(f['feat'], f['pos'], f['row_start'], f['row_cnt'], f['input_ids'], f['token_type_ids'], f['txt_len'],
+                             f['labels'], f['ids'], d['row_start'].shape[0], d['feat'].shape[0],
+                             d['feat'].shape[1] if D is None else D, d['input_ids'].shape[1] if T is None else T)
+    c = dict(dict(seed=1, draw=0, prob=0.15, cls=101, sep=102, pad=0, mask_token=103, vocab_lo=1000, vocab_hi=28996), **cfg)
+    mc = _lib.UniterMaskCfgC(c['seed'], c['draw'], c['prob'], c['cls'], c['sep'], c['pad'], c['mask_token'], c['vocab_lo'], c['vocab_hi'])
+    o = [None if 'out.' + k in drop else C.c_void_p(outs[k].t.data_ptr() + (ft_off if k == 'feat_targets' else 0)) for k in ALL_OUT]
+    return _lib.lib().uniter_collate_pretrain_batch(None if ds_null else C.byref(ds), None if sel_null else C.c_void_p(sel.data_ptr()),
+                                                    None, task, None if cfg_null else C.byref(mc), B, R, L_out, 0, *o, _lib.cur_stream())
+
+
+def test_refusals_return_their_codes_and_write_nothing():
+    D, R, T, B = 8, 5, 16, 3
+    a = synth(D, R, T, True)
+    d = to_device(a)
+    sel = torch.tensor([0, 1, 2], device='cuda')
+    L_out = T + R
+    outs = guarded_outputs('mrfr', B, R, D, T, L_out, True, every=True)      # (masked_positions: B * R rows -- MLM is only refused here)
+    MLM, MRFR, ITM = 0, 1, 2
+    E_ARG, E_SHAPE = -1, -2
+    cases = []
+    for task in (MLM, MRFR, ITM):
+        cases += [(task, 'a NULL dataset', E_ARG, dict(ds_null=True)), (task, 'a NULL selection', E_ARG, dict(sel_null=True))]
+        cases += [(task, 'dataset pointer %s NULL' % k, E_ARG, dict(drop=('ds.' + k,))) for k in ARRAY_KEYS if k != 'token_type_ids']
+        cases += [(task, 'output %s NULL' % k, E_ARG, dict(drop=('out.' + k,))) for k in COMMON if k != 'token_type_ids']
+        cases += [(task, 'D % 4 != 0', E_SHAPE, dict(D=6)), (task, 'a misaligned feat', E_ARG, dict(feat_ptr=d['feat'].data_ptr() + 4)),
+                  (task, 'B = 0', E_SHAPE, dict(B=0)), (task, 'B < 0', E_SHAPE, dict(B=-1)), (task, 'T = 0', E_SHAPE, dict(T=0)),
+                  (task, 'L_out = 0', E_SHAPE, dict(L_out=0)), (task, 'L_out > T + R', E_SHAPE, dict(L_out=T + R + 1))]
+    for task in (MLM, MRFR):
+        cases += [(task, 'a NULL configuration', E_ARG, dict(cfg_null=True)), (task, 'prob < 0', E_ARG, dict(prob=-0.01)),
+                  (task, 'prob > 1', E_ARG, dict(prob=1.5)), (task, 'prob NaN', E_ARG, dict(prob=float('nan'))),
+                  (task, 'masked_positions NULL', E_ARG, dict(drop=('out.masked_positions',))),
+                  (task, 'n_masked NULL', E_ARG, dict(drop=('out.n_masked',)))]
+    cases += [(MLM, 'txt_labels NULL', E_ARG, dict(drop=('out.txt_labels',))), (MLM, 'vocab_hi == vocab_lo', E_ARG, dict(vocab_hi=1000)),
+              (MLM, 'vocab_hi < vocab_lo', E_ARG, dict(vocab_lo=5, vocab_hi=4)), (MLM, 'T = 1', E_SHAPE, dict(T=1, L_out=1 + R)),
+              (MRFR, 'img_masks NULL', E_ARG, dict(drop=('out.img_masks',))), (MRFR, 'img_mask_tgt NULL', E_ARG, dict(drop=('out.img_mask_tgt',))),
+              (MRFR, 'feat_targets NULL', E_ARG, dict(drop=('out.feat_targets',))), (MRFR, 'a misaligned feat_targets', E_ARG, dict(ft_off=4)),
+              (ITM, 'targets NULL', E_ARG, dict(drop=('out.targets',))), (3, 'an unknown task', E_ARG, {}), (-1, 'a negative task', E_ARG, {})]
+    lib = _lib.lib()
+    for task, what, code, kw in cases:
+        rc = raw_call(task, d, sel, outs, **dict(dict(B=B, R=R, L_out=L_out), **kw))
+        assert rc == code, 'task %d, %s: rc %d' % (task, what, rc)
+        assert b'collate_pretrain_batch' in lib.uniter_last_error(), what
+    torch.cuda.synchronize()
+    for k, g in outs.items():
+        assert g.untouched(), '%s was written by a refused call' % k
+        g.check_guards(k)
+    # the wrapper refuses what is not a GPU tensor of the right type, and an unknown task, itself
+    arrays = [d[k] for k in ARRAY_KEYS]
+    with pytest.raises(_lib.UniterHipError, match='must live on the GPU'):
+        collate_pretrain_batch('mrfr', sel.cpu(), None, *arrays, R=R, L_out=L_out)
+    with pytest.raises(_lib.UniterHipError, match='txt_sel must be torch.int64'):
+        collate_pretrain_batch('itm', sel, sel.int(), *arrays, R=R, L_out=L_out)
+    with pytest.raises(ValueError, match='unknown task'):
+        collate_pretrain_batch('mrc', sel, None, *arrays, R=R, L_out=L_out)
+    with pytest.raises(_lib.UniterHipError, match='outside'):
+        collate_pretrain_batch('mlm', sel, None, *arrays, R=R, L_out=L_out, prob=1.25)
+    # and the valid call on the same buffers goes through
+    assert raw_call(MRFR, d, sel, outs, B, R, L_out) == 0
+    torch.cuda.synchronize()
+    written = DENSE['mrfr'] + ('masked_positions', 'feat_targets', 'n_masked')
+    assert not any(outs[k].untouched() for k in written)
+    assert all(outs[k].untouched() for k in ('txt_labels', 'targets'))
+    for k, g in outs.items():
+        g.check_guards(k)
