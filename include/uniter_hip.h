@@ -290,6 +290,12 @@ int uniter_wgrad_bf16_group_slots(int n, const int* M, const int* N, int max_wgs
  * chip's; nsplit_fixed > 0: the caller's k-pieces) -- host arithmetic; bench.py prices the launch's staging floor from it. */
 int uniter_wgrad_bf16_group_slots_cfg(int cfg, int n, const int* M, const int* N, int max_wgs);
 int uniter_gemm_bf16p_plan(int M, int N, int K, int avail_cus, int nsplit_fixed, int b_kmajor, int* cfg, int* nsplit);
+/* C / C_bf16 = (A . B) * aux_in on 128 x 256 tiles (cfg 7, one k-piece) AND, per 64 output rows, the column sums of the bf16 values
+ * it stored: colsum_part [(M + 63) / 64][N] floats, 16-byte aligned, N % 4 == 0; a row of it whose 64 output rows lie beyond M is
+ * not written.  The bf16 twin of uniter_gemm_x3_colpart; built for k-major weights (b_kmajor = 1: the input-gradient layout) only. */
+int uniter_gemm_bf16p_colpart(int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* C, int ldc,
+                              void* C_bf16, int ldcb, const void* aux_in, int aux_in_bf16, int ld_aux, float* colsum_part,
+                              void* stream);
 /* out[c] += sum_r X[r, c] for an x3 tensor X [rows][3][ldx] (bias gradient of intermediate.dense from dU). */
 int uniter_colsum_x3_add(const void* x3, int rows, int cols, int ldx, float* out, void* stream);
 /* uniter_ln_fwd_slabs / uniter_ln_bwd_rows_slabs whose operand copy for the next GEMM is x3 [M][3][H] instead of bf16 */

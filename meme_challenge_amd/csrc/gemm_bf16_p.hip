@@ -559,6 +559,17 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
   }
 }
 
+// the x aux product on 128 x 256 tiles, also leaving partial column sums of its STORED bf16 output: colsum_part[(i, n)] = sum of the
+// output rows 64 i .. 64 i + 63 of column n ([(M + 63) / 64][N] floats; the twin of uniter_gemm_x3_colpart: the product that writes
+// dU in the bf16 mode under UNITER_B16_PERSIST bits 4 + 8 -- model.cpp reaches it through gemm_b1p_run; this is the same call)
+extern "C" int uniter_gemm_bf16p_colpart(int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* C,
+                                         int ldc, void* C_bf16, int ldcb, const void* aux_in, int aux_in_bf16, int ld_aux,
+                                         float* colsum_part, void* stream) {
+  UCHECK_ARG(colsum_part, "gemm_bf16p_colpart: bad argument");
+  return gemm_b1p_run(7, 1, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, 0, C_bf16, ldcb, UNITER_EPI_MUL, nullptr, aux_in, aux_in_bf16,
+                      nullptr, 0, ld_aux, colsum_part, stream, LaunchOpts{});
+}
+
 // dW_p[M_p, N_p] (+)= A_p^T B_p for up to four products of one reduction length K (A_p [K][M_p], B_p [K][N_p] bf16, dW_p fp32 with
 // leading dimension N_p): ONE persistent launch of whole-K 128 x 256 tiles (216 for an encoder layer of UNITER-base: one round),
 // no atomics, bit-reproducible; optional riders (include/uniter_hip.h: uniter_x3_riders_t; 8 sum-of-squares slots per workgroup)
