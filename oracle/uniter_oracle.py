@@ -249,14 +249,16 @@ def self_attention(sd, lp, x, ext_mask, cfg, drop, layer, prec='fp32'):
     return c
 
 
-def bert_layer(sd, lp, x, ext_mask, cfg, drop, layer, prec='fp32'):
+def bert_layer(sd, lp, x, ext_mask, cfg, drop, layer, prec='fp32', hidden_index=None):
     # BertLayer.forward, model/layer.py:166-170
+    # hidden_index: optional int64 [B, L, H] element index of the two hidden-dropout sites (attention output, FFN output);
+    # None = the row-major index (b * L + l) * H + c of the padded layout (see packed_hidden_index)
     c = self_attention(sd, lp, x, ext_mask, cfg, drop, layer, prec)
     # BertSelfOutput.forward, model/layer.py:111-115
     o = lp + 'attention.output.'
     h = linear(c, sd[o + 'dense.weight'], sd[o + 'dense.bias'], prec)
     h = _apply_dropout(h, cfg['hidden_dropout_prob'], drop,
-                       philox.site_attn_out(layer))
+                       philox.site_attn_out(layer), index=hidden_index)
     y1 = layer_norm(h + x, sd[o + 'LayerNorm.weight'], sd[o + 'LayerNorm.bias'])
     # BertIntermediate.forward, model/layer.py:139-142
     u = linear(y1, sd[lp + 'intermediate.dense.weight'],
@@ -266,7 +268,7 @@ def bert_layer(sd, lp, x, ext_mask, cfg, drop, layer, prec='fp32'):
     o = lp + 'output.'
     h = linear(u, sd[o + 'dense.weight'], sd[o + 'dense.bias'], prec)
     h = _apply_dropout(h, cfg['hidden_dropout_prob'], drop,
-                       philox.site_ffn_out(layer))
+                       philox.site_ffn_out(layer), index=hidden_index)
     return layer_norm(h + y1, sd[o + 'LayerNorm.weight'],
                       sd[o + 'LayerNorm.bias'])
 
@@ -274,9 +276,10 @@ def bert_layer(sd, lp, x, ext_mask, cfg, drop, layer, prec='fp32'):
 def uniter_forward(sd, cfg, input_ids, position_ids, img_feat, img_pos_feat,
                    attention_mask, gather_index=None, img_masks=None,
                    output_all_encoded_layers=True, txt_type_ids=None,
-                   img_type_ids=None, drop=None, prefix='', return_embed=False, prec='fp32'):
+                   img_type_ids=None, drop=None, prefix='', return_embed=False, prec='fp32', hidden_index=None):
     """UniterModel.forward, model/model.py:336-367.  prec='bf16': the rounding points of the HIP
-    path's bf16 mode (see _LinearB16 above); 'fp32' is the reference arithmetic."""
+    path's bf16 mode (see _LinearB16 above); 'fp32' is the reference arithmetic.  hidden_index: the element
+    index of the encoder's hidden-dropout sites (bert_layer; packed_hidden_index builds the packed layout's)."""
     assert prec in ('fp32', 'bf16')
     p = prefix
     ext = attention_mask.unsqueeze(1).unsqueeze(2).to(torch.float32)
@@ -297,13 +300,39 @@ def uniter_forward(sd, cfg, input_ids, position_ids, img_feat, img_pos_feat,
     layers = []
     h = emb
     for i in range(cfg['num_hidden_layers']):          # model/model.py:282-292
-        h = bert_layer(sd, p + 'encoder.layer.%d.' % i, h, ext, cfg, drop, i, prec)
+        h = bert_layer(sd, p + 'encoder.layer.%d.' % i, h, ext, cfg, drop, i, prec, hidden_index)
         if output_all_encoded_layers:
             layers.append(h)
     out = layers if output_all_encoded_layers else h
     if return_embed:
         return out, emb
     return out
+
+
+def packed_hidden_index(seq_lens, L, H):
+    """Element index [B, L, H] of the encoder's hidden-dropout sites when the HIP path runs the PACKED layout
+    (UniterModel.pack_padded; csrc/model.cpp hands its row passes the Mp = sum(seq_lens) valid rows only):
+
+      * attention-output and FFN-output dropout of every layer (site_attn_out, site_ffn_out): the row passes draw element
+        r * H + c of an [Mp, H] tensor, r(b, l) = sum(seq_lens[:b]) + l the PACKED row of position l < seq_lens[b] (the
+        order of model.py's _pack: samples in turn, each sample's valid positions in turn) -- this function;
+      * attention probabilities: unchanged, ((b * nh + h) * L + i) * Lp + j with the PADDED L (Lp = L rounded up to 4): the
+        packed attention kernels address queries and keys by sample and local position;
+      * the two embedding sites: unchanged, the row-major index of the [B, T, H] text block and the [B, R, H] region block --
+        dropout is applied there before the rows are gathered into the packed tensor.
+
+    Padded positions (l >= seq_lens[b]) do not exist in the packed layout; here they get index 0, so the oracle computes
+    SOME value there, and the caller's loss must not read it (the HIP path returns zeros at those positions and drops any
+    gradient placed on them).  With every sample at full length the map is the identity of the default index."""
+    B = len(seq_lens)
+    idx = torch.zeros(B, L, H, dtype=torch.int64)
+    r0 = 0
+    for b, n in enumerate(seq_lens):
+        n = int(n)
+        rows = torch.arange(r0, r0 + n, dtype=torch.int64).view(n, 1)
+        idx[b, :n] = rows * H + torch.arange(H, dtype=torch.int64).view(1, H)
+        r0 += n
+    return idx
 
 
 def pooler(sd, prefix, hidden):
