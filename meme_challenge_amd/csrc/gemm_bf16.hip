@@ -486,10 +486,7 @@ int launch_b(GemmArgsB g, hipStream_t st, int slots, bool no_sk) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
   const int tiles = g.tiles_m * g.tiles_n;
-  const long panel = (long)BM * g.K * 4;
-  long bh = (3l << 19) / (panel > 0 ? panel : 1);
-  g.band_h = (int)(bh < 1 ? 1 : (bh > 16 ? 16 : bh));
-  if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
+  g.band_h = l2_band_height((long)BM * g.K * 4, g.tiles_m);
   const int grid = tiles < slots ? (tiles + 7) / 8 * 8 : slots;
   if (!no_sk && g.beta == 1 && g.epi == UNITER_EPI_NONE && !g.colsum_part && tiles >= 8) {
     const int rounds = (tiles + slots - 1) / slots;
@@ -537,29 +534,34 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
 
 }  // namespace
 
+// what neither launcher of this file can honour: x3 pieces, k-piece slabs, bf16 aux operands, a workspace
+static int refuse_unbuilt(const char* who, const GemmCall& c) {
+  UCHECK_ARG(!c.A.piece_stride && !c.B.piece_stride && !c.ps_copy && c.nsplit == 1 && !c.aux_in_bf16 && !c.aux_out_bf16 && !c.sk_ws,
+             "%s: no operand pieces, k-pieces, bf16 aux operands or workspace on these kernels", who);
+  return 0;
+}
+static GemmArgsB kernel_args(const GemmCall& c, const LaunchOpts& lo) {
+  return {c.M, c.N, c.K, c.A.p, c.A.ld, c.B.p, c.B.ld, c.C, c.ldc, (unsigned short*)c.Ccopy, c.ld_copy, c.epi, c.bias,
+          (const float*)c.aux_in, (float*)c.aux_out, c.ld_aux, c.beta, /*tiles_m, tiles_n*/ 0, 0, /*band_h*/ 1, c.colpart, lo.stamp};
+}
+
 // All-bf16 operands (resident activations / weight mirror), fp32 accumulate, fp32 and / or bf16 output.
 // lo: the stamp slot only -- these kernels set no wave priority (lo.prio is ignored here and in gemm_bf16_run) and are not persistent.
-int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B,
-                     int ldb, float* C, int ldc, void* Cb, int ldcb, int epilogue, const float* bias,
-                     const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
-                     const LaunchOpts& lo, int no_sk) {
-  UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16res: bad argument");
-  UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16res: bad epilogue %d", epilogue);
+int gemm_bf16res_run(int cfg, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, a_kmajor = c.A.kmajor, b_kmajor = c.B.kmajor;
+  UCHECK_RC(gemm_check_epilogue("gemm_bf16res", c, GEMM_EPI_ALL, false));
+  UCHECK_ARG(M > 0 && N > 0 && K > 0 && c.A.p && c.B.p && (c.C || c.Ccopy), "gemm_bf16res: bad argument");
+  UCHECK_RC(refuse_unbuilt("gemm_bf16res", c));
+  UCHECK_ARG(c.epi >= 0 && c.epi <= UNITER_EPI_MUL, "gemm_bf16res: bad epilogue %d", c.epi);
   UCHECK_ARG(!(a_kmajor && !b_kmajor), "gemm_bf16res: layout (A k-major, B k-contiguous) is not built");
-  UCHECK_ARG(!beta || (C && !Cb), "gemm_bf16res: C += needs the fp32 output and has no bf16 copy (the sum is formed by atomics)");
-  UCHECK_SHAPE((K % BKB == 0 || (a_kmajor && b_kmajor)) && lda % 8 == 0 && ldb % 8 == 0 &&
+  UCHECK_ARG(!c.beta || (c.C && !c.Ccopy), "gemm_bf16res: C += needs the fp32 output and has no bf16 copy (the sum is formed by atomics)");
+  UCHECK_SHAPE((K % BKB == 0 || (a_kmajor && b_kmajor)) && c.A.ld % 8 == 0 && c.B.ld % 8 == 0 &&
                (a_kmajor ? M % 8 == 0 : true) && (b_kmajor ? N % 8 == 0 : true) &&
-               ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0,
+               ((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0,
                "gemm_bf16res: K %% 64, leading dimensions %% 8 and 16-byte aligned operands required (M=%d N=%d K=%d)", M, N, K);
-  UCHECK_SHAPE((size_t)(a_kmajor ? K : M) * lda * 2 < (1ull << 31) && (size_t)(b_kmajor ? K : N) * ldb * 2 < (1ull << 31) &&
-               ((size_t)M + 128) * (ldc > 0 ? ldc : 1) * 4 < (1ull << 31) &&
-               ((size_t)M + 128) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31), "gemm_bf16res: operand beyond 31-bit offsets");
-  GemmArgsB g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-  g.Cb = (unsigned short*)Cb; g.ldcb = ldcb;
-  g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux; g.beta = beta;
-  g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = lo.stamp;
+  UCHECK_SHAPE((size_t)(a_kmajor ? K : M) * c.A.ld * 2 < (1ull << 31) && (size_t)(b_kmajor ? K : N) * c.B.ld * 2 < (1ull << 31) &&
+               gemm_f32_side_in_range(c, 128), "gemm_bf16res: operand beyond 31-bit offsets");
+  const GemmArgsB g = kernel_args(c, lo);
   if (cfg == 0) {
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     // measured (tests/tools/gemm_lab.py at M = 1424 / 2624 / 5248, profiles/r01_gemm_bf16_resident_tiles.txt): a
@@ -571,22 +573,21 @@ int gemm_bf16res_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, c
     const double e64 = (double)t64 / (768.0 * ((t64 + 767) / 768));
     cfg = (t128 >= 1024 || (!a_kmajor && e128 > e64)) ? 1 : 4;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (!a_kmajor && !b_kmajor) return dispatch_r<false, false>(cfg, g, st, no_sk != 0);
-  if (!a_kmajor && b_kmajor) return dispatch_r<false, true>(cfg, g, st, no_sk != 0);
-  return dispatch_r<true, true>(cfg, g, st, no_sk != 0);
+  hipStream_t st = (hipStream_t)c.stream;
+  if (!a_kmajor && !b_kmajor) return dispatch_r<false, false>(cfg, g, st, c.no_sk != 0);
+  if (!a_kmajor && b_kmajor) return dispatch_r<false, true>(cfg, g, st, c.no_sk != 0);
+  return dispatch_r<true, true>(cfg, g, st, c.no_sk != 0);
 }
 
 extern "C" int uniter_gemm_bf16res_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A,
                                        int lda, const void* B, int ldb, float* C, int ldc, void* C_bf16, int ldcb,
                                        int epilogue, const float* bias, const float* aux_in, float* aux_out,
                                        int ld_aux, int beta, void* stream) {
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || bias,
-             "gemm_bf16res: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
-             "gemm_bf16res: epilogue needs aux_in");
-  return gemm_bf16res_run(cfg, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, C_bf16, ldcb, epilogue, bias,
-                          aux_in, aux_out, ld_aux, beta, nullptr, stream, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, a_kmajor}; c.B = {B, ldb, 0, b_kmajor}; c.C = C; c.ldc = ldc;
+  c.Ccopy = C_bf16; c.ld_copy = ldcb;
+  c.epi = epilogue; c.bias = bias; c.aux_in = aux_in; c.aux_out = aux_out; c.ld_aux = ld_aux; c.beta = beta; c.stream = stream;
+  return gemm_bf16res_run(cfg, c, LaunchOpts{});
 }
 
 extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* stream) {
@@ -602,48 +603,40 @@ extern "C" int uniter_cast_bf16(const float* src, void* dst, size_t n, void* str
 
 // Same contract as gemm_f32_run, contraction on the bf16 matrix pipe.  Shapes the bf16 kernel does
 // not cover (K % 64 != 0, offsets beyond 31 bits) run on the exact fp32 kernel instead, which is handed lo whole.
-int gemm_bf16_run(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda,
-                  const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                  const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part, void* stream,
-                  const LaunchOpts& lo, int no_sk) {
-  UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C, "gemm_bf16: bad argument");
+int gemm_bf16_run(int cfg, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, a_kmajor = c.A.kmajor, b_kmajor = c.B.kmajor, lda = c.A.ld, ldb = c.B.ld;
+  UCHECK_RC(gemm_check_epilogue("gemm_bf16", c, GEMM_EPI_ALL, false));
+  UCHECK_ARG(M > 0 && N > 0 && K > 0 && c.A.p && c.B.p && c.C, "gemm_bf16: bad argument");
+  UCHECK_RC(refuse_unbuilt("gemm_bf16", c));
+  UCHECK_ARG(!c.Ccopy, "gemm_bf16: fp32 operands, fp32 output: no bf16 copy (gemm_bf16res_run writes one)");
   const bool ok = (K % BKB == 0 || (a_kmajor && b_kmajor)) && lda % 4 == 0 && ldb % 4 == 0 &&
-                  ((size_t)M + 128) * ldc * 4 < (1ull << 31) && ((size_t)M + 128) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31) &&
+                  ((size_t)M + 128) * c.ldc * 4 < (1ull << 31) && ((size_t)M + 128) * (c.ld_aux > 0 ? c.ld_aux : 1) * 4 < (1ull << 31) &&
                   (a_kmajor ? M % 4 == 0 : true) && (b_kmajor ? N % 4 == 0 : true) &&
                   (size_t)(a_kmajor ? K : M) * lda * 4 < (1ull << 31) &&
                   (size_t)(b_kmajor ? K : N) * ldb * 4 < (1ull << 31) &&
-                  ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0;
-  if (!ok)
-    return gemm_f32_run(0, 0, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in, aux_out,
-                        ld_aux, beta, colsum_part, stream, lo, no_sk);
-  UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16: bad epilogue %d", epilogue);
-  GemmArgsB g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-  g.Cb = nullptr; g.ldcb = 0;
-  g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux; g.beta = beta;
-  g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = lo.stamp;
+                  ((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0;
+  if (!ok) return gemm_f32_run(0, 0, c, lo);
+  UCHECK_ARG(c.epi >= 0 && c.epi <= UNITER_EPI_MUL, "gemm_bf16: bad epilogue %d", c.epi);
+  const GemmArgsB g = kernel_args(c, lo);
   if (cfg == 0) {
     // operand delivery bound: the biggest tile that still fills the chip
     // measured on MI355X (tests/tools/gemm_bf16_exp.py): 128x128 only pays once it fills the chip
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     cfg = t128 >= 448 ? 1 : 4;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (!a_kmajor && !b_kmajor) return dispatch_b<false, false>(cfg, g, st, no_sk != 0);
-  if (!a_kmajor && b_kmajor) return dispatch_b<false, true>(cfg, g, st, no_sk != 0);
-  if (a_kmajor && b_kmajor) return dispatch_b<true, true>(cfg, g, st, no_sk != 0);
-  return dispatch_b<true, false>(cfg, g, st, no_sk != 0);
+  hipStream_t st = (hipStream_t)c.stream;
+  if (!a_kmajor && !b_kmajor) return dispatch_b<false, false>(cfg, g, st, c.no_sk != 0);
+  if (!a_kmajor && b_kmajor) return dispatch_b<false, true>(cfg, g, st, c.no_sk != 0);
+  if (a_kmajor && b_kmajor) return dispatch_b<true, true>(cfg, g, st, c.no_sk != 0);
+  return dispatch_b<true, false>(cfg, g, st, c.no_sk != 0);
 }
 
 extern "C" int uniter_gemm_bf16_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,
                                     int lda, const float* B, int ldb, float* C, int ldc, int epilogue,
                                     const float* bias, const float* aux_in, float* aux_out, int ld_aux, int beta,
                                     void* stream) {
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || bias,
-             "gemm_bf16: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
-             "gemm_bf16: epilogue needs aux_in");
-  return gemm_bf16_run(cfg, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in, aux_out,
-                       ld_aux, beta, nullptr, stream, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, a_kmajor}; c.B = {B, ldb, 0, b_kmajor}; c.C = C; c.ldc = ldc;
+  c.epi = epilogue; c.bias = bias; c.aux_in = aux_in; c.aux_out = aux_out; c.ld_aux = ld_aux; c.beta = beta; c.stream = stream;
+  return gemm_bf16_run(cfg, c, LaunchOpts{});
 }

@@ -533,10 +533,7 @@ template <int BM>
 void plan_tiles(GArgsD& g, int BN) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
-  const long panel = (long)BM * g.K * 2;
-  long bh = (3l << 19) / (panel > 0 ? panel : 1);
-  g.band_h = (int)(bh < 1 ? 1 : (bh > 16 ? 16 : bh));
-  if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
+  g.band_h = l2_band_height((long)BM * g.K * 2, g.tiles_m);
 }
 
 template <int BM, int BN, bool AKM, bool BKM, bool SWAP, int ST, int EPI>
@@ -590,47 +587,40 @@ int dispatch_epi(int cfg, const GArgsD& g, hipStream_t st) {
 // cfg: 1 = 128x128 (2 stages), 2 = 128x256, 3 = 256x128, 4 = 128x128 (3 stages), 5 = 64x128 (2 waves); 0 = choose;
 // 6 / 7 / 8 = the persistent loader / compute kernels of gemm_bf16_p.hip (128 x 128 / 128 x 256 / 128 x 192 tiles).
 // beta = 1: C += A.B through fp32 atomics (lane = column orientation; no epilogue, no bf16 output).
-int gemm_bf16v2_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda,
-                    const void* B, int ldb, float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue,
-                    const float* bias, const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16,
-                    int ld_aux, int beta, void* stream, const LaunchOpts& lo) {
-  UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16v2: bad argument");
-  UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm_bf16v2: bad epilogue %d", epilogue);
-  UCHECK_ARG(!a_kmajor || (b_kmajor && epilogue == UNITER_EPI_NONE && !Cb),
+int gemm_bf16v2_run(int cfg, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, a_kmajor = c.A.kmajor, b_kmajor = c.B.kmajor, nsplit = c.nsplit, beta = c.beta;
+  UCHECK_RC(gemm_check_epilogue("gemm_bf16v2", c, GEMM_EPI_ALL, true));
+  UCHECK_ARG(M > 0 && N > 0 && K > 0 && c.A.p && c.B.p && (c.C || c.Ccopy), "gemm_bf16v2: bad argument");
+  UCHECK_ARG(!c.A.piece_stride && !c.B.piece_stride && !c.ps_copy && !c.sk_ws, "gemm_bf16v2: bf16 operands have no pieces, and no launch of this family takes a workspace");
+  UCHECK_ARG(c.epi >= 0 && c.epi <= UNITER_EPI_MUL, "gemm_bf16v2: bad epilogue %d", c.epi);
+  UCHECK_ARG(!a_kmajor || (b_kmajor && c.epi == UNITER_EPI_NONE && !c.Ccopy),
              "gemm_bf16v2: A k-major only as the weight-gradient layout (both operands k-major, no epilogue, fp32 output)");
-  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (C && !Cb && !beta && c_split_stride >= (long)M * ldc)),
+  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (c.C && !c.Ccopy && !beta && c.c_split_stride >= (long)M * c.ldc)),
              "gemm_bf16v2: split-K needs fp32 slabs (no bf16 output, no accumulate)");
-  UCHECK_ARG(!beta || (C && !Cb && epilogue == UNITER_EPI_NONE), "gemm_bf16v2: C += has no epilogue and no bf16 copy");
-  UCHECK_SHAPE((K % KT == 0 || (a_kmajor && b_kmajor)) && lda % 8 == 0 && ldb % 8 == 0 && N % 8 == 0 && (!a_kmajor || M % 8 == 0) &&
-               ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && (ldc % 4 == 0) && (ldcb % 8 == 0) &&
-               (ld_aux % 4 == 0) && ((uintptr_t)C & 15) == 0 && ((uintptr_t)Cb & 15) == 0 &&
-               ((uintptr_t)aux_in & 15) == 0 && ((uintptr_t)aux_out & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+  UCHECK_ARG(!beta || (c.C && !c.Ccopy && c.epi == UNITER_EPI_NONE), "gemm_bf16v2: C += has no epilogue and no bf16 copy");
+  UCHECK_SHAPE((K % KT == 0 || (a_kmajor && b_kmajor)) && c.A.ld % 8 == 0 && c.B.ld % 8 == 0 && N % 8 == 0 && (!a_kmajor || M % 8 == 0) &&
+               ((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0 && gemm_side_buffers_aligned(c),
                "gemm_bf16v2: K %% 64, N %% 8, leading dimensions %% 8 (bf16) / %% 4 (fp32) and 16-byte aligned "
                "buffers required (M=%d N=%d K=%d)", M, N, K);
-  UCHECK_SHAPE((size_t)(a_kmajor ? K : M + 256) * lda * 2 < (1ull << 31) && (size_t)(b_kmajor ? K + 64 : N + 256) * ldb * 2 < (1ull << 31) &&
-               ((size_t)M + 256) * (ldc > 0 ? ldc : 1) * 4 < (1ull << 31) &&
-               ((size_t)M + 256) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31), "gemm_bf16v2: operand beyond 31-bit offsets");
+  UCHECK_SHAPE((size_t)(a_kmajor ? K : M + 256) * c.A.ld * 2 < (1ull << 31) && (size_t)(b_kmajor ? K + 64 : N + 256) * c.B.ld * 2 < (1ull << 31) &&
+               gemm_f32_side_in_range(c, 256), "gemm_bf16v2: operand beyond 31-bit offsets");
   if ((cfg & 0xff) >= 6) {
     UCHECK_ARG(!a_kmajor && !beta, "gemm_bf16v2: cfg %d (persistent kernels) runs forward / input-gradient layouts without accumulate "
                "(weight gradients: uniter_wgrad_bf16_group, cfg 7)", cfg & 0xff);
-    return gemm_b1p_run(cfg & 0xff, nsplit, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, c_split_stride, Cb, ldcb, epilogue, bias, aux_in,
-                        aux_in_bf16, aux_out, aux_out_bf16, ld_aux, nullptr, stream, lo);
+    return gemm_b1p_run(cfg & 0xff, c, lo);
   }
-  GArgsD g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-  g.c_split_stride = c_split_stride; g.Cb = (unsigned short*)Cb; g.ldcb = ldcb; g.epi = epilogue; g.bias = bias;
-  g.aux_in = aux_in; g.aux_in_bf16 = aux_in_bf16; g.aux_out = aux_out; g.aux_out_bf16 = aux_out_bf16; g.ld_aux = ld_aux;
-  g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.nsplit = nsplit;
-  g.dbg = cfg >> 8; cfg &= 0xff;
-  g.stamp = lo.stamp;
-  g.prio = lo.prio;
+  UCHECK_ARG(!c.colpart, "gemm_bf16v2: column partials ride on the persistent kernels (cfg 7)");
+  GArgsD g = {M, N, K, c.A.p, c.A.ld, c.B.p, c.B.ld, c.C, c.ldc, c.c_split_stride, (unsigned short*)c.Ccopy, c.ld_copy, c.epi, c.bias,
+              c.aux_in, c.aux_in_bf16, c.aux_out, c.aux_out_bf16, c.ld_aux, /*tiles_m, tiles_n*/ 0, 0, /*band_h*/ 1, nsplit,
+              lo.stamp, lo.prio, /*dbg*/ cfg >> 8};
+  cfg &= 0xff;
   if (cfg == 0) {
     // few tiles and one k-piece (the attention-output products: 126 tiles of 128 x 128 for 256 CUs): 64 x 128 tiles,
     // twice the workgroups (12.0 -> 10.6 us forward, 11.7 -> 10.0 us input gradient; profiles/r02_gemm_bf16_v2.txt)
     const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
     cfg = (!a_kmajor && nsplit == 1 && tiles <= 160) ? 5 : 1;
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
   if (a_kmajor) return beta ? dispatch_wgrad<false>(cfg, g, st) : dispatch_wgrad<true>(cfg, g, st);
   if (beta) return b_kmajor ? dispatch_cfg<true, false, UNITER_EPI_NONE>(cfg, g, st) : dispatch_cfg<false, false, UNITER_EPI_NONE>(cfg, g, st);
   return b_kmajor ? dispatch_epi<true>(cfg, g, st) : dispatch_epi<false>(cfg, g, st);
@@ -652,55 +642,39 @@ static int wgrad_group_grid(int total, int max_wgs, int cu_reserve) {
   if (cap >= 8 && grid > cap) grid = cap;
   return grid;
 }
-static int wgrad_group_tiles(int n, const int* Mo, const int* No) {
-  int total = 0;
-  for (int p = 0; p < n; ++p) total += ((Mo[p] + 127) / 128) * ((No[p] + 127) / 128);
-  return total;
-}
-// sum-of-squares slots a launch with riders writes (4 per workgroup)
+// sum-of-squares slots a launch with riders writes (4 compute waves per workgroup)
 int gemm_bf16v2_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs, int cu_reserve) {
-  if (!Mo || !No || n < 1 || n > 4) return 0;
-  return 4 * wgrad_group_grid(wgrad_group_tiles(n, Mo, No), max_wgs, cu_reserve);
+  return rider_slots(4, wgrad_group_grid(wgrad_group_tiles(n, Mo, No, 128), max_wgs, cu_reserve));
 }
 // the smallest grid on which the tiles take no more rounds than on one workgroup per CU
 int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No, int cu_reserve) {
-  if (!Mo || !No || n < 1 || n > 4) return 0;
-  const int total = wgrad_group_tiles(n, Mo, No);
-  const int full = wgrad_group_grid(total, 0, cu_reserve);
-  const int rounds = (total + full - 1) / full;
-  const int wgs = ((total + rounds - 1) / rounds + 7) / 8 * 8;
-  return wgs < full ? wgs : full;
+  const int total = wgrad_group_tiles(n, Mo, No, 128);
+  return balanced_grid(total, wgrad_group_grid(total, 0, cu_reserve));
 }
 
-int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A,
-                            const void* const* B, float* const* dW, void* stream, int overwrite, int max_wgs,
-                            uniter_x3_riders_t* riders, const LaunchOpts& lo) {
-  UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_group: bad argument");
-  if (cfg == 7) return gemm_b1p_wgrad_group(n, Mo, No, K, A, B, dW, stream, overwrite, max_wgs, riders, lo);      // 128 x 256 tiles, persistent
+int gemm_bf16v2_wgrad_group(int cfg, const WgradGroupCall& c, const LaunchOpts& lo) {
+  static const char* const who = "wgrad_group";
+  UCHECK_RC(wgrad_group_check(who, c));
+  if (cfg == 7) return gemm_b1p_wgrad_group(c, lo);      // 128 x 256 tiles, persistent
+  UCHECK_ARG(!c.sk_ws, "%s: no launch of the bf16 family takes a workspace", who);
   GGroupD G;
   memset(&G.x, 0, sizeof(G.x));
-  int total = 0;
-  for (int p = 0; p < 4; ++p) {
-    G.start[p] = total;
-    if (p >= n) { G.p[p] = G.p[0]; continue; }
-    UCHECK_ARG(Mo[p] > 0 && No[p] > 0 && A[p] && B[p] && dW[p], "wgrad_group: bad product %d", p);
-    UCHECK_SHAPE(Mo[p] % 8 == 0 && No[p] % 8 == 0 && ((uintptr_t)A[p] & 15) == 0 && ((uintptr_t)B[p] & 15) == 0 &&
-                 ((uintptr_t)dW[p] & 15) == 0 && (size_t)(K + 64) * (Mo[p] > No[p] ? Mo[p] : No[p]) * 2 < (1ull << 31) &&
-                 ((size_t)Mo[p] + 256) * No[p] * 4 < (1ull << 31),
-                 "wgrad_group: M, N %% 8, 16-byte aligned buffers, 31-bit offsets (product %d: %d x %d, K=%d)", p, Mo[p], No[p], K);
-    GArgsD& g = G.p[p];
-    g.M = Mo[p]; g.N = No[p]; g.K = K; g.A = A[p]; g.lda = Mo[p]; g.B = B[p]; g.ldb = No[p]; g.C = dW[p]; g.ldc = No[p];
-    g.c_split_stride = 0; g.Cb = nullptr; g.ldcb = 0; g.epi = overwrite ? UNITER_EPI_NONE : UNITER_EPI_ADD; g.bias = nullptr;
-    g.aux_in = overwrite ? nullptr : dW[p]; g.aux_in_bf16 = 0; g.aux_out = nullptr; g.aux_out_bf16 = 0; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = lo.stamp; g.dbg = 0; g.prio = 0;
-    plan_tiles<128>(g, 128);
-    total += g.tiles_m * g.tiles_n;
-  }
-  G.start[4] = total;
-  for (int p = n; p < 4; ++p) G.start[p] = total;
-  const int grid = wgrad_group_grid(total, max_wgs, lo.cu_reserve);
-  hipStream_t st = (hipStream_t)stream;
-  if (riders) {
+  UCHECK_RC(wgrad_group_walk(who, c, G.start, [&](int p) { return wgrad_bf16_product_in_range(c, p); },
+    [&](int p) {
+      const int Mo = c.Mo[p], No = c.No[p];
+      float* const dW = c.dW[p];
+      GArgsD& g = G.p[p];
+      g = {Mo, No, c.K, c.A[p], Mo, c.B[p], No, dW, No, /*c_split_stride*/ 0, /*Cb*/ nullptr, 0,
+           c.overwrite ? UNITER_EPI_NONE : UNITER_EPI_ADD, /*bias*/ nullptr, /*aux_in*/ c.overwrite ? nullptr : dW, 0, /*aux_out*/ nullptr, 0,
+           /*ld_aux*/ No, /*tiles_m, tiles_n, band_h*/ 0, 0, 1, /*nsplit*/ 1, lo.stamp, /*prio*/ 0, /*dbg*/ 0};
+      plan_tiles<128>(g, 128);
+      return g.tiles_m * g.tiles_n;
+    },
+    [&](int p) { G.p[p] = G.p[0]; }));
+  const int grid = wgrad_group_grid(G.start[4], c.max_wgs, lo.cu_reserve);
+  hipStream_t st = (hipStream_t)c.stream;
+  const int overwrite = c.overwrite;
+  if (uniter_x3_riders_t* riders = c.riders) {
     UCHECK_ARG(cfg != 4, "wgrad_group: riders ride on the two-stage form (cfg 1)");
     riders->grid = grid;
     UCHECK_RC(riders_prepare(*riders, "wgrad_bf16_group"));
@@ -721,15 +695,17 @@ int gemm_bf16v2_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K,
   return 0;
 }
 
-extern "C" int uniter_wgrad_bf16_group(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
-                                       const void* const* B, float* const* dW, void* stream) {
-  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, 0, 0, nullptr, LaunchOpts{});
-}
-
 extern "C" int uniter_wgrad_bf16_group_riders(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                               const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                               uniter_x3_riders_t* riders, void* stream) {
-  return gemm_bf16v2_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, LaunchOpts{});
+  WgradGroupCall c;
+  c.n = n; c.Mo = M; c.No = N; c.K = K; c.A = A; c.B = B; c.dW = dW; c.overwrite = overwrite; c.max_wgs = max_wgs; c.riders = riders;
+  c.stream = stream;
+  return gemm_bf16v2_wgrad_group(cfg, c, LaunchOpts{});
+}
+extern "C" int uniter_wgrad_bf16_group(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
+                                       const void* const* B, float* const* dW, void* stream) {
+  return uniter_wgrad_bf16_group_riders(cfg, n, M, N, K, A, B, dW, 0, 0, nullptr, stream);
 }
 extern "C" int uniter_wgrad_bf16_group_slots(int n, const int* M, const int* N, int max_wgs) {
   return gemm_bf16v2_wgrad_group_slots(n, M, N, max_wgs, 0);
@@ -768,12 +744,10 @@ extern "C" int uniter_gemm_bf16v2_cfg(int cfg, int nsplit, int a_kmajor, int b_k
                                       long c_split_stride, void* C_bf16, int ldcb, int epilogue, const float* bias,
                                       const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16,
                                       int ld_aux, int beta, void* stream) {
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || bias,
-             "gemm_bf16v2: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
-             "gemm_bf16v2: epilogue needs aux_in");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || aux_out,
-             "gemm_bf16v2: epilogue needs aux_out");
-  return gemm_bf16v2_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, c_split_stride, C_bf16, ldcb,
-                         epilogue, bias, aux_in, aux_in_bf16, aux_out, aux_out_bf16, ld_aux, beta, stream, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, a_kmajor}; c.B = {B, ldb, 0, b_kmajor};
+  c.C = C; c.ldc = ldc; c.c_split_stride = c_split_stride; c.nsplit = nsplit; c.Ccopy = C_bf16; c.ld_copy = ldcb;
+  c.epi = epilogue; c.bias = bias; c.aux_in = aux_in; c.aux_in_bf16 = aux_in_bf16; c.aux_out = aux_out; c.aux_out_bf16 = aux_out_bf16;
+  c.ld_aux = ld_aux; c.beta = beta; c.stream = stream;
+  return gemm_bf16v2_run(cfg, c, LaunchOpts{});
 }

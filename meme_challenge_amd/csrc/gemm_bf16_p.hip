@@ -504,27 +504,23 @@ int gemm_b1p_pick_split(int M, int N, int K, int avail, int cu_reserve) {
 }
 
 // C / Cb = epi(A . B^T) on bf16 operands (fp32 accumulate): the persistent loader / compute kernels.  cfg 6..8 (dispatch_geo), 0 = choose.
-int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
-                 float* C, int ldc, long c_split_stride, void* Cb, int ldcb, int epilogue, const float* bias,
-                 const void* aux_in, int aux_in_bf16, void* aux_out, int aux_out_bf16, int ld_aux, float* colpart, void* stream,
-                 const LaunchOpts& lo) {
-  UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cb), "gemm_bf16p: bad argument");
-  UCHECK_ARG(epilogue == UNITER_EPI_NONE || epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_BIAS_GELU_D ||
-             epilogue == UNITER_EPI_MUL, "gemm_bf16p: epilogue %d is not built for the persistent kernels (none, bias, + aux, bias + GELU + gelu', x aux)", epilogue);
-  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (C && !Cb && c_split_stride >= (long)M * ldc)),
+int gemm_b1p_run(int cfg, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, b_kmajor = c.B.kmajor, nsplit = c.nsplit, epilogue = c.epi;
+  UCHECK_ARG(M > 0 && N > 0 && K > 0 && c.A.p && c.B.p && (c.C || c.Ccopy), "gemm_bf16p: bad argument");
+  UCHECK_ARG(!c.A.kmajor && !c.beta && !c.A.piece_stride && !c.B.piece_stride && !c.ps_copy && !c.sk_ws,
+             "gemm_bf16p: forward / input-gradient layouts of bf16 operands without accumulate (no pieces, no workspace)");
+  UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL && (GEMM_EPI_PERSISTENT >> epilogue & 1),
+             "gemm_bf16p: epilogue %d is not built for the persistent kernels (none, bias, + aux, bias + GELU + gelu', x aux)", epilogue);
+  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (c.C && !c.Ccopy && c.c_split_stride >= (long)M * c.ldc)),
              "gemm_bf16p: split-K needs fp32 slabs (no bf16 output)");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU_D) || bias, "gemm_bf16p: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in, "gemm_bf16p: epilogue needs aux_in");
-  UCHECK_ARG(epilogue != UNITER_EPI_BIAS_GELU_D || aux_out, "gemm_bf16p: epilogue needs aux_out");
-  UCHECK_ARG(!colpart || (epilogue == UNITER_EPI_MUL && nsplit == 1 && ((uintptr_t)colpart & 15) == 0 && N % 4 == 0),
+  UCHECK_RC(gemm_check_epilogue("gemm_bf16p", c, GEMM_EPI_PERSISTENT, true));
+  UCHECK_ARG(!c.colpart || (epilogue == UNITER_EPI_MUL && nsplit == 1 && ((uintptr_t)c.colpart & 15) == 0 && N % 4 == 0),
              "gemm_bf16p: column partials ride on the x aux epilogue, one k-piece");
-  UCHECK_SHAPE(K % KT == 0 && lda % 8 == 0 && ldb % 8 == 0 && N % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-               (ldc % 4 == 0) && (ldcb % 8 == 0) && (ld_aux % 4 == 0) && ((uintptr_t)C & 15) == 0 && ((uintptr_t)Cb & 15) == 0 &&
-               ((uintptr_t)aux_in & 15) == 0 && ((uintptr_t)aux_out & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+  UCHECK_SHAPE(K % KT == 0 && c.A.ld % 8 == 0 && c.B.ld % 8 == 0 && N % 8 == 0 && ((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0 &&
+               gemm_side_buffers_aligned(c),
                "gemm_bf16p: K %% 64, N %% 8, leading dimensions %% 8 (bf16) / %% 4 (fp32) and 16-byte aligned buffers required (M=%d N=%d K=%d)", M, N, K);
-  UCHECK_SHAPE((size_t)(M + 256) * lda * 2 < (1ull << 31) && (size_t)(b_kmajor ? K + 64 : N + 256) * ldb * 2 < (1ull << 31) &&
-               ((size_t)M + 256) * (ldc > 0 ? ldc : 1) * 4 < (1ull << 31) && ((size_t)M + 256) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31),
-               "gemm_bf16p: operand beyond 31-bit offsets");
+  UCHECK_SHAPE((size_t)(M + 256) * c.A.ld * 2 < (1ull << 31) && (size_t)(b_kmajor ? K + 64 : N + 256) * c.B.ld * 2 < (1ull << 31) &&
+               gemm_f32_side_in_range(c, 256), "gemm_bf16p: operand beyond 31-bit offsets");
   if (cfg == 0) {
     int ns_;
     b1p_choose(M, N, K, persistent_grid(1 << 20, 0, lo.cu_reserve), nsplit, b_kmajor != 0, &cfg, &ns_);
@@ -532,17 +528,14 @@ int gemm_b1p_run(int cfg, int nsplit, int b_kmajor, int M, int N, int K, const v
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
   P1Args& g = G.p[0];
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.c_split_stride = c_split_stride;
-  g.Cb = (unsigned short*)Cb; g.ldcb = ldcb; g.bias = bias; g.aux_in = aux_in; g.aux_in_bf16 = aux_in_bf16; g.aux_out = aux_out;
-  g.aux_out_bf16 = aux_out_bf16; g.ld_aux = ld_aux; g.nsplit = nsplit; g.colpart = colpart;
-  g.stamp = lo.stamp;
-  g.prio = lo.prio;
+  g = {M, N, K, c.A.p, c.A.ld, c.B.p, c.B.ld, c.C, c.ldc, c.c_split_stride, (unsigned short*)c.Ccopy, c.ld_copy, c.bias,
+       c.aux_in, c.aux_in_bf16, c.aux_out, c.aux_out_bf16, c.ld_aux, /*tiles_m, tiles_n, band_h*/ 0, 0, 1, nsplit, lo.stamp, lo.prio, c.colpart};
   plan_tiles_p(g, 128, cfg == 7 ? 256 : cfg == 8 ? 192 : 128);
   const int total = g.tiles_m * g.tiles_n * nsplit;
   for (int p = 1; p < 4; ++p) G.p[p] = g;
   G.start[0] = 0;
   for (int p = 1; p <= 4; ++p) G.start[p] = total;
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
   if (b_kmajor) {
     switch (epilogue) {
       case UNITER_EPI_NONE: return dispatch_geo<true, P1_NONE>(cfg, G, lo.cu_reserve, st);
@@ -566,49 +559,39 @@ extern "C" int uniter_gemm_bf16p_colpart(int b_kmajor, int M, int N, int K, cons
                                          int ldc, void* C_bf16, int ldcb, const void* aux_in, int aux_in_bf16, int ld_aux,
                                          float* colsum_part, void* stream) {
   UCHECK_ARG(colsum_part, "gemm_bf16p_colpart: bad argument");
-  return gemm_b1p_run(7, 1, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, 0, C_bf16, ldcb, UNITER_EPI_MUL, nullptr, aux_in, aux_in_bf16,
-                      nullptr, 0, ld_aux, colsum_part, stream, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, 0}; c.B = {B, ldb, 0, b_kmajor}; c.C = C; c.ldc = ldc; c.Ccopy = C_bf16; c.ld_copy = ldcb;
+  c.epi = UNITER_EPI_MUL; c.aux_in = aux_in; c.aux_in_bf16 = aux_in_bf16; c.ld_aux = ld_aux; c.colpart = colsum_part; c.stream = stream;
+  return gemm_b1p_run(7, c, LaunchOpts{});
 }
 
 // dW_p[M_p, N_p] (+)= A_p^T B_p for up to four products of one reduction length K (A_p [K][M_p], B_p [K][N_p] bf16, dW_p fp32 with
 // leading dimension N_p): ONE persistent launch of whole-K 128 x 256 tiles (216 for an encoder layer of UNITER-base: one round),
 // no atomics, bit-reproducible; optional riders (include/uniter_hip.h: uniter_x3_riders_t; 8 sum-of-squares slots per workgroup)
-static int b1p_wgrad_tiles(int n, const int* Mo, const int* No) {
-  int total = 0;
-  for (int p = 0; p < n; ++p) total += ((Mo[p] + 127) / 128) * ((No[p] + 255) / 256);
-  return total;
-}
 int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs, int cu_reserve) {
-  if (!Mo || !No || n < 1 || n > 4) return 0;
-  return 8 * persistent_grid(b1p_wgrad_tiles(n, Mo, No), max_wgs, cu_reserve);
+  return rider_slots(8, persistent_grid(wgrad_group_tiles(n, Mo, No, 256), max_wgs, cu_reserve));
 }
 // lo: the stamp slot and the reserve; the launch runs at the default wave priority whatever lo.prio says
-int gemm_b1p_wgrad_group(int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B, float* const* dW,
-                         void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders, const LaunchOpts& lo) {
-  UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_bf16p_group: bad argument");
+int gemm_b1p_wgrad_group(const WgradGroupCall& c, const LaunchOpts& lo) {
+  static const char* const who = "wgrad_bf16p_group";
+  UCHECK_ARG(!c.sk_ws, "%s: no launch of the bf16 family takes a workspace", who);
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
-  int total = 0;
-  for (int p = 0; p < 4; ++p) {
-    G.start[p] = total;
-    if (p >= n) { G.p[p] = G.p[0]; continue; }
-    UCHECK_ARG(Mo[p] > 0 && No[p] > 0 && A[p] && B[p] && dW[p], "wgrad_bf16p_group: bad product %d", p);
-    UCHECK_SHAPE(Mo[p] % 8 == 0 && No[p] % 8 == 0 && ((uintptr_t)A[p] & 15) == 0 && ((uintptr_t)B[p] & 15) == 0 &&
-                 ((uintptr_t)dW[p] & 15) == 0 && (size_t)(K + 64) * (Mo[p] > No[p] ? Mo[p] : No[p]) * 2 < (1ull << 31) &&
-                 ((size_t)Mo[p] + 256) * No[p] * 4 < (1ull << 31),
-                 "wgrad_bf16p_group: M, N %% 8, 16-byte aligned buffers, 31-bit offsets (product %d: %d x %d, K=%d)", p, Mo[p], No[p], K);
-    P1Args& g = G.p[p];
-    g.M = Mo[p]; g.N = No[p]; g.K = K; g.A = A[p]; g.lda = Mo[p]; g.B = B[p]; g.ldb = No[p]; g.C = dW[p]; g.ldc = No[p];
-    g.c_split_stride = 0; g.Cb = nullptr; g.ldcb = 0; g.bias = nullptr;
-    g.aux_in = overwrite ? nullptr : dW[p]; g.aux_in_bf16 = 0; g.aux_out = nullptr; g.aux_out_bf16 = 0; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = lo.stamp; g.prio = 0; g.colpart = nullptr;
-    plan_tiles_p(g, 128, 256);
-    total += g.tiles_m * g.tiles_n;
-  }
-  G.start[4] = total;
-  for (int p = n; p < 4; ++p) G.start[p] = total;
-  hipStream_t st = (hipStream_t)stream;
-  if (riders) {
+  UCHECK_RC(wgrad_group_walk(who, c, G.start, [&](int p) { return wgrad_bf16_product_in_range(c, p); },
+    [&](int p) {
+      const int Mo = c.Mo[p], No = c.No[p];
+      float* const dW = c.dW[p];
+      P1Args& g = G.p[p];
+      g = {Mo, No, c.K, c.A[p], Mo, c.B[p], No, dW, No, /*c_split_stride*/ 0, /*Cb*/ nullptr, 0, /*bias*/ nullptr,
+           /*aux_in*/ c.overwrite ? nullptr : dW, 0, /*aux_out*/ nullptr, 0, /*ld_aux*/ No, /*tiles_m, tiles_n, band_h*/ 0, 0, 1,
+           /*nsplit*/ 1, lo.stamp, /*prio*/ 0, /*colpart*/ nullptr};
+      plan_tiles_p(g, 128, 256);
+      return g.tiles_m * g.tiles_n;
+    },
+    [&](int p) { G.p[p] = G.p[0]; }));
+  const int total = G.start[4], overwrite = c.overwrite, max_wgs = c.max_wgs;
+  hipStream_t st = (hipStream_t)c.stream;
+  if (uniter_x3_riders_t* riders = c.riders) {
     UCHECK_ARG(!riders->colsum_out, "wgrad_bf16p_group: colsum_out does not ride on the 128 x 256 geometry (take the bias gradient from the "
                "producing product's column partials as a reduction job)");
     riders->grid = persistent_grid(total, max_wgs, lo.cu_reserve);

@@ -721,12 +721,7 @@ int launch_v3(GemmArgs g, hipStream_t st, int slots, bool allow_sk = true) {
   g.tiles_m = (g.M + BM - 1) / BM;
   g.tiles_n = (g.N + BN - 1) / BN;
   const int tiles = g.tiles_m * g.tiles_n;
-  {
-    const long panel = (long)BM * g.K * 4;
-    long bh = (3l << 19) / (panel > 0 ? panel : 1);
-    g.band_h = (int)(bh < 1 ? 1 : (bh > 16 ? 16 : bh));
-    if (g.band_h > g.tiles_m) g.band_h = g.tiles_m;
-  }
+  g.band_h = l2_band_height((long)BM * g.K * 4, g.tiles_m);
   int grid = tiles < slots ? (tiles + 7) / 8 * 8 : slots;
   // stream-K when the tiles fill the slots unevenly (only legal for a plain accumulating GEMM)
   const int sk_mode = uniter_switches().gemm_sk;     // 0 never, 1 heuristic, 2 whenever legal
@@ -785,89 +780,86 @@ int choose_cfg(int M, int N) {
 
 // dW_p[Mo_p, No_p] (+)= A_p^T B_p, p < n <= 4, A_p [K, Mo_p], B_p [K, No_p] fp32 (gemm_f32_wgrad_group_kernel); returns
 // UNITER_E_SHAPE for shapes the grouped kernel does not take (the caller then launches the products one by one)
-int gemm_f32_wgrad_group(int n, const int* Mo, const int* No, int K, const float* const* A, const float* const* B,
-                         float* const* dW, int overwrite, void* stream, const LaunchOpts& lo) {
-  UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_group_f32: bad argument");
+int gemm_f32_wgrad_group(const WgradGroupCall& c, const LaunchOpts& lo) {
+  static const char* const who = "wgrad_group_f32";
+  UCHECK_ARG(!c.riders && !c.max_wgs && !c.sk_ws, "%s: the fp32 launch takes no riders, no grid cap and no workspace", who);
   GemmGroup G = {};
-  int total = 0;
-  for (int p = 0; p < 4; ++p) {
-    G.start[p] = total;
-    if (p >= n) { G.A[p] = G.A[0]; G.B[p] = G.B[0]; G.C[p] = G.C[0]; G.M[p] = G.M[0]; G.N[p] = G.N[0];
-                  G.tiles_m[p] = G.tiles_m[0]; G.tiles_n[p] = G.tiles_n[0]; G.band_h[p] = G.band_h[0]; continue; }
-    UCHECK_ARG(Mo[p] > 0 && No[p] > 0 && A[p] && B[p] && dW[p], "wgrad_group_f32: bad product %d", p);
-    const bool ok = Mo[p] % 4 == 0 && No[p] % 4 == 0 && ((uintptr_t)A[p] & 15) == 0 && ((uintptr_t)B[p] & 15) == 0 &&
-                    (size_t)K * Mo[p] * 4 < (1ull << 31) && (size_t)K * No[p] * 4 < (1ull << 31) &&
-                    ((size_t)Mo[p] + 128) * No[p] * 4 < (1ull << 31);
-    if (!ok) { uniter_set_error("wgrad_group_f32: product %d (%d x %d, K = %d) outside the grouped kernel's range", p, Mo[p], No[p], K); return UNITER_E_SHAPE; }
-    G.A[p] = A[p]; G.B[p] = B[p]; G.C[p] = dW[p]; G.M[p] = Mo[p]; G.N[p] = No[p];
-    G.tiles_m[p] = (Mo[p] + 63) / 64; G.tiles_n[p] = (No[p] + 63) / 64;
-    const long panel = 64l * K * 4;
-    long bh = (3l << 19) / (panel > 0 ? panel : 1);
-    G.band_h[p] = (int)(bh < 1 ? 1 : (bh > 16 ? 16 : bh));
-    if (G.band_h[p] > G.tiles_m[p]) G.band_h[p] = G.tiles_m[p];
-    total += G.tiles_m[p] * G.tiles_n[p];
-  }
-  G.start[4] = total;
-  for (int p = n; p < 4; ++p) G.start[p] = total;
-  G.K = K; G.overwrite = overwrite; G.prio = lo.prio; G.stamp = lo.stamp;
+  const int K = c.K;
+  UCHECK_RC(wgrad_group_walk(who, c, G.start,
+    [&](int p) {
+      return c.Mo[p] % 4 == 0 && c.No[p] % 4 == 0 && ((uintptr_t)c.A[p] & 15) == 0 && ((uintptr_t)c.B[p] & 15) == 0 &&
+             (size_t)K * c.Mo[p] * 4 < (1ull << 31) && (size_t)K * c.No[p] * 4 < (1ull << 31) &&
+             ((size_t)c.Mo[p] + 128) * c.No[p] * 4 < (1ull << 31);
+    },
+    [&](int p) {
+      G.A[p] = (const float*)c.A[p]; G.B[p] = (const float*)c.B[p]; G.C[p] = c.dW[p]; G.M[p] = c.Mo[p]; G.N[p] = c.No[p];
+      G.tiles_m[p] = (c.Mo[p] + 63) / 64; G.tiles_n[p] = (c.No[p] + 63) / 64;
+      G.band_h[p] = l2_band_height(64l * K * 4, G.tiles_m[p]);
+      return G.tiles_m[p] * G.tiles_n[p];
+    },
+    [&](int p) {
+      G.A[p] = G.A[0]; G.B[p] = G.B[0]; G.C[p] = G.C[0]; G.M[p] = G.M[0]; G.N[p] = G.N[0];
+      G.tiles_m[p] = G.tiles_m[0]; G.tiles_n[p] = G.tiles_n[0]; G.band_h[p] = G.band_h[0];
+    }));
+  const int total = G.start[4];
+  G.K = K; G.overwrite = c.overwrite; G.prio = lo.prio; G.stamp = lo.stamp;
   const int slots_env = uniter_switches().wgrad_group_f32_slots;
   const int slots = slots_env >= 8 ? slots_env / 8 * 8 : 1024;
   const int grid = total < slots ? (total + 7) / 8 * 8 : slots;
-  hipLaunchKernelGGL(gemm_f32_wgrad_group_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, G);
+  hipLaunchKernelGGL(gemm_f32_wgrad_group_kernel, dim3(grid), dim3(256), 0, (hipStream_t)c.stream, G);
   UCHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int uniter_wgrad_f32_group(int n, const int* M, const int* N, int K, const float* const* A, const float* const* B,
                                       float* const* dW, int overwrite, void* stream) {
-  return gemm_f32_wgrad_group(n, M, N, K, A, B, dW, overwrite, stream, LaunchOpts{});
+  WgradGroupCall c;
+  c.n = n; c.Mo = M; c.No = N; c.K = K; c.A = (const void* const*)A; c.B = (const void* const*)B; c.dW = dW;
+  c.overwrite = overwrite; c.stream = stream;
+  return gemm_f32_wgrad_group(c, LaunchOpts{});
 }
 
 // tag != 0 selects a separately named instantiation of the x @ W^T kernel (TAG template
 // argument) so that one call site (the FFN-up forward GEMM) is its own row in rocprofv3 --stats.
-int gemm_f32_run(int cfg, int tag, int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,
-                 int lda, const float* B, int ldb, float* C, int ldc, int epilogue, const float* bias,
-                 const float* aux_in, float* aux_out, int ld_aux, int beta, float* colsum_part,
-                 void* stream, const LaunchOpts& lo, int no_sk) {
+int gemm_f32_run(int cfg, int tag, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, a_kmajor = c.A.kmajor, b_kmajor = c.B.kmajor, lda = c.A.ld, ldb = c.B.ld;
   UCHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad dims %d %d %d", M, N, K);
-  UCHECK_ARG(A && B && C, "gemm: null operand");
-  UCHECK_ARG(epilogue >= 0 && epilogue <= UNITER_EPI_MUL, "gemm: bad epilogue %d", epilogue);
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU || epilogue == UNITER_EPI_BIAS_GELU_D) || bias,
-             "gemm: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_DGELU || epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in,
-             "gemm: epilogue needs aux_in");
+  UCHECK_ARG(c.A.p && c.B.p && c.C, "gemm: null operand");
+  UCHECK_ARG(!c.A.piece_stride && !c.B.piece_stride && c.nsplit == 1 && !c.Ccopy && !c.aux_in_bf16 && !c.aux_out_bf16 && !c.sk_ws,
+             "gemm: the fp32 kernels take fp32 operands and write one fp32 output (no pieces, k-pieces, output copy, bf16 aux or workspace)");
+  UCHECK_ARG(c.epi >= 0 && c.epi <= UNITER_EPI_MUL, "gemm: bad epilogue %d", c.epi);
+  UCHECK_RC(gemm_check_epilogue("gemm", c, GEMM_EPI_ALL, false));
   // 16-byte vector loads along the contiguous dimension
   if (!a_kmajor) UCHECK_SHAPE(K % 4 == 0 && lda % 4 == 0, "gemm: K/lda must be multiples of 4 (A k-contiguous)");
   else           UCHECK_SHAPE(M % 4 == 0 && lda % 4 == 0, "gemm: M/lda must be multiples of 4 (A k-major)");
   if (!b_kmajor) UCHECK_SHAPE(K % 4 == 0 && ldb % 4 == 0, "gemm: K/ldb must be multiples of 4 (B k-contiguous)");
   else           UCHECK_SHAPE(N % 4 == 0 && ldb % 4 == 0, "gemm: N/ldb must be multiples of 4 (B k-major)");
-  UCHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "gemm: operands must be 16-byte aligned");
-  GemmArgs g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
-  g.epi = epilogue; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux;
-  g.beta = beta; g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.colsum_part = colsum_part;
-  g.stamp = lo.stamp;
-  g.prio = lo.prio;
+  UCHECK_ARG(((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0, "gemm: operands must be 16-byte aligned");
+  const GemmArgs g = {M, N, K, (const float*)c.A.p, lda, (const float*)c.B.p, ldb, c.C, c.ldc, c.epi, c.bias, (const float*)c.aux_in,
+                      (float*)c.aux_out, c.ld_aux, c.beta, /*tiles_m, tiles_n*/ 0, 0, /*band_h*/ 1, c.colpart, lo.stamp, lo.prio};
   if (cfg == 0) cfg = choose_cfg(M, N);
-  if (colsum_part) {
+  if (c.colpart) {
     const bool fast = (K % BK == 0 || (a_kmajor && b_kmajor)) && (size_t)(a_kmajor ? K : M) * lda * 4 < (1ull << 31) &&
                       (size_t)(b_kmajor ? K : N) * ldb * 4 < (1ull << 31);
-    UCHECK_SHAPE(fast && (cfg == 21 || cfg == 24 || cfg == 25) && beta == 0, "gemm: fused column sums need the v3 kernel (K %% 32 == 0)");
+    UCHECK_SHAPE(fast && (cfg == 21 || cfg == 24 || cfg == 25) && c.beta == 0, "gemm: fused column sums need the v3 kernel (K %% 32 == 0)");
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
+  const bool no_sk = c.no_sk != 0;
   if (!a_kmajor && !b_kmajor)
-    return tag ? dispatch_cfg<false, false, 1>(cfg, g, st, no_sk != 0) : dispatch_cfg<false, false, 0>(cfg, g, st, no_sk != 0);
-  if (!a_kmajor && b_kmajor) return dispatch_cfg<false, true, 0>(cfg, g, st, no_sk != 0);
-  if (a_kmajor && b_kmajor) return dispatch_cfg<true, true, 0>(cfg, g, st, no_sk != 0);
-  return dispatch_cfg<true, false, 0>(cfg, g, st, no_sk != 0);
+    return tag ? dispatch_cfg<false, false, 1>(cfg, g, st, no_sk) : dispatch_cfg<false, false, 0>(cfg, g, st, no_sk);
+  if (!a_kmajor && b_kmajor) return dispatch_cfg<false, true, 0>(cfg, g, st, no_sk);
+  if (a_kmajor && b_kmajor) return dispatch_cfg<true, true, 0>(cfg, g, st, no_sk);
+  return dispatch_cfg<true, false, 0>(cfg, g, st, no_sk);
 }
 
 extern "C" int uniter_gemm_f32_cfg(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K,
                                    const float* A, int lda, const float* B, int ldb, float* C,
                                    int ldc, int epilogue, const float* bias, const float* aux_in,
                                    float* aux_out, int ld_aux, int beta, void* stream) {
-  return gemm_f32_run(cfg, 0, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, epilogue, bias, aux_in,
-                      aux_out, ld_aux, beta, nullptr, stream, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, a_kmajor}; c.B = {B, ldb, 0, b_kmajor}; c.C = C; c.ldc = ldc;
+  c.epi = epilogue; c.bias = bias; c.aux_in = aux_in; c.aux_out = aux_out; c.ld_aux = ld_aux; c.beta = beta; c.stream = stream;
+  return gemm_f32_run(cfg, 0, c, LaunchOpts{});
 }
 
 extern "C" int uniter_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, const float* A,

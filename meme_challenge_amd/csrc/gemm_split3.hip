@@ -1293,42 +1293,35 @@ int riders_prepare(uniter_x3_riders_t& x, const char* who) {
 void x3_choose(int M, int N, int K, int avail, int nsplit_fixed, int* cfg_out, int* ns_out, bool allow192 = false);
 
 // C / Cx = epi(A . B^T) on x3 operands (fp32-accurate, six bf16 MFMA products per block, fp32 accumulate).
-int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, int psa,
-                const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride, void* Cx, int ldcx, int pscx,
-                int epilogue, const float* bias, const float* aux_in, float* aux_out, int ld_aux, void* stream,
-                float* colsum_part, void* sk_ws, size_t sk_ws_bytes, const LaunchOpts& lo) {
-  UCHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && (C || Cx), "gemm_x3: bad argument");
+int gemm_x3_run(int cfg, const GemmCall& c, const LaunchOpts& lo) {
+  const int M = c.M, N = c.N, K = c.K, a_kmajor = c.A.kmajor, b_kmajor = c.B.kmajor, nsplit = c.nsplit, epilogue = c.epi;
+  const int lda = c.A.ld, psa = c.A.piece_stride, ldb = c.B.ld, psb = c.B.piece_stride, ldcx = c.ld_copy, pscx = c.ps_copy;
+  void* const Cx = c.Ccopy;
+  UCHECK_ARG(M > 0 && N > 0 && K > 0 && c.A.p && c.B.p && (c.C || Cx), "gemm_x3: bad argument");
+  UCHECK_ARG(!c.beta && !c.aux_in_bf16 && !c.aux_out_bf16, "gemm_x3: no accumulate (an input gradient adds through its + aux epilogue), fp32 aux operands");
   UCHECK_ARG(!a_kmajor || (b_kmajor && !Cx && (epilogue == UNITER_EPI_NONE || epilogue == UNITER_EPI_ADD)),
              "gemm_x3: A k-major only as the weight-gradient layout (both operands k-major, fp32 output, none / add)");
-  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (C && !Cx && c_split_stride >= (long)M * ldc)),
+  UCHECK_ARG(nsplit >= 1 && nsplit <= 8 && (nsplit == 1 || (c.C && !Cx && c.c_split_stride >= (long)M * c.ldc)),
              "gemm_x3: split-K needs fp32 slabs (no x3 output)");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_BIAS || epilogue == UNITER_EPI_BIAS_GELU_D) || bias, "gemm_x3: epilogue needs bias");
-  UCHECK_ARG(!(epilogue == UNITER_EPI_ADD || epilogue == UNITER_EPI_MUL) || aux_in, "gemm_x3: epilogue needs aux_in");
-  UCHECK_ARG(epilogue != UNITER_EPI_BIAS_GELU_D || aux_out, "gemm_x3: epilogue needs aux_out");
+  UCHECK_RC(gemm_check_epilogue("gemm_x3", c, GEMM_EPI_PERSISTENT, true));
   UCHECK_SHAPE(((a_kmajor && b_kmajor) || K % 32 == 0) && lda % 8 == 0 && ldb % 8 == 0 && psa % 8 == 0 && psb % 8 == 0 && N % 8 == 0 &&
-               (!a_kmajor || M % 8 == 0) && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && (ldc % 4 == 0) &&
-               (ldcx % 8 == 0) && (pscx % 8 == 0) && (ld_aux % 4 == 0) && ((uintptr_t)C & 15) == 0 && ((uintptr_t)Cx & 15) == 0 &&
-               ((uintptr_t)aux_in & 15) == 0 && ((uintptr_t)aux_out & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+               (!a_kmajor || M % 8 == 0) && ((uintptr_t)c.A.p & 15) == 0 && ((uintptr_t)c.B.p & 15) == 0 && (pscx % 8 == 0) &&
+               gemm_side_buffers_aligned(c),
                "gemm_x3: K %% 32, N %% 8, strides %% 8 (x3) / %% 4 (fp32) and 16-byte aligned buffers required "
                "(M=%d N=%d K=%d)", M, N, K);
   UCHECK_SHAPE(lda > 0 && ldb > 0 && psa >= 0 && psb >= 0 && x3_fits(a_kmajor ? K : M, lda, psa, a_kmajor ? M : K) &&
                x3_fits(b_kmajor ? K : N, ldb, psb, b_kmajor ? N : K) && (!Cx || (ldcx > 0 && pscx >= 0 && x3_fits(M, ldcx, pscx, N))) &&
-               ((size_t)M + 256) * (ldc > 0 ? ldc : 1) * 4 < (1ull << 31) &&
-               ((size_t)M + 256) * (ld_aux > 0 ? ld_aux : 1) * 4 < (1ull << 31), "gemm_x3: operand beyond 31-bit offsets");
-  S3Args g;
-  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.psa = psa; g.B = B; g.ldb = ldb; g.psb = psb; g.C = C; g.ldc = ldc;
-  g.c_split_stride = c_split_stride; g.Cx = (unsigned short*)Cx; g.ldcx = ldcx; g.pscx = pscx; g.bias = bias;
-  g.aux_in = aux_in; g.aux_out = aux_out; g.ld_aux = ld_aux;
-  g.tiles_m = g.tiles_n = 0; g.band_h = 1; g.nsplit = nsplit;
-  g.dbg = cfg >> 8; g.b_paired = (cfg >> 6) & 1; cfg &= 0x3f;      // (cfg | 64: B in the paired-row layout of the weight mirror)
+               gemm_f32_side_in_range(c, 256), "gemm_x3: operand beyond 31-bit offsets");
+  // (cfg | 64: B in the paired-row layout of the weight mirror)
+  const S3Args g = {M, N, K, c.A.p, lda, psa, c.B.p, ldb, psb, c.C, c.ldc, c.c_split_stride, (unsigned short*)Cx, ldcx, pscx, c.bias,
+                    (const float*)c.aux_in, (float*)c.aux_out, c.ld_aux, /*tiles_m, tiles_n, band_h*/ 0, 0, 1, nsplit, lo.stamp, lo.prio,
+                    /*dbg*/ cfg >> 8, /*b_paired*/ (cfg >> 6) & 1, c.colpart};
+  cfg &= 0x3f;
   UCHECK_ARG(!g.b_paired || (!a_kmajor && N % 2 == 0 && ldb % 32 == 0), "gemm_x3: paired rows are the layout of a weight (B, forward or input-gradient "
              "product) with an even number of rows and a row length that is a multiple of 32");
-  g.stamp = lo.stamp;
-  g.prio = lo.prio;
   UCHECK_ARG((cfg & 0xff) != 5 || (!a_kmajor && !b_kmajor && !Cx), "gemm_x3: cfg 5 (128 x 192 tiles) is built for the forward layout with an fp32 output");
-  UCHECK_ARG(!colsum_part || (epilogue == UNITER_EPI_MUL && nsplit == 1 && (cfg == 0 || cfg >= 3) && ((uintptr_t)colsum_part & 15) == 0 && N % 4 == 0),
+  UCHECK_ARG(!c.colpart || (epilogue == UNITER_EPI_MUL && nsplit == 1 && (cfg == 0 || cfg >= 3) && ((uintptr_t)c.colpart & 15) == 0 && N % 4 == 0),
              "gemm_x3: column partials ride on the x aux epilogue of the 16x16x32 geometries (cfg 0, 3, 4), one k-piece");
-  g.colpart = colsum_part;
   // in the step: 4 x (64 x 64) compute waves + 4 loaders are +1.2 % over cfg 1 (8 x (64 x 32)); the 16x16x32 MFMA shape another
   // +3 % (10.51 -> 10.21 ms, same box): the chip holds a higher clock under it
   if (cfg == 0) {
@@ -1343,8 +1336,8 @@ int gemm_x3_run(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, i
       x3_choose(M, N, K, persistent_grid(1 << 20, 0, lo.cu_reserve), nsplit, &cfg, &ns_, !b_kmajor && !Cx);
     }
   }
-  hipStream_t st = (hipStream_t)stream;
-  const SkWs sk = {sk_ws, sk_ws_bytes};
+  hipStream_t st = (hipStream_t)c.stream;
+  const SkWs sk = {c.sk_ws, c.sk_ws_bytes};
   if (a_kmajor) return dispatch_epi3<true, true>(cfg, g, epilogue, st, sk, lo.cu_reserve);
   return b_kmajor ? dispatch_epi3<false, true>(cfg, g, epilogue, st, sk, lo.cu_reserve) : dispatch_epi3<false, false>(cfg, g, epilogue, st, sk, lo.cu_reserve);
 }
@@ -1406,15 +1399,7 @@ int gemm_x3_pick_split(int M, int N, int K) {
   return (tiles <= 160 && K >= 512) ? 2 : 1;
 }
 
-extern "C" int uniter_gemm_x3_cfg(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A,
-                                  int lda, int psa, const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride,
-                                  void* C_x3, int ldcx, int pscx, int epilogue, const float* bias, const float* aux_in,
-                                  float* aux_out, int ld_aux, void* stream) {
-  return gemm_x3_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, c_split_stride, C_x3, ldcx,
-                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, nullptr, 0, LaunchOpts{});
-}
-
-// the same, with the workspace of the balanced walk (uniter_gemm_x3_balanced_ws_bytes; its first 16 KB zero before the first launch,
+// gemm_x3_run with the workspace of the balanced walk (uniter_gemm_x3_balanced_ws_bytes; its first 16 KB zero before the first launch,
 // every launch leaves them zero; one workspace per stream that launches concurrently): a 128 x 256-tile forward product with a bias
 // epilogue whose tiles do not fill whole rounds of the chip is cut into equal runs of k-tiles instead (gemm_s3p_kernel, "balanced walk")
 extern "C" size_t uniter_gemm_x3_balanced_ws_bytes(void) { return gemm_x3_sk_ws_bytes(); }
@@ -1422,8 +1407,20 @@ extern "C" int uniter_gemm_x3_cfg_ws(int cfg, int nsplit, int a_kmajor, int b_km
                                      int lda, int psa, const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride,
                                      void* C_x3, int ldcx, int pscx, int epilogue, const float* bias, const float* aux_in,
                                      float* aux_out, int ld_aux, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_x3_run(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, c_split_stride, C_x3, ldcx,
-                     pscx, epilogue, bias, aux_in, aux_out, ld_aux, stream, nullptr, ws, ws_bytes, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, psa, a_kmajor}; c.B = {B, ldb, psb, b_kmajor};
+  c.C = C; c.ldc = ldc; c.c_split_stride = c_split_stride; c.nsplit = nsplit; c.Ccopy = C_x3; c.ld_copy = ldcx; c.ps_copy = pscx;
+  c.epi = epilogue; c.bias = bias; c.aux_in = aux_in; c.aux_out = aux_out; c.ld_aux = ld_aux;
+  c.sk_ws = ws; c.sk_ws_bytes = ws_bytes; c.stream = stream;
+  return gemm_x3_run(cfg, c, LaunchOpts{});
+}
+// ... and without one
+extern "C" int uniter_gemm_x3_cfg(int cfg, int nsplit, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A,
+                                  int lda, int psa, const void* B, int ldb, int psb, float* C, int ldc, long c_split_stride,
+                                  void* C_x3, int ldcx, int pscx, int epilogue, const float* bias, const float* aux_in,
+                                  float* aux_out, int ld_aux, void* stream) {
+  return uniter_gemm_x3_cfg_ws(cfg, nsplit, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, c_split_stride, C_x3, ldcx,
+                               pscx, epilogue, bias, aux_in, aux_out, ld_aux, nullptr, 0, stream);
 }
 
 // the same product, also leaving partial column sums of its output: colsum_part[(i, n)] = sum of the output rows 64 i .. 64 i + 63
@@ -1432,8 +1429,11 @@ extern "C" int uniter_gemm_x3_cfg_ws(int cfg, int nsplit, int a_kmajor, int b_km
 extern "C" int uniter_gemm_x3_colpart(int cfg, int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int lda, int psa,
                                       const void* B, int ldb, int psb, float* C, int ldc, void* C_x3, int ldcx, int pscx,
                                       const float* aux_in, int ld_aux, float* colsum_part, void* stream) {
-  return gemm_x3_run(cfg, 1, a_kmajor, b_kmajor, M, N, K, A, lda, psa, B, ldb, psb, C, ldc, 0, C_x3, ldcx, pscx, UNITER_EPI_MUL,
-                     nullptr, aux_in, nullptr, ld_aux, stream, colsum_part, nullptr, 0, LaunchOpts{});
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, psa, a_kmajor}; c.B = {B, ldb, psb, b_kmajor};
+  c.C = C; c.ldc = ldc; c.Ccopy = C_x3; c.ld_copy = ldcx; c.ps_copy = pscx;
+  c.epi = UNITER_EPI_MUL; c.aux_in = aux_in; c.ld_aux = ld_aux; c.colpart = colsum_part; c.stream = stream;
+  return gemm_x3_run(cfg, c, LaunchOpts{});
 }
 
 extern "C" int uniter_split3(const float* x, int rows, int cols, int ld, void* x3, size_t row_stride, size_t piece_stride,
@@ -1506,46 +1506,36 @@ extern "C" int uniter_colsum_x3_add_det(const void* x3, int rows, int cols, int 
 // default wave priority whatever lo.prio says.
 // tile width of the grouped weight-gradient launch: cfg 4 = 128 x 256 tiles (round 5), else 128 x 128
 static int wgrad_bn(int cfg) { return cfg == 4 ? 256 : 128; }
-static int wgrad_tiles(int cfg, int n, const int* Mo, const int* No) {
-  int total = 0;
-  for (int p = 0; p < n; ++p) total += ((Mo[p] + 127) / 128) * ((No[p] + wgrad_bn(cfg) - 1) / wgrad_bn(cfg));
-  return total;
-}
 // the default geometry of the grouped launch (UNITER_X3_WGRAD_CFG = 3 | 4 overrides)
 int gemm_x3_wgrad_default_cfg() { return uniter_switches().x3_wgrad_cfg; }
 
-int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, const void* const* A, const void* const* B,
-                        float* const* dW, void* stream, int overwrite, int max_wgs, uniter_x3_riders_t* riders,
-                        void* sk_ws, size_t sk_ws_bytes, const LaunchOpts& lo) {
-  UCHECK_ARG(n >= 1 && n <= 4 && K > 0 && Mo && No && A && B && dW, "wgrad_x3_group: bad argument");
+int gemm_x3_wgrad_group(int cfg, const WgradGroupCall& c, const LaunchOpts& lo) {
+  static const char* const who = "wgrad_x3_group";
+  UCHECK_RC(wgrad_group_check(who, c));
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
   S3Group G;
   memset(&G.x, 0, sizeof(G.x));
   G.sk_part = nullptr; G.sk_flag = nullptr; G.sk_units = G.sk_nk = 0;
-  int total = 0;
-  for (int p = 0; p < 4; ++p) {
-    G.start[p] = total;
-    if (p >= n) { G.p[p] = G.p[0]; continue; }
-    UCHECK_ARG(Mo[p] > 0 && No[p] > 0 && A[p] && B[p] && dW[p], "wgrad_x3_group: bad product %d", p);
-    UCHECK_SHAPE(Mo[p] % 8 == 0 && No[p] % 8 == 0 && ((uintptr_t)A[p] & 15) == 0 && ((uintptr_t)B[p] & 15) == 0 &&
-                 ((uintptr_t)dW[p] & 15) == 0 && x3_fits(K, 3 * Mo[p], Mo[p], Mo[p]) && x3_fits(K, 3 * No[p], No[p], No[p]) &&
-                 ((size_t)Mo[p] + 256) * No[p] * 4 < (1ull << 31),
-                 "wgrad_x3_group: M, N %% 8, 16-byte aligned buffers, 31-bit offsets (product %d: %d x %d, K=%d)", p, Mo[p], No[p], K);
-    S3Args& g = G.p[p];
-    g.M = Mo[p]; g.N = No[p]; g.K = K; g.A = A[p]; g.lda = 3 * Mo[p]; g.psa = Mo[p]; g.B = B[p]; g.ldb = 3 * No[p]; g.psb = No[p];
-    g.C = dW[p]; g.ldc = No[p];
-    g.c_split_stride = 0; g.Cx = nullptr; g.ldcx = 0; g.pscx = 0; g.bias = nullptr;
-    g.aux_in = overwrite ? nullptr : dW[p]; g.aux_out = nullptr; g.ld_aux = No[p];
-    g.nsplit = 1; g.stamp = lo.stamp; g.prio = 0; g.dbg = 0; g.colpart = nullptr; g.b_paired = 0;
-    plan_tiles3<128>(g, wgrad_bn(cfg));
-    total += g.tiles_m * g.tiles_n;
-  }
-  G.start[4] = total;
-  for (int p = n; p < 4; ++p) G.start[p] = total;
-  hipStream_t st = (hipStream_t)stream;
+  const int K = c.K, overwrite = c.overwrite, max_wgs = c.max_wgs;
+  UCHECK_RC(wgrad_group_walk(who, c, G.start,
+    [&](int p) { return wgrad_product_aligned8(c, p) && x3_fits(K, 3 * c.Mo[p], c.Mo[p], c.Mo[p]) && x3_fits(K, 3 * c.No[p], c.No[p], c.No[p]); },
+    [&](int p) {
+      const int Mo = c.Mo[p], No = c.No[p];
+      float* const dW = c.dW[p];
+      S3Args& g = G.p[p];
+      g = {Mo, No, K, c.A[p], 3 * Mo, Mo, c.B[p], 3 * No, No, dW, No, /*c_split_stride*/ 0, /*Cx*/ nullptr, 0, 0, /*bias*/ nullptr,
+           /*aux_in*/ overwrite ? nullptr : dW, /*aux_out*/ nullptr, /*ld_aux*/ No, /*tiles_m, tiles_n, band_h*/ 0, 0, 1, /*nsplit*/ 1,
+           lo.stamp, /*prio*/ 0, /*dbg*/ 0, /*b_paired*/ 0, /*colpart*/ nullptr};
+      plan_tiles3<128>(g, wgrad_bn(cfg));
+      return g.tiles_m * g.tiles_n;
+    },
+    [&](int p) { G.p[p] = G.p[0]; }));
+  const int total = G.start[4];
+  hipStream_t st = (hipStream_t)c.stream;
+  void* const sk_ws = c.sk_ws;
   // the balanced walk (128 x 256 tiles, a workspace given): 216 tiles for UNITER-base on 256 CUs -- 82 k-tiles per workgroup become 70
-  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (K + 31) / 32, max_wgs, lo.cu_reserve, sk_ws, sk_ws_bytes) : 0;
-  if (riders) {
+  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (K + 31) / 32, max_wgs, lo.cu_reserve, sk_ws, c.sk_ws_bytes) : 0;
+  if (uniter_x3_riders_t* riders = c.riders) {
     // riders ride on the v_mfma_f32_16x16x32_bf16 geometries: 4 compute waves of 64 x 64 (cfg 3) or the 128 x 256 tile's 8 (cfg 4)
     UCHECK_ARG(cfg == 3 || cfg == 4, "wgrad_x3_group: riders need cfg 3 or 4");
     uniter_x3_riders_t& x = *riders;
@@ -1575,29 +1565,24 @@ int gemm_x3_wgrad_group(int cfg, int n, const int* Mo, const int* No, int K, con
 // sum-of-squares slots a launch with riders writes (one per compute wave: 4 per workgroup, 8 with 128 x 256 tiles) for these products;
 // K > 0 and a workspace size: the launch is given the balanced walk's workspace (it then runs on every CU it may use)
 int gemm_x3_wgrad_group_slots(int cfg, int n, const int* Mo, const int* No, int max_wgs, int K, size_t sk_ws_bytes, int cu_reserve) {
-  if (!Mo || !No || n < 1 || n > 4) return 0;
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
-  const int total = wgrad_tiles(cfg, n, Mo, No);
+  const int total = wgrad_group_tiles(n, Mo, No, wgrad_bn(cfg));
   // (x3_sk_grid checks the pointer's alignment only: any aligned non-null value stands for the workspace here)
   const int sk_grid = (cfg == 4 && K > 0) ? x3_sk_grid(total, (K + 31) / 32, max_wgs, cu_reserve, (const void*)256, sk_ws_bytes) : 0;
-  return (cfg == 4 ? 8 : 4) * (sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs, cu_reserve));
+  return rider_slots(cfg == 4 ? 8 : 4, sk_grid > 0 ? sk_grid : persistent_grid(total, max_wgs, cu_reserve));
 }
 
 // the smallest grid (a multiple of 8) on which these products' tiles take no more rounds than on one workgroup per CU
 int gemm_x3_wgrad_group_balanced_wgs(int cfg, int n, const int* Mo, const int* No, int cu_reserve) {
-  if (!Mo || !No || n < 1 || n > 4) return 0;
   if (cfg == 0) cfg = gemm_x3_wgrad_default_cfg();
-  const int total = wgrad_tiles(cfg, n, Mo, No);
-  const int full = persistent_grid(total, 0, cu_reserve);
-  const int rounds = (total + full - 1) / full;
-  const int wgs = ((total + rounds - 1) / rounds + 7) / 8 * 8;
-  return wgs < full ? wgs : full;
+  const int total = wgrad_group_tiles(n, Mo, No, wgrad_bn(cfg));
+  return balanced_grid(total, persistent_grid(total, 0, cu_reserve));
 }
 
 extern "C" int uniter_wgrad_x3_group_riders(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                             const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                             uniter_x3_riders_t* riders, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, nullptr, 0, LaunchOpts{});
+  return uniter_wgrad_x3_group_ws(cfg, n, M, N, K, A, B, dW, overwrite, max_wgs, riders, nullptr, 0, stream);
 }
 extern "C" int uniter_wgrad_x3_group_slots(int cfg, int n, const int* M, const int* N, int max_wgs) {
   return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, 0, 0, 0);
@@ -1608,7 +1593,10 @@ extern "C" int uniter_wgrad_x3_group_slots(int cfg, int n, const int* M, const i
 extern "C" int uniter_wgrad_x3_group_ws(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                         const void* const* B, float* const* dW, int overwrite, int max_wgs,
                                         uniter_x3_riders_t* riders, void* ws, size_t ws_bytes, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, riders, ws, ws_bytes, LaunchOpts{});
+  WgradGroupCall c;
+  c.n = n; c.Mo = M; c.No = N; c.K = K; c.A = A; c.B = B; c.dW = dW; c.overwrite = overwrite; c.max_wgs = max_wgs; c.riders = riders;
+  c.sk_ws = ws; c.sk_ws_bytes = ws_bytes; c.stream = stream;
+  return gemm_x3_wgrad_group(cfg, c, LaunchOpts{});
 }
 extern "C" int uniter_wgrad_x3_group_slots_ws(int cfg, int n, const int* M, const int* N, int K, int max_wgs, size_t ws_bytes) {
   return gemm_x3_wgrad_group_slots(cfg, n, M, N, max_wgs, K, ws_bytes, 0);
@@ -1616,5 +1604,5 @@ extern "C" int uniter_wgrad_x3_group_slots_ws(int cfg, int n, const int* M, cons
 
 extern "C" int uniter_wgrad_x3_group(int cfg, int n, const int* M, const int* N, int K, const void* const* A,
                                      const void* const* B, float* const* dW, int overwrite, int max_wgs, void* stream) {
-  return gemm_x3_wgrad_group(cfg, n, M, N, K, A, B, dW, stream, overwrite, max_wgs, nullptr, nullptr, 0, LaunchOpts{});
+  return uniter_wgrad_x3_group_ws(cfg, n, M, N, K, A, B, dW, overwrite, max_wgs, nullptr, nullptr, 0, stream);
 }

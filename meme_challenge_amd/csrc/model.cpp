@@ -371,11 +371,13 @@ int gemm(uniter_model* m, int kind, hipStream_t st, int akm, int bkm, int M, int
   }
   // wave priority of the critical path's GEMMs over the side stream's weight gradients (common.h; UNITER_MAIN_PRIO, default 0)
   const LaunchOpts lo = {ps.stamp, kind == UNITER_K_GEMM_WGRAD ? 0 : sw.main_prio, m->launch_reserve};
+  GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.A = {A, lda, 0, akm}; c.B = {B, ldb, 0, bkm}; c.C = C; c.ldc = ldc;
+  c.epi = epi; c.bias = bias; c.aux_in = aux_in; c.aux_out = aux_out; c.ld_aux = ld_aux;
+  c.beta = beta; c.no_sk = no_sk; c.colpart = colsum_part; c.stream = st;
   if (prec == PREC_BF16_MFMA || prec == PREC_BF16)      // embeddings' projections (fp32 inputs) also run on the bf16 pipe in mode 2
-    return gemm_bf16_run(0, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias, aux_in, aux_out, ld_aux, beta,
-                         colsum_part, st, lo, no_sk);
-  return gemm_f32_run(cfg, kind == UNITER_K_GEMM_FFN_UP_FWD, akm, bkm, M, N, K, A, lda, B, ldb, C, ldc, epi, bias,
-                      aux_in, aux_out, ld_aux, beta, colsum_part, st, lo, no_sk);
+    return gemm_bf16_run(0, c, lo);
+  return gemm_f32_run(cfg, kind == UNITER_K_GEMM_FFN_UP_FWD, c, lo);
 }
 
 // One dense product of encoder layer l against weight w (L_QW, L_OW, L_W1, L_W2): c = epilogue(a . W^T), or with b_kmajor the input
@@ -398,17 +400,21 @@ int linear(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int
     return gemm(m, kind, st, 0, bkm, M, N, K, a.f, K, m->LP(l, w), ldw, C, N, epi, bias, aux_in, aux_out, ld_aux, 0, colpart);
   }
   ProfScope ps(m, kind, st);
+  GemmCall g;      // what every operand format shares: the weight from the mirror, `pieces` fp32 slabs or the operand-format copy
+  g.M = M; g.N = N; g.K = K; g.B = {m->WB(l, w), ldw, 0, bkm}; g.C = C; g.ldc = N; g.c_split_stride = (long)M * N; g.nsplit = pieces;
+  g.Ccopy = c.b; g.epi = epi; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out; g.colpart = colpart; g.stream = st;
   if (pl.prec == PREC_X3) {
     const int cfg = (kind == UNITER_K_GEMM_FFN_UP_FWD && sw.x3_cfg_ffn_up_fwd) ? sw.x3_cfg_ffn_up_fwd : sw.x3_cfg;
     const LaunchOpts lo = {ps.stamp, sw.main_prio_x3, m->launch_reserve};
+    g.A = {a.b, 3 * K, K, 0}; g.B.piece_stride = (int)m->mirror_numel; g.ld_copy = 3 * N; g.ps_copy = N; g.ld_aux = N;
     // (every product of this helper runs on the main stream: the balanced walk's main-stream workspace)
+    g.sk_ws = pl.sk_main; g.sk_ws_bytes = pl.sk_main ? pl.sk_bytes : 0;
     // (cfg | 64: the weight's pieces in the paired-row layout -- full 128-byte source lines for the loaders of the forward products)
-    return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), pieces, 0, bkm, M, N, K, a.b, 3 * K, K, m->WB(l, w), ldw, (int)m->mirror_numel, C, N,
-                       (long)M * N, c.b, 3 * N, N, epi, bias, aux_in, aux_out, N, st, colpart, pl.sk_main, pl.sk_main ? pl.sk_bytes : 0, lo);
+    return gemm_x3_run(cfg | (m->mirror_paired ? 64 : 0), g, lo);
   }
   const LaunchOpts lo = {ps.stamp, sw.main_prio_bf16, m->launch_reserve};
-  const int aux_in_b16 = epi == UNITER_EPI_MUL || epi == UNITER_EPI_DGELU, aux_out_b16 = epi == UNITER_EPI_BIAS_GELU || epi == UNITER_EPI_BIAS_GELU_D;
-  const int ldcb = c.b ? N : 0;
+  g.A = {a.b, K, 0, 0}; g.ld_copy = c.b ? N : 0; g.ld_aux = ld_aux;
+  g.aux_in_bf16 = epi == UNITER_EPI_MUL || epi == UNITER_EPI_DGELU; g.aux_out_bf16 = epi == UNITER_EPI_BIAS_GELU || epi == UNITER_EPI_BIAS_GELU_D;
   // round 6: the persistent loader / compute kernels (csrc/gemm_bf16_p.hip) for the products UNITER_B16_PERSIST names (default: none):
   // 1 = QKV forward, 2 = N = hidden products, 8 = the wide products as well (4: the grouped weight gradients, wgrad_group())
   int cfg = 0;
@@ -421,11 +427,9 @@ int linear(uniter_model* m, int kind, hipStream_t st, int bkm, int M, int N, int
   }
   if (colpart) {      // (the product that writes dU also leaves its column partials: the persistent 128 x 256 kernel's epilogue)
     UCHECK_ARG(epi_ok && K % 64 == 0 && pieces == 1, "linear: column partials ride on the persistent kernels");
-    return gemm_b1p_run(7, 1, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in, aux_in_b16, aux_out,
-                        aux_out_b16, ld_aux, colpart, st, lo);
+    return gemm_b1p_run(7, g, lo);
   }
-  return gemm_bf16v2_run(cfg, pieces, 0, bkm, M, N, K, a.b, K, m->WB(l, w), ldw, C, N, (long)M * N, c.b, ldcb, epi, bias, aux_in,
-                         aux_in_b16, aux_out, aux_out_b16, ld_aux, 0, st, lo);
+  return gemm_bf16v2_run(cfg, g, lo);
 }
 // The attention kernel of a plan's forward pass (`keep_pre`: the forward drew the dropout keep flags ahead of its kernels) or of its
 // backward pass (bwd).  The kernels of attention_x3.hip (ATTN_X3, ATTN_B16X) read the keep flags and draw none, so with dropout they
@@ -445,12 +449,7 @@ AttnKernel attn_kernel(const Plan& pl, float p_drop, bool save, bool keep_pre, b
 }
 // CUs the backward pass's persistent launches may use: the chip's minus what the caller reserved for a gradient exchange
 int x3_backward_cus(const uniter_model* m) {
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 8 ? n / 8 * 8 : 256;
-  }();
-  const int a = (cus - m->cu_reserve) / 8 * 8;
+  const int a = (gemm_chip_cus() - m->cu_reserve) / 8 * 8;
   return a >= 8 ? a : 8;
 }
 // The grouped weight-gradient launch of layer l's backward pass (precision 2 or 3: four products, Mo = {I, H, 3H, H}, No = {H, I, H, H}):
@@ -560,11 +559,14 @@ int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, const WgradProduc
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, st);
     const LaunchOpts lo = {ps.stamp, 0, m->launch_reserve};
-    if (pieces == 0 || !pl.wg_slabs)
-      return gemm_bf16res_run(0, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, t.dW[p], No, nullptr, 0, UNITER_EPI_NONE, nullptr, nullptr,
-                              nullptr, 0, 1, nullptr, st, lo, pl.det ? 1 : 0);      // (deterministic plan: whole tiles, no stream-K)
-    UCHECK_RC(gemm_bf16v2_run(0, pieces, 1, 1, Mo, No, K, t.A[p], Mo, t.B[p], No, pl.wg_slabs, No, (long)Mo * No, nullptr, 0,
-                              UNITER_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 0, 0, st, lo));
+    GemmCall c;
+    c.M = Mo; c.N = No; c.K = K; c.A = {t.A[p], Mo, 0, 1}; c.B = {t.B[p], No, 0, 1}; c.ldc = No; c.stream = st;
+    if (pieces == 0 || !pl.wg_slabs) {
+      c.C = t.dW[p]; c.beta = 1; c.no_sk = pl.det ? 1 : 0;      // (deterministic plan: whole tiles, no stream-K)
+      return gemm_bf16res_run(0, c, lo);
+    }
+    c.C = pl.wg_slabs; c.nsplit = pieces; c.c_split_stride = (long)Mo * No;
+    UCHECK_RC(gemm_bf16v2_run(0, c, lo));
   }
   return uniter_slab_reduce_add(pl.wg_slabs, pieces, (size_t)Mo * No, t.dW[p], (size_t)Mo * No, st);
 }
@@ -580,12 +582,16 @@ int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t,
   const void *A[4], *B[4];
   float* dW[4];
   for (int i = 0; i < n; ++i) { Mo[i] = t.Mo[idx[i]]; No[i] = t.No[idx[i]]; A[i] = t.A[idx[i]]; B[i] = t.B[idx[i]]; dW[i] = t.dW[idx[i]]; }
-  const int overwrite = m->wg_overwrite ? 1 : 0;
+  WgradGroupCall c;
+  c.n = n; c.Mo = Mo; c.No = No; c.K = pl.M; c.A = A; c.B = B; c.dW = dW; c.overwrite = m->wg_overwrite ? 1 : 0; c.max_wgs = max_wgs;
+  c.riders = riders; c.stream = sd;
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
     const LaunchOpts lo = {ps.stamp, 0, m->launch_reserve};
-    if (x3) UCHECK_RC(gemm_x3_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, pl.sk_side, pl.sk_side ? pl.sk_bytes : 0, lo));
-    else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, n, Mo, No, pl.M, A, B, dW, sd, overwrite, max_wgs, riders, lo));
+    if (x3) {
+      c.sk_ws = pl.sk_side; c.sk_ws_bytes = pl.sk_side ? pl.sk_bytes : 0;
+      UCHECK_RC(gemm_x3_wgrad_group(cfg, c, lo));
+    } else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, c, lo));
   }
   if (!colsum_after) return 0;
   if (pl.det) {      // in a fixed order; the block partials go to the layer's dU column-partial buffer, which nothing else uses without riders
@@ -1184,11 +1190,13 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     bool grouped = false;
     if (group_env && sw.wgrad_whole == 15 && sw.wgrad_cfg == 0 && pl.prec == PREC_F32 && fuse_db1) {
       const int Mo[4] = {H, I, H, 3 * H}, No[4] = {I, H, H, H};
-      const float* const As[4] = {g2.f, lb.du, g1.f, lb.dqkv};
-      const float* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x.f};
+      const void* const As[4] = {g2.f, lb.du, g1.f, lb.dqkv};
+      const void* const Bs[4] = {lb.hact, lb.y1, lb.ctx, x.f};
       float* const dWs[4] = {m->LG(l, L_W2), m->LG(l, L_W1), m->LG(l, L_OW), m->LG(l, L_QW)};
       ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
-      const int rc = gemm_f32_wgrad_group(4, Mo, No, M, As, Bs, dWs, m->wg_overwrite ? 1 : 0, sd, LaunchOpts{ps.stamp, 0, m->launch_reserve});
+      WgradGroupCall c;
+      c.n = 4; c.Mo = Mo; c.No = No; c.K = M; c.A = As; c.B = Bs; c.dW = dWs; c.overwrite = m->wg_overwrite ? 1 : 0; c.stream = sd;
+      const int rc = gemm_f32_wgrad_group(c, LaunchOpts{ps.stamp, 0, m->launch_reserve});
       if (rc == 0) grouped = true;
       else if (rc != UNITER_E_SHAPE) return rc;
     }
