@@ -21,8 +21,8 @@ extern "C" const char* uniter_build_info(void) {
 
 // The NEXT attention-backward call of this host thread writes its per-sample bias partials in a fixed order (include/uniter_hip.h).
 // A hand-over of the C ABI only: the public attention-backward wrappers take it as their first statement (a refused call and the forms
-// that emit no bias partials included) and pass it down as an argument; the model's schedule passes Plan::det to the internal entry
-// points (gemm_internal.h) instead.
+// that emit no bias partials included) and pass it down as AttnCall::det; the model's schedule sets that field from Plan::det
+// (attn_internal.h) instead.
 // One per HOST THREAD, so that two threads driving the library can never take each other's flag.
 static thread_local int g_attn_bwd_next_det = 0;
 extern "C" int uniter_attn_bwd_set_next_det(int on) {

@@ -621,33 +621,73 @@ __global__ __launch_bounds__(768) void attn_b16_bwd_fused_det_kernel(const Args 
   b16_dkv_body<true>(a, Lr, red_dkv);
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-  UCHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)bytes));
+size_t max2(size_t x, size_t y) { return x > y ? x : y; }
+
+// the kernel arguments both passes share; refuses what no kernel of this file honours
+int fill(Args& a, const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.pieces == 1 && c.dctx_slabs == 1, "%s: the bf16 attention kernels take one dctx slab and write bf16 copies (pieces = 1)", who);
+  UCHECK_ARG(c.B > 0 && c.L > 0 && c.nh > 0, "attn_bf16: bad dims B=%d L=%d nh=%d", c.B, c.L, c.nh);
+  UCHECK_SHAPE(c.L <= MAXL, "attn_bf16: L %d > %d", c.L, MAXL);
+  UCHECK_ARG(c.p_drop >= 0.f && c.p_drop < 1.f, "attn_bf16: bad dropout p");
+  a.B = c.B; a.L = c.L; a.nh = c.nh; a.H = c.nh * D; a.Lp4 = (c.L + 3) / 4;
+  a.scale = 0.125f;        // 1/sqrt(64), model/layer.py:86
+  a.drop = make_drop(c.p_drop, c.seed, c.offset, c.site);
+  a.prio = uniter_switches().attn_prio;
+  a.qkv = c.qkv; a.qb16 = c.qkv_is_bf16; a.mask = c.mask; a.cu = c.cu_seqlens; a.ctx = c.ctx; a.lse = c.lse;
+  a.keep_bits = (u16*)c.keep_bits;
   return 0;
 }
-size_t max3(size_t x, size_t y, size_t z) { return x > y ? (x > z ? x : z) : (y > z ? y : z); }
 
-int fill(Args& a, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site) {
-  UCHECK_ARG(B > 0 && L > 0 && nh > 0, "attn_bf16: bad dims B=%d L=%d nh=%d", B, L, nh);
-  UCHECK_SHAPE(L <= MAXL, "attn_bf16: L %d > %d", L, MAXL);
-  UCHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "attn_bf16: bad dropout p");
-  a.B = B; a.L = L; a.nh = nh; a.H = nh * D; a.Lp4 = (L + 3) / 4;
-  a.scale = 0.125f;        // 1/sqrt(64), model/layer.py:86
-  a.drop = make_drop(p_drop, seed, offset, site);
-  a.prio = uniter_switches().attn_prio;
-  return 0;
+// the backward launches: fused, or dQ then dK|dV through the scratch
+int launch_bwd(const Args& a, int Lr, hipStream_t st, bool det) {
+  // the kernels of this call's Q|K|V format (bf16 or fp32), with and without the order-fixed bias partials
+  const auto fused_det = a.qb16 ? attn_b16_bwd_fused_det_kernel<true> : attn_b16_bwd_fused_det_kernel<false>;
+  const auto dq_det = a.qb16 ? attn_b16_dq_det_kernel<true> : attn_b16_dq_det_kernel<false>;
+  const auto fused = a.qb16 ? attn_b16_bwd_fused_kernel<true> : attn_b16_bwd_fused_kernel<false>;
+  const auto dq = a.qb16 ? attn_b16_dq_kernel<true> : attn_b16_dq_kernel<false>;
+  const int nblk = Lr / 32;
+  const dim3 grid(a.B * a.nh), block(Lr * 4);
+  // the 192-float column-sum area sits behind both the staged images and the exchange area that later aliases them
+  const size_t red_dq = max2((size_t)(2 * Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4);
+  const size_t red_dkv = max2((size_t)(2 * D * TLD) * 2, (size_t)nblk * 64 * 64 * 4);
+  // det (AttnCall::det): the slots of the order-fixed bias partials, [nblk][128] floats behind the 192
+  const size_t tail = 192 * 4 + (det ? (size_t)nblk * 128 * 4 : 0);
+  const size_t lds_dq = red_dq + tail, lds_dkv = red_dkv + tail;
+  if (uniter_switches().attn_bwd_fused)
+    return launch_lds(det ? fused_det : fused, grid, block, max2(lds_dq, lds_dkv), st, a, Lr, (int)red_dq, (int)red_dkv);
+  UCHECK_RC(launch_lds(det ? dq_det : dq, grid, block, lds_dq, st, a, Lr, (int)red_dq));
+  return launch_lds(det ? attn_b16_dkv_det_kernel : attn_b16_dkv_kernel, grid, block, lds_dkv, st, a, Lr, (int)red_dkv);
 }
 
 }  // namespace
 
-extern "C" size_t uniter_attn_bf16_bwd_ws_bytes(int B, int L, int nh) {
-  const int Lr = (L + 31) / 32 * 32;
-  if (B <= 0 || nh <= 0 || L > MAXL) return 0;
-  return (size_t)2 * B * nh * Lr * Lr * sizeof(unsigned short);
+extern "C" size_t uniter_attn_bf16_bwd_ws_bytes(int B, int L, int nh) { return L > MAXL ? 0 : attn_bf16_bwd_ws_bytes(B, L, nh); }
+
+int attn_bf16_fwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.qkv && c.ctx && attn_one_row_source(c), "%s: need attn_mask or cu_seqlens (not both)", who);
+  UCHECK_ARG(!c.keep_ready || c.keep_bits, "attn_bf16_fwd_pre: keep_bits_ready without keep_bits");
+  Args a = {};
+  UCHECK_RC(fill(a, who, c));
+  a.ctx_b16 = (u16*)c.ctx_copy; a.keep_ready = c.keep_ready;
+  const int Lr = attn_block_rows(c.L), nblk = Lr / 32;
+  const size_t lds = max2((size_t)(Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4);
+  return launch_lds(attn_b16_fwd_kernel, dim3(c.B * c.nh), dim3(Lr * 4), lds, (hipStream_t)c.stream, a, Lr);
 }
 
+int attn_bf16_bwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.qkv && c.ctx && c.lse && c.dctx && (c.dqkv || c.dqkv_copy) && c.delta && c.ws && attn_one_row_source(c),
+             "%s: null pointer, or not exactly one of attn_mask / cu_seqlens", who);
+  UCHECK_ARG(c.ws_bytes >= uniter_attn_bf16_bwd_ws_bytes(c.B, c.L, c.nh), "%s: workspace too small", who);
+  Args a = {};
+  UCHECK_RC(fill(a, who, c));
+  a.dctx = c.dctx; a.dqkv = c.dqkv; a.dqkv_b16 = (u16*)c.dqkv_copy; a.bias_part = c.bias_part; a.delta = c.delta;
+  const int Lr = attn_block_rows(c.L);
+  a.pd_ws = (u16*)c.ws;
+  a.ds_ws = a.pd_ws + (size_t)c.B * c.nh * Lr * Lr;
+  return launch_bwd(a, Lr, (hipStream_t)c.stream, c.det && c.bias_part);
+}
+
+// ---- the C ABI ----
 extern "C" int uniter_attn_bf16_fwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
                                     void* ctx_bf16, float* lse, void* keep_bits, int B, int L, int nh, float p_drop,
                                     uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
@@ -659,19 +699,11 @@ extern "C" int uniter_attn_bf16_fwd_pre(const void* qkv, int qkv_is_bf16, const 
                                         float* ctx, void* ctx_bf16, float* lse, void* keep_bits, int keep_bits_ready, int B,
                                         int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
                                         void* stream) {
-  UCHECK_ARG(qkv && ctx && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_bf16_fwd: need attn_mask or cu_seqlens (not both)");
-  UCHECK_ARG(!keep_bits_ready || keep_bits, "attn_bf16_fwd_pre: keep_bits_ready without keep_bits");
-  Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.qb16 = qkv_is_bf16; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = ctx; a.ctx_b16 = (u16*)ctx_bf16; a.lse = lse;
-  a.keep_bits = (u16*)keep_bits; a.keep_ready = keep_bits_ready;
-  const int Lr = (L + 31) / 32 * 32, nblk = Lr / 32;
-  const size_t lds = max3((size_t)(Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4, 0);
-  UCHECK_RC(set_lds(attn_b16_fwd_kernel, lds));
-  hipLaunchKernelGGL(attn_b16_fwd_kernel, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr);
-  UCHECK_LAUNCH();
-  return 0;
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.qkv_is_bf16 = qkv_is_bf16; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.ctx_copy = ctx_bf16; c.pieces = 1; c.keep_bits = keep_bits; c.keep_ready = keep_bits_ready;
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.stream = stream;
+  return attn_bf16_fwd_run("attn_bf16_fwd", c);
 }
 
 extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens,
@@ -680,81 +712,11 @@ extern "C" int uniter_attn_bf16_bwd(const void* qkv, int qkv_is_bf16, const floa
                                     int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
                                     size_t ws_bytes, void* stream) {
   const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
-  return attn_bf16_bwd_run(qkv, qkv_is_bf16, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, bias_part, keep_bits, delta, B, L, nh,
-                           p_drop, seed, offset, site, ws, ws_bytes, stream, det);
-}
-
-// det: the per-sample bias partials in a fixed order (the model's Plan::det; the C ABI: uniter_attn_bwd_set_next_det)
-int attn_bf16_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
-                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
-                      float* delta, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                      size_t ws_bytes, void* stream, bool det) {
-  UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_bf16_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  UCHECK_ARG(ws_bytes >= uniter_attn_bf16_bwd_ws_bytes(B, L, nh), "attn_bf16_bwd: workspace too small");
-  Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.qb16 = qkv_is_bf16; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dqkv = dqkv; a.dqkv_b16 = (u16*)dqkv_bf16; a.bias_part = bias_part; a.keep_bits = (u16*)keep_bits; a.delta = delta;
-  const int Lr = (L + 31) / 32 * 32, nblk = Lr / 32;
-  a.pd_ws = (u16*)ws;
-  a.ds_ws = a.pd_ws + (size_t)B * nh * Lr * Lr;
-  // the 192-float column-sum area sits behind both the staged images and the exchange area that later aliases them
-  const size_t red_dq = max3((size_t)(2 * Lr * KLD + D * TLD) * 2 + Lr * 4, (size_t)nblk * XROW * 64 * 4, 0);
-  const size_t red_dkv = max3((size_t)(2 * D * TLD) * 2, (size_t)nblk * 64 * 64 * 4, 0);
-  const size_t lds_dq = red_dq + 192 * 4, lds_dkv = red_dkv + 192 * 4;
-  if (det && bias_part) {      // (the slots: [nblk][128] floats behind the 192)
-    const size_t slots = (size_t)nblk * 128 * 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (uniter_switches().attn_bwd_fused) {
-      const size_t lds = (lds_dq > lds_dkv ? lds_dq : lds_dkv) + slots;
-      if (a.qb16) {
-        UCHECK_RC(set_lds(attn_b16_bwd_fused_det_kernel<true>, lds));
-        hipLaunchKernelGGL(attn_b16_bwd_fused_det_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds, st, a, Lr, (int)red_dq, (int)red_dkv);
-      } else {
-        UCHECK_RC(set_lds(attn_b16_bwd_fused_det_kernel<false>, lds));
-        hipLaunchKernelGGL(attn_b16_bwd_fused_det_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds, st, a, Lr, (int)red_dq, (int)red_dkv);
-      }
-      UCHECK_LAUNCH();
-      return 0;
-    }
-    UCHECK_RC(set_lds(attn_b16_dkv_det_kernel, lds_dkv + slots));
-    if (a.qb16) {
-      UCHECK_RC(set_lds(attn_b16_dq_det_kernel<true>, lds_dq + slots));
-      hipLaunchKernelGGL(attn_b16_dq_det_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds_dq + slots, st, a, Lr, (int)red_dq);
-    } else {
-      UCHECK_RC(set_lds(attn_b16_dq_det_kernel<false>, lds_dq + slots));
-      hipLaunchKernelGGL(attn_b16_dq_det_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds_dq + slots, st, a, Lr, (int)red_dq);
-    }
-    UCHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_b16_dkv_det_kernel, dim3(B * nh), dim3(Lr * 4), lds_dkv + slots, st, a, Lr, (int)red_dkv);
-    UCHECK_LAUNCH();
-    return 0;
-  }
-  if (uniter_switches().attn_bwd_fused) {
-    const size_t lds = lds_dq > lds_dkv ? lds_dq : lds_dkv;
-    if (a.qb16) {
-      UCHECK_RC(set_lds(attn_b16_bwd_fused_kernel<true>, lds));
-      hipLaunchKernelGGL(attn_b16_bwd_fused_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr, (int)red_dq,
-                         (int)red_dkv);
-    } else {
-      UCHECK_RC(set_lds(attn_b16_bwd_fused_kernel<false>, lds));
-      hipLaunchKernelGGL(attn_b16_bwd_fused_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr, (int)red_dq,
-                         (int)red_dkv);
-    }
-    UCHECK_LAUNCH();
-    return 0;
-  }
-  UCHECK_RC(set_lds(attn_b16_dkv_kernel, lds_dkv));
-  if (a.qb16) {
-    UCHECK_RC(set_lds(attn_b16_dq_kernel<true>, lds_dq));
-    hipLaunchKernelGGL(attn_b16_dq_kernel<true>, dim3(B * nh), dim3(Lr * 4), lds_dq, (hipStream_t)stream, a, Lr, (int)red_dq);
-  } else {
-    UCHECK_RC(set_lds(attn_b16_dq_kernel<false>, lds_dq));
-    hipLaunchKernelGGL(attn_b16_dq_kernel<false>, dim3(B * nh), dim3(Lr * 4), lds_dq, (hipStream_t)stream, a, Lr, (int)red_dq);
-  }
-  UCHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_b16_dkv_kernel, dim3(B * nh), dim3(Lr * 4), lds_dkv, (hipStream_t)stream, a, Lr, (int)red_dkv);
-  UCHECK_LAUNCH();
-  return 0;
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.qkv_is_bf16 = qkv_is_bf16; c.mask = attn_mask; c.cu_seqlens = cu_seqlens;
+  c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.keep_bits = const_cast<void*>(keep_bits);
+  c.dctx = dctx; c.dqkv = dqkv; c.dqkv_copy = dqkv_bf16; c.pieces = 1; c.bias_part = bias_part; c.delta = delta;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.det = det; c.stream = stream;
+  return attn_bf16_bwd_run("attn_bf16_bwd", c);
 }

@@ -1057,84 +1057,98 @@ constexpr int RES_MAX_LR = 256;      // 8 waves (2 per SIMD: 256 VGPRs each); 2*
 
 inline size_t res_lds_bytes(int Lr) { return (size_t)(2 * Lr * LDT + 2 * Lr + 192) * sizeof(float); }
 
-template <typename K>
-int set_dyn_lds(K kernel, size_t bytes) {
-  UCHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return 0;
-}
-
 bool split_enabled() { return uniter_switches().attn_split; }
 bool bwd_fused() { return uniter_switches().attn_bwd_fused; }
 
-int make_args(AttnArgs& a, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
-              uint32_t site) {
-  UCHECK_ARG(B > 0 && L > 0 && nh > 0, "attention: bad dims B=%d L=%d nh=%d", B, L, nh);
-  UCHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "attention: bad dropout p");
-  a.B = B; a.L = L; a.nh = nh; a.H = nh * D; a.Lp4 = (L + 3) / 4;
+// the kernel arguments both passes share
+int make_args(AttnArgs& a, const char* who, const AttnCall& c) {
+  UCHECK_ARG(!c.qkv_is_bf16 && c.dctx_slabs == 1 && (c.pieces == 1 || c.pieces == 3),
+             "%s: the fp32 attention kernels take fp32 Q|K|V, one dctx slab and copies of 1 or 3 pieces", who);
+  UCHECK_RC(attn_check_dims("attention", c));
+  a.B = c.B; a.L = c.L; a.nh = c.nh; a.H = c.nh * D; a.Lp4 = (c.L + 3) / 4;
   a.scale = 0.125f;   // 1/sqrt(64), model/layer.py:86
-  a.drop = make_drop(p_drop, seed, offset, site);
+  a.drop = make_drop(c.p_drop, c.seed, c.offset, c.site);
   a.prio = uniter_switches().attn_prio;
+  a.qkv = (const float*)c.qkv; a.mask = c.mask; a.cu = c.cu_seqlens; a.ctx = c.ctx; a.lse = c.lse;
+  a.keep_bits = (unsigned short*)c.keep_bits; a.b16_pieces = c.pieces;
   return 0;
 }
-
-int launch_bwd_split(const AttnArgs& a, int Lr, float* pd_ws, float* ds_ws, hipStream_t st, bool det) {
-  const size_t lds = res_lds_bytes(Lr);
-  if (det && a.bias_part) {      // (uniter_attn_bwd_set_next_det; the slots: [Lr / 32][128] floats behind `red`)
-    const size_t lds_det = lds + (size_t)(Lr / 32) * 128 * sizeof(float);
-    if (bwd_fused()) {
-      UCHECK_RC(set_dyn_lds(attn_bwd_fused_split_det_kernel, lds_det));
-      hipLaunchKernelGGL(attn_bwd_fused_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
-      UCHECK_LAUNCH();
-      return 0;
-    }
-    UCHECK_RC(set_dyn_lds(attn_bwd_dq_split_det_kernel, lds_det));
-    UCHECK_RC(set_dyn_lds(attn_bwd_dkv_split_det_kernel, lds_det));
-    hipLaunchKernelGGL(attn_bwd_dq_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
-    UCHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_bwd_dkv_split_det_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr, pd_ws, ds_ws);
-    UCHECK_LAUNCH();
-    return 0;
-  }
-  if (bwd_fused()) {
-    UCHECK_RC(set_dyn_lds(attn_bwd_fused_split_kernel, lds));
-    hipLaunchKernelGGL(attn_bwd_fused_split_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws);
-    UCHECK_LAUNCH();
-    return 0;
-  }
-  UCHECK_RC(set_dyn_lds(attn_bwd_dq_split_kernel, lds));
-  UCHECK_RC(set_dyn_lds(attn_bwd_dkv_split_kernel, lds));
-  hipLaunchKernelGGL(attn_bwd_dq_split_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws);
-  UCHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_bwd_dkv_split_kernel, dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws);
-  UCHECK_LAUNCH();
+// the resident and streaming kernels (L beyond the L <= 192 kernels, or UNITER_ATTN_SPLIT=0) read a padded mask and write fp32 only
+int beyond_split_check(const char* who, const AttnCall& c) {
+  UCHECK_ARG(!c.cu_seqlens && !c.ctx_copy && !c.dqkv_copy && !c.keep_bits && !c.bias_part,
+             "%s: cu_seqlens, operand copies, keep flags and bias partials need the L <= %d kernels (L = %d)", who,
+             uniter_attn_varlen_max_len(), c.L);
+  return 0;
+}
+// the forms that have only the L <= 192 kernels (the C ABI's _varlen, _ex and _pre entry points)
+int split_len_check(const char* who, int L) {
+  UCHECK_SHAPE(attn_block_rows(L) <= uniter_attn_varlen_max_len(), "%s: L %d > %d", who, L, uniter_attn_varlen_max_len());
   return 0;
 }
 
 }  // namespace
 
+int attn_f32_fwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.qkv && c.ctx && attn_one_row_source(c), "%s: null pointer, or not exactly one of attn_mask / cu_seqlens", who);
+  UCHECK_ARG(!c.keep_ready || c.keep_bits, "attn_fwd_pre: keep_bits_ready without keep_bits");
+  AttnArgs a = {};
+  UCHECK_RC(make_args(a, who, c));
+  a.ctx_b16 = (unsigned short*)c.ctx_copy; a.keep_ready = c.keep_ready;
+  const int Lr = attn_block_rows(c.L);
+  const dim3 heads(c.B * c.nh);
+  hipStream_t st = (hipStream_t)c.stream;
+  if (Lr <= SPLIT_MAX_LR && split_enabled())
+    return launch_lds(attn_fwd_split_kernel, heads, dim3(Lr * 4), res_lds_bytes(Lr), st, a, Lr);
+  UCHECK_RC(beyond_split_check(who, c));
+  if (Lr <= RES_MAX_LR) return launch_lds(attn_fwd_res_kernel, heads, dim3(Lr * 2), res_lds_bytes(Lr), st, a, Lr);
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3((c.L + 32 * NW - 1) / (32 * NW), c.B * c.nh), dim3(NW * 64), 0, st, a);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+int attn_f32_bwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.qkv && c.ctx && c.lse && c.dctx && (c.dqkv || c.dqkv_copy) && c.delta && attn_one_row_source(c),
+             "%s: null pointer, or not exactly one of attn_mask / cu_seqlens", who);
+  AttnArgs a = {};
+  UCHECK_RC(make_args(a, who, c));
+  a.dctx = c.dctx; a.dqkv = c.dqkv; a.dqkv_b16 = (unsigned short*)c.dqkv_copy; a.bias_part = c.bias_part; a.delta = c.delta;
+  const int Lr = attn_block_rows(c.L);
+  const dim3 heads(c.B * c.nh);
+  hipStream_t st = (hipStream_t)c.stream;
+  if (Lr <= SPLIT_MAX_LR && split_enabled()) {
+    UCHECK_ARG(c.ws && c.ws_bytes >= attn_f32_bwd_ws_bytes(c.B, c.L, c.nh), "%s: workspace too small (uniter_attn_bwd_ws_bytes)", who);
+    float* pd_ws = (float*)c.ws;
+    float* ds_ws = pd_ws + (size_t)c.B * c.nh * Lr * Lr;
+    // det (AttnCall::det): the slots of the order-fixed bias partials, [Lr / 32][128] floats behind `red`
+    const bool det = c.det && c.bias_part;
+    const size_t lds = res_lds_bytes(Lr) + (det ? (size_t)(Lr / 32) * 128 * sizeof(float) : 0);
+    if (bwd_fused())
+      return launch_lds(det ? attn_bwd_fused_split_det_kernel : attn_bwd_fused_split_kernel, heads, dim3(Lr * 4), lds, st, a, Lr, pd_ws,
+                        ds_ws);
+    UCHECK_RC(launch_lds(det ? attn_bwd_dq_split_det_kernel : attn_bwd_dq_split_kernel, heads, dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws));
+    return launch_lds(det ? attn_bwd_dkv_split_det_kernel : attn_bwd_dkv_split_kernel, heads, dim3(Lr * 4), lds, st, a, Lr, pd_ws, ds_ws);
+  }
+  UCHECK_RC(beyond_split_check(who, c));
+  if (Lr <= RES_MAX_LR) {
+    UCHECK_RC(launch_lds(attn_bwd_dq_res_kernel, heads, dim3(Lr * 2), res_lds_bytes(Lr), st, a, Lr));
+    return launch_lds(attn_bwd_dkv_res_kernel, heads, dim3(Lr * 2), res_lds_bytes(Lr), st, a, Lr);
+  }
+  const dim3 grid((c.L + 32 * NW - 1) / (32 * NW), c.B * c.nh);
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(NW * 64), 0, st, a);
+  UCHECK_LAUNCH();
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(NW * 64), 0, st, a);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the C ABI: each entry point states its call by name, and the preconditions that are its own ----
 extern "C" int uniter_attn_fwd(const float* qkv, const float* attn_mask, float* ctx, float* lse, int B,
                                int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                uint32_t site, void* stream) {
-  UCHECK_ARG(qkv && attn_mask && ctx, "attn_fwd: null pointer");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = attn_mask; a.ctx = ctx; a.lse = lse;
-  const int Lr = (L + 31) / 32 * 32;
-  if (Lr <= SPLIT_MAX_LR && split_enabled()) {
-    const size_t lds = res_lds_bytes(Lr);
-    UCHECK_RC(set_dyn_lds(attn_fwd_split_kernel, lds));
-    hipLaunchKernelGGL(attn_fwd_split_kernel, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr);
-  } else if (Lr <= RES_MAX_LR) {
-    const size_t lds = res_lds_bytes(Lr);
-    UCHECK_RC(set_dyn_lds(attn_fwd_res_kernel, lds));
-    hipLaunchKernelGGL(attn_fwd_res_kernel, dim3(B * nh), dim3(Lr * 2), lds, (hipStream_t)stream, a, Lr);
-  } else {
-    dim3 grid((L + 32 * NW - 1) / (32 * NW), B * nh);
-    hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(NW * 64), 0, (hipStream_t)stream, a);
-  }
-  UCHECK_LAUNCH();
-  return 0;
+  AttnCall c;      // a mask only; any length
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.ctx = ctx; c.lse = lse;
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.stream = stream;
+  return attn_f32_fwd_run("attn_fwd", c);
 }
 
 // Packed batches (uniter_hip.h): the split kernels only -- Lmax <= 192.
@@ -1143,17 +1157,11 @@ extern "C" int uniter_attn_varlen_max_len(void) { return split_enabled() ? SPLIT
 extern "C" int uniter_attn_fwd_varlen(const float* qkv, const int32_t* cu_seqlens, float* ctx, float* lse, int B,
                                       int Lmax, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                       uint32_t site, void* stream) {
-  UCHECK_ARG(qkv && cu_seqlens && ctx, "attn_fwd_varlen: null pointer");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, Lmax, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = nullptr; a.cu = cu_seqlens; a.ctx = ctx; a.lse = lse;
-  const int Lr = (Lmax + 31) / 32 * 32;
-  UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_fwd_varlen: Lmax %d > %d", Lmax, uniter_attn_varlen_max_len());
-  const size_t lds = res_lds_bytes(Lr);
-  UCHECK_RC(set_dyn_lds(attn_fwd_split_kernel, lds));
-  hipLaunchKernelGGL(attn_fwd_split_kernel, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr);
-  UCHECK_LAUNCH();
-  return 0;
+  UCHECK_RC(split_len_check("attn_fwd_varlen", Lmax));
+  AttnCall c;
+  c.B = B; c.L = Lmax; c.nh = nh; c.qkv = qkv; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.stream = stream;
+  return attn_f32_fwd_run("attn_fwd_varlen", c);
 }
 
 extern "C" int uniter_attn_bwd_varlen(const float* qkv, const int32_t* cu_seqlens, const float* ctx,
@@ -1161,23 +1169,17 @@ extern "C" int uniter_attn_bwd_varlen(const float* qkv, const int32_t* cu_seqlen
                                       int Lmax, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                       uint32_t site, void* ws, size_t ws_bytes, void* stream) {
   (void)attn_bwd_take_next_det();      // (this form emits no bias partials: nothing to order)
-  UCHECK_ARG(qkv && cu_seqlens && ctx && lse && dctx && dqkv && delta && ws, "attn_bwd_varlen: null pointer");
-  const int Lr = (Lmax + 31) / 32 * 32;
-  UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_bwd_varlen: Lmax %d > %d", Lmax, uniter_attn_varlen_max_len());
-  UCHECK_ARG(ws_bytes >= (size_t)2 * B * nh * Lr * Lr * sizeof(float), "attn_bwd_varlen: workspace too small");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, Lmax, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = nullptr; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dqkv = dqkv; a.delta = delta;
-  float* pd_ws = (float*)ws;
-  float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, false);
+  UCHECK_RC(split_len_check("attn_bwd_varlen", Lmax));
+  AttnCall c;
+  c.B = B; c.L = Lmax; c.nh = nh; c.qkv = qkv; c.cu_seqlens = cu_seqlens; c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site;
+  c.dctx = dctx; c.dqkv = dqkv; c.delta = delta; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return attn_f32_bwd_run("attn_bwd_varlen", c);
 }
 
 // General forms: mask XOR cu_seqlens, optional bf16 copies of the outputs (split kernels only: L <= 192).
 extern "C" size_t uniter_attn_keep_bits_bytes(int B, int L, int nh) {
-  const int Lr = (L + 31) / 32 * 32;
-  return (size_t)B * nh * L * (Lr / 32) * 2 * sizeof(unsigned short);
+  return (size_t)B * nh * L * (attn_block_rows(L) / 32) * 2 * sizeof(unsigned short);
 }
 
 extern "C" int uniter_attn_keep_bits_gen(void* keep_bits, size_t layer_stride_bytes, int nlayers, int B, int L, int nh,
@@ -1186,7 +1188,7 @@ extern "C" int uniter_attn_keep_bits_gen(void* keep_bits, size_t layer_stride_by
   UCHECK_ARG(keep_bits && nlayers >= 1 && nlayers <= 65535 && B > 0 && L > 0 && nh > 0 && layer_stride_bytes % 2 == 0,
              "attn_keep_bits_gen: bad argument");
   UCHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "attn_keep_bits_gen: bad dropout p");
-  const int Lr = (L + 31) / 32 * 32, nblk = Lr / 32;
+  const int Lr = attn_block_rows(L), nblk = Lr / 32;
   UCHECK_SHAPE(Lr <= SPLIT_MAX_LR, "attn_keep_bits_gen: L %d > %d", L, SPLIT_MAX_LR);
   const size_t words = (size_t)B * nh * L * nblk * 2;
   UCHECK_ARG(nlayers == 1 || layer_stride_bytes >= words * 2, "attn_keep_bits_gen: layers overlap");
@@ -1204,41 +1206,27 @@ extern "C" int uniter_attn_fwd_ex(const float* qkv, const float* attn_mask, cons
                              stream);
 }
 
-static int attn_fwd_pre_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
-                            void* ctx_bf16, int pieces, float* lse, void* keep_bits, int keep_bits_ready, int B, int L, int nh,
-                            float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream);
-
 extern "C" int uniter_attn_fwd_pre(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
                                    void* ctx_bf16, float* lse, void* keep_bits, int keep_bits_ready, int B, int L, int nh,
                                    float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
-  return attn_fwd_pre_run(qkv, attn_mask, cu_seqlens, ctx, ctx_bf16, 1, lse, keep_bits, keep_bits_ready, B, L, nh, p_drop, seed,
-                          offset, site, stream);
+  UCHECK_RC(split_len_check("attn_fwd_ex", L));
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.ctx_copy = ctx_bf16; c.pieces = 1; c.keep_bits = keep_bits; c.keep_ready = keep_bits_ready;
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.stream = stream;
+  return attn_f32_fwd_run("attn_fwd_ex", c);
 }
 
 extern "C" int uniter_attn_fwd_pre_x3(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
                                       void* ctx_x3, float* lse, void* keep_bits, int keep_bits_ready, int B, int L, int nh,
                                       float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
   UCHECK_ARG(ctx_x3 && ((uintptr_t)ctx_x3 & 7) == 0, "attn_fwd_pre_x3: ctx_x3 is NULL or misaligned");
-  return attn_fwd_pre_run(qkv, attn_mask, cu_seqlens, ctx, ctx_x3, 3, lse, keep_bits, keep_bits_ready, B, L, nh, p_drop, seed,
-                          offset, site, stream);
-}
-
-static int attn_fwd_pre_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
-                            void* ctx_bf16, int pieces, float* lse, void* keep_bits, int keep_bits_ready, int B, int L, int nh,
-                            float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
-  UCHECK_ARG(qkv && ctx && ((attn_mask != nullptr) != (cu_seqlens != nullptr)), "attn_fwd_ex: need attn_mask or cu_seqlens (not both)");
-  UCHECK_ARG(!keep_bits_ready || keep_bits, "attn_fwd_pre: keep_bits_ready without keep_bits");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = ctx; a.ctx_b16 = (unsigned short*)ctx_bf16; a.b16_pieces = pieces; a.lse = lse;
-  a.keep_bits = (unsigned short*)keep_bits; a.keep_ready = keep_bits_ready;
-  const int Lr = (L + 31) / 32 * 32;
-  UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_fwd_ex: L %d > %d", L, uniter_attn_varlen_max_len());
-  const size_t lds = res_lds_bytes(Lr);
-  UCHECK_RC(set_dyn_lds(attn_fwd_split_kernel, lds));
-  hipLaunchKernelGGL(attn_fwd_split_kernel, dim3(B * nh), dim3(Lr * 4), lds, (hipStream_t)stream, a, Lr);
-  UCHECK_LAUNCH();
-  return 0;
+  UCHECK_RC(split_len_check("attn_fwd_ex", L));
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.ctx_copy = ctx_x3; c.pieces = 3; c.keep_bits = keep_bits; c.keep_ready = keep_bits_ready;
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.stream = stream;
+  return attn_f32_fwd_run("attn_fwd_ex", c);
 }
 
 extern "C" int uniter_attn_bwd_ex(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
@@ -1248,8 +1236,13 @@ extern "C" int uniter_attn_bwd_ex(const float* qkv, const float* attn_mask, cons
                                   size_t ws_bytes, void* stream) {
   const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
   UCHECK_ARG(dqkv, "attn_bwd_ex: dqkv is NULL");
-  return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, 1, bias_part, keep_bits, delta, B, L, nh,
-                         p_drop, seed, offset, site, ws, ws_bytes, stream, det);
+  UCHECK_RC(split_len_check("attn_bwd_ex", L));
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.keep_bits = const_cast<void*>(keep_bits);
+  c.dctx = dctx; c.dqkv = dqkv; c.dqkv_copy = dqkv_bf16; c.pieces = 1; c.bias_part = bias_part; c.delta = delta;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.det = det; c.stream = stream;
+  return attn_f32_bwd_run("attn_bwd_ex", c);
 }
 
 extern "C" int uniter_attn_bwd_ex_x3(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
@@ -1259,33 +1252,18 @@ extern "C" int uniter_attn_bwd_ex_x3(const float* qkv, const float* attn_mask, c
                                      size_t ws_bytes, void* stream) {
   const bool det = attn_bwd_take_next_det();
   UCHECK_ARG(dqkv_x3 && ((uintptr_t)dqkv_x3 & 7) == 0, "attn_bwd_ex_x3: dqkv_x3 is NULL or misaligned");
-  return attn_bwd_ex_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_x3, 3, bias_part, keep_bits, delta, B, L, nh,
-                         p_drop, seed, offset, site, ws, ws_bytes, stream, det);
-}
-
-int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens,
-                    const float* ctx, const float* lse, const float* dctx, float* dqkv,
-                    void* dqkv_bf16, int pieces, float* bias_part, const void* keep_bits, float* delta, int B, int L,
-                    int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                    size_t ws_bytes, void* stream, bool det) {
-  UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ws && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_bwd_ex: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  const int Lr = (L + 31) / 32 * 32;
-  UCHECK_SHAPE(Lr <= uniter_attn_varlen_max_len(), "attn_bwd_ex: L %d > %d", L, uniter_attn_varlen_max_len());
-  UCHECK_ARG(ws_bytes >= (size_t)2 * B * nh * Lr * Lr * sizeof(float), "attn_bwd_ex: workspace too small");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dqkv = dqkv; a.dqkv_b16 = (unsigned short*)dqkv_bf16; a.b16_pieces = pieces; a.bias_part = bias_part; a.keep_bits = (unsigned short*)keep_bits; a.delta = delta;
-  float* pd_ws = (float*)ws;
-  float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-  return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, det);
+  UCHECK_RC(split_len_check("attn_bwd_ex", L));
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site; c.keep_bits = const_cast<void*>(keep_bits);
+  c.dctx = dctx; c.dqkv = dqkv; c.dqkv_copy = dqkv_x3; c.pieces = 3; c.bias_part = bias_part; c.delta = delta;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.det = det; c.stream = stream;
+  return attn_f32_bwd_run("attn_bwd_ex", c);
 }
 
 extern "C" size_t uniter_attn_bwd_ws_bytes(int B, int L, int nh) {
-  const int Lr = (L + 31) / 32 * 32;
-  if (B <= 0 || nh <= 0 || Lr > SPLIT_MAX_LR || !split_enabled()) return 0;
-  return (size_t)2 * B * nh * Lr * Lr * sizeof(float);
+  if (attn_block_rows(L) > SPLIT_MAX_LR || !split_enabled()) return 0;
+  return attn_f32_bwd_ws_bytes(B, L, nh);
 }
 
 extern "C" int uniter_attn_bwd(const float* qkv, const float* attn_mask, const float* ctx,
@@ -1293,35 +1271,11 @@ extern "C" int uniter_attn_bwd(const float* qkv, const float* attn_mask, const f
                                int L, int nh, float p_drop, uint64_t seed, uint32_t offset,
                                uint32_t site, void* ws, size_t ws_bytes, void* stream) {
   (void)attn_bwd_take_next_det();      // (no bias partials here either)
-  UCHECK_ARG(qkv && attn_mask && ctx && lse && dctx && dqkv && delta, "attn_bwd: null pointer");
-  UCHECK_ARG(ws_bytes >= uniter_attn_bwd_ws_bytes(B, L, nh) && (ws || ws_bytes == 0 || uniter_attn_bwd_ws_bytes(B, L, nh) == 0),
-             "attn_bwd: workspace too small (uniter_attn_bwd_ws_bytes)");
-  AttnArgs a = {};
-  UCHECK_RC(make_args(a, B, L, nh, p_drop, seed, offset, site));
-  a.qkv = qkv; a.mask = attn_mask; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dqkv = dqkv; a.delta = delta;
-  const int Lr = (L + 31) / 32 * 32;
-  if (Lr <= SPLIT_MAX_LR && split_enabled()) {
-    float* pd_ws = (float*)ws;
-    float* ds_ws = pd_ws + (size_t)B * nh * Lr * Lr;
-    return launch_bwd_split(a, Lr, pd_ws, ds_ws, (hipStream_t)stream, false);
-  }
-  if (Lr <= RES_MAX_LR) {
-    const size_t lds = res_lds_bytes(Lr);
-    UCHECK_RC(set_dyn_lds(attn_bwd_dq_res_kernel, lds));
-    UCHECK_RC(set_dyn_lds(attn_bwd_dkv_res_kernel, lds));
-    hipLaunchKernelGGL(attn_bwd_dq_res_kernel, dim3(B * nh), dim3(Lr * 2), lds, (hipStream_t)stream, a, Lr);
-    UCHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_bwd_dkv_res_kernel, dim3(B * nh), dim3(Lr * 2), lds, (hipStream_t)stream, a, Lr);
-    UCHECK_LAUNCH();
-    return 0;
-  }
-  dim3 grid((L + 32 * NW - 1) / (32 * NW), B * nh);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(NW * 64), 0, (hipStream_t)stream, a);
-  UCHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, dim3(NW * 64), 0, (hipStream_t)stream, a);
-  UCHECK_LAUNCH();
-  return 0;
+  AttnCall c;      // a mask only; any length (beyond the L <= 192 kernels no workspace is read)
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.seed = seed; c.offset = offset; c.site = site;
+  c.dctx = dctx; c.dqkv = dqkv; c.delta = delta; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return attn_f32_bwd_run("attn_bwd", c);
 }
 
 #ifdef ATTN_STAMPS

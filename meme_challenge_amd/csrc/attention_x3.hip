@@ -776,98 +776,97 @@ __global__ __launch_bounds__(768) void attn_x3_bwd_kernel(const Args a, int Lr) 
   }
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-  UCHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)bytes));
-  return 0;
-}
-
-int fill(Args& a, int B, int L, int nh, float p_drop, const void* keep_bits, const char* who) {
-  UCHECK_ARG(B > 0 && L > 0 && nh > 0, "%s: bad dims B=%d L=%d nh=%d", who, B, L, nh);
-  UCHECK_SHAPE(L <= MAXL, "%s: L %d > %d", who, L, MAXL);
-  UCHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: bad dropout p", who);
-  UCHECK_ARG(p_drop == 0.f || keep_bits, "%s: dropout needs the keep flags (uniter_attn_keep_bits_gen)", who);
-  a.B = B; a.L = L; a.nh = nh; a.H = nh * D;
+// the kernel arguments both passes share; refuses what no kernel of this file honours: they draw no dropout (the keep flags are
+// read), take no workspace, and only the x3 backward (pieces = 3, fp32 Q|K|V) sums dctx slabs
+int fill(Args& a, const char* who, const AttnCall& c) {
+  UCHECK_ARG((c.pieces == 3 && !c.qkv_is_bf16) || (c.pieces == 1 && c.dctx_slabs == 1),
+             "%s: pieces = 3 with fp32 Q|K|V, or pieces = 1 with one dctx slab", who);
+  UCHECK_ARG(!c.seed && !c.offset && !c.site && !c.ws && !c.ws_bytes, "%s: these kernels draw no dropout and take no workspace", who);
+  UCHECK_ARG(c.B > 0 && c.L > 0 && c.nh > 0, "%s: bad dims B=%d L=%d nh=%d", who, c.B, c.L, c.nh);
+  UCHECK_SHAPE(c.L <= MAXL, "%s: L %d > %d", who, c.L, MAXL);
+  UCHECK_ARG(c.p_drop >= 0.f && c.p_drop < 1.f, "%s: bad dropout p", who);
+  UCHECK_ARG(c.p_drop == 0.f || c.keep_bits, "%s: dropout needs the keep flags (uniter_attn_keep_bits_gen)", who);
+  a.B = c.B; a.L = c.L; a.nh = c.nh; a.H = c.nh * D;
   a.scale = 0.125f;        // 1/sqrt(64), model/layer.py:86
-  a.keep_bits = p_drop > 0.f ? static_cast<const u16*>(keep_bits) : nullptr;
-  a.drop_scale = 1.0f / (1.0f - p_drop);
+  a.keep_bits = c.p_drop > 0.f ? static_cast<const u16*>(c.keep_bits) : nullptr;
+  a.drop_scale = 1.0f / (1.0f - c.p_drop);
   a.prio = uniter_switches().attn_prio;
+  a.qkv = c.qkv; a.mask = c.mask; a.cu = c.cu_seqlens; a.ctx = c.ctx; a.lse = c.lse;
   return 0;
 }
 
 template <int NP, bool QB16>
 int launch_fwd(const Args& a, hipStream_t st) {
-  const int Lr = (a.L + 31) / 32 * 32;
-  const size_t lds = (size_t)2 * NP * IMG + (size_t)Lr * 4;
-  UCHECK_RC(set_lds(attn_x3_fwd_kernel<NP, QB16>, lds));
-  hipLaunchKernelGGL((attn_x3_fwd_kernel<NP, QB16>), dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr);
-  UCHECK_LAUNCH();
-  return 0;
+  const int Lr = attn_block_rows(a.L);
+  return launch_lds(attn_x3_fwd_kernel<NP, QB16>, dim3(a.B * a.nh), dim3(Lr * 4), (size_t)2 * NP * IMG + (size_t)Lr * 4, st, a, Lr);
 }
 
 template <int NP, bool QB16>
 int launch_bwd(const Args& a, hipStream_t st, bool det) {
-  const int Lr = (a.L + 31) / 32 * 32;
+  const int Lr = attn_block_rows(a.L);
+  const dim3 grid(a.B * a.nh), block(Lr * 4);
   const size_t lds = (size_t)2 * NP * IMG + (size_t)3 * Lr * 4 + 192 * 4 + (size_t)Lr * (Lr / 32) * 4;
-  if (det) {      // (uniter_attn_bwd_set_next_det: the dQ slots, [Lr / 16 waves][64] floats, behind the keep words)
-    const size_t lds_det = lds + (size_t)(Lr / 16) * 64 * 4;
-    UCHECK_RC(set_lds(attn_x3_bwd_kernel<NP, QB16, X3_DET>, lds_det));
-    hipLaunchKernelGGL((attn_x3_bwd_kernel<NP, QB16, X3_DET>), dim3(a.B * a.nh), dim3(Lr * 4), lds_det, st, a, Lr);
-    UCHECK_LAUNCH();
-    return 0;
-  }
+  // det (AttnCall::det): the dQ slots, [Lr / 16 waves][64] floats, behind the keep words
+  if (det) return launch_lds(attn_x3_bwd_kernel<NP, QB16, X3_DET>, grid, block, lds + (size_t)(Lr / 16) * 64 * 4, st, a, Lr);
 #ifdef UNITER_X3_LAB
   if constexpr (NP == 3 && !QB16) {
     const int lab = uniter_switch_attn_x3_lab();
-#define X3A_LAB_CASE(N)                                                                                                  \
-    if (lab == N) {                                                                                                      \
-      UCHECK_RC(set_lds(attn_x3_bwd_kernel<3, false, N>, lds));                                                          \
-      hipLaunchKernelGGL((attn_x3_bwd_kernel<3, false, N>), dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr);             \
-      UCHECK_LAUNCH();                                                                                                   \
-      return 0;                                                                                                          \
-    }
+#define X3A_LAB_CASE(N) if (lab == N) return launch_lds(attn_x3_bwd_kernel<3, false, N>, grid, block, lds, st, a, Lr);
     X3A_LAB_CASE(1) X3A_LAB_CASE(2) X3A_LAB_CASE(3) X3A_LAB_CASE(4) X3A_LAB_CASE(5) X3A_LAB_CASE(6) X3A_LAB_CASE(8) X3A_LAB_CASE(11)
 #undef X3A_LAB_CASE
   }
 #endif
-  UCHECK_RC(set_lds(attn_x3_bwd_kernel<NP, QB16, 0>, lds));
-  hipLaunchKernelGGL((attn_x3_bwd_kernel<NP, QB16, 0>), dim3(a.B * a.nh), dim3(Lr * 4), lds, st, a, Lr);
-  UCHECK_LAUNCH();
-  return 0;
+  return launch_lds(attn_x3_bwd_kernel<NP, QB16, 0>, grid, block, lds, st, a, Lr);
 }
+// instantiated here, in the order in which the device object has always listed its kernels (x3, then b16x): the object's bytes
+// do not depend on which launcher below names a format first
+template int launch_fwd<3, false>(const Args&, hipStream_t);
+template int launch_bwd<3, false>(const Args&, hipStream_t, bool);
+template int launch_fwd<1, true>(const Args&, hipStream_t);
+template int launch_fwd<1, false>(const Args&, hipStream_t);
+template int launch_bwd<1, true>(const Args&, hipStream_t, bool);
+template int launch_bwd<1, false>(const Args&, hipStream_t, bool);
 
 }  // namespace
 
 extern "C" int uniter_attn_x3_max_len(void) { return MAXL; }
 
-extern "C" int uniter_attn_x3_fwd(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx, void* ctx_x3,
-                                  float* lse, const void* keep_bits, int B, int L, int nh, float p_drop, void* stream) {
-  UCHECK_ARG(qkv && (ctx || ctx_x3) && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_x3_fwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  UCHECK_ARG(((uintptr_t)ctx_x3 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0, "attn_x3_fwd: misaligned pointer");
+int attn_x3_fwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.qkv && (c.ctx || c.ctx_copy) && attn_one_row_source(c), "%s: null pointer, or not exactly one of attn_mask / cu_seqlens", who);
+  UCHECK_ARG(((uintptr_t)c.ctx_copy & 15) == 0 && ((uintptr_t)c.qkv & 15) == 0 && ((uintptr_t)c.ctx & 15) == 0, "%s: misaligned pointer", who);
+  UCHECK_ARG(!c.keep_bits || c.keep_ready, "%s: keep flags are read here, never drawn (keep_ready)", who);
   Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, keep_bits, "attn_x3_fwd"));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = ctx; a.ctx_x3 = (u16*)ctx_x3; a.lse = lse;
-  return launch_fwd<3, false>(a, (hipStream_t)stream);
+  UCHECK_RC(fill(a, who, c));
+  a.ctx_x3 = (u16*)c.ctx_copy;
+  hipStream_t st = (hipStream_t)c.stream;
+  if (c.pieces == 3) return launch_fwd<3, false>(a, st);
+  return c.qkv_is_bf16 ? launch_fwd<1, true>(a, st) : launch_fwd<1, false>(a, st);
 }
 
-// det: the per-sample bias partials in a fixed order (the model's Plan::det; the C ABI: uniter_attn_bwd_set_next_det)
-int attn_x3_bwd_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx, const float* lse,
-                    const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv, void* dqkv_x3, float* bias_part,
-                    const void* keep_bits, float* delta, int B, int L, int nh, float p_drop, void* stream, bool det) {
-  UCHECK_ARG(dctx_slabs >= 1 && dctx_slabs <= 4 && (dctx_slabs == 1 || dctx_slab_stride % 4 == 0),
-             "attn_x3_bwd: dctx_slabs %d (1..4) / slab stride not a multiple of 4 elements", dctx_slabs);
-  UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_x3) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_x3_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  UCHECK_ARG(((uintptr_t)dqkv_x3 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0 &&
-                 ((uintptr_t)dctx & 15) == 0 && ((uintptr_t)dqkv & 15) == 0, "attn_x3_bwd: misaligned pointer");
+int attn_x3_bwd_run(const char* who, const AttnCall& c) {
+  UCHECK_ARG(c.dctx_slabs >= 1 && c.dctx_slabs <= 4 && (c.dctx_slabs == 1 || c.dctx_slab_stride % 4 == 0),
+             "%s: dctx_slabs %d (1..4) / slab stride not a multiple of 4 elements", who, c.dctx_slabs);
+  UCHECK_ARG(c.qkv && c.ctx && c.lse && c.dctx && (c.dqkv || c.dqkv_copy) && c.delta && attn_one_row_source(c),
+             "%s: null pointer, or not exactly one of attn_mask / cu_seqlens", who);
+  UCHECK_ARG(((uintptr_t)c.dqkv_copy & 15) == 0 && ((uintptr_t)c.qkv & 15) == 0 && ((uintptr_t)c.ctx & 15) == 0 &&
+                 ((uintptr_t)c.dctx & 15) == 0 && ((uintptr_t)c.dqkv & 15) == 0, "%s: misaligned pointer", who);
   Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, keep_bits, "attn_x3_bwd"));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dctx_slabs = dctx_slabs; a.dctx_slab_stride = dctx_slab_stride;
-  a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_x3; a.bias_part = bias_part; a.delta = delta;
-  return launch_bwd<3, false>(a, (hipStream_t)stream, det);
+  UCHECK_RC(fill(a, who, c));
+  a.dctx = c.dctx; a.dctx_slabs = c.dctx_slabs; a.dctx_slab_stride = c.dctx_slab_stride;
+  a.dqkv = c.dqkv; a.dqkv_x3 = (u16*)c.dqkv_copy; a.bias_part = c.bias_part; a.delta = c.delta;
+  hipStream_t st = (hipStream_t)c.stream;
+  if (c.pieces == 3) return launch_bwd<3, false>(a, st, c.det);
+  return c.qkv_is_bf16 ? launch_bwd<1, true>(a, st, c.det) : launch_bwd<1, false>(a, st, c.det);
+}
+
+// ---- the C ABI ----
+extern "C" int uniter_attn_x3_fwd(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, float* ctx, void* ctx_x3,
+                                  float* lse, const void* keep_bits, int B, int L, int nh, float p_drop, void* stream) {
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.ctx_copy = ctx_x3; c.pieces = 3; c.p_drop = p_drop; c.keep_bits = const_cast<void*>(keep_bits); c.keep_ready = keep_bits != nullptr;
+  c.stream = stream;
+  return attn_x3_fwd_run("attn_x3_fwd", c);
 }
 
 extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
@@ -875,8 +874,12 @@ extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, cons
                                   void* dqkv_x3, float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh,
                                   float p_drop, void* stream) {
   const bool det = attn_bwd_take_next_det();      // (first: a refused call takes the flag with it)
-  return attn_x3_bwd_run(qkv, attn_mask, cu_seqlens, ctx, lse, dctx, dctx_slabs, dctx_slab_stride, dqkv, dqkv_x3, bias_part, keep_bits,
-                         delta, B, L, nh, p_drop, stream, det);
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse);
+  c.p_drop = p_drop; c.keep_bits = const_cast<void*>(keep_bits);
+  c.dctx = dctx; c.dctx_slabs = dctx_slabs; c.dctx_slab_stride = dctx_slab_stride;
+  c.dqkv = dqkv; c.dqkv_copy = dqkv_x3; c.pieces = 3; c.bias_part = bias_part; c.delta = delta; c.det = det; c.stream = stream;
+  return attn_x3_bwd_run("attn_x3_bwd", c);
 }
 
 // The bf16 mode's attention in the same decomposition (one wave per 16 rows, one LDS image per operand read row-wise and
@@ -886,28 +889,11 @@ extern "C" int uniter_attn_x3_bwd(const float* qkv, const float* attn_mask, cons
 extern "C" int uniter_attn_b16x_fwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, float* ctx,
                                     void* ctx_bf16, float* lse, const void* keep_bits, int B, int L, int nh, float p_drop,
                                     void* stream) {
-  UCHECK_ARG(qkv && (ctx || ctx_bf16) && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_b16x_fwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  UCHECK_ARG(((uintptr_t)ctx_bf16 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0, "attn_b16x_fwd: misaligned pointer");
-  Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, keep_bits, "attn_b16x_fwd"));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = ctx; a.ctx_x3 = (u16*)ctx_bf16; a.lse = lse;
-  return qkv_is_bf16 ? launch_fwd<1, true>(a, (hipStream_t)stream) : launch_fwd<1, false>(a, (hipStream_t)stream);
-}
-
-int attn_b16x_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
-                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
-                      float* delta, int B, int L, int nh, float p_drop, void* stream, bool det) {
-  UCHECK_ARG(qkv && ctx && lse && dctx && (dqkv || dqkv_bf16) && delta && ((attn_mask != nullptr) != (cu_seqlens != nullptr)),
-             "attn_b16x_bwd: null pointer, or not exactly one of attn_mask / cu_seqlens");
-  UCHECK_ARG(((uintptr_t)dqkv_bf16 & 15) == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0 &&
-                 ((uintptr_t)dctx & 15) == 0 && ((uintptr_t)dqkv & 15) == 0, "attn_b16x_bwd: misaligned pointer");
-  Args a = {};
-  UCHECK_RC(fill(a, B, L, nh, p_drop, keep_bits, "attn_b16x_bwd"));
-  a.qkv = qkv; a.mask = attn_mask; a.cu = cu_seqlens; a.ctx = const_cast<float*>(ctx); a.lse = const_cast<float*>(lse);
-  a.dctx = dctx; a.dctx_slabs = 1; a.dctx_slab_stride = 0;
-  a.dqkv = dqkv; a.dqkv_x3 = (u16*)dqkv_bf16; a.bias_part = bias_part; a.delta = delta;
-  return qkv_is_bf16 ? launch_bwd<1, true>(a, (hipStream_t)stream, det) : launch_bwd<1, false>(a, (hipStream_t)stream, det);
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.qkv_is_bf16 = qkv_is_bf16; c.mask = attn_mask; c.cu_seqlens = cu_seqlens; c.ctx = ctx; c.lse = lse;
+  c.ctx_copy = ctx_bf16; c.pieces = 1; c.p_drop = p_drop; c.keep_bits = const_cast<void*>(keep_bits); c.keep_ready = keep_bits != nullptr;
+  c.stream = stream;
+  return attn_x3_fwd_run("attn_b16x_fwd", c);
 }
 
 extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens,
@@ -915,6 +901,9 @@ extern "C" int uniter_attn_b16x_bwd(const void* qkv, int qkv_is_bf16, const floa
                                     float* bias_part, const void* keep_bits, float* delta, int B, int L, int nh, float p_drop,
                                     void* stream) {
   const bool det = attn_bwd_take_next_det();
-  return attn_b16x_bwd_run(qkv, qkv_is_bf16, attn_mask, cu_seqlens, ctx, lse, dctx, dqkv, dqkv_bf16, bias_part, keep_bits, delta, B, L,
-                           nh, p_drop, stream, det);
+  AttnCall c;
+  c.B = B; c.L = L; c.nh = nh; c.qkv = qkv; c.qkv_is_bf16 = qkv_is_bf16; c.mask = attn_mask; c.cu_seqlens = cu_seqlens;
+  c.ctx = const_cast<float*>(ctx); c.lse = const_cast<float*>(lse); c.p_drop = p_drop; c.keep_bits = const_cast<void*>(keep_bits);
+  c.dctx = dctx; c.dqkv = dqkv; c.dqkv_copy = dqkv_bf16; c.pieces = 1; c.bias_part = bias_part; c.delta = delta; c.det = det; c.stream = stream;
+  return attn_x3_bwd_run("attn_b16x_bwd", c);
 }

@@ -188,25 +188,8 @@ int txt_embed_bwd_det_run(const float* dcat, const int64_t* input_ids, const int
                           void* stream);
 int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int rows, int D, hipStream_t st);
 
-// ---- attention backward: attention_f32.hip, attention_x3.hip, attention_bf16.hip ----
-// The entry points behind uniter_attn_bwd_ex(_x3) (pieces = 1 / 3), uniter_attn_x3_bwd, uniter_attn_b16x_bwd and uniter_attn_bf16_bwd with the
-// order of their bias partials as an argument: det = the per-sample partials are summed in a fixed order.
-int attn_bwd_ex_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx, const float* lse,
-                    const float* dctx, float* dqkv, void* dqkv_copy, int pieces, float* bias_part, const void* keep_bits, float* delta,
-                    int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws, size_t ws_bytes,
-                    void* stream, bool det);
-int attn_x3_bwd_run(const float* qkv, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx, const float* lse,
-                    const float* dctx, int dctx_slabs, size_t dctx_slab_stride, float* dqkv, void* dqkv_x3, float* bias_part,
-                    const void* keep_bits, float* delta, int B, int L, int nh, float p_drop, void* stream, bool det);
-int attn_b16x_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
-                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
-                      float* delta, int B, int L, int nh, float p_drop, void* stream, bool det);
-int attn_bf16_bwd_run(const void* qkv, int qkv_is_bf16, const float* attn_mask, const int32_t* cu_seqlens, const float* ctx,
-                      const float* lse, const float* dctx, float* dqkv, void* dqkv_bf16, float* bias_part, const void* keep_bits,
-                      float* delta, int B, int L, int nh, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                      size_t ws_bytes, void* stream, bool det);
-// api.cpp: the hand-over of uniter_attn_bwd_set_next_det, taken (and reset) by the PUBLIC attention-backward wrappers as their first statement
-bool attn_bwd_take_next_det();
+// ---- attention: attention_f32.hip, attention_x3.hip, attention_bf16.hip ----
+#include "attn_internal.h"
 
 // ---- persistent launches ----
 int gemm_chip_cus();      // gemm_split3.hip: CUs of the current device, a multiple of 8

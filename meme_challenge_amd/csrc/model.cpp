@@ -73,17 +73,6 @@ enum Precision {
 // PREC_X3, none below).  As an output: a product that is given a place for the operand copy writes ONLY that.
 struct Act { float* f; unsigned short* b; };
 
-// the attention kernel of a plan, by its forward entry point; the backward entry point follows from it (backward_layer)
-enum AttnKernel {
-  ATTN_F32,          // uniter_attn_fwd / uniter_attn_bwd: any length, reads the padded mask
-  ATTN_F32_PRE,      // uniter_attn_fwd_pre / uniter_attn_bwd_ex: the L <= 192 kernels (packed batches, saved plans)
-  ATTN_F32_PRE_X3,   // uniter_attn_fwd_pre_x3 / uniter_attn_bwd_ex_x3: the same with x3 pieces out (precision 3)
-  ATTN_X3,           // uniter_attn_x3_fwd / _bwd: precision 3, the attention's own products on the bf16 pipe
-  ATTN_BF16_PRE,     // uniter_attn_bf16_fwd_pre / uniter_attn_bf16_bwd: precision 2 (attention_bf16.hip)
-  ATTN_B16X          // uniter_attn_b16x_fwd / _bwd: precision 2 in attention_x3.hip's decomposition
-};
-inline bool attn_is_b16(AttnKernel k) { return k == ATTN_BF16_PRE || k == ATTN_B16X; }
-
 struct Plan {
   int B, T, R, L, S, T0, M, mode;
   bool has_txt, has_img;
@@ -920,32 +909,20 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     UCHECK_RC(linear(m, UNITER_K_GEMM_QKV_FWD, st, 0, M, 3 * H, H, l, L_QW, x, qkv, 1, UNITER_EPI_BIAS, m->LP(l, L_QB), nullptr, nullptr));
     {
       ProfScope ps(m, UNITER_K_ATTN_FWD, st);
-      // the dropout keep flags: attention_x3.hip's kernels only read them; the others draw them (or read them: keep_pre) for the backward pass
-      unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;
-      unsigned short* keep_wr = save ? lb.keepb : nullptr;
-      switch (pl.attn_fwd) {
-      case ATTN_B16X:      // precision 2: the attention products run on the bf16 pipe as well
-        UCHECK_RC(uniter_attn_b16x_fwd(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_rd, B, L, nh, pa, st));
-        break;
-      case ATTN_BF16_PRE:
-        UCHECK_RC(uniter_attn_bf16_fwd_pre(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
-                                           seed, offset, SITE_ATTN_PROBS(l), st));
-        break;
-      case ATTN_X3:      // the attention's own products on the bf16 pipe as well
-        UCHECK_RC(uniter_attn_x3_fwd(lb.qkv, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_rd, B, L, nh, pa, st));
-        break;
-      case ATTN_F32_PRE_X3:      // the context leaves the kernel as x3 pieces too
-        UCHECK_RC(uniter_attn_fwd_pre_x3(lb.qkv, mask, cu_seqlens, lb.ctx, lb.ctxb, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
-                                         seed, offset, SITE_ATTN_PROBS(l), st));
-        break;
-      case ATTN_F32_PRE:
-        UCHECK_RC(uniter_attn_fwd_pre(lb.qkv, mask, cu_seqlens, lb.ctx, nullptr, lb.lse, keep_wr, keep_pre ? 1 : 0, B, L, nh, pa,
-                                      seed, offset, SITE_ATTN_PROBS(l), st));
-        break;
-      case ATTN_F32:      // (never packed)
-        UCHECK_RC(uniter_attn_fwd(lb.qkv, mask, lb.ctx, lb.lse, B, L, nh, pa, seed, offset, SITE_ATTN_PROBS(l), st));
-        break;
-      }
+      const AttnKernel k = pl.attn_fwd;
+      const bool flags_only = attn_reads_flags_only(k);
+      AttnCall c;
+      c.B = B; c.L = L; c.nh = nh; c.qkv = lb.qkv; c.qkv_is_bf16 = attn_b16; c.mask = mask; c.cu_seqlens = cu_seqlens;
+      c.ctx = lb.ctx; c.lse = lb.lse; c.p_drop = pa; c.stream = st;
+      // the context leaves the kernel in the operand format too (precision 2: bf16, 3: x3 pieces), but for the two plain fp32 forms
+      c.ctx_copy = (k == ATTN_F32 || k == ATTN_F32_PRE) ? nullptr : lb.ctxb;
+      c.pieces = pl.prec == PREC_X3 ? 3 : 1;
+      // the dropout keep flags: attention_x3.hip's kernels only read them; the others draw them (or read them: keep_pre) and write
+      // them for the backward pass of a plan that is saved -- never the any-length form
+      c.keep_bits = (k != ATTN_F32 && (flags_only || save)) ? lb.keepb : nullptr;
+      c.keep_ready = c.keep_bits && (flags_only || keep_pre);
+      c.seed = flags_only ? 0 : seed; c.offset = flags_only ? 0 : offset; c.site = flags_only ? 0 : SITE_ATTN_PROBS(l);
+      UCHECK_RC(attn_forward(k, "attn_forward", c));
     }
     // the probabilities as an output (uniter_model_set_attn_probs): here, because only between this layer's attention launch and the
     // next layer's query|key|value product does lb.qkv hold layer l's values in a pass that saves nothing
@@ -1093,40 +1070,23 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   }
   {
     ProfScope ps(m, UNITER_K_ATTN_BWD, st);
-    const float* mask = pl.packed ? nullptr : m->batch.attention_mask;
-    const int32_t* cu_seqlens = pl.packed ? m->batch.cu_seqlens : nullptr;
-    unsigned short* keep_rd = pa > 0.f ? lb.keepb : nullptr;      // attention_x3.hip's kernels (the forward pass of a saved plan left the flags)
-    // (pl.det: the kernel's bias partials in a fixed order)
-    switch (pl.attn_bwd) {
-    case ATTN_B16X:
-      UCHECK_RC(attn_b16x_bwd_run(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, lb.qb_part, keep_rd, lb.delta,
-                                  B, L, nh, pa, st, pl.det));
-      break;
-    case ATTN_BF16_PRE:
-      UCHECK_RC(attn_bf16_bwd_run(lb.qkv, 1, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx,
-                                  nullptr /* fp32 dqkv has no reader in this mode: bias partials are fused */,
-                                  lb.dqkvb, lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset,
-                                  SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
-      break;
-    case ATTN_X3:
-      UCHECK_RC(attn_x3_bwd_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, ns_dctx, MH, nullptr, lb.dqkvb, lb.qb_part, keep_rd,
-                                lb.delta, B, L, nh, pa, st, pl.det));
-      break;
-    case ATTN_F32_PRE_X3:      // dqkv leaves the kernel as x3 pieces only: nothing reads an fp32 copy in this mode
-      UCHECK_RC(attn_bwd_ex_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, nullptr, lb.dqkvb, 3,
-                                lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
-                                pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
-      break;
-    case ATTN_F32_PRE:
-      UCHECK_RC(attn_bwd_ex_run(lb.qkv, mask, cu_seqlens, lb.ctx, lb.lse, lb.dctx, lb.dqkv, nullptr, 1,
-                                lb.qb_part, lb.keepb, lb.delta, B, L, nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l),
-                                pl.attn_ws, pl.attn_ws_bytes, st, pl.det));
-      break;
-    case ATTN_F32:      // (never packed)
-      UCHECK_RC(uniter_attn_bwd(lb.qkv, mask, lb.ctx, lb.lse, lb.dctx, lb.dqkv, lb.delta, B, L,
-                                nh, pa, m->seed, m->offset, SITE_ATTN_PROBS(l), pl.attn_ws, pl.attn_ws_bytes, st));
-      break;
-    }
+    const AttnKernel k = pl.attn_bwd;
+    const bool flags_only = attn_reads_flags_only(k);
+    AttnCall c;
+    c.B = B; c.L = L; c.nh = nh; c.qkv = lb.qkv; c.qkv_is_bf16 = attn_b16;
+    c.mask = pl.packed ? nullptr : m->batch.attention_mask; c.cu_seqlens = pl.packed ? m->batch.cu_seqlens : nullptr;
+    c.ctx = lb.ctx; c.lse = lb.lse; c.p_drop = pa; c.stream = st;
+    // the flags the forward pass of a saved plan left; without them the kernels that can draw repeat the forward pass's draw
+    c.keep_bits = fused_qb ? lb.keepb : nullptr;
+    c.seed = flags_only ? 0 : m->seed; c.offset = flags_only ? 0 : m->offset; c.site = flags_only ? 0 : SITE_ATTN_PROBS(l);
+    c.dctx = lb.dctx; c.dctx_slabs = ns_dctx; c.dctx_slab_stride = ns_dctx > 1 ? MH : 0;
+    // dqkv leaves the kernel in the operand format only (nothing reads an fp32 copy in those modes), but for the two plain fp32 forms
+    const bool copy_out = k != ATTN_F32 && k != ATTN_F32_PRE;
+    c.dqkv = copy_out ? nullptr : lb.dqkv; c.dqkv_copy = copy_out ? lb.dqkvb : nullptr; c.pieces = pl.prec == PREC_X3 ? 3 : 1;
+    c.bias_part = fused_qb ? lb.qb_part : nullptr; c.delta = lb.delta;
+    c.ws = flags_only ? nullptr : pl.attn_ws; c.ws_bytes = flags_only ? 0 : pl.attn_ws_bytes;
+    c.det = pl.det;      // the kernel's bias partials in a fixed order
+    UCHECK_RC(attn_backward(k, "attn_backward", c));
   }
   // dqkv's operand copy where the attention kernel left none: PREC_BF16 unless the kernel was a bf16 one; PREC_X3 behind uniter_attn_bwd only
   if (pl.prec == PREC_BF16 ? !attn_b16 : pl.prec == PREC_X3 && !fused_qb) UCHECK_RC(operand_copy(pl, dqkv, M, 3 * H, st));

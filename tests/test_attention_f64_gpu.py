@@ -289,6 +289,14 @@ def test_fp32_piece_variants():
     _report('pre_x3')
 
 
+def test_fp32_piece_variants_on_a_packed_batch():
+    """the same pair behind cu_seqlens: the three-piece copies of ctx and dqkv land on a packed batch's rows (lengths 1 .. 192, the
+    reference and the bounds of test_fp32_packed_forms)"""
+    for call in LISTS['PACKED']():
+        judge('pre_x3', call)
+    _report('pre_x3')
+
+
 @pytest.mark.parametrize('which', ['LONG', 'LENGTHS3', 'MASKS'])
 def test_fp32_plain_forms(which):
     """uniter_attn_fwd / uniter_attn_bwd: L <= 192 as the general forms, to 256 the resident kernels, beyond the streaming ones (with
