@@ -537,182 +537,34 @@ int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int r
   return 0;
 }
 
-#define NV_DISPATCH(KERNEL, GRID, ARG)                                                         \
-  switch ((H / 4 + 63) / 64) {                                                                 \
-    case 1: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(256), 0, st, ARG); break;               \
-    case 2: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(256), 0, st, ARG); break;               \
-    case 3: hipLaunchKernelGGL((KERNEL<3>), GRID, dim3(256), 0, st, ARG); break;               \
-    case 4: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, st, ARG); break;               \
-    default: uniter_set_error("embed: hidden size %d unsupported (max 1024)", H);              \
-             return UNITER_E_SHAPE;                                                            \
-  }
-
-// KERNEL<NV, further template arguments>
-#define NV_DISPATCH_T(KERNEL, GRID, ARG, ...)                                                           \
+// KERNEL<NV, further template arguments>(ARG) for the NV 16-byte pieces per lane that H takes
+#define NV_DISPATCH(KERNEL, GRID, ARG, ...)                                                             \
   switch ((H / 4 + 63) / 64) {                                                                          \
-    case 1: hipLaunchKernelGGL((KERNEL<1, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
-    case 2: hipLaunchKernelGGL((KERNEL<2, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
-    case 3: hipLaunchKernelGGL((KERNEL<3, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
-    case 4: hipLaunchKernelGGL((KERNEL<4, __VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;           \
+    case 1: hipLaunchKernelGGL((KERNEL<1, ##__VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 2: hipLaunchKernelGGL((KERNEL<2, ##__VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 3: hipLaunchKernelGGL((KERNEL<3, ##__VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;         \
+    case 4: hipLaunchKernelGGL((KERNEL<4, ##__VA_ARGS__>), GRID, dim3(256), 0, st, ARG); break;         \
     default: uniter_set_error("embed: hidden size %d unsupported (max 1024)", H);                       \
              return UNITER_E_SHAPE;                                                                     \
   }
+
+// A code object holds its kernel templates' instantiations in the order the host code first names them.  This list names them in the
+// order the launchers named them while the plain, _delta and _det forms were separate functions, so the device code stays byte for
+// byte what it was under the merged launchers below; nothing reads it.
+#define NV4(K) (const void*)K<1>, (const void*)K<2>, (const void*)K<3>, (const void*)K<4>
+#define NV4_T(K, ...) (const void*)K<1, __VA_ARGS__>, (const void*)K<2, __VA_ARGS__>, (const void*)K<3, __VA_ARGS__>, (const void*)K<4, __VA_ARGS__>
+[[maybe_unused]] static const void* const kernel_order[] = {
+    NV4(txt_embed_fwd_kernel), NV4_T(txt_embed_bwd_kernel, false, true), NV4(txt_embed_bwd_kernel), NV4(img_embed_fwd_kernel),
+    NV4(img_embed_bwd_kernel), NV4_T(txt_embed_fwd_kernel, true), NV4(det_chunk_kernel), NV4(det_owner_kernel),
+    NV4_T(txt_embed_bwd_kernel, true, true), NV4_T(txt_embed_bwd_kernel, true), NV4_T(img_embed_bwd_kernel, true)};
+#undef NV4
+#undef NV4_T
 
 extern "C" size_t uniter_embed_bwd_ws_bytes(int rows, int H) {
   return (size_t)bwd_blocks(rows) * 7 * H * sizeof(float);
 }
 
-extern "C" int uniter_txt_embed_fwd(const int64_t* input_ids, const int64_t* position_ids,
-                                    const int64_t* type_ids, const float* word, const float* pos,
-                                    const float* type, const float* gamma, const float* beta, float* cat,
-                                    int B, int T, int S, int H, int vocab, int max_pos, int type_vocab,
-                                    int pos_bcast, float p_drop, uint64_t seed, uint32_t offset,
-                                    void* stream) {
-  UCHECK_ARG(input_ids && position_ids && word && pos && type && gamma && beta && cat, "txt_embed_fwd: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && T <= S, "txt_embed_fwd: bad shape");
-  if (B * T <= 0) return 0;
-  TxtArgs a = {};
-  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
-  a.type = type; a.gamma = gamma; a.beta = beta; a.cat = cat; a.B = B; a.T = T; a.S = S; a.H = H;
-  a.vocab = vocab; a.max_pos = max_pos; a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
-  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
-  hipStream_t st = (hipStream_t)stream;
-  NV_DISPATCH(txt_embed_fwd_kernel, dim3((B * T + 3) / 4), a);
-  UCHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int uniter_txt_embed_bwd(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
-                                    const int64_t* type_ids, const float* word, const float* pos,
-                                    const float* type, const float* gamma, float* dword, float* dpos,
-                                    float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H,
-                                    int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop,
-                                    uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
-  return txt_embed_bwd_run(dcat, input_ids, position_ids, type_ids, word, pos, type, gamma, nullptr, dword, dpos, dtype, dgamma, dbeta, B, T,
-                           S, H, vocab, max_pos, type_vocab, pos_bcast, p_drop, seed, offset, ws, ws_bytes, stream);
-}
-
-// uniter_txt_embed_bwd behind a forward pass that had `delta` added to the word rows (uniter_txt_embed_fwd_delta): the LayerNorm's
-// input is recomputed with it.  delta == NULL: the kernels uniter_txt_embed_bwd always ran
-int txt_embed_bwd_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
-                      const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
-                      float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
-                      int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
-                      void* stream) {
-  UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && dword && dpos && dtype &&
-             dgamma && dbeta && ws, "txt_embed_bwd: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && T <= S, "txt_embed_bwd: bad shape");
-  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_ws_bytes(B * T, H), "txt_embed_bwd: workspace too small");
-  if (B * T <= 0) return 0;
-  TxtDeltaArgs a = {};
-  a.delta = delta;
-  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
-  a.type = type; a.gamma = gamma; a.dcat = dcat; a.dword = dword; a.dpos = dpos; a.dtype = dtype;
-  a.part = (float*)ws; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
-  a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
-  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bwd_blocks(B * T);
-  if (delta) {
-    NV_DISPATCH_T(txt_embed_bwd_kernel, dim3(nblk), a, false, true);
-  } else {
-    const TxtArgs& plain = a;
-    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), plain);
-  }
-  UCHECK_LAUNCH();
-  float* outs[3] = {dgamma, dbeta, type_ids ? nullptr : dtype};
-  return finalize_partials_multi(a.part, nblk, (size_t)3 * H, outs, 3, H, st);
-}
-
-extern "C" int uniter_img_embed_fwd(const float* imgfc, const float* pos7, const int64_t* img_type_ids,
-                                    const float* Wp, const float* bp, const float* type, const float* g_i,
-                                    const float* b_i, const float* g_p, const float* b_p, const float* g_f,
-                                    const float* b_f, float* cat, float* stats, int B, int R, int T0, int S,
-                                    int H, int type_vocab, float p_drop, uint64_t seed, uint32_t offset,
-                                    void* stream) {
-  UCHECK_ARG(imgfc && pos7 && Wp && bp && type && g_i && b_i && g_p && b_p && g_f && b_f && cat,
-             "img_embed_fwd: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && T0 + R <= S && type_vocab >= 2, "img_embed_fwd: bad shape");
-  if (B * R <= 0) return 0;
-  ImgArgs a = {};
-  a.imgfc = imgfc; a.pos7 = pos7; a.type_ids = img_type_ids; a.Wp = Wp; a.bp = bp; a.type = type;
-  a.g_i = g_i; a.b_i = b_i; a.g_p = g_p; a.b_p = b_p; a.g_f = g_f; a.b_f = b_f; a.cat = cat;
-  a.stats = stats; a.B = B; a.R = R; a.T0 = T0; a.S = S; a.H = H; a.type_vocab = type_vocab;
-  a.drop = make_drop(p_drop, seed, offset, SITE_IMG_EMB);
-  hipStream_t st = (hipStream_t)stream;
-  NV_DISPATCH(img_embed_fwd_kernel, dim3((B * R + 3) / 4), a);
-  UCHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int uniter_img_embed_bwd(const float* dcat, const float* imgfc, const float* pos7,
-                                    const int64_t* img_type_ids, const float* Wp, const float* bp,
-                                    const float* type, const float* g_i, const float* b_i, const float* g_p,
-                                    const float* b_p, const float* g_f, const float* stats, float* d_imgfc,
-                                    float* d_posfc, float* dWp, float* dbp, float* dtype, float* dg_i,
-                                    float* db_i, float* dg_p, float* db_p, float* dg_f, float* db_f, int B,
-                                    int R, int T0, int S, int H, int type_vocab, float p_drop, uint64_t seed,
-                                    uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
-  UCHECK_ARG(dcat && imgfc && pos7 && Wp && bp && type && g_i && b_i && g_p && b_p && g_f && stats &&
-             d_imgfc && d_posfc && dWp && dbp && dtype && dg_i && db_i && dg_p && db_p && dg_f && db_f && ws,
-             "img_embed_bwd: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && T0 + R <= S && type_vocab >= 2, "img_embed_bwd: bad shape");
-  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_ws_bytes(B * R, H), "img_embed_bwd: workspace too small");
-  if (B * R <= 0) return 0;
-  ImgArgs a = {};
-  a.imgfc = imgfc; a.pos7 = pos7; a.type_ids = img_type_ids; a.Wp = Wp; a.bp = bp; a.type = type;
-  a.g_i = g_i; a.b_i = b_i; a.g_p = g_p; a.b_p = b_p; a.g_f = g_f; a.stats = const_cast<float*>(stats);
-  a.dcat = dcat; a.d_imgfc = d_imgfc; a.d_posfc = d_posfc; a.dtype = dtype; a.part = (float*)ws;
-  a.B = B; a.R = R; a.T0 = T0; a.S = S; a.H = H; a.type_vocab = type_vocab;
-  a.drop = make_drop(p_drop, seed, offset, SITE_IMG_EMB);
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bwd_blocks(B * R);
-  NV_DISPATCH(img_embed_bwd_kernel, dim3(nblk), a);
-  UCHECK_LAUNCH();
-  float* outs[7] = {dg_f, db_f, dg_i, db_i, dg_p, db_p, img_type_ids ? nullptr : dtype + H};
-  UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)7 * H, outs, 7, H, st));
-  hipLaunchKernelGGL(pos_linear_wgrad_kernel, dim3((H + 255) / 256, (B * R + 31) / 32), dim3(256), 0, st,
-                     d_posfc, pos7, dWp, dbp, B * R, H);
-  UCHECK_LAUNCH();
-  return 0;
-}
-
-// ---- the deterministic backward's entry points (include/uniter_hip.h) ----
-#define NV_DISPATCH_DET(KERNEL, GRID, ARG)                                                     \
-  switch ((H / 4 + 63) / 64) {                                                                 \
-    case 1: hipLaunchKernelGGL((KERNEL<1, true>), GRID, dim3(256), 0, st, ARG); break;         \
-    case 2: hipLaunchKernelGGL((KERNEL<2, true>), GRID, dim3(256), 0, st, ARG); break;         \
-    case 3: hipLaunchKernelGGL((KERNEL<3, true>), GRID, dim3(256), 0, st, ARG); break;         \
-    case 4: hipLaunchKernelGGL((KERNEL<4, true>), GRID, dim3(256), 0, st, ARG); break;         \
-    default: uniter_set_error("embed: hidden size %d unsupported (max 1024)", H);              \
-             return UNITER_E_SHAPE;                                                            \
-  }
-
-// uniter_txt_embed_fwd with delta[B][T][H] added to the word rows (include/uniter_hip.h); delta == NULL is that call itself
-extern "C" int uniter_txt_embed_fwd_delta(const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
-                                          const float* word, const float* pos, const float* type, const float* gamma,
-                                          const float* beta, const float* delta, float* cat, int B, int T, int S, int H, int vocab,
-                                          int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset,
-                                          void* stream) {
-  if (!delta)
-    return uniter_txt_embed_fwd(input_ids, position_ids, type_ids, word, pos, type, gamma, beta, cat, B, T, S, H, vocab, max_pos,
-                                type_vocab, pos_bcast, p_drop, seed, offset, stream);
-  UCHECK_ARG(input_ids && position_ids && word && pos && type && gamma && beta && cat, "txt_embed_fwd_delta: null pointer");
-  UCHECK_ARG(((uintptr_t)delta & 15) == 0, "txt_embed_fwd_delta: delta must be 16-byte aligned");
-  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_fwd_delta: bad shape (H %% 4, H <= 1024, T <= S)");
-  if (B * T <= 0) return 0;
-  TxtDeltaArgs a = {};
-  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
-  a.type = type; a.gamma = gamma; a.beta = beta; a.cat = cat; a.B = B; a.T = T; a.S = S; a.H = H;
-  a.vocab = vocab; a.max_pos = max_pos; a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
-  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
-  a.delta = delta;
-  hipStream_t st = (hipStream_t)stream;
-  NV_DISPATCH_T(txt_embed_fwd_kernel, dim3((B * T + 3) / 4), a, true);
-  UCHECK_LAUNCH();
-  return 0;
-}
-
+// ---- the deterministic backward (include/uniter_hip.h): its workspace and its fold ----
 namespace {
 
 // the workspace of one _det call: column partials | drow | per table: order, skey, pieces | position-projection partials
@@ -761,113 +613,256 @@ extern "C" size_t uniter_embed_bwd_det_ws_bytes(int txt_rows, int img_rows, int 
   return t > i ? t : i;
 }
 
-extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
-                                        const int64_t* type_ids, const float* word, const float* pos,
-                                        const float* type, const float* gamma, float* dword, float* dpos,
-                                        float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H,
-                                        int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop,
-                                        uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
-  return txt_embed_bwd_det_run(dcat, input_ids, position_ids, type_ids, word, pos, type, gamma, nullptr, dword, dpos, dtype, dgamma, dbeta,
-                               B, T, S, H, vocab, max_pos, type_vocab, pos_bcast, p_drop, seed, offset, ws, ws_bytes, stream);
+// ---- the launchers: one call per side (rowpass_internal.h) ----
+static void fill(TxtArgs& a, const TxtEmbedCall& c) {
+  a.ids = c.ids; a.pos_ids = c.pos_ids; a.type_ids = c.type_ids; a.word = c.word; a.pos = c.pos; a.type = c.type;
+  a.gamma = c.gamma; a.beta = c.beta; a.cat = c.cat; a.dcat = c.dcat; a.dword = c.dword; a.dpos = c.dpos; a.dtype = c.dtype;
+  a.part = (float*)c.ws; a.B = c.B; a.T = c.T; a.S = c.S; a.H = c.H; a.vocab = c.vocab; a.max_pos = c.max_pos;
+  a.type_vocab = c.type_vocab; a.pos_bcast = c.pos_bcast; a.drop = make_drop(c.drop);
+}
+static void fill(ImgArgs& a, const ImgEmbedCall& c) {
+  a.imgfc = c.imgfc; a.pos7 = c.pos7; a.type_ids = c.type_ids; a.Wp = c.Wp; a.bp = c.bp; a.type = c.type;
+  a.g_i = c.g_i; a.b_i = c.b_i; a.g_p = c.g_p; a.b_p = c.b_p; a.g_f = c.g_f; a.b_f = c.b_f; a.cat = c.cat; a.stats = c.stats;
+  a.dcat = c.dcat; a.d_imgfc = c.d_imgfc; a.d_posfc = c.d_posfc; a.dtype = c.dtype; a.part = (float*)c.ws;
+  a.B = c.B; a.R = c.R; a.T0 = c.T0; a.S = c.S; a.H = c.H; a.type_vocab = c.type_vocab; a.drop = make_drop(c.drop);
 }
 
-// uniter_txt_embed_bwd_det with the forward pass's perturbation, as txt_embed_bwd_run
-int txt_embed_bwd_det_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
-                          const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
-                          float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
-                          int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
-                          void* stream) {
-  UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && dword && dpos && dtype &&
-             dgamma && dbeta && ws, "txt_embed_bwd_det: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_bwd_det: bad shape (H %% 4, H <= 1024, T <= S)");
-  UCHECK_SHAPE((long long)B * T <= UNITER_EMBED_DET_MAX_ROWS, "txt_embed_bwd_det: %lld rows, the stable rank covers at most %d",
-               (long long)B * T, UNITER_EMBED_DET_MAX_ROWS);
-  if (B * T <= 0) return 0;
-  const int rows = B * T;
-  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_det_ws_bytes(rows, 0, H), "txt_embed_bwd_det: workspace too small");
-  const DetWs w = det_carve(ws, rows, H, 3, 3, false);
-  TxtDetDeltaArgs a = {};
-  a.delta = delta;
-  a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos;
-  a.type = type; a.gamma = gamma; a.dcat = dcat; a.dword = dword; a.dpos = dpos; a.dtype = dtype;
-  a.part = w.part; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
-  a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
-  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
-  a.drow = w.drow;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bwd_blocks(rows);
-  if (delta) {
-    NV_DISPATCH_T(txt_embed_bwd_kernel, dim3(nblk), a, true, true);
+// c.delta: [B][T][H] added to the word rows (uniter_txt_embed_fwd_delta), 16-byte aligned; NULL = uniter_txt_embed_fwd itself
+int txt_embed_fwd_run(const TxtEmbedCall& c) {
+  const char* who = c.delta ? "txt_embed_fwd_delta" : "txt_embed_fwd";
+  const int H = c.H;
+  UCHECK_ARG(c.ids && c.pos_ids && c.word && c.pos && c.type && c.gamma && c.beta && c.cat, "%s: null pointer", who);
+  if (c.delta) {
+    UCHECK_ARG(((uintptr_t)c.delta & 15) == 0, "txt_embed_fwd_delta: delta must be 16-byte aligned");
+    UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && c.T <= c.S, "txt_embed_fwd_delta: bad shape (H %% 4, H <= 1024, T <= S)");
   } else {
-    const TxtDetArgs& plain = a;
-    NV_DISPATCH_DET(txt_embed_bwd_kernel, dim3(nblk), plain);
+    UCHECK_SHAPE(H % 4 == 0 && c.T <= c.S, "txt_embed_fwd: bad shape");
+  }
+  if (c.B * c.T <= 0) return 0;
+  TxtDeltaArgs a = {};
+  fill(a, c); a.delta = c.delta;
+  hipStream_t st = (hipStream_t)c.stream;
+  const dim3 grid((c.B * c.T + 3) / 4);
+  if (c.delta) {
+    NV_DISPATCH(txt_embed_fwd_kernel, grid, a, true);
+  } else {
+    const TxtArgs& plain = a;
+    NV_DISPATCH(txt_embed_fwd_kernel, grid, plain);
   }
   UCHECK_LAUNCH();
-  float* outs[3] = {dgamma, dbeta, type_ids ? nullptr : dtype};
-  UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)3 * H, outs, 3, H, st));
+  return 0;
+}
+
+// The text side's backward pass; c.delta: the forward pass's perturbation, with which the LayerNorm's input is recomputed.  c.det: the
+// order-fixed form (uniter_txt_embed_bwd_det) -- the row gradients go to the carved workspace and are folded into the tables by rank
+int txt_embed_bwd_run(const TxtEmbedCall& c) {
+  const char* who = c.det ? "txt_embed_bwd_det" : "txt_embed_bwd";
+  const int H = c.H, rows = c.B * c.T;
+  UCHECK_ARG(c.dcat && c.ids && c.pos_ids && c.word && c.pos && c.type && c.gamma && c.dword && c.dpos && c.dtype &&
+             c.dgamma && c.dbeta && c.ws, "%s: null pointer", who);
+  if (c.det) {
+    UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && c.T <= c.S, "txt_embed_bwd_det: bad shape (H %% 4, H <= 1024, T <= S)");
+    UCHECK_SHAPE((long long)c.B * c.T <= UNITER_EMBED_DET_MAX_ROWS, "txt_embed_bwd_det: %lld rows, the stable rank covers at most %d",
+                 (long long)c.B * c.T, UNITER_EMBED_DET_MAX_ROWS);
+  } else {
+    UCHECK_SHAPE(H % 4 == 0 && c.T <= c.S, "txt_embed_bwd: bad shape");
+    UCHECK_ARG(c.ws_bytes >= uniter_embed_bwd_ws_bytes(rows, H), "txt_embed_bwd: workspace too small");
+  }
+  if (rows <= 0) return 0;
+  if (c.det) UCHECK_ARG(c.ws_bytes >= uniter_embed_bwd_det_ws_bytes(rows, 0, H), "txt_embed_bwd_det: workspace too small");
+  const DetWs w = c.det ? det_carve(c.ws, rows, H, 3, 3, false) : DetWs{};
+  TxtDetDeltaArgs a = {};
+  fill(a, c); a.delta = c.delta;
+  if (c.det) { a.part = w.part; a.drow = w.drow; }
+  hipStream_t st = (hipStream_t)c.stream;
+  const int nblk = bwd_blocks(rows);
+  if (c.det && c.delta) {
+    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), a, true, true);
+  } else if (c.det) {
+    const TxtDetArgs& plain = a;
+    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), plain, true);
+  } else if (c.delta) {
+    const TxtDeltaArgs d = {a, c.delta};
+    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), d, false, true);
+  } else {
+    const TxtArgs& plain = a;
+    NV_DISPATCH(txt_embed_bwd_kernel, dim3(nblk), plain);
+  }
+  UCHECK_LAUNCH();
+  float* outs[3] = {c.dgamma, c.dbeta, c.type_ids ? nullptr : c.dtype};
+  UCHECK_RC(finalize_partials_multi({a.part, nblk, (size_t)3 * H}, outs, 3, H, st));
+  if (!c.det) return 0;
   DetArgs d = {};
   d.drow = w.drow; d.rows = rows; d.H = H;
-  const int64_t* src[3] = {input_ids, position_ids, type_ids};
-  float* grad[3] = {dword, dpos, dtype};
-  const int hi[3] = {vocab, max_pos, type_vocab};
-  const int ntab = type_ids ? 3 : 2;
+  const int64_t* src[3] = {c.ids, c.pos_ids, c.type_ids};
+  float* grad[3] = {c.dword, c.dpos, c.dtype};
+  const int hi[3] = {c.vocab, c.max_pos, c.type_vocab};
+  const int ntab = c.type_ids ? 3 : 2;
   for (int i = 0; i < ntab; ++i) {
     DetTable& t = d.t[i];
     t.ids = src[i]; t.grad = grad[i]; t.order = w.order[i]; t.skey = w.skey[i]; t.piece = w.piece[i]; t.hi = hi[i];
-    t.bcast_T = (i == 1 && pos_bcast) ? T : 0;
+    t.bcast_T = (i == 1 && c.pos_bcast) ? c.T : 0;
     t.skip = i == 0 ? 0 : -1;                           // padding_idx = 0
   }
   return det_fold(d, ntab, st);
 }
 
-extern "C" int uniter_img_embed_bwd_det(const float* dcat, const float* imgfc, const float* pos7,
-                                        const int64_t* img_type_ids, const float* Wp, const float* bp,
-                                        const float* type, const float* g_i, const float* b_i, const float* g_p,
-                                        const float* b_p, const float* g_f, const float* stats, float* d_imgfc,
-                                        float* d_posfc, float* dWp, float* dbp, float* dtype, float* dg_i,
-                                        float* db_i, float* dg_p, float* db_p, float* dg_f, float* db_f, int B,
-                                        int R, int T0, int S, int H, int type_vocab, float p_drop, uint64_t seed,
-                                        uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
-  UCHECK_ARG(dcat && imgfc && pos7 && Wp && bp && type && g_i && b_i && g_p && b_p && g_f && stats &&
-             d_imgfc && d_posfc && dWp && dbp && dtype && dg_i && db_i && dg_p && db_p && dg_f && db_f && ws,
-             "img_embed_bwd_det: null pointer");
-  UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && T0 + R <= S && type_vocab >= 2,
-               "img_embed_bwd_det: bad shape (H %% 4, H <= 1024, T0 + R <= S, type_vocab >= 2)");
-  UCHECK_SHAPE((long long)B * R <= UNITER_EMBED_DET_MAX_ROWS, "img_embed_bwd_det: %lld rows, the stable rank covers at most %d",
-               (long long)B * R, UNITER_EMBED_DET_MAX_ROWS);
-  if (B * R <= 0) return 0;
-  const int rows = B * R;
-  UCHECK_ARG(ws_bytes >= uniter_embed_bwd_det_ws_bytes(0, rows, H), "img_embed_bwd_det: workspace too small");
-  const DetWs w = det_carve(ws, rows, H, 7, 1, true);
-  ImgDetArgs a = {};
-  a.imgfc = imgfc; a.pos7 = pos7; a.type_ids = img_type_ids; a.Wp = Wp; a.bp = bp; a.type = type;
-  a.g_i = g_i; a.b_i = b_i; a.g_p = g_p; a.b_p = b_p; a.g_f = g_f; a.stats = const_cast<float*>(stats);
-  a.dcat = dcat; a.d_imgfc = d_imgfc; a.d_posfc = d_posfc; a.dtype = dtype; a.part = w.part;
-  a.B = B; a.R = R; a.T0 = T0; a.S = S; a.H = H; a.type_vocab = type_vocab;
-  a.drop = make_drop(p_drop, seed, offset, SITE_IMG_EMB);
-  a.drow = w.drow;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bwd_blocks(rows);
-  NV_DISPATCH_DET(img_embed_bwd_kernel, dim3(nblk), a);
-  UCHECK_LAUNCH();
-  float* outs[7] = {dg_f, db_f, dg_i, db_i, dg_p, db_p, img_type_ids ? nullptr : dtype + H};
-  UCHECK_RC(finalize_partials_multi(a.part, nblk, (size_t)7 * H, outs, 7, H, st));
-  if (img_type_ids) {
-    DetArgs d = {};
-    d.drow = w.drow; d.rows = rows; d.H = H;
-    DetTable& t = d.t[0];
-    t.ids = img_type_ids; t.grad = dtype; t.order = w.order[0]; t.skey = w.skey[0]; t.piece = w.piece[0];
-    t.hi = type_vocab; t.bcast_T = 0; t.skip = -1;
-    UCHECK_RC(det_fold(d, 1, st));
-  }
-  const int wchunks = (rows + DET_WG_ROWS - 1) / DET_WG_ROWS;
-  hipLaunchKernelGGL(pos_linear_wgrad_part_kernel, dim3((H + 255) / 256, wchunks), dim3(256), 0, st, d_posfc, pos7, w.wpart,
-                     rows, H);
-  UCHECK_LAUNCH();
-  hipLaunchKernelGGL(pos_linear_wgrad_fold_kernel, dim3((H * 8 + 255) / 256), dim3(256), 0, st, w.wpart, dWp, dbp, wchunks, H);
+int img_embed_fwd_run(const ImgEmbedCall& c) {
+  const int H = c.H;
+  UCHECK_ARG(c.imgfc && c.pos7 && c.Wp && c.bp && c.type && c.g_i && c.b_i && c.g_p && c.b_p && c.g_f && c.b_f && c.cat,
+             "img_embed_fwd: null pointer");
+  UCHECK_SHAPE(H % 4 == 0 && c.T0 + c.R <= c.S && c.type_vocab >= 2, "img_embed_fwd: bad shape");
+  if (c.B * c.R <= 0) return 0;
+  ImgArgs a = {};
+  fill(a, c);
+  hipStream_t st = (hipStream_t)c.stream;
+  NV_DISPATCH(img_embed_fwd_kernel, dim3((c.B * c.R + 3) / 4), a);
   UCHECK_LAUNCH();
   return 0;
 }
+
+// The image side's backward pass; c.det: the order-fixed form (uniter_img_embed_bwd_det), whose token-type gradient of explicit ids is
+// folded by rank and whose position-projection gradient is summed in two passes
+int img_embed_bwd_run(const ImgEmbedCall& c) {
+  const char* who = c.det ? "img_embed_bwd_det" : "img_embed_bwd";
+  const int H = c.H, rows = c.B * c.R;
+  UCHECK_ARG(c.dcat && c.imgfc && c.pos7 && c.Wp && c.bp && c.type && c.g_i && c.b_i && c.g_p && c.b_p && c.g_f && c.stats &&
+             c.d_imgfc && c.d_posfc && c.dWp && c.dbp && c.dtype && c.dg_i && c.db_i && c.dg_p && c.db_p && c.dg_f && c.db_f && c.ws,
+             "%s: null pointer", who);
+  if (c.det) {
+    UCHECK_SHAPE(H % 4 == 0 && H <= 1024 && c.T0 + c.R <= c.S && c.type_vocab >= 2,
+                 "img_embed_bwd_det: bad shape (H %% 4, H <= 1024, T0 + R <= S, type_vocab >= 2)");
+    UCHECK_SHAPE((long long)c.B * c.R <= UNITER_EMBED_DET_MAX_ROWS, "img_embed_bwd_det: %lld rows, the stable rank covers at most %d",
+                 (long long)c.B * c.R, UNITER_EMBED_DET_MAX_ROWS);
+  } else {
+    UCHECK_SHAPE(H % 4 == 0 && c.T0 + c.R <= c.S && c.type_vocab >= 2, "img_embed_bwd: bad shape");
+    UCHECK_ARG(c.ws_bytes >= uniter_embed_bwd_ws_bytes(rows, H), "img_embed_bwd: workspace too small");
+  }
+  if (rows <= 0) return 0;
+  if (c.det) UCHECK_ARG(c.ws_bytes >= uniter_embed_bwd_det_ws_bytes(0, rows, H), "img_embed_bwd_det: workspace too small");
+  const DetWs w = c.det ? det_carve(c.ws, rows, H, 7, 1, true) : DetWs{};
+  ImgDetArgs a = {};
+  fill(a, c);
+  if (c.det) { a.part = w.part; a.drow = w.drow; }
+  hipStream_t st = (hipStream_t)c.stream;
+  const int nblk = bwd_blocks(rows);
+  if (c.det) {
+    NV_DISPATCH(img_embed_bwd_kernel, dim3(nblk), a, true);
+  } else {
+    const ImgArgs& plain = a;
+    NV_DISPATCH(img_embed_bwd_kernel, dim3(nblk), plain);
+  }
+  UCHECK_LAUNCH();
+  float* outs[7] = {c.dg_f, c.db_f, c.dg_i, c.db_i, c.dg_p, c.db_p, c.type_ids ? nullptr : c.dtype + H};
+  UCHECK_RC(finalize_partials_multi({a.part, nblk, (size_t)7 * H}, outs, 7, H, st));
+  if (!c.det) {
+    hipLaunchKernelGGL(pos_linear_wgrad_kernel, dim3((H + 255) / 256, (rows + 31) / 32), dim3(256), 0, st,
+                       c.d_posfc, c.pos7, c.dWp, c.dbp, rows, H);
+    UCHECK_LAUNCH();
+    return 0;
+  }
+  if (c.type_ids) {
+    DetArgs d = {};
+    d.drow = w.drow; d.rows = rows; d.H = H;
+    DetTable& t = d.t[0];
+    t.ids = c.type_ids; t.grad = c.dtype; t.order = w.order[0]; t.skey = w.skey[0]; t.piece = w.piece[0];
+    t.hi = c.type_vocab; t.bcast_T = 0; t.skip = -1;
+    UCHECK_RC(det_fold(d, 1, st));
+  }
+  const int wchunks = (rows + DET_WG_ROWS - 1) / DET_WG_ROWS;
+  hipLaunchKernelGGL(pos_linear_wgrad_part_kernel, dim3((H + 255) / 256, wchunks), dim3(256), 0, st, c.d_posfc, c.pos7, w.wpart,
+                     rows, H);
+  UCHECK_LAUNCH();
+  hipLaunchKernelGGL(pos_linear_wgrad_fold_kernel, dim3((H * 8 + 255) / 256), dim3(256), 0, st, w.wpart, c.dWp, c.dbp, wchunks, H);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the C ABI: each entry point fills a call ----
+#define TXT_IN(c)                                                                                                                  \
+  TxtEmbedCall c;                                                                                                                  \
+  c.ids = input_ids; c.pos_ids = position_ids; c.type_ids = type_ids; c.word = word; c.pos = pos; c.type = type; c.gamma = gamma;  \
+  c.B = B; c.T = T; c.S = S; c.H = H; c.vocab = vocab; c.max_pos = max_pos; c.type_vocab = type_vocab; c.pos_bcast = pos_bcast;    \
+  c.drop = {p_drop, seed, offset, SITE_TXT_EMB}; c.stream = stream
+#define TXT_GRADS(c) \
+  c.dcat = dcat; c.dword = dword; c.dpos = dpos; c.dtype = dtype; c.dgamma = dgamma; c.dbeta = dbeta; c.ws = ws; c.ws_bytes = ws_bytes
+
+extern "C" int uniter_txt_embed_fwd(const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids, const float* word,
+                                    const float* pos, const float* type, const float* gamma, const float* beta, float* cat, int B, int T,
+                                    int S, int H, int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed,
+                                    uint32_t offset, void* stream) {
+  TXT_IN(c); c.beta = beta; c.cat = cat;
+  return txt_embed_fwd_run(c);
+}
+
+// uniter_txt_embed_fwd with delta[B][T][H] added to the word rows (include/uniter_hip.h); delta == NULL is that call itself
+extern "C" int uniter_txt_embed_fwd_delta(const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids, const float* word,
+                                          const float* pos, const float* type, const float* gamma, const float* beta, const float* delta,
+                                          float* cat, int B, int T, int S, int H, int vocab, int max_pos, int type_vocab, int pos_bcast,
+                                          float p_drop, uint64_t seed, uint32_t offset, void* stream) {
+  TXT_IN(c); c.beta = beta; c.delta = delta; c.cat = cat;
+  return txt_embed_fwd_run(c);
+}
+
+extern "C" int uniter_txt_embed_bwd(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                                    const float* word, const float* pos, const float* type, const float* gamma, float* dword, float* dpos,
+                                    float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
+                                    int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  TXT_IN(c); TXT_GRADS(c);
+  return txt_embed_bwd_run(c);
+}
+
+extern "C" int uniter_txt_embed_bwd_det(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                                        const float* word, const float* pos, const float* type, const float* gamma, float* dword,
+                                        float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab,
+                                        int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  TXT_IN(c); TXT_GRADS(c); c.det = 1;
+  return txt_embed_bwd_run(c);
+}
+#undef TXT_IN
+#undef TXT_GRADS
+
+#define IMG_IN(c)                                                                                                              \
+  ImgEmbedCall c;                                                                                                              \
+  c.imgfc = imgfc; c.pos7 = pos7; c.type_ids = img_type_ids; c.Wp = Wp; c.bp = bp; c.type = type; c.g_i = g_i; c.b_i = b_i;    \
+  c.g_p = g_p; c.b_p = b_p; c.g_f = g_f; c.B = B; c.R = R; c.T0 = T0; c.S = S; c.H = H; c.type_vocab = type_vocab;            \
+  c.drop = {p_drop, seed, offset, SITE_IMG_EMB}; c.stream = stream
+#define IMG_GRADS(c)                                                                                                           \
+  c.dcat = dcat; c.stats = const_cast<float*>(stats); c.d_imgfc = d_imgfc; c.d_posfc = d_posfc; c.dWp = dWp; c.dbp = dbp;      \
+  c.dtype = dtype; c.dg_i = dg_i; c.db_i = db_i; c.dg_p = dg_p; c.db_p = db_p; c.dg_f = dg_f; c.db_f = db_f; c.ws = ws;       \
+  c.ws_bytes = ws_bytes
+
+extern "C" int uniter_img_embed_fwd(const float* imgfc, const float* pos7, const int64_t* img_type_ids, const float* Wp, const float* bp,
+                                    const float* type, const float* g_i, const float* b_i, const float* g_p, const float* b_p,
+                                    const float* g_f, const float* b_f, float* cat, float* stats, int B, int R, int T0, int S, int H,
+                                    int type_vocab, float p_drop, uint64_t seed, uint32_t offset, void* stream) {
+  IMG_IN(c); c.b_f = b_f; c.cat = cat; c.stats = stats;
+  return img_embed_fwd_run(c);
+}
+
+extern "C" int uniter_img_embed_bwd(const float* dcat, const float* imgfc, const float* pos7, const int64_t* img_type_ids, const float* Wp,
+                                    const float* bp, const float* type, const float* g_i, const float* b_i, const float* g_p,
+                                    const float* b_p, const float* g_f, const float* stats, float* d_imgfc, float* d_posfc, float* dWp,
+                                    float* dbp, float* dtype, float* dg_i, float* db_i, float* dg_p, float* db_p, float* dg_f, float* db_f,
+                                    int B, int R, int T0, int S, int H, int type_vocab, float p_drop, uint64_t seed, uint32_t offset,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  IMG_IN(c); IMG_GRADS(c);
+  return img_embed_bwd_run(c);
+}
+
+extern "C" int uniter_img_embed_bwd_det(const float* dcat, const float* imgfc, const float* pos7, const int64_t* img_type_ids,
+                                        const float* Wp, const float* bp, const float* type, const float* g_i, const float* b_i,
+                                        const float* g_p, const float* b_p, const float* g_f, const float* stats, float* d_imgfc,
+                                        float* d_posfc, float* dWp, float* dbp, float* dtype, float* dg_i, float* db_i, float* dg_p,
+                                        float* db_p, float* dg_f, float* db_f, int B, int R, int T0, int S, int H, int type_vocab,
+                                        float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes, void* stream) {
+  IMG_IN(c); IMG_GRADS(c); c.det = 1;
+  return img_embed_bwd_run(c);
+}
+#undef IMG_IN
+#undef IMG_GRADS
 
 extern "C" int uniter_gather_rows(const float* cat, const int64_t* gather_index, float* out, int B, int S,
                                   int Lout, int H, void* stream) {

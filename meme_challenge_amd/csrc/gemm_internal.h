@@ -1,7 +1,8 @@
-// Host-side declarations shared by the kernel files and the schedule (model.cpp), stated once: the internal entry points behind the
-// C ABI, the one description of a dense product they all take (GemmCall, WgradGroupCall), the argument rules every family shares,
-// and the rules every persistent launch shares (band height of the tile walk, grid cap, rounds).  The defining file and every user
-// include this header, so a changed signature fails where it is defined, at compile time.
+// Host-side declarations shared by the kernel files and the schedule (model.cpp), stated once: the one description of a dense product
+// every GEMM launcher takes (GemmCall, WgradGroupCall) with the argument rules the families share, the rules every persistent launch
+// shares (band height of the tile walk, grid cap, rounds), and -- each in a header of its own, included here -- the row passes and
+// embeddings (rowpass_internal.h) and the attention launchers (attn_internal.h).  The defining file and every user include this
+// header, so a changed signature fails where it is defined, at compile time.
 #pragma once
 #include "common.h"
 
@@ -154,39 +155,8 @@ static inline int balanced_grid(int total, int full) {
 // sum-of-squares slots a launch with riders writes: one per compute wave of each of its `grid` workgroups
 static inline int rider_slots(int waves, int grid) { return waves * grid; }
 
-// ---- row passes: layernorm.hip, embed.hip ----
-int launch_add_f32(float* out, const float* a, const float* b, size_t n, hipStream_t st);
-// out[n] (+)= sum_p part[p*stride + n]
-int finalize_partials(const float* part, int nparts, size_t stride, float* out, int N, int beta, hipStream_t st);
-// second pass of the order-fixed column sums (uniter_colsum_*_add_det): out[c] = out[c] + (((P0 + P1) + P2) + ...) over part[nblocks][cols]
-int colsum_det_finish(const float* part, int nblocks, int cols, float* out, hipStream_t st);
-// outs[j][c] += sum_p part[p*stride + j*H + c] for j < nout (<= 8); NULL outputs skipped
-int finalize_partials_multi(const float* part, int nparts, size_t stride, float* const* outs, int nout, int H,
-                            hipStream_t st);
-int finalize_partials_jobs(int njobs, const float* const* part, const int* nparts, const size_t* stride,
-                           float* const (*outs)[3], const int* nout, const int* seg, hipStream_t st);
-int ln_bwd_partial_rows(int M);
-// The LayerNorm row passes behind uniter_ln_fwd_slabs(_x3) / uniter_ln_bwd_rows_slabs(_x3): pieces = 1 (bf16 copy) or 3 (x3 copy, which needs
-// H % 8 == 0 and a 16-byte aligned buffer: the caller checks), keep_bits = this pass's dropout keep flags drawn ahead or NULL = draw them
-int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma, const float* beta, float* z_out,
-               float* y, void* y_copy, int pieces, float* mean, float* rstd, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-               uint32_t site, const unsigned char* keep_bits, void* stream);
-int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean, const float* rstd,
-                    const float* gamma, float* dz, float* dx, void* dx_copy, int pieces, int want_dbias, int M, int H, float p_drop,
-                    uint64_t seed, uint32_t offset, uint32_t site, const unsigned char* keep_bits, void* ws, size_t ws_bytes, void* stream);
-// the text embedding backward (uniter_txt_embed_bwd / _det) behind a forward pass with a perturbation of the word rows: delta [B, T, H]
-// as uniter_txt_embed_fwd_delta had it, NULL = none (the public entry points)
-int txt_embed_bwd_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
-                      const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
-                      float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
-                      int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
-                      void* stream);
-int txt_embed_bwd_det_run(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
-                          const float* word, const float* pos, const float* type, const float* gamma, const float* delta, float* dword,
-                          float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int T, int S, int H, int vocab, int max_pos,
-                          int type_vocab, int pos_bcast, float p_drop, uint64_t seed, uint32_t offset, void* ws, size_t ws_bytes,
-                          void* stream);
-int launch_masked_rowsum(const float* x, const int64_t* masks, float* out, int rows, int D, hipStream_t st);
+// ---- row passes and embeddings: layernorm.hip, embed.hip, input_grads.hip ----
+#include "rowpass_internal.h"
 
 // ---- attention: attention_f32.hip, attention_x3.hip, attention_bf16.hip ----
 #include "attn_internal.h"

@@ -184,24 +184,32 @@ inline int adv_parts(int n) { return (n + ADV_CHUNK - 1) / ADV_CHUNK; }
     default: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, st, __VA_ARGS__); break;      \
   }
 
-extern "C" int uniter_txt_embed_bwd_rows(const float* dcat, const int64_t* input_ids, const int64_t* position_ids,
-                                         const int64_t* type_ids, const float* word, const float* pos, const float* type,
-                                         const float* gamma, const float* delta, float* d_rows, int B, int T, int S, int H,
-                                         int vocab, int max_pos, int type_vocab, int pos_bcast, float p_drop, uint64_t seed,
-                                         uint32_t offset, void* stream) {
-  UCHECK_ARG(dcat && input_ids && position_ids && word && pos && type && gamma && d_rows, "txt_embed_bwd_rows: null pointer");
-  UCHECK_ARG((((uintptr_t)delta | (uintptr_t)d_rows) & 15) == 0, "txt_embed_bwd_rows: delta and d_rows must be 16-byte aligned");
-  UCHECK_SHAPE(H > 0 && H % 4 == 0 && H <= 1024 && T <= S, "txt_embed_bwd_rows: bad shape (H %% 4, H <= 1024, T <= S)");
-  if (B * T <= 0) return 0;
+// the per-token pass behind the text side's gradient pass: the same call (rowpass_internal.h), its d_rows written
+int txt_embed_bwd_rows_run(const TxtEmbedCall& c) {
+  const int H = c.H;
+  UCHECK_ARG(c.dcat && c.ids && c.pos_ids && c.word && c.pos && c.type && c.gamma && c.d_rows, "txt_embed_bwd_rows: null pointer");
+  UCHECK_ARG((((uintptr_t)c.delta | (uintptr_t)c.d_rows) & 15) == 0, "txt_embed_bwd_rows: delta and d_rows must be 16-byte aligned");
+  UCHECK_SHAPE(H > 0 && H % 4 == 0 && H <= 1024 && c.T <= c.S, "txt_embed_bwd_rows: bad shape (H %% 4, H <= 1024, T <= S)");
+  if (c.B * c.T <= 0) return 0;
   RowsArgs a = {};
-  a.dcat = dcat; a.ids = input_ids; a.pos_ids = position_ids; a.type_ids = type_ids; a.word = word; a.pos = pos; a.type = type;
-  a.gamma = gamma; a.delta = delta; a.d_rows = d_rows; a.B = B; a.T = T; a.S = S; a.H = H; a.vocab = vocab; a.max_pos = max_pos;
-  a.type_vocab = type_vocab; a.pos_bcast = pos_bcast;
-  a.drop = make_drop(p_drop, seed, offset, SITE_TXT_EMB);
-  hipStream_t st = (hipStream_t)stream;
-  IG_NV_DISPATCH(txt_embed_bwd_rows_kernel, dim3((B * T + 3) / 4), a);
+  a.dcat = c.dcat; a.ids = c.ids; a.pos_ids = c.pos_ids; a.type_ids = c.type_ids; a.word = c.word; a.pos = c.pos; a.type = c.type;
+  a.gamma = c.gamma; a.delta = c.delta; a.d_rows = c.d_rows; a.B = c.B; a.T = c.T; a.S = c.S; a.H = H; a.vocab = c.vocab;
+  a.max_pos = c.max_pos; a.type_vocab = c.type_vocab; a.pos_bcast = c.pos_bcast; a.drop = make_drop(c.drop);
+  hipStream_t st = (hipStream_t)c.stream;
+  IG_NV_DISPATCH(txt_embed_bwd_rows_kernel, dim3((c.B * c.T + 3) / 4), a);
   UCHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int uniter_txt_embed_bwd_rows(const float* dcat, const int64_t* input_ids, const int64_t* position_ids, const int64_t* type_ids,
+                                         const float* word, const float* pos, const float* type, const float* gamma, const float* delta,
+                                         float* d_rows, int B, int T, int S, int H, int vocab, int max_pos, int type_vocab, int pos_bcast,
+                                         float p_drop, uint64_t seed, uint32_t offset, void* stream) {
+  TxtEmbedCall c;
+  c.dcat = dcat; c.ids = input_ids; c.pos_ids = position_ids; c.type_ids = type_ids; c.word = word; c.pos = pos; c.type = type;
+  c.gamma = gamma; c.delta = delta; c.d_rows = d_rows; c.B = B; c.T = T; c.S = S; c.H = H; c.vocab = vocab; c.max_pos = max_pos;
+  c.type_vocab = type_vocab; c.pos_bcast = pos_bcast; c.drop = {p_drop, seed, offset, SITE_TXT_EMB}; c.stream = stream;
+  return txt_embed_bwd_rows_run(c);
 }
 
 extern "C" int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, int rows, int H, void* stream) {

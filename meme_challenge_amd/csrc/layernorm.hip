@@ -359,11 +359,10 @@ int launch_add_f32(float* out, const float* a, const float* b, size_t n, hipStre
 }
 
 // accumulate nout (<= 8) outputs of H columns each; NULL outputs are skipped
-int finalize_partials_multi(const float* part, int nparts, size_t stride, float* const* outs, int nout, int H,
-                            hipStream_t st) {
+int finalize_partials_multi(const PartialSums& p, float* const* outs, int nout, int H, hipStream_t st) {
   MultiOut mo = {};
   for (int j = 0; j < nout && j < 8; ++j) mo.out[j] = outs[j];
-  hipLaunchKernelGGL(finalize_multi_kernel, dim3((nout * H + 15) / 16), dim3(256), 0, st, part, nparts, stride,
+  hipLaunchKernelGGL(finalize_multi_kernel, dim3((nout * H + 15) / 16), dim3(256), 0, st, p.part, p.nparts, p.stride,
                      mo, nout, H);
   UCHECK_LAUNCH();
   return 0;
@@ -371,14 +370,13 @@ int finalize_partials_multi(const float* part, int nparts, size_t stride, float*
 
 // Up to 4 jobs: job i accumulates nout[i] (<= 3) outputs of seg[i] columns each out of part[i] (nparts[i] rows of
 // `stride[i]` floats).  NULL outputs are skipped; jobs with part == NULL are dropped.
-int finalize_partials_jobs(int njobs, const float* const* part, const int* nparts, const size_t* stride,
-                           float* const (*outs)[3], const int* nout, const int* seg, hipStream_t st) {
+int finalize_partials_jobs(int njobs, const PartialJobs& j, hipStream_t st) {
   FinJobs J = {};
   int k = 0, blocks = 0;
   for (int i = 0; i < njobs && k < 4; ++i) {
-    if (!part[i] || nparts[i] <= 0) continue;
-    J.part[k] = part[i]; J.nparts[k] = nparts[i]; J.stride[k] = stride[i]; J.seg[k] = seg[i]; J.n[k] = nout[i] * seg[i];
-    for (int o = 0; o < 3; ++o) J.out[k][o] = o < nout[i] ? outs[i][o] : nullptr;
+    if (!j.part[i] || j.nparts[i] <= 0) continue;
+    J.part[k] = j.part[i]; J.nparts[k] = j.nparts[i]; J.stride[k] = j.stride[i]; J.seg[k] = j.seg[i]; J.n[k] = j.nout[i] * j.seg[i];
+    for (int o = 0; o < 3; ++o) J.out[k][o] = o < j.nout[i] ? j.outs[i][o] : nullptr;
     J.first_block[k] = blocks;
     blocks += (J.n[k] + 15) / 16;
     ++k;
@@ -390,10 +388,9 @@ int finalize_partials_jobs(int njobs, const float* const* part, const int* npart
   return 0;
 }
 
-int finalize_partials(const float* part, int nparts, size_t stride, float* out, int N, int beta,
-                      hipStream_t st) {
-  hipLaunchKernelGGL(finalize_partials_kernel, dim3((N + 31) / 32), dim3(256), 0, st, part, nparts,
-                     stride, out, N, beta);
+int finalize_partials(const PartialSums& p, float* out, int N, int beta, hipStream_t st) {
+  hipLaunchKernelGGL(finalize_partials_kernel, dim3((N + 31) / 32), dim3(256), 0, st, p.part, p.nparts,
+                     p.stride, out, N, beta);
   UCHECK_LAUNCH();
   return 0;
 }
@@ -412,7 +409,7 @@ extern "C" int uniter_colsum_f32(const float* X, int M, int N, int ld, float* ou
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 255) / 256, splits), dim3(256), 0, st, X, M, N, ld,
                      (float*)ws);
   UCHECK_LAUNCH();
-  return finalize_partials((const float*)ws, splits, (size_t)N, out, N, beta, st);
+  return finalize_partials({(const float*)ws, splits, (size_t)N}, out, N, beta, st);
 }
 
 extern "C" int uniter_slab_reduce_add(const float* slabs, int nslab, size_t slab_stride, float* out, size_t n, void* stream) {
@@ -462,33 +459,66 @@ extern "C" int uniter_colsum_bf16_add_det(const void* X, int M, int N, int ld, f
   return colsum_det_finish((const float*)ws, nb, N, out, (hipStream_t)stream);
 }
 
-#define LN_DISPATCH(NVv, KERNEL, GRID, ...) LN_DISPATCH_T(NVv, KERNEL, GRID, 256, __VA_ARGS__)
+// KERNEL(NV): the instantiation for NV 16-byte pieces per lane
+#define LN_FWD_K(NV) ln_fwd_kernel<NV>
+#define LN_BWD_K4(NV) ln_bwd_kernel<NV, 4>
+#define LN_BWD_K8(NV) ln_bwd_kernel<NV, 8>
 #define LN_DISPATCH_T(NVv, KERNEL, GRID, THREADS, ...)                                           \
   switch (NVv) {                                                                                 \
-    case 1: hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
-    case 2: hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
-    case 3: hipLaunchKernelGGL((KERNEL<3>), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
-    case 4: hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
-    default: uniter_set_error("layernorm: hidden size %d unsupported (max 1024)", H);            \
+    case 1: hipLaunchKernelGGL((KERNEL(1)), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
+    case 2: hipLaunchKernelGGL((KERNEL(2)), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
+    case 3: hipLaunchKernelGGL((KERNEL(3)), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
+    case 4: hipLaunchKernelGGL((KERNEL(4)), GRID, dim3(THREADS), 0, st, __VA_ARGS__); break;     \
+    default: uniter_set_error("layernorm: hidden size %d unsupported (max 1024)", c.H);          \
              return UNITER_E_SHAPE;                                                              \
   }
 
-extern "C" int uniter_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta,
-                             float* z_out, float* y, float* mean, float* rstd, int M, int H,
-                             float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
-                             void* stream) {
-  return uniter_ln_fwd_b16(x, res, gamma, beta, z_out, y, nullptr, mean, rstd, M, H, p_drop, seed, offset, site, stream);
+// what the two row passes ask alike (required: the pass's own pointers are there)
+static int ln_check(const char* who, const LnCall& c, bool required) {
+  UCHECK_SHAPE(c.pieces != 3 || (c.H % 8 == 0 && ((uintptr_t)c.copy & 15) == 0), "%s: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer", who);
+  UCHECK_ARG(required, "%s: null pointer", who);
+  UCHECK_ARG(c.nslab >= 1 && (c.nslab == 1 || c.slab_stride >= (size_t)c.M * c.H), "%s: bad slab count / stride", who);
+  UCHECK_SHAPE(c.H % 4 == 0 && c.H >= 4, "%s: H must be a multiple of 4", who);
+  return 0;
+}
+static int ln_nv(int H) { return (H / 4 + 63) / 64; }
+
+int ln_fwd_run(const LnCall& c) {
+  UCHECK_RC(ln_check("ln_fwd", c, c.x && c.gamma && c.beta && c.out));
+  UCHECK_ARG((c.mean == nullptr) == (c.rstd == nullptr), "ln_fwd: mean/rstd must both be given or NULL");
+  UCHECK_ARG(c.drop.p >= 0.f && c.drop.p < 1.f, "ln_fwd: bad dropout p");
+  if (c.M <= 0) return 0;
+  hipStream_t st = (hipStream_t)c.stream;
+  LN_DISPATCH_T(ln_nv(c.H), LN_FWD_K, dim3((c.M + 3) / 4), 256, c.x, c.res, c.gamma, c.beta, c.z, c.out, c.mean, c.rstd, c.M, c.H,
+                make_drop(c.drop), (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces);
+  UCHECK_LAUNCH();
+  return 0;
 }
 
-extern "C" int uniter_ln_fwd_b16(const float* x, const float* res, const float* gamma, const float* beta,
-                                 float* z_out, float* y, void* y_bf16, float* mean, float* rstd, int M, int H,
-                                 float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
-  return uniter_ln_fwd_slabs(x, 1, 0, res, gamma, beta, z_out, y, y_bf16, mean, rstd, M, H, p_drop, seed, offset, site, stream);
+extern "C" size_t uniter_ln_bwd_ws_bytes(int M, int H) {
+  return (size_t)ln_bwd_blocks(M) * 3 * H * sizeof(float);
 }
 
+int ln_bwd_rows_run(const LnCall& c) {
+  UCHECK_RC(ln_check("ln_bwd", c, c.x && c.z && c.mean && c.rstd && c.gamma && c.ws));
+  UCHECK_ARG(c.dz || c.out || c.copy, "ln_bwd: need dz or dx");
+  UCHECK_ARG(c.ws_bytes >= uniter_ln_bwd_ws_bytes(c.M, c.H), "ln_bwd: workspace too small");
+  if (c.M <= 0) return 0;
+  hipStream_t st = (hipStream_t)c.stream;
+  const int nv = ln_nv(c.H), nblk = ln_bwd_blocks(c.M);
+#define LNB_ARGS c.x, c.z, c.mean, c.rstd, c.gamma, c.dz, c.out, (float*)c.ws, c.M, c.H, make_drop(c.drop), c.want_dbias != 0, \
+                 (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces
+  if (lnb_waves() == 8) { LN_DISPATCH_T(nv, LN_BWD_K8, dim3(nblk), 512, LNB_ARGS); }
+  else { LN_DISPATCH_T(nv, LN_BWD_K4, dim3(nblk), 256, LNB_ARGS); }
+#undef LNB_ARGS
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the C ABI's nine row passes: each fills a call ----
 // The keep flags the NEXT public LayerNorm row pass of this host thread reads instead of drawing them (uniter_ln_set_next_keep_bits, at
-// the end of this file).  A hand-over of the C ABI only: the four public *_slabs wrappers take it as their first statement -- a call
-// refused further down has taken it too -- and pass it to ln_fwd_run / ln_bwd_rows_run, which the model's schedule calls directly.
+// the end of this file).  A hand-over of the C ABI only: every public row pass takes it as its first statement -- a call refused
+// further down has taken it too; the model's schedule states its flags in the call (DropSite::keep_bits).
 static thread_local const unsigned char* g_next_keep_bits = nullptr;
 static const unsigned char* take_next_keep_bits() {
   const unsigned char* p = g_next_keep_bits;
@@ -496,145 +526,102 @@ static const unsigned char* take_next_keep_bits() {
   return p;
 }
 
-// keep_bits: this pass's dropout keep flags drawn ahead (DropCfg::bits), or NULL = draw them
-int ln_fwd_run(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
-               const float* beta, float* z_out, float* y, void* y_bf16, int pieces, float* mean, float* rstd,
-               int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, const unsigned char* keep_bits,
-               void* stream) {
-  UCHECK_ARG(x && gamma && beta && y, "ln_fwd: null pointer");
-  UCHECK_ARG(nslab >= 1 && (nslab == 1 || slab_stride >= (size_t)M * H), "ln_fwd: bad slab count / stride");
-  UCHECK_ARG((mean == nullptr) == (rstd == nullptr), "ln_fwd: mean/rstd must both be given or NULL");
-  UCHECK_SHAPE(H % 4 == 0 && H >= 4, "ln_fwd: H must be a multiple of 4");
-  UCHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "ln_fwd: bad dropout p");
-  if (M <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  DropCfg drop = make_drop(p_drop, seed, offset, site);
-  drop.bits = drop.active ? keep_bits : nullptr;
-  const int nv = (H / 4 + 63) / 64;
-  LN_DISPATCH(nv, ln_fwd_kernel, dim3((M + 3) / 4), x, res, gamma, beta, z_out, y, mean, rstd, M, H, drop,
-              (unsigned short*)y_bf16, nslab, slab_stride, pieces);
-  UCHECK_LAUNCH();
-  return 0;
+// what the positional lists share, by their parameters' names (LN_CALL's first statement takes the keep flags handed over)
+#define LN_CALL(c) \
+  LnCall c;        \
+  c.drop = {p_drop, seed, offset, site, take_next_keep_bits()}; c.M = M; c.H = H; c.stream = stream
+#define LN_FWD_IN(c) c.x = x; c.res = res; c.gamma = gamma; c.beta = beta; c.z = z_out; c.out = y; c.mean = mean; c.rstd = rstd
+
+extern "C" int uniter_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* z_out, float* y, float* mean,
+                             float* rstd, int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
+  LN_CALL(c); LN_FWD_IN(c);
+  return ln_fwd_run(c);
 }
 
-extern "C" int uniter_ln_fwd_slabs(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
-                                   const float* beta, float* z_out, float* y, void* y_bf16, float* mean, float* rstd,
-                                   int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
-                                   void* stream) {
-  const unsigned char* ahead = take_next_keep_bits();
-  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_bf16, 1, mean, rstd, M, H, p_drop, seed, offset, site, ahead, stream);
+extern "C" int uniter_ln_fwd_b16(const float* x, const float* res, const float* gamma, const float* beta, float* z_out, float* y,
+                                 void* y_bf16, float* mean, float* rstd, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
+                                 uint32_t site, void* stream) {
+  LN_CALL(c); LN_FWD_IN(c); c.copy = y_bf16;
+  return ln_fwd_run(c);
+}
+
+extern "C" int uniter_ln_fwd_slabs(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma, const float* beta,
+                                   float* z_out, float* y, void* y_bf16, float* mean, float* rstd, int M, int H, float p_drop,
+                                   uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
+  LN_CALL(c); LN_FWD_IN(c); c.nslab = nslab; c.slab_stride = slab_stride; c.copy = y_bf16;
+  return ln_fwd_run(c);
 }
 
 extern "C" int uniter_ln_fwd_slabs_x3(const float* x, int nslab, size_t slab_stride, const float* res, const float* gamma,
-                                      const float* beta, float* z_out, float* y, void* y_x3, float* mean, float* rstd,
-                                      int M, int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site,
-                                      void* stream) {
-  const unsigned char* ahead = take_next_keep_bits();
-  UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)y_x3 & 15) == 0, "ln_fwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
-  return ln_fwd_run(x, nslab, slab_stride, res, gamma, beta, z_out, y, y_x3, 3, mean, rstd, M, H, p_drop, seed, offset, site, ahead, stream);
+                                      const float* beta, float* z_out, float* y, void* y_x3, float* mean, float* rstd, int M, int H,
+                                      float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* stream) {
+  LN_CALL(c); LN_FWD_IN(c); c.nslab = nslab; c.slab_stride = slab_stride; c.copy = y_x3; c.pieces = 3;
+  return ln_fwd_run(c);
 }
 
-extern "C" size_t uniter_ln_bwd_ws_bytes(int M, int H) {
-  return (size_t)ln_bwd_blocks(M) * 3 * H * sizeof(float);
-}
+// (z, mean and rstd are LnCall's forward outputs: the backward pass only reads them)
+#define LN_BWD_IN(c) \
+  c.x = dy; c.z = const_cast<float*>(z); c.mean = const_cast<float*>(mean); c.rstd = const_cast<float*>(rstd); c.gamma = gamma; \
+  c.dz = dz; c.out = dx; c.ws = ws; c.ws_bytes = ws_bytes
 
-extern "C" int uniter_ln_bwd(const float* dy, const float* z, const float* mean, const float* rstd,
-                             const float* gamma, float* dz, float* dx, float* dgamma, float* dbeta,
-                             float* dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-                             uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  return uniter_ln_bwd_b16(dy, z, mean, rstd, gamma, dz, dx, nullptr, dgamma, dbeta, dbias, M, H, p_drop, seed, offset,
-                           site, ws, ws_bytes, stream);
-}
-
-extern "C" int uniter_ln_bwd_b16(const float* dy, const float* z, const float* mean, const float* rstd,
-                                 const float* gamma, float* dz, float* dx, void* dx_bf16, float* dgamma,
-                                 float* dbeta, float* dbias, int M, int H, float p_drop, uint64_t seed,
-                                 uint32_t offset, uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int uniter_ln_bwd(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma, float* dz,
+                             float* dx, float* dgamma, float* dbeta, float* dbias, int M, int H, float p_drop, uint64_t seed,
+                             uint32_t offset, uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  LN_CALL(c);
   UCHECK_ARG(dgamma && dbeta, "ln_bwd: null pointer");
-  UCHECK_RC(uniter_ln_bwd_rows(dy, z, mean, rstd, gamma, dz, dx, dx_bf16, dbias != nullptr, M, H, p_drop, seed, offset,
-                               site, ws, ws_bytes, stream));
+  LN_BWD_IN(c); c.want_dbias = dbias != nullptr;
+  UCHECK_RC(ln_bwd_rows_run(c));
+  return uniter_ln_bwd_finalize(ws, ws_bytes, M, H, dgamma, dbeta, dbias, stream);
+}
+
+extern "C" int uniter_ln_bwd_b16(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma, float* dz,
+                                 float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* dbias, int M, int H, float p_drop,
+                                 uint64_t seed, uint32_t offset, uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  LN_CALL(c);
+  UCHECK_ARG(dgamma && dbeta, "ln_bwd: null pointer");
+  LN_BWD_IN(c); c.copy = dx_bf16; c.want_dbias = dbias != nullptr;
+  UCHECK_RC(ln_bwd_rows_run(c));
   return uniter_ln_bwd_finalize(ws, ws_bytes, M, H, dgamma, dbeta, dbias, stream);
 }
 
 // The two halves of uniter_ln_bwd_b16 as separate calls: the row pass produces everything the
 // backward CHAIN needs (dz, dx); the column reduction only feeds parameter gradients and can run
 // later on another stream, out of the critical path (the caller keeps `ws` untouched in between).
-extern "C" int uniter_ln_bwd_rows(const float* dy, const float* z, const float* mean, const float* rstd,
-                                  const float* gamma, float* dz, float* dx, void* dx_bf16, int want_dbias, int M,
-                                  int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws,
-                                  size_t ws_bytes, void* stream) {
-  return uniter_ln_bwd_rows_slabs(dy, 1, 0, z, mean, rstd, gamma, dz, dx, dx_bf16, want_dbias, M, H, p_drop, seed, offset,
-                                  site, ws, ws_bytes, stream);
-}
-
-int ln_bwd_rows_run(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
-                    const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16, int pieces,
-                    int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-                    uint32_t site, const unsigned char* keep_bits, void* ws, size_t ws_bytes, void* stream) {
-  UCHECK_ARG(dy && z && mean && rstd && gamma && ws, "ln_bwd: null pointer");
-  UCHECK_ARG(nslab >= 1 && (nslab == 1 || slab_stride >= (size_t)M * H), "ln_bwd: bad slab count / stride");
-  UCHECK_ARG(dz || dx || dx_bf16, "ln_bwd: need dz or dx");
-  UCHECK_SHAPE(H % 4 == 0 && H >= 4, "ln_bwd: H must be a multiple of 4");
-  UCHECK_ARG(ws_bytes >= uniter_ln_bwd_ws_bytes(M, H), "ln_bwd: workspace too small");
-  if (M <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  DropCfg drop = make_drop(p_drop, seed, offset, site);
-  drop.bits = drop.active ? keep_bits : nullptr;
-  const int nv = (H / 4 + 63) / 64;
-  const int nblk = ln_bwd_blocks(M);
-  float* part = (float*)ws;
-#define LNB_ARGS dy, z, mean, rstd, gamma, dz, dx, part, M, H, drop, want_dbias != 0, (unsigned short*)dx_bf16, nslab, slab_stride, pieces
-  if (lnb_waves() == 8) {
-    switch (nv) {
-      case 1: hipLaunchKernelGGL((ln_bwd_kernel<1, 8>), dim3(nblk), dim3(512), 0, st, LNB_ARGS); break;
-      case 2: hipLaunchKernelGGL((ln_bwd_kernel<2, 8>), dim3(nblk), dim3(512), 0, st, LNB_ARGS); break;
-      case 3: hipLaunchKernelGGL((ln_bwd_kernel<3, 8>), dim3(nblk), dim3(512), 0, st, LNB_ARGS); break;
-      case 4: hipLaunchKernelGGL((ln_bwd_kernel<4, 8>), dim3(nblk), dim3(512), 0, st, LNB_ARGS); break;
-      default: uniter_set_error("layernorm: hidden size %d unsupported (max 1024)", H); return UNITER_E_SHAPE;
-    }
-  } else {
-    switch (nv) {
-      case 1: hipLaunchKernelGGL((ln_bwd_kernel<1, 4>), dim3(nblk), dim3(256), 0, st, LNB_ARGS); break;
-      case 2: hipLaunchKernelGGL((ln_bwd_kernel<2, 4>), dim3(nblk), dim3(256), 0, st, LNB_ARGS); break;
-      case 3: hipLaunchKernelGGL((ln_bwd_kernel<3, 4>), dim3(nblk), dim3(256), 0, st, LNB_ARGS); break;
-      case 4: hipLaunchKernelGGL((ln_bwd_kernel<4, 4>), dim3(nblk), dim3(256), 0, st, LNB_ARGS); break;
-      default: uniter_set_error("layernorm: hidden size %d unsupported (max 1024)", H); return UNITER_E_SHAPE;
-    }
-  }
-#undef LNB_ARGS
-  UCHECK_LAUNCH();
-  return 0;
+extern "C" int uniter_ln_bwd_rows(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma, float* dz,
+                                  float* dx, void* dx_bf16, int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
+                                  uint32_t site, void* ws, size_t ws_bytes, void* stream) {
+  LN_CALL(c); LN_BWD_IN(c); c.copy = dx_bf16; c.want_dbias = want_dbias;
+  return ln_bwd_rows_run(c);
 }
 
 extern "C" int uniter_ln_bwd_rows_slabs(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
-                                        const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16,
-                                        int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-                                        uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  const unsigned char* ahead = take_next_keep_bits();
-  return ln_bwd_rows_run(dy, nslab, slab_stride, z, mean, rstd, gamma, dz, dx, dx_bf16, 1, want_dbias, M, H, p_drop, seed,
-                         offset, site, ahead, ws, ws_bytes, stream);
+                                        const float* rstd, const float* gamma, float* dz, float* dx, void* dx_bf16, int want_dbias, int M,
+                                        int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws, size_t ws_bytes,
+                                        void* stream) {
+  LN_CALL(c); LN_BWD_IN(c); c.nslab = nslab; c.slab_stride = slab_stride; c.copy = dx_bf16; c.want_dbias = want_dbias;
+  return ln_bwd_rows_run(c);
 }
 
 extern "C" int uniter_ln_bwd_rows_slabs_x3(const float* dy, int nslab, size_t slab_stride, const float* z, const float* mean,
-                                           const float* rstd, const float* gamma, float* dz, float* dx, void* dx_x3,
-                                           int want_dbias, int M, int H, float p_drop, uint64_t seed, uint32_t offset,
-                                           uint32_t site, void* ws, size_t ws_bytes, void* stream) {
-  const unsigned char* ahead = take_next_keep_bits();
-  UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)dx_x3 & 15) == 0, "ln_bwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
-  return ln_bwd_rows_run(dy, nslab, slab_stride, z, mean, rstd, gamma, dz, dx, dx_x3, 3, want_dbias, M, H, p_drop, seed,
-                         offset, site, ahead, ws, ws_bytes, stream);
+                                           const float* rstd, const float* gamma, float* dz, float* dx, void* dx_x3, int want_dbias, int M,
+                                           int H, float p_drop, uint64_t seed, uint32_t offset, uint32_t site, void* ws, size_t ws_bytes,
+                                           void* stream) {
+  LN_CALL(c); LN_BWD_IN(c); c.nslab = nslab; c.slab_stride = slab_stride; c.copy = dx_x3; c.pieces = 3; c.want_dbias = want_dbias;
+  return ln_bwd_rows_run(c);
 }
+#undef LN_CALL
+#undef LN_FWD_IN
+#undef LN_BWD_IN
 
 // internal: the partial-row count / row stride of a row pass over M rows (for finalize_partials_jobs)
 int ln_bwd_partial_rows(int M) { return ln_bwd_blocks(M); }
 
-extern "C" int uniter_ln_bwd_finalize(const void* ws, size_t ws_bytes, int M, int H, float* dgamma, float* dbeta,
-                                      float* dbias, void* stream) {
+extern "C" int uniter_ln_bwd_finalize(const void* ws, size_t ws_bytes, int M, int H, float* dgamma, float* dbeta, float* dbias,
+                                      void* stream) {
   UCHECK_ARG(ws && dgamma && dbeta && ws_bytes >= uniter_ln_bwd_ws_bytes(M, H), "ln_bwd_finalize: bad argument");
   if (M <= 0) return 0;
   float* outs[3] = {dgamma, dbeta, dbias};
-  return finalize_partials_multi((const float*)ws, ln_bwd_blocks(M), (size_t)3 * H, outs, dbias ? 3 : 2, H,
-                                 (hipStream_t)stream);
+  return finalize_partials_multi({(const float*)ws, ln_bwd_blocks(M), (size_t)3 * H}, outs, dbias ? 3 : 2, H, (hipStream_t)stream);
 }
 
 // ---- hidden-dropout keep flags drawn ahead (round 5) ----------------------------------------------------------------------

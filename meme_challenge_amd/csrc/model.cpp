@@ -507,6 +507,10 @@ int operand_copy(const Plan& pl, Act a, int rows, int cols, hipStream_t st) {
   if (pl.prec == PREC_X3) return uniter_split3(a.f, rows, cols, cols, a.b, (size_t)3 * cols, (size_t)cols, st);
   return uniter_cast_bf16(a.f, a.b, (size_t)rows * cols, st);
 }
+// the keep flags drawn ahead for layer l's hidden-dropout site (second = 1: behind the FFN), NULL = the row pass draws them
+static const unsigned char* hid_keep_bits(const Plan& pl, int l, int second) {
+  return pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;
+}
 // Dropout + residual + LayerNorm behind layer l's attention output (second = 0) or FFN output (second = 1): t is `pieces` k-piece slabs
 // of the product in front [M][H] each (one slab: stride 0, as uniter_ln_fwd_b16 passes it); y.b takes the operand copy of the result where the plan has one.  mean / rstd are kept
 // only by a pass that saves for a backward pass.
@@ -517,11 +521,12 @@ int ln_fwd(uniter_model* m, hipStream_t st, int l, int second, const float* t, i
   const int g = second ? L_LN2_G : L_LN1_G;      // (its bias follows it)
   const int H = m->cfg.hidden_size;
   ProfScope ps(m, UNITER_K_LN, st);
-  const unsigned char* keep = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;
-  const bool x3 = pl.prec == PREC_X3;
-  if (x3) UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)y.b & 15) == 0, "ln_fwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
-  return ln_fwd_run(t, pieces, pieces > 1 ? (size_t)pl.M * H : 0, resid, m->LP(l, g), m->LP(l, g + 1), z, y.f, y.b, x3 ? 3 : 1, save ? mean : nullptr,
-                    save ? rstd : nullptr, pl.M, H, ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), keep, st);
+  LnCall c;
+  c.x = t; c.nslab = pieces; c.slab_stride = pieces > 1 ? (size_t)pl.M * H : 0; c.res = resid; c.gamma = m->LP(l, g); c.beta = m->LP(l, g + 1);
+  c.z = z; c.out = y.f; c.copy = y.b; c.pieces = pl.prec == PREC_X3 ? 3 : 1; c.M = pl.M; c.H = H; c.stream = st;
+  if (save) { c.mean = mean; c.rstd = rstd; }
+  c.drop = {ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), hid_keep_bits(pl, l, second)};
+  return ln_fwd_run(c);
 }
 // its backward row pass: dy is `pieces` slabs [M][H]; g takes the dropped gradient (fp32 and / or operand copy), ws the column partials
 int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, int pieces, const float* z, const float* mean,
@@ -529,11 +534,34 @@ int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, 
   const Plan& pl = m->plan;
   const int H = m->cfg.hidden_size;
   ProfScope ps(m, UNITER_K_LN_BWD, st);
-  const unsigned char* keep = pl.hid_on ? pl.hid_keepb + (size_t)(2 * l + second) * pl.hid_stride : nullptr;      // (the forward pass's flags)
-  const bool x3 = pl.prec == PREC_X3;
-  if (x3) UCHECK_SHAPE(H % 8 == 0 && ((uintptr_t)g.b & 15) == 0, "ln_bwd: the x3 copy needs H %% 8 == 0 and a 16-byte aligned buffer");
-  return ln_bwd_rows_run(dy, pieces, (size_t)pl.M * H, z, mean, rstd, m->LP(l, second ? L_LN2_G : L_LN1_G), dz, g.f, g.b, x3 ? 3 : 1, 1, pl.M, H, ph,
-                         m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), keep, ws, pl.ln_ws_bytes, st);
+  LnCall c;
+  c.x = dy; c.nslab = pieces; c.slab_stride = (size_t)pl.M * H; c.gamma = m->LP(l, second ? L_LN2_G : L_LN1_G);
+  c.z = const_cast<float*>(z); c.mean = const_cast<float*>(mean); c.rstd = const_cast<float*>(rstd);      // (read only)
+  c.dz = dz; c.out = g.f; c.copy = g.b; c.pieces = pl.prec == PREC_X3 ? 3 : 1; c.want_dbias = 1;
+  c.M = pl.M; c.H = H; c.ws = ws; c.ws_bytes = pl.ln_ws_bytes; c.stream = st;
+  c.drop = {ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), hid_keep_bits(pl, l, second)};      // (the forward pass's flags)
+  return ln_bwd_rows_run(c);
+}
+// What the embeddings' forward and backward passes of the plan's batch state alike: ids, tables, LayerNorm weights, dims and the
+// dropout identity (ph: the pass's hidden-dropout p).  The caller adds its outputs or gradients, workspace and stream.
+static TxtEmbedCall txt_embed_call(const uniter_model* m, const uniter_batch_t& b, float ph) {
+  const uniter_config_t& c = m->cfg;
+  TxtEmbedCall e;
+  e.ids = b.input_ids; e.pos_ids = b.position_ids; e.type_ids = b.txt_type_ids; e.word = m->P(P_WORD); e.pos = m->P(P_POS);
+  e.type = m->P(P_TYPE); e.gamma = m->P(P_ELN_G); e.delta = m->ig.txt_delta;
+  e.B = m->plan.B; e.T = m->plan.T; e.S = m->plan.S; e.H = c.hidden_size; e.vocab = c.vocab_size; e.max_pos = c.max_position_embeddings;
+  e.type_vocab = c.type_vocab_size; e.pos_bcast = b.pos_bcast;
+  e.drop = {ph, m->seed, m->offset, SITE_TXT_EMB};
+  return e;
+}
+static ImgEmbedCall img_embed_call(const uniter_model* m, const uniter_batch_t& b, float ph) {
+  const Plan& pl = m->plan;
+  ImgEmbedCall e;
+  e.imgfc = pl.imgfc; e.pos7 = b.img_pos_feat; e.type_ids = b.img_type_ids; e.Wp = m->P(P_POSL_W); e.bp = m->P(P_POSL_B);
+  e.type = m->P(P_TYPE); e.g_i = m->P(P_ILN_G); e.b_i = m->P(P_ILN_B); e.g_p = m->P(P_PLN_G); e.b_p = m->P(P_PLN_B); e.g_f = m->P(P_FLN_G);
+  e.B = pl.B; e.R = pl.R; e.T0 = pl.T0; e.S = pl.S; e.H = m->cfg.hidden_size; e.type_vocab = m->cfg.type_vocab_size;
+  e.drop = {ph, m->seed, m->offset, SITE_IMG_EMB};
+  return e;
 }
 // The four weight gradients of a layer in PREC_BF16 / PREC_X3, dW[p] [Mo[p], No[p]] += A[p]^T B[p] over the plan's M rows, in the grouped
 // launch's order {W1, W2, QKV, attention output}.  Product 0 must be dW1 = dU^T y1: its A operand's column sums are intermediate.dense's
@@ -774,7 +802,7 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
   hipStream_t st = (hipStream_t)stream;
   const float ph = train == 1 ? c.hidden_dropout_prob : 0.f;
   const float pa = train == 1 ? c.attention_probs_dropout_prob : 0.f;
-  const int B = b->B, T = b->T, R = b->R, L = b->L, S = pl.S, M = pl.M;
+  const int B = b->B, R = b->R, L = b->L, S = pl.S, M = pl.M;
   const bool save = train != 0;
   const Switches& sw = uniter_switches();
   const bool gelu_d = sw.gelu_d || pl.prec == PREC_X3;      // UNITER_GELU_D=0: A/B switch (store the pre-activation, libm erf twice)
@@ -861,23 +889,15 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
       UCHECK_RC(gemm(m, 0, st, 0, 0, B * R, H, c.img_dim, feat, c.img_dim, m->P(P_IMG_W), c.img_dim, pl.imgfc, H,
                      UNITER_EPI_BIAS, m->P(P_IMG_B), nullptr, nullptr, 0, 0));
     }
-    UCHECK_RC(uniter_img_embed_fwd(pl.imgfc, b->img_pos_feat, b->img_type_ids, m->P(P_POSL_W), m->P(P_POSL_B),
-                                   m->P(P_TYPE), m->P(P_ILN_G), m->P(P_ILN_B), m->P(P_PLN_G), m->P(P_PLN_B),
-                                   m->P(P_FLN_G), m->P(P_FLN_B), pl.cat, save ? pl.img_stats : nullptr, B, R,
-                                   pl.T0, S, H, c.type_vocab_size, ph, seed, offset, st));
+    ImgEmbedCall e = img_embed_call(m, *b, ph);
+    e.b_f = m->P(P_FLN_B); e.cat = pl.cat; e.stats = save ? pl.img_stats : nullptr; e.stream = st;
+    UCHECK_RC(img_embed_fwd_run(e));
   }
   if (has_txt) {
     if (word_split) UCHECK_HIP(hipStreamWaitEvent(st, m->ready[nl + 1], 0));
-    if (m->ig.txt_delta)
-      UCHECK_RC(uniter_txt_embed_fwd_delta(b->input_ids, b->position_ids, b->txt_type_ids, m->P(P_WORD), m->P(P_POS),
-                                           m->P(P_TYPE), m->P(P_ELN_G), m->P(P_ELN_B), m->ig.txt_delta, pl.cat, B, T, S, H,
-                                           c.vocab_size, c.max_position_embeddings, c.type_vocab_size, b->pos_bcast,
-                                           ph, seed, offset, st));
-    else
-    UCHECK_RC(uniter_txt_embed_fwd(b->input_ids, b->position_ids, b->txt_type_ids, m->P(P_WORD), m->P(P_POS),
-                                   m->P(P_TYPE), m->P(P_ELN_G), m->P(P_ELN_B), pl.cat, B, T, S, H,
-                                   c.vocab_size, c.max_position_embeddings, c.type_vocab_size, b->pos_bcast,
-                                   ph, seed, offset, st));
+    TxtEmbedCall e = txt_embed_call(m, *b, ph);      // (with m->ig.txt_delta, the perturbation of the word rows, where one is set)
+    e.beta = m->P(P_ELN_B); e.cat = pl.cat; e.stream = st;
+    UCHECK_RC(txt_embed_fwd_run(e));
   }
   if (!save) m->ig = uniter_model::InputGrads();      // an inference forward: no backward pass follows
   const bool joint = has_txt && has_img;
@@ -1115,7 +1135,7 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
                                {m->LG(l, L_B1), nullptr, nullptr}};
     const int nout[4] = {3, 3, 1, 1};
     const int seg[4] = {H, H, 3 * H, I};
-    UCHECK_RC(finalize_partials_jobs(4, parts, nparts, strides, outs, nout, seg, sd));
+    UCHECK_RC(finalize_partials_jobs(4, PartialJobs{parts, nparts, strides, outs, nout, seg}, sd));
   }
   if (wg_early) {
     UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_late, 1, 1, 0, nullptr, false));
@@ -1212,24 +1232,19 @@ extern "C" int uniter_model_backward_embed(uniter_model_t* m) {
     UCHECK_HIP(hipEventRecord(m->ev_emb0, st));               // dcat is complete
     UCHECK_HIP(hipStreamWaitEvent(ax, m->ev_emb0, 0));
   }
-  if (pl.has_txt)
-    // (m->ig.txt_delta: the forward pass's perturbation of the word rows, NULL = none -- then the public entry points' launches)
-    UCHECK_RC((pl.det ? txt_embed_bwd_det_run : txt_embed_bwd_run)(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD),
-                                   m->P(P_POS), m->P(P_TYPE), m->P(P_ELN_G), m->ig.txt_delta, m->G(P_WORD), m->G(P_POS),
-                                   m->G(P_TYPE), m->G(P_ELN_G), m->G(P_ELN_B), B, T, S, H, c.vocab_size,
-                                   c.max_position_embeddings, c.type_vocab_size, b.pos_bcast, ph, m->seed,
-                                   m->offset, ax ? pl.emb_ws2 : pl.emb_ws, pl.emb_ws_bytes, ax ? ax : st));
-  if (pl.has_txt && m->ig.d_txt_rows)      // the per-token gradient: its own launch behind the text branch, on that branch's stream
-    UCHECK_RC(uniter_txt_embed_bwd_rows(pl.dcat, b.input_ids, b.position_ids, b.txt_type_ids, m->P(P_WORD), m->P(P_POS), m->P(P_TYPE),
-                                        m->P(P_ELN_G), m->ig.txt_delta, m->ig.d_txt_rows, B, T, S, H, c.vocab_size,
-                                        c.max_position_embeddings, c.type_vocab_size, b.pos_bcast, ph, m->seed, m->offset, ax ? ax : st));
+  if (pl.has_txt) {
+    TxtEmbedCall e = txt_embed_call(m, b, ph);      // (with the forward pass's perturbation of the word rows, where one was set)
+    e.dcat = pl.dcat; e.dword = m->G(P_WORD); e.dpos = m->G(P_POS); e.dtype = m->G(P_TYPE); e.dgamma = m->G(P_ELN_G); e.dbeta = m->G(P_ELN_B);
+    e.d_rows = m->ig.d_txt_rows; e.det = pl.det; e.ws = ax ? pl.emb_ws2 : pl.emb_ws; e.ws_bytes = pl.emb_ws_bytes; e.stream = ax ? ax : st;
+    UCHECK_RC(txt_embed_bwd_run(e));
+    if (e.d_rows) UCHECK_RC(txt_embed_bwd_rows_run(e));      // the per-token gradient: its own launch behind the text branch, on its stream
+  }
   if (pl.has_img) {
-    UCHECK_RC((pl.det ? uniter_img_embed_bwd_det : uniter_img_embed_bwd)(pl.dcat, pl.imgfc, b.img_pos_feat, b.img_type_ids, m->P(P_POSL_W),
-                                   m->P(P_POSL_B), m->P(P_TYPE), m->P(P_ILN_G), m->P(P_ILN_B), m->P(P_PLN_G),
-                                   m->P(P_PLN_B), m->P(P_FLN_G), pl.img_stats, pl.d_imgfc, pl.d_posfc,
-                                   m->G(P_POSL_W), m->G(P_POSL_B), m->G(P_TYPE), m->G(P_ILN_G), m->G(P_ILN_B),
-                                   m->G(P_PLN_G), m->G(P_PLN_B), m->G(P_FLN_G), m->G(P_FLN_B), B, R, pl.T0, S, H,
-                                   c.type_vocab_size, ph, m->seed, m->offset, pl.emb_ws, pl.emb_ws_bytes, st));
+    ImgEmbedCall e = img_embed_call(m, b, ph);
+    e.dcat = pl.dcat; e.stats = pl.img_stats; e.d_imgfc = pl.d_imgfc; e.d_posfc = pl.d_posfc; e.dWp = m->G(P_POSL_W); e.dbp = m->G(P_POSL_B);
+    e.dtype = m->G(P_TYPE); e.dg_i = m->G(P_ILN_G); e.db_i = m->G(P_ILN_B); e.dg_p = m->G(P_PLN_G); e.db_p = m->G(P_PLN_B);
+    e.dg_f = m->G(P_FLN_G); e.db_f = m->G(P_FLN_B); e.det = pl.det; e.ws = pl.emb_ws; e.ws_bytes = pl.emb_ws_bytes; e.stream = st;
+    UCHECK_RC(img_embed_bwd_run(e));
     const float* feat = b.img_masks ? pl.feat_eff : b.img_feat;
     // NOT pl.col_ws: the side stream's bias-gradient reductions of layer 0 may still be using it
     if (ax) {      // the region projection's bias column sums beside its weight gradient: behind the text branch on the auxiliary stream

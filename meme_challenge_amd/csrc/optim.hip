@@ -327,71 +327,168 @@ extern "C" int uniter_sumsq_combine(const double* parts, int n, double* out, voi
   return 0;
 }
 
-extern "C" int uniter_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale,
-                                float max_norm, float lr, float beta1, float beta2, float eps,
+namespace {
+
+// One optimizer step over a flat buffer: what an entry point states, by name.  An unset field means "absent".  The eleven entry points
+// below fill one from their positional lists and hand it to step_run, which holds every check and the one launch.
+struct StepCall {
+  const char* who = "adam_step";      // prefix of the messages of the checks only some entry points have
+  int rule = RULE_ADAM;               // rule_of(kind); < 0 = a kind outside 0 .. 3
+  float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;      // (RULE_SGD neither reads nor writes v: it may be NULL and is dropped)
+  const void* g16 = nullptr;          // the gradients as bf16 instead (AdamArgs::g16)
+  const uint8_t* flags = nullptr;
+  size_t n = 0;
+  const double* sumsq = nullptr;
+  float grad_scale = 1.f, max_norm = 0.f;
+  uniter_optim_group_t hp = {};       // the launch's hyper-parameters, or (grouped) a table of n_groups rows of them in host memory
+  bool grouped = false;
+  const uniter_optim_group_t* groups = nullptr;
+  int n_groups = 0, step = 0, adamw = 0, zero_grads = 0;
+  void* mirror = nullptr;             // bf16 copy of the updated parameters; piece_stride > 0: its three x3 pieces
+  size_t piece_stride = 0, first_element = 0;      // first_element: the flat-buffer offset of p, which pair_src's entries are relative to
+  const int* pair_src = nullptr;      // the paired-row source table of this launch's first chunk (AdamArgs::vsrc)
+  bool by_rows = false;               // one table split by rows (uniter_adam_step_rows): row_mask one byte per row of row_len elements
+  const uint8_t* row_mask = nullptr;
+  int row_len = 0, rows_touched = 0;
+  bool averaged = false;              // an exponential moving average of the parameters in the same walk (AvgArgs)
+  float* avg = nullptr;
+  float avg_weight = 0.f;
+  int max_workgroups = 0;
+  void* stream = nullptr;
+};
+
+inline int rule_of(int kind) { return kind == 0 || kind == 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : kind == 3 ? RULE_SGD : -1; }
+
+// a group's hyper-parameters with its bias corrections at `step`, formed in double once per group (and once per launch for the scalars)
+GroupRow group_row(const uniter_optim_group_t& g, int step) {
+  const double bc1 = 1.0 - pow((double)g.beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)g.beta2, (double)step);
+  return GroupRow{g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, (float)((double)g.lr / bc1), (float)(1.0 / sqrt(bc2)), 0.f};
+}
+GroupTable group_table(const uniter_optim_group_t* groups, int n_groups, int step) {
+  GroupTable t;
+  t.n = n_groups;
+  for (int k = 0; k < MAX_GROUPS; ++k) t.row[k] = group_row(groups[k < n_groups ? k : 0], step);
+  return t;
+}
+
+template <bool GROUPED, bool AVG>
+void step_launch(int rule, int nb, hipStream_t st, const WalkArgs<GROUPED, AVG>& w) {
+  switch (rule) {
+    case RULE_ADAMAX: hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, GROUPED, AVG>), dim3(nb), dim3(256), 0, st, w); break;
+    case RULE_SGD: hipLaunchKernelGGL((adam_kernel<RULE_SGD, GROUPED, AVG>), dim3(nb), dim3(256), 0, st, w); break;
+    default: hipLaunchKernelGGL((adam_kernel<RULE_ADAM, GROUPED, AVG>), dim3(nb), dim3(256), 0, st, w); break;
+  }
+}
+
+int step_run(const StepCall& c) {
+  // what only some forms state: every argument is checked HERE, before anything is launched
+  UCHECK_ARG(c.rule >= 0, "%s: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)", c.who);
+  UCHECK_ARG(!c.averaged || c.avg, "%s: avg is NULL", c.who);
+  UCHECK_ARG(!c.averaged || (c.avg_weight >= 0.f && c.avg_weight <= 1.f), "%s: avg_weight must lie in [0, 1] (got %g)", c.who, (double)c.avg_weight);
+  UCHECK_SHAPE(!c.averaged || ((uintptr_t)c.avg & 15) == 0, "%s: avg must be 16-byte aligned", c.who);
+  UCHECK_ARG(!c.by_rows || (c.row_mask && c.row_len > 0 && c.row_len % CHUNK == 0 && c.n % (size_t)c.row_len == 0),
+             "%s: row_len must be a multiple of 64 dividing n", c.who);
+  UCHECK_ARG(!c.pair_src || (c.mirror && c.piece_stride > 0 && c.first_element % CHUNK == 0 && ((uintptr_t)c.pair_src & 7) == 0),
+             "%s: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table", c.who);
+  UCHECK_ARG(!c.grouped || (c.groups && c.n_groups >= 1 && c.n_groups <= MAX_GROUPS), "%s: n_groups must be 1 .. 32 (got %d) with a table", c.who,
+             c.n_groups);
+  UCHECK_ARG(!c.grouped || c.step >= 1, "%s: step must be >= 1", c.who);
+  // what every form states
+  UCHECK_SHAPE(c.piece_stride % 4 == 0 && (c.piece_stride == 0 || c.mirror), "adam_step: bad mirror piece stride");
+  UCHECK_ARG(c.p && c.g && c.m && (c.v || c.rule == RULE_SGD) && c.flags, "adam_step: null pointer");
+  UCHECK_SHAPE(((uintptr_t)c.g16 & 7) == 0, "adam_step: bf16 gradients must be 8-byte aligned");
+  UCHECK_SHAPE(c.n % CHUNK == 0, "adam_step: n must be a multiple of 64");
+  UCHECK_ARG(c.step >= 1, "adam_step: step must be >= 1");
+  UCHECK_ARG(c.max_norm <= 0.f || c.sumsq, "adam_step: clipping needs sumsq");
+  const GroupRow h = group_row(c.hp, c.step);      // (grouped: zeros, unused -- every chunk reads its group's row)
+  AdamArgs a;
+  a.p = c.p; a.g = c.g; a.m = c.m; a.v = c.rule == RULE_SGD ? nullptr : c.v; a.flags = c.flags; a.n4 = c.n / 4;
+  a.sumsq = c.sumsq; a.gscale = c.grad_scale; a.max_norm = c.max_norm; a.lr = h.lr; a.b1 = h.b1; a.b2 = h.b2;
+  a.eps = h.eps; a.wd = h.wd; a.step_size = h.step_size; a.inv_sqrt_bc2 = h.inv_sqrt_bc2; a.adamw = c.adamw; a.zero_grads = c.zero_grads;
+  a.mirror = (unsigned short*)c.mirror; a.mirror_ps = c.piece_stride; a.g16 = (const unsigned short*)c.g16;
+  a.rowmask = c.by_rows ? c.row_mask : nullptr; a.row_chunks = c.by_rows ? c.row_len / CHUNK : 1; a.rows_want = c.by_rows && c.rows_touched ? 1 : 0;
+  a.vsrc = (const int2*)c.pair_src; a.vsrc_base = (long)c.first_element;
+  int nb = sumsq_blocks(c.n);
+  if (c.max_workgroups > 0) {
+    // an explicit grid: up to the one in which every thread takes its two items once (short-lived workgroups: what a persistent
+    // product of the forward pass that wants the CU waits for is ONE workgroup's lifetime)
+    const size_t full = (a.n4 + 511) / 512;
+    nb = (int)(full < (size_t)c.max_workgroups ? (full < 1 ? 1 : full) : (size_t)c.max_workgroups);
+  }
+  hipStream_t st = (hipStream_t)c.stream;
+  const AvgArgs e = {c.avg, c.avg_weight};
+  if (c.averaged && c.grouped) step_launch(c.rule, nb, st, WalkArgs<true, true>{a, group_table(c.groups, c.n_groups, c.step), e});
+  else if (c.averaged) step_launch(c.rule, nb, st, WalkArgs<false, true>{a, e});
+  else if (c.grouped) step_launch(c.rule, nb, st, WalkArgs<true, false>{a, group_table(c.groups, c.n_groups, c.step)});
+  else step_launch(c.rule, nb, st, WalkArgs<false, false>{a});
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+// what the entry points' positional lists share, by their parameters' names: the buffers and the step; the launch's own
+// hyper-parameters; the x3 mirror with its pair source
+#define STEP_IN(c)                                                                                                                      \
+  StepCall c;                                                                                                                           \
+  c.p = params; c.g = grads; c.m = exp_avg; c.v = exp_avg_sq; c.flags = chunk_flags; c.n = n; c.sumsq = sumsq; c.grad_scale = grad_scale; \
+  c.max_norm = max_norm; c.step = step; c.zero_grads = zero_grads; c.stream = stream
+#define STEP_SCALARS(c) c.hp = {lr, beta1, beta2, eps, weight_decay}; c.adamw = adamw
+#define STEP_X3P(c)                                                                                                              \
+  c.g16 = grads_bf16; c.mirror = mirror; c.piece_stride = mirror_piece_stride; c.pair_src = pair_src; c.first_element = first_element; \
+  c.max_workgroups = max_workgroups
+
+extern "C" int uniter_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,
+                                const double* sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, int adamw, int zero_grads, void* stream) {
-  return uniter_adam_step_mirror(params, grads, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr,
-                                 beta1, beta2, eps, weight_decay, step, adamw, zero_grads, nullptr, stream);
+  STEP_IN(c); STEP_SCALARS(c);
+  return step_run(c);
 }
 
-extern "C" int uniter_adam_step_mirror(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                       const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale,
-                                       float max_norm, float lr, float beta1, float beta2, float eps,
-                                       float weight_decay, int step, int adamw, int zero_grads,
-                                       void* mirror_bf16, void* stream) {
-  return uniter_adam_step_ex(params, grads, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1,
-                             beta2, eps, weight_decay, step, adamw, zero_grads, mirror_bf16, 0, stream);
+extern "C" int uniter_adam_step_mirror(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,
+                                       const double* sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                                       float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16, void* stream) {
+  STEP_IN(c); STEP_SCALARS(c); c.mirror = mirror_bf16;
+  return step_run(c);
 }
 
-extern "C" int uniter_adam_step_ex(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
-                                   const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale,
-                                   float max_norm, float lr, float beta1, float beta2, float eps,
-                                   float weight_decay, int step, int adamw, int zero_grads,
-                                   void* mirror_bf16, int max_workgroups, void* stream) {
-  return uniter_adam_step_g16(params, grads, nullptr, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr,
-                              beta1, beta2, eps, weight_decay, step, adamw, zero_grads, mirror_bf16, max_workgroups, stream);
+extern "C" int uniter_adam_step_ex(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,
+                                   const double* sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16, int max_workgroups,
+                                   void* stream) {
+  STEP_IN(c); STEP_SCALARS(c); c.mirror = mirror_bf16; c.max_workgroups = max_workgroups;
+  return step_run(c);
 }
 
-extern "C" int uniter_adam_step_g16(float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                    float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                    float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
-                                    int max_workgroups, void* stream) {
-  return uniter_adam_step_x3(params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr,
-                             beta1, beta2, eps, weight_decay, step, adamw, zero_grads, mirror_bf16, 0, max_workgroups, stream);
+extern "C" int uniter_adam_step_g16(float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                    const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
+                                    void* mirror_bf16, int max_workgroups, void* stream) {
+  STEP_IN(c); STEP_SCALARS(c); c.g16 = grads_bf16; c.mirror = mirror_bf16; c.max_workgroups = max_workgroups;
+  return step_run(c);
 }
 
-static int adam_step_impl(int rule, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                          float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                          float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                          float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
-                          size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups = nullptr, const AvgArgs* avg = nullptr);
-
-extern "C" int uniter_adam_step_x3(float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                   float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                   float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                                   float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
-                                   size_t mirror_piece_stride, int max_workgroups, void* stream) {
-  return adam_step_impl(RULE_ADAM, params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
-                        eps, weight_decay, step, adamw, zero_grads, mirror_bf16, mirror_piece_stride, max_workgroups, nullptr, 0, 0, nullptr, 0, stream);
+extern "C" int uniter_adam_step_x3(float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                   const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
+                                   void* mirror_bf16, size_t mirror_piece_stride, int max_workgroups, void* stream) {
+  STEP_IN(c); STEP_SCALARS(c); c.g16 = grads_bf16; c.mirror = mirror_bf16; c.piece_stride = mirror_piece_stride;
+  c.max_workgroups = max_workgroups;
+  return step_run(c);
 }
 
 // uniter_adam_step_x3 that writes the weight pieces in the PAIRED-ROW layout (round 6) by walking the buffer in the MIRROR's order:
 // pair_src points at the source table's entry for this launch's first 64-element chunk -- two int32 per chunk, the flat-buffer
 // element offsets of the chunk's two 32-element units ({s0 < 0, ..} = the chunk is its own source; ParamStore.pair_src);
 // first_element = the flat-buffer offset of `params` (the table's offsets are absolute).
-extern "C" int uniter_adam_step_x3p(float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                    float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                    float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, int step, int adamw, int zero_grads, void* mirror,
-                                    size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream) {
-  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
-             "adam_step_x3p: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
-  return adam_step_impl(RULE_ADAM, params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2,
-                        eps, weight_decay, step, adamw, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src,
-                        (long)first_element, stream);
+extern "C" int uniter_adam_step_x3p(float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                    const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
+                                    void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups,
+                                    void* stream) {
+  STEP_IN(c); c.who = "adam_step_x3p"; STEP_SCALARS(c); STEP_X3P(c);
+  return step_run(c);
 }
 
 // The update of ONE table split by rows (round 6): a fine-tuning step touches at most B x T of the word-embedding table's 28996 rows
@@ -402,166 +499,61 @@ extern "C" int uniter_adam_step_x3p(float* params, float* grads, const void* gra
 // time after the previous step's update, e.g. beside the backward pass; rows_touched = 1 -- the masked rows with their gradients,
 // clipped, behind the backward pass as before (a few per cent of the table).  Same arithmetic per element: bit-identical parameters.
 // params .. chunk_flags point at the TABLE (row 0); n = rows x row_len with row_len % 64 == 0; row_mask one byte per row.
-extern "C" int uniter_adam_step_rows(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags,
-                                     size_t n, const double* sumsq, float grad_scale, float max_norm, float lr, float beta1,
-                                     float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
-                                     const uint8_t* row_mask, int row_len, int rows_touched, int max_workgroups, void* stream) {
-  UCHECK_ARG(row_mask && row_len > 0 && row_len % CHUNK == 0 && n % (size_t)row_len == 0, "adam_step_rows: row_len must be a multiple of 64 dividing n");
-  return adam_step_impl(RULE_ADAM, params, grads, nullptr, exp_avg, exp_avg_sq, chunk_flags, n, rows_touched ? sumsq : nullptr, grad_scale,
-                        rows_touched ? max_norm : 0.f, lr, beta1, beta2, eps, weight_decay, step, adamw, zero_grads, nullptr, 0,
-                        max_workgroups, row_mask, row_len / CHUNK, rows_touched ? 1 : 0, nullptr, 0, stream);
+extern "C" int uniter_adam_step_rows(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const uint8_t* chunk_flags, size_t n,
+                                     const double* sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                                     float weight_decay, int step, int adamw, int zero_grads, const uint8_t* row_mask, int row_len,
+                                     int rows_touched, int max_workgroups, void* stream) {
+  STEP_IN(c); c.who = "adam_step_rows"; STEP_SCALARS(c); c.max_workgroups = max_workgroups;
+  c.by_rows = true; c.row_mask = row_mask; c.row_len = row_len; c.rows_touched = rows_touched;
+  // the untouched rows' g is zero whatever the norm: their launch neither reads sumsq nor clips (and may run before the norm exists)
+  if (!rows_touched) { c.sumsq = nullptr; c.max_norm = 0.f; }
+  return step_run(c);
 }
 
-static int adam_step_impl(int rule, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                          float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                          float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                          float weight_decay, int step, int adamw, int zero_grads, void* mirror_bf16,
-                          size_t mirror_piece_stride, int max_workgroups, const uint8_t* row_mask, int row_chunks, int rows_want,
-                          const void* vsrc, long vsrc_base, void* stream, const GroupTable* groups, const AvgArgs* avg) {
-  UCHECK_SHAPE(mirror_piece_stride % 4 == 0 && (mirror_piece_stride == 0 || mirror_bf16), "adam_step: bad mirror piece stride");
-  UCHECK_ARG(params && grads && exp_avg && (exp_avg_sq || rule == RULE_SGD) && chunk_flags, "adam_step: null pointer");
-  UCHECK_SHAPE(((uintptr_t)grads_bf16 & 7) == 0, "adam_step: bf16 gradients must be 8-byte aligned");
-  UCHECK_SHAPE(n % CHUNK == 0, "adam_step: n must be a multiple of 64");
-  UCHECK_ARG(step >= 1, "adam_step: step must be >= 1");
-  UCHECK_ARG(max_norm <= 0.f || sumsq, "adam_step: clipping needs sumsq");
-  AdamArgs a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.flags = chunk_flags; a.n4 = n / 4;
-  a.sumsq = sumsq; a.gscale = grad_scale; a.max_norm = max_norm; a.lr = lr; a.b1 = beta1; a.b2 = beta2;
-  a.eps = eps; a.wd = weight_decay; a.adamw = adamw; a.zero_grads = zero_grads;
-  a.mirror = (unsigned short*)mirror_bf16;
-  a.mirror_ps = mirror_piece_stride;
-  a.g16 = (const unsigned short*)grads_bf16;
-  a.rowmask = row_mask; a.row_chunks = row_chunks > 0 ? row_chunks : 1; a.rows_want = rows_want;
-  a.vsrc = (const int2*)vsrc; a.vsrc_base = vsrc_base;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  a.step_size = (float)((double)lr / bc1);
-  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  int nb = sumsq_blocks(n);
-  if (max_workgroups > 0) {
-    // an explicit grid: up to the one in which every thread takes its two items once (short-lived workgroups: what a persistent
-    // product of the forward pass that wants the CU waits for is ONE workgroup's lifetime)
-    const size_t full = (a.n4 + 511) / 512;
-    nb = (int)(full < (size_t)max_workgroups ? (full < 1 ? 1 : full) : (size_t)max_workgroups);
-  }
-  if (avg) {         // (the _avg entry points: the same walk with the average's stream, see AvgArgs)
-    if (groups) {
-      const WalkArgs<true, true> wg = {a, *groups, *avg};
-      if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-      else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-      else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-    } else {
-      const WalkArgs<false, true> wa = {a, *avg};
-      if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
-      else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
-      else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wa);
-    }
-  }
-  else if (groups) {      // (uniter_optim_step_groups: the scalars above are unused, every chunk reads its group's row)
-    const WalkArgs<true, false> wg = {a, *groups};
-    if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-    else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-    else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, true, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, wg);
-  }
-  else if (rule == RULE_ADAMAX) hipLaunchKernelGGL((adam_kernel<RULE_ADAMAX, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
-  else if (rule == RULE_SGD) hipLaunchKernelGGL((adam_kernel<RULE_SGD, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
-  else hipLaunchKernelGGL((adam_kernel<RULE_ADAM, false, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, WalkArgs<false, false>{a});
-  UCHECK_LAUNCH();
-  return 0;
-}
-
-// The optimizer family behind one entry point (include/uniter_hip.h): kind 0 / 1 = uniter_adam_step_x3p with adamw = 0 / 1, kind 2 =
-// torch.optim.Adamax, kind 3 = torch.optim.SGD with momentum beta1 (exp_avg_sq may be NULL and is neither read nor written).
-extern "C" int uniter_optim_step(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                 float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                 float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, int step, int adamw, int zero_grads, void* mirror,
+// The optimizer family behind one entry point (include/uniter_hip.h): kind 0 / 1 = uniter_adam_step_x3p with adamw = 0 / 1 (and its
+// message prefix), kind 2 = torch.optim.Adamax, kind 3 = torch.optim.SGD with momentum beta1 (exp_avg_sq may be NULL and is neither
+// read nor written).  The adamw argument is not read: the kind says it.
+extern "C" int uniter_optim_step(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                 const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads, void* mirror,
                                  size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups, void* stream) {
-  UCHECK_ARG(kind >= 0 && kind <= 3, "optim_step: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)");
-  if (kind <= 1)
-    return uniter_adam_step_x3p(params, grads, grads_bf16, exp_avg, exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1,
-                                beta2, eps, weight_decay, step, kind, zero_grads, mirror, mirror_piece_stride, pair_src, first_element,
-                                max_workgroups, stream);
-  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
-             "optim_step: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
-  return adam_step_impl(kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg, kind == 3 ? nullptr : exp_avg_sq,
-                        chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, step, 0, zero_grads, mirror,
-                        mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element, stream);
+  STEP_IN(c); c.rule = rule_of(kind);
+  c.who = c.rule == RULE_ADAM ? "adam_step_x3p" : "optim_step";
+  STEP_SCALARS(c); STEP_X3P(c); c.adamw = kind == 1;
+  return step_run(c);
 }
 
 // uniter_optim_step with the hyper-parameters PER PARAMETER GROUP (include/uniter_hip.h): bits 3-7 of a chunk's flag name its row of
 // `groups` (host memory, copied into the launch's arguments); the clip coefficient stays one value for the launch.
-extern "C" int uniter_optim_step_groups(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                        float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                        float grad_scale, float max_norm, const uniter_optim_group_t* groups, int n_groups,
-                                        int step, int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src,
-                                        size_t first_element, int max_workgroups, void* stream) {
-  UCHECK_ARG(kind >= 0 && kind <= 3, "optim_step_groups: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)");
-  UCHECK_ARG(groups && n_groups >= 1 && n_groups <= MAX_GROUPS, "optim_step_groups: n_groups must be 1 .. 32 (got %d) with a table", n_groups);
-  UCHECK_ARG(step >= 1, "optim_step_groups: step must be >= 1");
-  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
-             "optim_step_groups: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table");
-  GroupTable t;
-  t.n = n_groups;
-  for (int k = 0; k < MAX_GROUPS; ++k) {
-    const uniter_optim_group_t& g = groups[k < n_groups ? k : 0];
-    const double bc1 = 1.0 - pow((double)g.beta1, (double)step);      // (formed in double, once per group, as adam_step_impl does)
-    const double bc2 = 1.0 - pow((double)g.beta2, (double)step);
-    t.row[k] = GroupRow{g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, (float)((double)g.lr / bc1), (float)(1.0 / sqrt(bc2)), 0.f};
-  }
-  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
-                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, 0.f, 0.f, 0.f, 0.f, 0.f, step,
-                        kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element,
-                        stream, &t);
+extern "C" int uniter_optim_step_groups(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                        const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm,
+                                        const uniter_optim_group_t* groups, int n_groups, int step, int zero_grads, void* mirror,
+                                        size_t mirror_piece_stride, const int* pair_src, size_t first_element, int max_workgroups,
+                                        void* stream) {
+  STEP_IN(c); c.who = "optim_step_groups"; c.rule = rule_of(kind);
+  STEP_X3P(c); c.adamw = kind == 1; c.grouped = true; c.groups = groups; c.n_groups = n_groups;
+  return step_run(c);
 }
 
 // uniter_optim_step / uniter_optim_step_groups with an exponential moving average of the parameters updated by the same launch
 // (include/uniter_hip.h): avg points at the element `params` points at; a' = a + avg_weight (p' - a) on every updated element.
-// Every argument is checked HERE, before anything is launched; the launch itself is adam_step_impl's.
-static int avg_args_ok(const char* who, int kind, const float* avg, float avg_weight, const void* mirror, size_t mirror_piece_stride,
-                       const int* pair_src, size_t first_element) {
-  UCHECK_ARG(kind >= 0 && kind <= 3, "%s: kind must be 0 (Adam), 1 (AdamW), 2 (Adamax) or 3 (SGD with momentum)", who);
-  UCHECK_ARG(avg, "%s: avg is NULL", who);
-  UCHECK_ARG(avg_weight >= 0.f && avg_weight <= 1.f, "%s: avg_weight must lie in [0, 1] (got %g)", who, (double)avg_weight);
-  UCHECK_SHAPE(((uintptr_t)avg & 15) == 0, "%s: avg must be 16-byte aligned", who);
-  UCHECK_ARG(!pair_src || (mirror && mirror_piece_stride > 0 && first_element % CHUNK == 0 && ((uintptr_t)pair_src & 7) == 0),
-             "%s: a source table needs the x3 mirror, a launch that starts on a chunk and an 8-byte aligned table", who);
-  return 0;
-}
-
-extern "C" int uniter_optim_step_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                     float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                     float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
-                                     float weight_decay, int step, int adamw, int zero_grads, void* mirror,
-                                     size_t mirror_piece_stride, const int* pair_src, size_t first_element, float* avg,
+extern "C" int uniter_optim_step_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg, float* exp_avg_sq,
+                                     const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale, float max_norm, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int step, int adamw, int zero_grads,
+                                     void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element, float* avg,
                                      float avg_weight, int max_workgroups, void* stream) {
-  if (int rc = avg_args_ok("optim_step_avg", kind, avg, avg_weight, mirror, mirror_piece_stride, pair_src, first_element)) return rc;
-  const AvgArgs e = {avg, avg_weight};
-  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
-                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay,
-                        step, kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src,
-                        (long)first_element, stream, nullptr, &e);
+  STEP_IN(c); c.who = "optim_step_avg"; c.rule = rule_of(kind);
+  STEP_SCALARS(c); STEP_X3P(c); c.adamw = kind == 1; c.averaged = true; c.avg = avg; c.avg_weight = avg_weight;
+  return step_run(c);
 }
 
 extern "C" int uniter_optim_step_groups_avg(int kind, float* params, float* grads, const void* grads_bf16, float* exp_avg,
-                                            float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq,
-                                            float grad_scale, float max_norm, const uniter_optim_group_t* groups, int n_groups,
-                                            int step, int zero_grads, void* mirror, size_t mirror_piece_stride, const int* pair_src,
-                                            size_t first_element, float* avg, float avg_weight, int max_workgroups, void* stream) {
-  if (int rc = avg_args_ok("optim_step_groups_avg", kind, avg, avg_weight, mirror, mirror_piece_stride, pair_src, first_element)) return rc;
-  UCHECK_ARG(groups && n_groups >= 1 && n_groups <= MAX_GROUPS, "optim_step_groups_avg: n_groups must be 1 .. 32 (got %d) with a table", n_groups);
-  UCHECK_ARG(step >= 1, "optim_step_groups_avg: step must be >= 1");
-  GroupTable t;
-  t.n = n_groups;
-  for (int k = 0; k < MAX_GROUPS; ++k) {
-    const uniter_optim_group_t& g = groups[k < n_groups ? k : 0];
-    const double bc1 = 1.0 - pow((double)g.beta1, (double)step);      // (as uniter_optim_step_groups forms them)
-    const double bc2 = 1.0 - pow((double)g.beta2, (double)step);
-    t.row[k] = GroupRow{g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, (float)((double)g.lr / bc1), (float)(1.0 / sqrt(bc2)), 0.f};
-  }
-  const AvgArgs e = {avg, avg_weight};
-  return adam_step_impl(kind <= 1 ? RULE_ADAM : kind == 2 ? RULE_ADAMAX : RULE_SGD, params, grads, grads_bf16, exp_avg,
-                        kind == 3 ? nullptr : exp_avg_sq, chunk_flags, n, sumsq, grad_scale, max_norm, 0.f, 0.f, 0.f, 0.f, 0.f, step,
-                        kind == 1, zero_grads, mirror, mirror_piece_stride, max_workgroups, nullptr, 0, 0, pair_src, (long)first_element,
-                        stream, &t, &e);
+                                            float* exp_avg_sq, const uint8_t* chunk_flags, size_t n, const double* sumsq, float grad_scale,
+                                            float max_norm, const uniter_optim_group_t* groups, int n_groups, int step, int zero_grads,
+                                            void* mirror, size_t mirror_piece_stride, const int* pair_src, size_t first_element, float* avg,
+                                            float avg_weight, int max_workgroups, void* stream) {
+  STEP_IN(c); c.who = "optim_step_groups_avg"; c.rule = rule_of(kind);
+  STEP_X3P(c); c.adamw = kind == 1; c.grouped = true; c.groups = groups; c.n_groups = n_groups;
+  c.averaged = true; c.avg = avg; c.avg_weight = avg_weight;
+  return step_run(c);
 }

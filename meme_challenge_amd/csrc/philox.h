@@ -37,6 +37,20 @@ static inline DropCfg make_drop(float p, uint64_t seed, uint32_t offset, uint32_
   return d;
 }
 
+// The dropout identity of one pass as its caller states it: the mask is a function of (p, seed, offset, site) alone.  keep_bits: the
+// site's keep flags drawn ahead (DropCfg::bits), NULL = the pass draws them; a pass without dropout (p = 0) never reads them.
+struct DropSite {
+  float p = 0.f;
+  uint64_t seed = 0;
+  uint32_t offset = 0, site = 0;
+  const unsigned char* keep_bits = nullptr;
+};
+static inline DropCfg make_drop(const DropSite& s) {
+  DropCfg d = make_drop(s.p, s.seed, s.offset, s.site);
+  d.bits = d.active ? s.keep_bits : nullptr;
+  return d;
+}
+
 #ifdef __HIPCC__
 struct u32x4 { uint32_t x, y, z, w; };
 
