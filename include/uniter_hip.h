@@ -654,6 +654,15 @@ int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, 
 int uniter_adv_delta_step(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
                           void* stream);
 size_t uniter_adv_delta_ws_bytes(int B, int n);
+/* The L-infinity twin (csrc/adv.hip), same arguments and argument checks:
+ *   delta_b <- clamp(delta_b + step_size * g_b / max|g_b|, -max_norm, +max_norm)     element by element
+ * max|g_b| = 0: nothing is added; max_norm <= 0: no clamp; step_size = 0 clamps only.  The factor step_size / max|g_b| is formed
+ * in fp32.  A sample that neither steps nor clamps keeps its bits.  Two launches of ceil(n / 4096) workgroups per sample: one
+ * max|g| per chunk in ws (one writer each), folded in ascending order by every workgroup of the second launch.  No atomics:
+ * bit-reproducible.  ws: uniter_adv_delta_linf_ws_bytes(B, n) bytes, 8-byte aligned. */
+int uniter_adv_delta_step_linf(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
+                               void* stream);
+size_t uniter_adv_delta_linf_ws_bytes(int B, int n);
 
 /* ------------------------------------------------------------------------- *
  * Pooler + classification head (replaces BertPooler.forward model/layer.py:179-185
@@ -688,6 +697,18 @@ int uniter_pool_head_bwd(const float* dlogits, const float* pooled, const float*
 int uniter_bce_logits(const float* logits, const int64_t* labels, float pos_weight,
                       float* loss, float* probs, float* dlogits, float grad_scale,
                       int B, void* stream);
+/* The loss of a perturbed pass of VILLA and its gradient with respect to the perturbed logits, one launch (csrc/adv.hip).  With
+ * z = logits[b], c = clean_logits[b], q = sigmoid(z), p = sigmoid(c):
+ *   bce     = uniter_bce_logits' loss (mean over B, pos_weight)
+ *   kl      = mean_b [ KL(p||q) + KL(q||p) ] over Bernoulli distributions = mean_b (p - q)(c - z): non-negative, exactly 0 where
+ *             z == c, no logarithm to overflow
+ *   terms   = {bce + kl_weight * kl, bce, kl}
+ *   dlogits[b] = grad_scale / B * ( bce' + kl_weight * ((q - p) + q (1 - q)(z - c)) ),  bce' = uniter_bce_logits' per-element term
+ * The clean logits are constants: no gradient flows to them.  With kl_weight = 0, terms[0], probs and dlogits are
+ * uniter_bce_logits' bits.  One workgroup, a fixed summation order (bit-reproducible), any B > 0.  terms [3], probs [B] and
+ * dlogits [B] may each be NULL and are then not touched.  Refused: a NULL input, B <= 0, a NaN kl_weight. */
+int uniter_bce_kl_logits(const float* logits, const float* clean_logits, const int64_t* labels, float pos_weight,
+                         float kl_weight, float* terms, float* probs, float* dlogits, float grad_scale, int B, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Pretraining heads (BASELINE config 5: UniterForPretraining.forward_{mlm,mrfr,itm},

@@ -174,6 +174,10 @@ _SIGS = {
     'uniter_adv_delta_step': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
     'uniter_adv_delta_ws_bytes': (_SZ, [_I, _I]),
     'uniter_model_set_input_grads': (_I, [_P, _P, _P, _P, _P]),
+    # VILLA: the perturbed pass's loss with its KL term, and the L-infinity ascent step (csrc/adv.hip)
+    'uniter_bce_kl_logits': (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I, _P]),
+    'uniter_adv_delta_step_linf': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
+    'uniter_adv_delta_linf_ws_bytes': (_SZ, [_I, _I]),
     # the attention probabilities as an output, and rollout on them (csrc/attn_probs.hip)
     'uniter_attn_probs': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_attn_rollout': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),

@@ -268,8 +268,9 @@ class TrainerTemplate(object):
         self.log.add(probs, batch_label, loss, ids=self._ids)
 
     def adversarial_train_iter(self, batch):
-        """--adv_steps K > 0: one FreeLB micro-batch in place of forward + calculate_loss (trainer.TrainStep runs the K passes and
-        takes the step when the accumulation modulo says so); the epoch log gets the first, least perturbed pass."""
+        """--adv_steps K > 0: one FreeLB (or, with --adv_algo villa, VILLA) micro-batch in place of forward + calculate_loss
+        (trainer.TrainStep runs the passes and takes the step when the accumulation modulo says so); the epoch log gets the
+        first, least perturbed pass (VILLA: the clean one)."""
         if self._adv_step is None:
             self._adv_step = TrainStep(self.model, self.optimizer, self.scheduler, self.config, grad_sync=self.grad_sync)
         self._adv_step.optimizer, self._adv_step.scheduler = self.optimizer, self.scheduler
@@ -533,6 +534,10 @@ class TrainerTemplate(object):
              # embeddings and / or the region features (0 = off), ascent step size, radius of the L2 ball, magnitude of the random start
              ('adv_steps', int, 0), ('adv_lr', float, 1e-1), ('adv_max_norm', float, 1.0), ('adv_init_mag', float, 0.0),
              ('adv_modality', str, 'both'),
+             # additive: VILLA on top of it (trainer.adv_config): 'villa' adds the clean pass and, weighted by adv_kl_weight, the
+             # symmetric KL divergence of every perturbed prediction to the clean one; 'linf' swaps the L2 ball for the L-infinity one;
+             # --adv_modality each (villa only) perturbs the text and the regions in a round each
+             ('adv_algo', str, 'freelb'), ('adv_kl_weight', float, 0.0), ('adv_norm_type', str, 'l2'),
              # additive: evaluate and checkpoint an exponential moving average of the weights, kept by the fused step (0 = off);
              # add optimizer_state_dict to the checkpoint (utils/save.py:60-61)
              ('ema_decay', float, 0.0), ('save_optimizer_state', None, False))

@@ -103,6 +103,48 @@ def bce_with_logits_loss(logits, labels, pos_weight=1.0, return_probs=False):
     return (loss, probs) if return_probs else loss
 
 
+class _BceKlLogitsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, clean_logits, labels, pos_weight, kl_weight, grad_scale):
+        _lib.require_gpu_tensor(logits, torch.float32, 'logits')
+        _lib.require_gpu_tensor(clean_logits, torch.float32, 'clean_logits')
+        x = logits.reshape(-1).contiguous()
+        c = clean_logits.detach().reshape(-1).contiguous()
+        y = labels.reshape(-1).to(torch.int64).contiguous()
+        if x.numel() != y.numel() or x.numel() != c.numel():
+            raise ValueError('logits/clean_logits/labels size mismatch')
+        B = x.numel()
+        terms = torch.empty(3, dtype=torch.float32, device=x.device)
+        dlog = torch.empty(B, dtype=torch.float32, device=x.device)
+        check(_lib.lib().uniter_bce_kl_logits(ptr(x), ptr(c), ptr(y), float(pos_weight), float(kl_weight), ptr(terms), None,
+                                              ptr(dlog), float(grad_scale), B, _lib.cur_stream()), 'uniter_bce_kl_logits')
+        ctx.save_for_backward(dlog)
+        ctx.shape = logits.shape
+        loss = terms[0]                            # (a view: the total needs no launch of its own)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, dloss, _dterms):
+        (dlog,) = ctx.saved_tensors
+        if dloss is None:
+            return None, None, None, None, None, None
+        unit = _UNIT.get(dlog.device)
+        if unit is not None and dloss.data_ptr() == unit.data_ptr():
+            return dlog.view(ctx.shape), None, None, None, None, None
+        return (dlog * dloss).view(ctx.shape), None, None, None, None, None
+
+
+def bce_kl_with_logits_loss(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale=1.0, return_terms=False):
+    """The loss of a perturbed pass of VILLA, one launch (uniter_bce_kl_logits): bce_with_logits_loss(logits, labels, pos_weight)
+    + kl_weight * mean_b [KL(p||q) + KL(q||p)] with q = sigmoid(logits), p = sigmoid(clean_logits).  Differentiable in `logits`
+    only: the clean logits are constants.  The gradient handed back is grad_scale times the loss's (the launch applies the
+    1 / K of the K passes itself); the value is not scaled.  return_terms: also the device tensor [total, bce, kl]."""
+    loss, terms = _BceKlLogitsFn.apply(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale)
+    return (loss, terms) if return_terms else loss
+
+
 # --------------------------------------------------------------------------- #
 # optimizer
 # --------------------------------------------------------------------------- #
@@ -1121,27 +1163,49 @@ def sync_step(optimizer, grad_sync, accum, max_grad_norm):
 
 
 
-ADV_MODALITIES = ('both', 'txt', 'img')
-AdvConfig = namedtuple('AdvConfig', 'steps lr max_norm init_mag modality')
+ADV_MODALITIES = ('both', 'txt', 'img', 'each')
+ADV_ALGOS = ('freelb', 'villa')
+ADV_NORM_TYPES = ('l2', 'linf')
+AdvConfig = namedtuple('AdvConfig', 'steps lr max_norm init_mag modality algo kl_weight norm_type')
 
 
 def adv_config(config):
-    """The FreeLB settings of a trainer config (adv_steps = 0, the default, switches the adversarial step off):
-    adv_steps K, adv_lr (ascent step size), adv_max_norm (radius of the L2 ball, <= 0: none), adv_init_mag (magnitude of the
-    random start, 0: start from zero), adv_modality ('both' | 'txt' | 'img': which inputs are perturbed)."""
+    """The adversarial settings of a trainer config (adv_steps = 0, the default, switches the adversarial step off):
+    adv_steps K, adv_lr (ascent step size), adv_max_norm (radius of the ball, <= 0: none), adv_init_mag (magnitude of the
+    random start, 0: start from zero), adv_modality ('both' | 'txt' | 'img': which inputs are perturbed; 'each', VILLA only: the
+    text and the regions in a round each), adv_algo ('freelb' | 'villa': VILLA adds the clean pass and the KL consistency term),
+    adv_kl_weight (weight of that term, VILLA only), adv_norm_type ('l2' | 'linf': the ball and the ascent step's norm)."""
     adv = AdvConfig(int(config.get('adv_steps', 0) or 0), float(config.get('adv_lr', 0.0) or 0.0),
                     float(config.get('adv_max_norm', 0.0) or 0.0), float(config.get('adv_init_mag', 0.0) or 0.0),
-                    config.get('adv_modality', 'both') or 'both')
+                    config.get('adv_modality', 'both') or 'both', config.get('adv_algo', 'freelb') or 'freelb',
+                    float(config.get('adv_kl_weight', 0.0) or 0.0), config.get('adv_norm_type', 'l2') or 'l2')
     if adv.modality not in ADV_MODALITIES:
         raise ValueError("adv_modality must be one of %s, got %r" % (', '.join(repr(m) for m in ADV_MODALITIES), adv.modality))
+    if adv.algo not in ADV_ALGOS:
+        raise ValueError("adv_algo must be one of %s, got %r" % (', '.join(repr(m) for m in ADV_ALGOS), adv.algo))
+    if adv.norm_type not in ADV_NORM_TYPES:
+        raise ValueError("adv_norm_type must be one of %s, got %r" % (', '.join(repr(m) for m in ADV_NORM_TYPES), adv.norm_type))
     if adv.steps < 0 or adv.lr < 0 or adv.init_mag < 0:
         raise ValueError('adv_steps, adv_lr and adv_init_mag must not be negative')
+    if not adv.kl_weight >= 0:
+        raise ValueError('adv_kl_weight must not be negative, got %r' % adv.kl_weight)
+    if adv.algo == 'freelb':
+        if adv.kl_weight > 0:
+            raise ValueError("adv_kl_weight > 0 needs adv_algo='villa': the KL term pulls towards the clean pass, which FreeLB does not run")
+        if adv.modality == 'each':
+            raise ValueError("adv_modality='each' needs adv_algo='villa'")
+    elif adv.steps < 1:
+        raise ValueError("adv_algo='villa' needs adv_steps >= 1")
     return adv
 
 
-def adv_delta_step(delta, grad, step_size, max_norm):
-    """delta[b] <- project(delta[b] + step_size * grad[b] / |grad[b]|) onto the L2 ball of radius max_norm, per sample of the
-    leading dimension, in place (uniter_adv_delta_step; step_size = 0 projects only)."""
+def adv_delta_step(delta, grad, step_size, max_norm, norm_type='l2'):
+    """One ascent step of a perturbation and its projection, per sample of the leading dimension, in place (step_size = 0
+    projects only).  'l2' (uniter_adv_delta_step): delta[b] <- project(delta[b] + step_size * grad[b] / |grad[b]|) onto the L2
+    ball of radius max_norm; 'linf' (uniter_adv_delta_step_linf): delta[b] <- clamp(delta[b] + step_size * grad[b] / max|grad[b]|,
+    -max_norm, max_norm)."""
+    if norm_type not in ADV_NORM_TYPES:
+        raise ValueError("norm_type must be one of %s, got %r" % (', '.join(repr(m) for m in ADV_NORM_TYPES), norm_type))
     _lib.require_gpu_tensor(delta, torch.float32, 'delta')
     _lib.require_gpu_tensor(grad, torch.float32, 'grad')
     if delta.shape != grad.shape or not delta.is_contiguous() or not grad.is_contiguous():
@@ -1149,9 +1213,10 @@ def adv_delta_step(delta, grad, step_size, max_norm):
     B = delta.shape[0]
     n = delta.numel() // max(B, 1)
     lib = _lib.lib()
-    ws = torch.empty(max(lib.uniter_adv_delta_ws_bytes(B, n), 8), dtype=torch.uint8, device=delta.device)
-    check(lib.uniter_adv_delta_step(ptr(delta), ptr(grad), B, n, float(step_size), float(max_norm), ptr(ws), _lib.cur_stream()),
-          'uniter_adv_delta_step')
+    ws_bytes, step, name = ((lib.uniter_adv_delta_ws_bytes, lib.uniter_adv_delta_step, 'uniter_adv_delta_step') if norm_type == 'l2' else
+                            (lib.uniter_adv_delta_linf_ws_bytes, lib.uniter_adv_delta_step_linf, 'uniter_adv_delta_step_linf'))
+    ws = torch.empty(max(ws_bytes(B, n), 8), dtype=torch.uint8, device=delta.device)
+    check(step(ptr(delta), ptr(grad), B, n, float(step_size), float(max_norm), ptr(ws), _lib.cur_stream()), name)
     return delta
 
 
@@ -1164,6 +1229,13 @@ class TrainStep(object):
     normalised ascent step (projected onto the ball of radius ``adv_max_norm``) between two passes.  The parameter gradients
     of the K passes accumulate as micro-batches do and the optimizer step divides by K on top of ``gradient_accumulation``.
     The logged loss and probabilities are the first (least perturbed) pass's.
+
+    With ``adv_algo`` = 'villa' the micro-batch is a VILLA step instead (`_train_iter_villa`): a clean pass with today's loss,
+    then per round K perturbed passes whose loss is BCE + ``adv_kl_weight`` x the symmetric KL divergence to the clean
+    prediction (`bce_kl_with_logits_loss`, its gradient scaled by 1 / K in the launch), so that the accumulated gradient is
+    g_clean + (1 / K) sum_k g_adv,k per round.  ``adv_modality`` = 'each' runs a text round and an image round, each with a
+    perturbation of its own; ``adv_norm_type`` chooses the L2 or the L-infinity ball.  The logged loss and probabilities are
+    the clean pass's; `last_adv_terms` holds [total, bce, kl] of the last perturbed pass.
 
     Quirk kept on purpose: the modulo test is on the per-epoch iteration index
     starting at 0, so iteration 0 steps immediately with a single micro-batch whose
@@ -1187,13 +1259,17 @@ class TrainStep(object):
         if self.adv.steps > 0 and grad_sync is not None:
             # (the exchange's prepare(will_step=...) would have to be held back to the last of the K passes: not built, because it
             # could not be checked without a multi-rank run)
-            raise UniterHipError('adv_steps > 0 (FreeLB) is built for the single-process step: not with a data-parallel gradient exchange')
+            raise UniterHipError('adv_steps > 0 (FreeLB) is built for the single-process step: not with a data-parallel gradient exchange'
+                                 if self.adv.algo == 'freelb' else
+                                 "adv_algo='villa' is built for the single-process step: not with a data-parallel gradient exchange")
         self._adv_gen = None
-        self.last_adv_delta = None      # (delta_txt, delta_img) after the last FreeLB micro-batch's final ascent step
+        self.last_adv_delta = None      # (delta_txt, delta_img) after the last adversarial micro-batch's final ascent step
+        self.last_adv_terms = None      # VILLA: the device tensor [total, bce, kl] of the last perturbed pass
 
     def _adv_start(self, batch, shape):
-        """delta_0 of one perturbation: uniform in [-1, 1] * adv_init_mag / sqrt(n) per sample (n = its elements per sample)
-        from a device generator seeded with the config's seed, projected onto the ball; zeros for adv_init_mag = 0"""
+        """delta_0 of one perturbation: uniform in [-1, 1] * adv_init_mag / sqrt(n) per sample (n = its elements per sample;
+        adv_norm_type = 'linf': uniform in [-1, 1] * adv_init_mag) from a device generator seeded with the config's seed,
+        projected onto the ball; zeros for adv_init_mag = 0"""
         dev = batch['labels'].device
         if self.adv.init_mag <= 0:
             return torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -1203,9 +1279,11 @@ class TrainStep(object):
         n = 1
         for d in shape[1:]:
             n *= int(d)
-        delta = (torch.rand(shape, generator=self._adv_gen, dtype=torch.float32, device=dev) * 2 - 1) * (self.adv.init_mag / n ** 0.5)
+        linf = self.adv.norm_type == 'linf'
+        mag = self.adv.init_mag if linf else self.adv.init_mag / n ** 0.5
+        delta = (torch.rand(shape, generator=self._adv_gen, dtype=torch.float32, device=dev) * 2 - 1) * mag
         if self.adv.max_norm > 0:
-            adv_delta_step(delta, delta, 0.0, self.adv.max_norm)
+            adv_delta_step(delta, delta, 0.0, self.adv.max_norm, self.adv.norm_type)
         return delta
 
     def _train_iter_adv(self, batch, stepping, delta0=None):
@@ -1240,13 +1318,62 @@ class TrainStep(object):
                 first = (loss.detach(), probs)
             if ascend:
                 for d, leaf in leaves:
-                    adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm)
+                    adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm, adv.norm_type)
         self.last_adv_delta = (d_txt, d_img)
         if stepping:
             # the K passes' gradients were accumulated like K micro-batches: the step's grad_scale carries the extra 1 / K
             sync_step(self.optimizer, None, cfg['gradient_accumulation'] * K, cfg['max_grad_norm'])
             self.scheduler.step()
         return first
+
+    def _train_iter_villa(self, batch, stepping, delta0=None):
+        """A VILLA micro-batch (class docstring): the clean pass, then the rounds of K perturbed passes.  delta0 as in
+        `_train_iter_adv`; with adv_modality = 'each' its 'txt' starts the text round and its 'img' the image round."""
+        cfg, adv = self.config, self.adv
+        K = adv.steps
+        delta0 = delta0 or {}
+        preds = self.model(**self.forward_kwargs(batch))
+        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'], return_probs=True)
+        loss.backward(unit_gradient(loss.device))
+        clean = preds.detach().squeeze(1)       # (no copy: every forward pass returns logits in a tensor of its own)
+        rounds = {'txt': (('txt',),), 'img': (('img',),), 'both': (('txt', 'img'),), 'each': (('txt',), ('img',))}[adv.modality]
+        final = {'txt': None, 'img': None}
+        for which in rounds:
+            deltas = []                                 # (key of the forward call, delta) of this round
+            if 'txt' in which and batch.get('input_ids') is not None:
+                H = self.model.uniter_model.config.hidden_size
+                shape = tuple(batch['input_ids'].shape) + (H,)
+                deltas.append(('txt_embed_delta', delta0['txt'].detach().clone().float().contiguous()
+                               if delta0.get('txt') is not None else self._adv_start(batch, shape)))
+            if 'img' in which and batch.get('img_feat') is not None:
+                deltas.append(('img_feat', delta0['img'].detach().clone().float().contiguous()
+                               if delta0.get('img') is not None else self._adv_start(batch, tuple(batch['img_feat'].shape))))
+            if not deltas:
+                continue
+            for k in range(K):
+                ascend = k < K - 1          # the last pass needs no gradient of the perturbation
+                kw = self.forward_kwargs(batch)
+                leaves = []
+                for key, d in deltas:
+                    leaf = d.detach().requires_grad_(ascend)        # (shares d's memory)
+                    leaves.append((d, leaf))
+                    kw[key] = leaf if key == 'txt_embed_delta' else batch['img_feat'] + leaf
+                preds = self.model(**kw)
+                # the 1 / K of the round's average sits in the loss launch: the optimizer step's grad_scale stays the plain one
+                ploss, terms = bce_kl_with_logits_loss(preds.squeeze(1), clean, batch['labels'], cfg['pos_wt'], adv.kl_weight,
+                                                       grad_scale=1.0 / K, return_terms=True)
+                ploss.backward(unit_gradient(ploss.device))
+                self.last_adv_terms = terms
+                if ascend:
+                    for d, leaf in leaves:
+                        adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm, adv.norm_type)
+            for key, d in deltas:
+                final['txt' if key == 'txt_embed_delta' else 'img'] = d
+        self.last_adv_delta = (final['txt'], final['img'])
+        if stepping:
+            sync_step(self.optimizer, None, cfg['gradient_accumulation'], cfg['max_grad_norm'])
+            self.scheduler.step()
+        return loss.detach(), probs
 
     @staticmethod
     def forward_kwargs(batch):
@@ -1269,7 +1396,8 @@ class TrainStep(object):
             if stepping:
                 opt.early_word_update()
         if self.adv.steps > 0:
-            self.last_loss, self.last_probs = self._train_iter_adv(batch, stepping, adv_delta0)
+            run = self._train_iter_villa if self.adv.algo == 'villa' else self._train_iter_adv
+            self.last_loss, self.last_probs = run(batch, stepping, adv_delta0)
             self.iters += 1
             return self.last_loss
         preds = self.model(**self.forward_kwargs(batch))
