@@ -643,8 +643,8 @@ int uniter_txt_embed_bwd_rows(const float* dcat, const int64_t* input_ids, const
 /* d_pos7[rows, 7] = d_posfc[rows, H] @ Wp[H, 7]: the gradient of img_pos_feat through pos_linear (model/model.py:268), d_posfc
  * as uniter_img_embed_bwd leaves it.  One wave per row. */
 int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, int rows, int H, void* stream);
-/* One ascent step of an adversarial perturbation and its projection onto the L2 ball, per sample b over its n contiguous
- * floats (n % 4 == 0, delta and grad [B, n], 16-byte aligned):
+/* One ascent step of an adversarial perturbation and its projection onto the L2 ball (csrc/adv.hip), per sample b over its n
+ * contiguous floats (n % 4 == 0, delta and grad [B, n], 16-byte aligned):
  *   delta_b <- delta_b + step_size * g_b / |g_b|_2      (|g_b| = 0: nothing is added)
  *   delta_b <- delta_b * min(1, max_norm / |delta_b|_2) (max_norm <= 0: no projection)
  * A sample with g_b = 0 that lies inside the ball keeps its bits.  Two launches of ceil(n / 4096) workgroups per sample: the
@@ -654,7 +654,7 @@ int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, float* d_pos7, 
 int uniter_adv_delta_step(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
                           void* stream);
 size_t uniter_adv_delta_ws_bytes(int B, int n);
-/* The L-infinity twin (csrc/adv.hip), same arguments and argument checks:
+/* The L-infinity twin (csrc/adv.hip, behind the same launcher), same arguments and argument checks:
  *   delta_b <- clamp(delta_b + step_size * g_b / max|g_b|, -max_norm, +max_norm)     element by element
  * max|g_b| = 0: nothing is added; max_norm <= 0: no clamp; step_size = 0 clamps only.  The factor step_size / max|g_b| is formed
  * in fp32.  A sample that neither steps nor clamps keeps its bits.  Two launches of ceil(n / 4096) workgroups per sample: one
@@ -697,7 +697,7 @@ int uniter_pool_head_bwd(const float* dlogits, const float* pooled, const float*
 int uniter_bce_logits(const float* logits, const int64_t* labels, float pos_weight,
                       float* loss, float* probs, float* dlogits, float grad_scale,
                       int B, void* stream);
-/* The loss of a perturbed pass of VILLA and its gradient with respect to the perturbed logits, one launch (csrc/adv.hip).  With
+/* The loss of a perturbed pass of VILLA and its gradient with respect to the perturbed logits, one launch (csrc/head.hip).  With
  * z = logits[b], c = clean_logits[b], q = sigmoid(z), p = sigmoid(c):
  *   bce     = uniter_bce_logits' loss (mean over B, pos_weight)
  *   kl      = mean_b [ KL(p||q) + KL(q||p) ] over Bernoulli distributions = mean_b (p - q)(c - z): non-negative, exactly 0 where

@@ -167,14 +167,14 @@ _SIGS = {
     'uniter_txt_embed_bwd_det': (_I, [_P] * 13 + [_I] * 8 + [_F, _U64, _U32, _P, _SZ, _P]),
     'uniter_img_embed_bwd_det': (_I, [_P] * 24 + [_I] * 6 + [_F, _U64, _U32, _P, _SZ, _P]),
     'uniter_embed_bwd_det_ws_bytes': (_SZ, [_I, _I, _I]),
-    # input gradients and the adversarial perturbation's step (csrc/input_grads.hip)
+    # input gradients (csrc/input_grads.hip) and the adversarial perturbation's step (csrc/adv.hip)
     'uniter_txt_embed_fwd_delta': (_I, [_P] * 10 + [_I] * 8 + [_F, _U64, _U32, _P]),
     'uniter_txt_embed_bwd_rows': (_I, [_P] * 10 + [_I] * 8 + [_F, _U64, _U32, _P]),
     'uniter_pos_feat_dgrad': (_I, [_P, _P, _P, _I, _I, _P]),
     'uniter_adv_delta_step': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
     'uniter_adv_delta_ws_bytes': (_SZ, [_I, _I]),
     'uniter_model_set_input_grads': (_I, [_P, _P, _P, _P, _P]),
-    # VILLA: the perturbed pass's loss with its KL term, and the L-infinity ascent step (csrc/adv.hip)
+    # VILLA: the perturbed pass's loss with its KL term (csrc/head.hip), and the L-infinity ascent step (csrc/adv.hip)
     'uniter_bce_kl_logits': (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I, _P]),
     'uniter_adv_delta_step_linf': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
     'uniter_adv_delta_linf_ws_bytes': (_SZ, [_I, _I]),

@@ -185,27 +185,77 @@ __global__ __launch_bounds__(256) void linear_small_bwd_kernel(const float* __re
   }
 }
 
-// single workgroup; loss = mean_b [ (1-y) x + (1 + (pw-1) y) softplus(-x) ]
-__global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict__ logits,
-                                                         const int64_t* __restrict__ labels, float pw,
-                                                         float* __restrict__ loss, float* __restrict__ probs,
-                                                         float* __restrict__ dlogits, float gscale, int B) {
-  __shared__ float red[4];
-  float acc = 0.f;
+// The logits loss, single workgroup: loss = mean_b [ (1-y) x + (1 + (pw-1) y) softplus(-x) ], and with KL the symmetric divergence to
+// the clean prediction on top (a perturbed pass of VILLA).  One body for both kernels; without KL none of the KL arithmetic exists,
+// and the BCE statements are the same ones in the same order either way, so with klw = 0 the total, the probabilities and the
+// gradient of the KL kernel are the plain kernel's bits.  With z the perturbed logit, c the clean one, q = sigmoid(z),
+// p = sigmoid(c):  KL(p||q) + KL(q||p) = (p - q)(c - z)  (the logarithms of the two divergences combine to the logit difference),
+// d/dz = (q - p) + q (1 - q)(z - c).  Both vanish exactly where z == c: p and q are then one expression of one value.  q (1 - q) is
+// formed as e / (1 + e)^2 with e = exp(-|z|), which keeps its relative accuracy where fp32 q rounds to 1.
+// out: the loss, or with KL the terms [total, bce, kl].
+template <bool KL>
+__device__ __forceinline__ void bce_logits_body(const float* __restrict__ logits, const float* __restrict__ clean,
+                                                const int64_t* __restrict__ labels, float pw, float klw, float* __restrict__ out,
+                                                float* __restrict__ probs, float* __restrict__ dlogits, float gscale, int B) {
+  __shared__ float red[4][KL ? 2 : 1];
+  float acc = 0.f, kacc = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) {
     const float x = logits[b];
+    float c = 0.f;
+    if constexpr (KL) c = clean[b];
     const float y = (float)labels[b];
     const float lw = 1.0f + (pw - 1.0f) * y;
     const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);     // softplus(-x)
     acc += (1.0f - y) * x + lw * sp;
     const float sg = 1.0f / (1.0f + expf(-x));
-    if (probs) probs[b] = sg;
-    if (dlogits) dlogits[b] = ((1.0f - y) - lw * (1.0f - sg)) * (gscale / (float)B);
+    if constexpr (KL) {
+      const float sc = 1.0f / (1.0f + expf(-c));
+      kacc += (sc - sg) * (c - x);
+      if (probs) probs[b] = sg;
+      if (dlogits) {
+        const float e = expf(-fabsf(x));
+        const float qq = e / ((1.0f + e) * (1.0f + e));               // q (1 - q)
+        const float kg = (sg - sc) + qq * (x - c);
+        dlogits[b] = (((1.0f - y) - lw * (1.0f - sg)) + klw * kg) * (gscale / (float)B);
+      }
+    } else {
+      if (probs) probs[b] = sg;
+      if (dlogits) dlogits[b] = ((1.0f - y) - lw * (1.0f - sg)) * (gscale / (float)B);
+    }
   }
   acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  if constexpr (KL) kacc = wave_sum(kacc);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = acc;
+    if constexpr (KL) red[threadIdx.x >> 6][1] = kacc;
+  }
   __syncthreads();
-  if (threadIdx.x == 0 && loss) *loss = (red[0] + red[1] + red[2] + red[3]) / (float)B;
+  if (threadIdx.x == 0 && out) {
+    const float bce = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (float)B;
+    if constexpr (KL) {
+      const float kl = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) / (float)B;
+      out[0] = bce + klw * kl;
+      out[1] = bce;
+      out[2] = kl;
+    } else {
+      *out = bce;
+    }
+  }
+}
+
+// (the two instantiations under the kernel names every profile and trace of the step knows)
+__global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ labels, float pw,
+                                                         float* __restrict__ loss, float* __restrict__ probs,
+                                                         float* __restrict__ dlogits, float gscale, int B) {
+  bce_logits_body<false>(logits, nullptr, labels, pw, 0.f, loss, probs, dlogits, gscale, B);
+}
+
+__global__ __launch_bounds__(256) void bce_kl_logits_kernel(const float* __restrict__ logits, const float* __restrict__ clean,
+                                                            const int64_t* __restrict__ labels, float pw, float klw,
+                                                            float* __restrict__ terms, float* __restrict__ probs,
+                                                            float* __restrict__ dlogits, float gscale, int B) {
+  bce_logits_body<true>(logits, clean, labels, pw, klw, terms, probs, dlogits, gscale, B);
 }
 
 
@@ -494,6 +544,17 @@ extern "C" int uniter_bce_logits(const float* logits, const int64_t* labels, flo
   UCHECK_ARG(logits && labels && B > 0, "bce_logits: bad argument");
   hipLaunchKernelGGL(bce_logits_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels,
                      pos_weight, loss, probs, dlogits, grad_scale, B);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int uniter_bce_kl_logits(const float* logits, const float* clean_logits, const int64_t* labels, float pos_weight,
+                                    float kl_weight, float* terms, float* probs, float* dlogits, float grad_scale, int B,
+                                    void* stream) {
+  UCHECK_ARG(logits && clean_logits && labels && B > 0, "bce_kl_logits: bad argument");
+  UCHECK_ARG(kl_weight == kl_weight, "bce_kl_logits: kl_weight is NaN");
+  hipLaunchKernelGGL(bce_kl_logits_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, clean_logits, labels, pos_weight,
+                     kl_weight, terms, probs, dlogits, grad_scale, B);
   UCHECK_LAUNCH();
   return 0;
 }

@@ -1,10 +1,9 @@
-// Gradients with respect to the model's INPUTS, and the update of an adversarial perturbation (FreeLB):
+// Gradients with respect to the model's INPUTS:
 //   uniter_txt_embed_bwd_rows  per-token gradient of the sum that enters the text embeddings' LayerNorm
 //                              (autograd of model/model.py:232-245 with respect to words_embeddings)
 //   uniter_pos_feat_dgrad      d_pos7 = d_posfc @ Wp (autograd of pos_linear, model/model.py:268, with respect to img_pos_feat)
-//   uniter_adv_delta_step      delta <- project(delta + step * g / |g|) per sample
 // The region-feature gradient is the schedule's own dense product (model.cpp); the perturbed text forward is an instantiation of
-// the text row kernel (embed.hip).
+// the text row kernel (embed.hip); the update of an adversarial perturbation from these gradients is adv.hip's.
 //
 // Row kernels in the style of embed.hip: one wave per row, 16-byte accesses, H % 4 == 0, H <= 1024.  No float atomics anywhere:
 // every result is a function of the inputs alone, every output element has one writer and is overwritten.
@@ -100,80 +99,6 @@ __global__ __launch_bounds__(256) void pos_feat_dgrad_kernel(const float* __rest
   if (lane < 7) d_pos7[(size_t)row * 7 + lane] = o;
 }
 
-// ---- uniter_adv_delta_step ----
-constexpr int ADV_CHUNK = 4096;      // floats of a sample one workgroup owns: 256 threads x 4 x 16 bytes
-
-// sum of a double over the workgroup in a fixed order: lanes by the shuffle tree, then the four waves in ascending index
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// grid (P, B): part[b][p] = {g.g, delta.g, delta.delta} over the chunk, in double (a product of two floats is exact there)
-__global__ __launch_bounds__(256) void adv_partials_kernel(const float* __restrict__ delta, const float* __restrict__ grad,
-                                                           double* __restrict__ part, int n4) {
-  __shared__ double red[4][3];
-  const int p = blockIdx.x, b = blockIdx.y, P = gridDim.x;
-  const f32x4* d4 = reinterpret_cast<const f32x4*>(delta) + (size_t)b * n4;
-  const f32x4* g4 = reinterpret_cast<const f32x4*>(grad) + (size_t)b * n4;
-  double gg = 0.0, dg = 0.0, dd = 0.0;
-#pragma unroll
-  for (int j = 0; j < ADV_CHUNK / 1024; ++j) {
-    const int i = p * (ADV_CHUNK / 4) + j * 256 + (int)threadIdx.x;
-    if (i < n4) {
-      const f32x4 dv = d4[i], gv = g4[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double x = (double)dv[e], y = (double)gv[e];
-        gg += y * y; dg += x * y; dd += x * x;
-      }
-    }
-  }
-  gg = wave_sum_f64(gg); dg = wave_sum_f64(dg); dd = wave_sum_f64(dd);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red[wave][0] = gg; red[wave][1] = dg; red[wave][2] = dd; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    part[((size_t)b * P + p) * 3 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
-}
-
-// grid (P, B), behind adv_partials_kernel: every thread folds the sample's P partials in ascending order (the same value in every
-// thread and workgroup), forms the step and the projection's factor from them, and updates its elements of the chunk:
-//   a = step / |g|;  |delta + a g|^2 = dd + 2 a dg + a^2 gg;  delta <- (delta + a g) * min(1, max_norm / |delta + a g|)
-__global__ __launch_bounds__(256) void adv_update_kernel(float* __restrict__ delta, const float* __restrict__ grad,
-                                                         const double* __restrict__ part, int n4, float step_size, float max_norm) {
-  const int p = blockIdx.x, b = blockIdx.y, P = gridDim.x;
-  const double* pp = part + (size_t)b * P * 3;
-  double gg = 0.0, dg = 0.0, dd = 0.0;
-  for (int q = 0; q < P; ++q) { gg += pp[3 * q]; dg += pp[3 * q + 1]; dd += pp[3 * q + 2]; }       // (P: uniform)
-  const double a = gg > 0.0 ? (double)step_size / sqrt(gg) : 0.0;
-  const float af = (float)a;
-  const double ad = (double)af;                                   // (the factor the elements are stepped with)
-  double n2 = dd + 2.0 * ad * dg + ad * ad * gg;
-  n2 = n2 > 0.0 ? n2 : 0.0;
-  const double nrm = sqrt(n2);
-  const float sf = (max_norm > 0.f && nrm > (double)max_norm) ? (float)((double)max_norm / nrm) : 1.0f;
-  if (af == 0.f && sf == 1.0f) return;                            // (uniform: the sample keeps its bits)
-  f32x4* d4 = reinterpret_cast<f32x4*>(delta) + (size_t)b * n4;
-  const f32x4* g4 = reinterpret_cast<const f32x4*>(grad) + (size_t)b * n4;
-#pragma unroll
-  for (int j = 0; j < ADV_CHUNK / 1024; ++j) {
-    const int i = p * (ADV_CHUNK / 4) + j * 256 + (int)threadIdx.x;
-    if (i < n4) {
-      f32x4 dv = d4[i];
-      const f32x4 gv = g4[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dv[e] = (dv[e] + af * gv[e]) * sf;
-      d4[i] = dv;
-    }
-  }
-}
-
-inline int adv_parts(int n) { return (n + ADV_CHUNK - 1) / ADV_CHUNK; }
-
 }  // namespace
 
 #define IG_NV_DISPATCH(KERNEL, GRID, ...)                                                      \
@@ -219,29 +144,6 @@ extern "C" int uniter_pos_feat_dgrad(const float* d_posfc, const float* Wp, floa
   if (rows <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   IG_NV_DISPATCH(pos_feat_dgrad_kernel, dim3((rows + 3) / 4), d_posfc, Wp, d_pos7, rows, H);
-  UCHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" size_t uniter_adv_delta_ws_bytes(int B, int n) {
-  if (B <= 0 || n <= 0) return 0;
-  return (size_t)B * adv_parts(n) * 3 * sizeof(double);
-}
-
-extern "C" int uniter_adv_delta_step(float* delta, const float* grad, int B, int n, float step_size, float max_norm, void* ws,
-                                     void* stream) {
-  UCHECK_ARG(delta && grad && ws, "adv_delta_step: null pointer");
-  UCHECK_ARG((((uintptr_t)delta | (uintptr_t)grad) & 15) == 0 && ((uintptr_t)ws & 7) == 0,
-             "adv_delta_step: delta and grad must be 16-byte aligned, the workspace 8-byte");
-  UCHECK_ARG(step_size == step_size && max_norm == max_norm, "adv_delta_step: step_size / max_norm is NaN");
-  UCHECK_SHAPE(B >= 0 && n >= 0 && n % 4 == 0, "adv_delta_step: n must be a multiple of 4 (got %d)", n);
-  UCHECK_SHAPE(B <= 65535, "adv_delta_step: at most 65535 samples (got %d)", B);
-  if (B == 0 || n == 0) return 0;
-  const dim3 grid(adv_parts(n), B);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adv_partials_kernel, grid, dim3(256), 0, st, delta, grad, (double*)ws, n / 4);
-  UCHECK_LAUNCH();
-  hipLaunchKernelGGL(adv_update_kernel, grid, dim3(256), 0, st, delta, grad, (const double*)ws, n / 4, step_size, max_norm);
   UCHECK_LAUNCH();
   return 0;
 }

@@ -51,35 +51,47 @@ def optim_switches():
 # --------------------------------------------------------------------------- #
 # loss
 # --------------------------------------------------------------------------- #
-class _BceLogitsFn(torch.autograd.Function):
+class _LogitsLossFn(torch.autograd.Function):
+    """BCE with logits, one launch forward and none backward.  clean_logits None: uniter_bce_logits -> (loss, probs); else
+    uniter_bce_kl_logits (a perturbed pass of VILLA) -> (the view terms[0], terms), its gradient scaled by grad_scale."""
     @staticmethod
-    def forward(ctx, logits, labels, pos_weight):
+    def forward(ctx, logits, clean_logits, labels, pos_weight, kl_weight, grad_scale):
         _lib.require_gpu_tensor(logits, torch.float32, 'logits')
         x = logits.reshape(-1).contiguous()
         y = labels.reshape(-1).to(torch.int64).contiguous()
-        if x.numel() != y.numel():
-            raise ValueError('logits/labels size mismatch')
         B = x.numel()
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        probs = torch.empty(B, dtype=torch.float32, device=x.device)
         dlog = torch.empty(B, dtype=torch.float32, device=x.device)
-        check(_lib.lib().uniter_bce_logits(ptr(x), ptr(y), float(pos_weight), ptr(loss), ptr(probs),
-                                           ptr(dlog), 1.0, B, _lib.cur_stream()), 'uniter_bce_logits')
+        if clean_logits is None:
+            if B != y.numel():
+                raise ValueError('logits/labels size mismatch')
+            loss = torch.empty((), dtype=torch.float32, device=x.device)
+            extra = torch.empty(B, dtype=torch.float32, device=x.device)       # the probabilities
+            check(_lib.lib().uniter_bce_logits(ptr(x), ptr(y), float(pos_weight), ptr(loss), ptr(extra),
+                                               ptr(dlog), 1.0, B, _lib.cur_stream()), 'uniter_bce_logits')
+        else:
+            _lib.require_gpu_tensor(clean_logits, torch.float32, 'clean_logits')
+            c = clean_logits.detach().reshape(-1).contiguous()
+            if B != y.numel() or B != c.numel():
+                raise ValueError('logits/clean_logits/labels size mismatch')
+            extra = torch.empty(3, dtype=torch.float32, device=x.device)       # [total, bce, kl]
+            check(_lib.lib().uniter_bce_kl_logits(ptr(x), ptr(c), ptr(y), float(pos_weight), float(kl_weight), ptr(extra), None,
+                                                  ptr(dlog), float(grad_scale), B, _lib.cur_stream()), 'uniter_bce_kl_logits')
+            loss = extra[0]                        # (a view: the total needs no launch of its own)
         ctx.save_for_backward(dlog)
         ctx.shape = logits.shape
-        ctx.mark_non_differentiable(probs)
-        ctx.set_materialize_grads(False)           # no zero tensor for the probabilities' (absent) gradient
-        return loss, probs
+        ctx.mark_non_differentiable(extra)
+        ctx.set_materialize_grads(False)           # no zero tensor for the second output's (absent) gradient
+        return loss, extra
 
     @staticmethod
-    def backward(ctx, dloss, _dprobs):
+    def backward(ctx, dloss, _dextra):
         (dlog,) = ctx.saved_tensors
         if dloss is None:
-            return None, None, None
+            return (None,) * 6
         unit = _UNIT.get(dlog.device)
         if unit is not None and dloss.data_ptr() == unit.data_ptr():
-            return dlog.view(ctx.shape), None, None          # loss.backward(unit_gradient(..)): d loss = 1, nothing to multiply
-        return (dlog * dloss).view(ctx.shape), None, None
+            return (dlog.view(ctx.shape),) + (None,) * 5     # loss.backward(unit_gradient(..)): d loss = 1, nothing to multiply
+        return ((dlog * dloss).view(ctx.shape),) + (None,) * 5
 
 
 _UNIT = {}
@@ -87,7 +99,7 @@ _UNIT = {}
 
 def unit_gradient(device):
     """A cached scalar 1.0 to pass as loss.backward(gradient=...): saves the ones_like fill autograd would launch for the
-    root and (recognised by its address in _BceLogitsFn.backward) the multiply by it -- two launch-latency-sized kernels
+    root and (recognised by its address in _LogitsLossFn.backward) the multiply by it -- two launch-latency-sized kernels
     in the host-bound stretch between forward and backward."""
     device = torch.device(device)
     t = _UNIT.get(device)
@@ -99,41 +111,8 @@ def unit_gradient(device):
 def bce_with_logits_loss(logits, labels, pos_weight=1.0, return_probs=False):
     """BCEWithLogitsLoss(pos_weight=[w]) with mean reduction; labels are cast to
     float as train_template.py:99 does.  Also yields sigmoid(logits)."""
-    loss, probs = _BceLogitsFn.apply(logits, labels, pos_weight)
+    loss, probs = _LogitsLossFn.apply(logits, None, labels, pos_weight, 0.0, 1.0)
     return (loss, probs) if return_probs else loss
-
-
-class _BceKlLogitsFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, clean_logits, labels, pos_weight, kl_weight, grad_scale):
-        _lib.require_gpu_tensor(logits, torch.float32, 'logits')
-        _lib.require_gpu_tensor(clean_logits, torch.float32, 'clean_logits')
-        x = logits.reshape(-1).contiguous()
-        c = clean_logits.detach().reshape(-1).contiguous()
-        y = labels.reshape(-1).to(torch.int64).contiguous()
-        if x.numel() != y.numel() or x.numel() != c.numel():
-            raise ValueError('logits/clean_logits/labels size mismatch')
-        B = x.numel()
-        terms = torch.empty(3, dtype=torch.float32, device=x.device)
-        dlog = torch.empty(B, dtype=torch.float32, device=x.device)
-        check(_lib.lib().uniter_bce_kl_logits(ptr(x), ptr(c), ptr(y), float(pos_weight), float(kl_weight), ptr(terms), None,
-                                              ptr(dlog), float(grad_scale), B, _lib.cur_stream()), 'uniter_bce_kl_logits')
-        ctx.save_for_backward(dlog)
-        ctx.shape = logits.shape
-        loss = terms[0]                            # (a view: the total needs no launch of its own)
-        ctx.mark_non_differentiable(terms)
-        ctx.set_materialize_grads(False)
-        return loss, terms
-
-    @staticmethod
-    def backward(ctx, dloss, _dterms):
-        (dlog,) = ctx.saved_tensors
-        if dloss is None:
-            return None, None, None, None, None, None
-        unit = _UNIT.get(dlog.device)
-        if unit is not None and dloss.data_ptr() == unit.data_ptr():
-            return dlog.view(ctx.shape), None, None, None, None, None
-        return (dlog * dloss).view(ctx.shape), None, None, None, None, None
 
 
 def bce_kl_with_logits_loss(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale=1.0, return_terms=False):
@@ -141,7 +120,9 @@ def bce_kl_with_logits_loss(logits, clean_logits, labels, pos_weight, kl_weight,
     + kl_weight * mean_b [KL(p||q) + KL(q||p)] with q = sigmoid(logits), p = sigmoid(clean_logits).  Differentiable in `logits`
     only: the clean logits are constants.  The gradient handed back is grad_scale times the loss's (the launch applies the
     1 / K of the K passes itself); the value is not scaled.  return_terms: also the device tensor [total, bce, kl]."""
-    loss, terms = _BceKlLogitsFn.apply(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale)
+    if clean_logits is None:
+        raise ValueError('bce_kl_with_logits_loss needs the clean logits')
+    loss, terms = _LogitsLossFn.apply(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale)
     return (loss, terms) if return_terms else loss
 
 
@@ -1199,6 +1180,12 @@ def adv_config(config):
     return adv
 
 
+def adv_rounds(adv):
+    """The rounds of an adversarial micro-batch under the AdvConfig `adv`, each the tuple of the modalities it perturbs together:
+    one round, or with adv_modality = 'each' a text round and then an image round"""
+    return {'both': (('txt', 'img'),), 'txt': (('txt',),), 'img': (('img',),), 'each': (('txt',), ('img',))}[adv.modality]
+
+
 def adv_delta_step(delta, grad, step_size, max_norm, norm_type='l2'):
     """One ascent step of a perturbation and its projection, per sample of the leading dimension, in place (step_size = 0
     projects only).  'l2' (uniter_adv_delta_step): delta[b] <- project(delta[b] + step_size * grad[b] / |grad[b]|) onto the L2
@@ -1224,15 +1211,15 @@ class TrainStep(object):
     """`TrainerTemplate.calculate_loss` (train_template.py:95-126) + the forward of
     `TrainerUniter.train_iter_step` (train_uniter.py:67-72).
 
-    With ``adv_steps`` = K > 0 in the config a micro-batch is a FreeLB step (`adv_config`): K forward / backward passes on
-    the batch with a perturbation on the word-embedding rows and / or the region features, the perturbation taking one
-    normalised ascent step (projected onto the ball of radius ``adv_max_norm``) between two passes.  The parameter gradients
-    of the K passes accumulate as micro-batches do and the optimizer step divides by K on top of ``gradient_accumulation``.
-    The logged loss and probabilities are the first (least perturbed) pass's.
+    With ``adv_steps`` = K > 0 in the config a micro-batch is a FreeLB step (`adv_config`, `_train_iter_adv`): K forward /
+    backward passes on the batch (`_adv_passes`) with a perturbation on the word-embedding rows and / or the region features, the
+    perturbation taking one normalised ascent step (projected onto the ball of radius ``adv_max_norm``) between two passes.  The
+    parameter gradients of the K passes accumulate as micro-batches do and the optimizer step divides by K on top of
+    ``gradient_accumulation``.  The logged loss and probabilities are the first (least perturbed) pass's.
 
-    With ``adv_algo`` = 'villa' the micro-batch is a VILLA step instead (`_train_iter_villa`): a clean pass with today's loss,
-    then per round K perturbed passes whose loss is BCE + ``adv_kl_weight`` x the symmetric KL divergence to the clean
-    prediction (`bce_kl_with_logits_loss`, its gradient scaled by 1 / K in the launch), so that the accumulated gradient is
+    With ``adv_algo`` = 'villa' the micro-batch is a VILLA step instead, the same passes in another frame: a clean pass with
+    today's loss (`_clean_pass`), then per round (`adv_rounds`) K perturbed passes whose loss is BCE + ``adv_kl_weight`` x the
+    symmetric KL divergence to the clean prediction (`bce_kl_with_logits_loss`, its gradient scaled by 1 / K in the launch), so that the accumulated gradient is
     g_clean + (1 / K) sum_k g_adv,k per round.  ``adv_modality`` = 'each' runs a text round and an image round, each with a
     perturbation of its own; ``adv_norm_type`` chooses the L2 or the L-infinity ball.  The logged loss and probabilities are
     the clean pass's; `last_adv_terms` holds [total, bce, kl] of the last perturbed pass.
@@ -1286,94 +1273,78 @@ class TrainStep(object):
             adv_delta_step(delta, delta, 0.0, self.adv.max_norm, self.adv.norm_type)
         return delta
 
-    def _train_iter_adv(self, batch, stepping, delta0=None):
-        """The K passes of a FreeLB micro-batch (class docstring).  delta0: {'txt': [B, T, H], 'img': [B, R, D]} to start from
-        (either may be missing) instead of the seeded random start."""
-        cfg, adv = self.config, self.adv
-        K = adv.steps
-        delta0 = delta0 or {}
-        d_txt = d_img = None
-        if adv.modality in ('both', 'txt') and batch.get('input_ids') is not None:
-            H = self.model.uniter_model.config.hidden_size
-            shape = tuple(batch['input_ids'].shape) + (H,)
-            d_txt = delta0['txt'].detach().clone().float().contiguous() if delta0.get('txt') is not None else self._adv_start(batch, shape)
-        if adv.modality in ('both', 'img') and batch.get('img_feat') is not None:
-            d_img = delta0['img'].detach().clone().float().contiguous() if delta0.get('img') is not None else \
-                self._adv_start(batch, tuple(batch['img_feat'].shape))
-        first = None
+    def _clean_pass(self, batch):
+        """forward + the plain loss -> (logits, loss, probs); the caller runs backward (or none: eval_iter)"""
+        preds = self.model(**self.forward_kwargs(batch))
+        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], self.config['pos_wt'], return_probs=True)
+        return preds, loss, probs
+
+    def _adv_deltas(self, batch, which, delta0):
+        """The perturbations a round starts from, text before image: {'txt': [B, T, H], 'img': [B, R, D]} without the modalities
+        the round leaves alone or the batch lacks; from delta0 where it holds one, else the seeded random start"""
+        deltas = {}
+        for m, key in (('txt', 'input_ids'), ('img', 'img_feat')):
+            if m not in which or batch.get(key) is None:
+                continue
+            if delta0.get(m) is not None:
+                deltas[m] = delta0[m].detach().clone().float().contiguous()
+            else:
+                tail = (self.model.uniter_model.config.hidden_size,) if m == 'txt' else ()
+                deltas[m] = self._adv_start(batch, tuple(batch[key].shape) + tail)
+        return deltas
+
+    def _adv_passes(self, batch, deltas, loss_fn):
+        """K forward / backward passes on the batch under `deltas` (_adv_deltas), which take one ascent step between two passes, in
+        place.  loss_fn(logits) -> (loss, what it yields besides).  -> [(loss, the latter)] of the K passes"""
+        adv, K, out = self.adv, self.adv.steps, []
         for k in range(K):
             ascend = k < K - 1              # the last pass needs no gradient of the perturbation
             kw = self.forward_kwargs(batch)
-            leaves = []
-            for key, d in (('txt_embed_delta', d_txt), ('img_feat', d_img)):
-                if d is None:
-                    continue
-                leaf = d.detach().requires_grad_(ascend)        # (shares d's memory)
-                leaves.append((d, leaf))
-                kw[key] = leaf if key == 'txt_embed_delta' else batch['img_feat'] + leaf
-            preds = self.model(**kw)
-            loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'], return_probs=True)
+            leaves = {m: d.detach().requires_grad_(ascend) for m, d in deltas.items()}      # (each shares its delta's memory)
+            if 'txt' in leaves:
+                kw['txt_embed_delta'] = leaves['txt']
+            if 'img' in leaves:
+                kw['img_feat'] = batch['img_feat'] + leaves['img']
+            loss, extra = loss_fn(self.model(**kw).squeeze(1))
             loss.backward(unit_gradient(loss.device))
-            if first is None:
-                first = (loss.detach(), probs)
+            out.append((loss.detach(), extra))
             if ascend:
-                for d, leaf in leaves:
-                    adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm, adv.norm_type)
-        self.last_adv_delta = (d_txt, d_img)
-        if stepping:
-            # the K passes' gradients were accumulated like K micro-batches: the step's grad_scale carries the extra 1 / K
-            sync_step(self.optimizer, None, cfg['gradient_accumulation'] * K, cfg['max_grad_norm'])
-            self.scheduler.step()
-        return first
+                for m, leaf in leaves.items():
+                    adv_delta_step(deltas[m], leaf.grad.contiguous(), adv.lr, adv.max_norm, adv.norm_type)
+        return out
 
-    def _train_iter_villa(self, batch, stepping, delta0=None):
-        """A VILLA micro-batch (class docstring): the clean pass, then the rounds of K perturbed passes.  delta0 as in
-        `_train_iter_adv`; with adv_modality = 'each' its 'txt' starts the text round and its 'img' the image round."""
+    def _train_iter_adv(self, batch, stepping, delta0=None):
+        """An adversarial micro-batch (class docstring): VILLA's clean pass, then per round (adv_rounds) the K passes.  delta0:
+        {'txt': [B, T, H], 'img': [B, R, D]} to start from (either may be missing) instead of the seeded random start; with
+        adv_modality = 'each' its 'txt' starts the text round and its 'img' the image round."""
         cfg, adv = self.config, self.adv
-        K = adv.steps
-        delta0 = delta0 or {}
-        preds = self.model(**self.forward_kwargs(batch))
-        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'], return_probs=True)
-        loss.backward(unit_gradient(loss.device))
-        clean = preds.detach().squeeze(1)       # (no copy: every forward pass returns logits in a tensor of its own)
-        rounds = {'txt': (('txt',),), 'img': (('img',),), 'both': (('txt', 'img'),), 'each': (('txt',), ('img',))}[adv.modality]
-        final = {'txt': None, 'img': None}
-        for which in rounds:
-            deltas = []                                 # (key of the forward call, delta) of this round
-            if 'txt' in which and batch.get('input_ids') is not None:
-                H = self.model.uniter_model.config.hidden_size
-                shape = tuple(batch['input_ids'].shape) + (H,)
-                deltas.append(('txt_embed_delta', delta0['txt'].detach().clone().float().contiguous()
-                               if delta0.get('txt') is not None else self._adv_start(batch, shape)))
-            if 'img' in which and batch.get('img_feat') is not None:
-                deltas.append(('img_feat', delta0['img'].detach().clone().float().contiguous()
-                               if delta0.get('img') is not None else self._adv_start(batch, tuple(batch['img_feat'].shape))))
-            if not deltas:
+        K, villa, labels, pos_wt = adv.steps, adv.algo == 'villa', batch['labels'], cfg['pos_wt']
+        if villa:
+            preds, loss, probs = self._clean_pass(batch)
+            loss.backward(unit_gradient(loss.device))
+            result = loss.detach(), probs
+            clean = preds.detach().squeeze(1)       # (no copy: every forward pass returns logits in a tensor of its own)
+            # the 1 / K of the round's average sits in the loss launch: the optimizer step's grad_scale stays the plain one
+            loss_fn = lambda z: bce_kl_with_logits_loss(z, clean, labels, pos_wt, adv.kl_weight, grad_scale=1.0 / K, return_terms=True)
+        else:
+            loss_fn = lambda z: bce_with_logits_loss(z, labels, pos_wt, return_probs=True)
+        final = {}
+        for which in adv_rounds(adv):
+            deltas = self._adv_deltas(batch, which, delta0 or {})
+            if villa and not deltas:        # (nothing to perturb: VILLA has its clean pass; FreeLB's K passes run regardless)
                 continue
-            for k in range(K):
-                ascend = k < K - 1          # the last pass needs no gradient of the perturbation
-                kw = self.forward_kwargs(batch)
-                leaves = []
-                for key, d in deltas:
-                    leaf = d.detach().requires_grad_(ascend)        # (shares d's memory)
-                    leaves.append((d, leaf))
-                    kw[key] = leaf if key == 'txt_embed_delta' else batch['img_feat'] + leaf
-                preds = self.model(**kw)
-                # the 1 / K of the round's average sits in the loss launch: the optimizer step's grad_scale stays the plain one
-                ploss, terms = bce_kl_with_logits_loss(preds.squeeze(1), clean, batch['labels'], cfg['pos_wt'], adv.kl_weight,
-                                                       grad_scale=1.0 / K, return_terms=True)
-                ploss.backward(unit_gradient(ploss.device))
-                self.last_adv_terms = terms
-                if ascend:
-                    for d, leaf in leaves:
-                        adv_delta_step(d, leaf.grad.contiguous(), adv.lr, adv.max_norm, adv.norm_type)
-            for key, d in deltas:
-                final['txt' if key == 'txt_embed_delta' else 'img'] = d
-        self.last_adv_delta = (final['txt'], final['img'])
+            passes = self._adv_passes(batch, deltas, loss_fn)
+            final.update(deltas)
+            if villa:
+                self.last_adv_terms = passes[-1][1]
+            else:
+                result = passes[0]
+        self.last_adv_delta = (final.get('txt'), final.get('img'))
         if stepping:
-            sync_step(self.optimizer, None, cfg['gradient_accumulation'], cfg['max_grad_norm'])
+            # FreeLB's K passes were accumulated like K micro-batches: the step's grad_scale carries the extra 1 / K
+            sync_step(self.optimizer, None, cfg['gradient_accumulation'] * (1 if villa else K), cfg['max_grad_norm'])
             self.scheduler.step()
-        return loss.detach(), probs
+        return result
 
     @staticmethod
     def forward_kwargs(batch):
@@ -1396,13 +1367,10 @@ class TrainStep(object):
             if stepping:
                 opt.early_word_update()
         if self.adv.steps > 0:
-            run = self._train_iter_villa if self.adv.algo == 'villa' else self._train_iter_adv
-            self.last_loss, self.last_probs = run(batch, stepping, adv_delta0)
+            self.last_loss, self.last_probs = self._train_iter_adv(batch, stepping, adv_delta0)
             self.iters += 1
             return self.last_loss
-        preds = self.model(**self.forward_kwargs(batch))
-        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], cfg['pos_wt'],
-                                           return_probs=True)
+        _, loss, probs = self._clean_pass(batch)
         if self.grad_sync is not None:
             self.grad_sync.prepare(will_step=stepping, token_ids=batch['input_ids'])
         loss.backward(unit_gradient(loss.device))
@@ -1415,10 +1383,7 @@ class TrainStep(object):
 
     @torch.no_grad()
     def eval_iter(self, batch):
-        preds = self.model(**self.forward_kwargs(batch))
-        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], self.config['pos_wt'],
-                                           return_probs=True)
-        return loss, probs
+        return self._clean_pass(batch)[1:]
 
     @torch.no_grad()
     def test_iter(self, batch):

@@ -1,4 +1,4 @@
-"""Float64 references of the VILLA kernels (csrc/adv.hip: uniter_bce_kl_logits, uniter_adv_delta_step_linf), the case lists their
+"""Float64 references of the VILLA kernels (uniter_bce_kl_logits in csrc/head.hip, uniter_adv_delta_step_linf in csrc/adv.hip), the case lists their
 tests share, and per-element error bounds for an fp32 evaluation.  Plain numpy on the CPU: no GPU, no library.  Written after
 tests/loss_ref.py, whose BCE reference, constants and helpers are used as they are.
 

@@ -1,4 +1,4 @@
-"""uniter_bce_kl_logits and uniter_adv_delta_step_linf (csrc/adv.hip) through the C ABI, against the float64 references, case lists
+"""uniter_bce_kl_logits (csrc/head.hip) and uniter_adv_delta_step_linf (csrc/adv.hip) through the C ABI, against the float64 references, case lists
 and bounds of tests/adv_ref.py (derivation there; tests/test_adv_bounds_cpu.py is the standing proof that an fp32 evaluation of the
 formulas keeps them and that wrong formulas do not).
 

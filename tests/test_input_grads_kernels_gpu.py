@@ -1,6 +1,6 @@
 """The input-gradient kernels (csrc/input_grads.hip and the perturbed instantiation of the text row kernel in csrc/embed.hip) through
 the C ABI against float64 torch: the text embedding forward with an additive perturbation, the per-token gradient of the sum that
-enters its LayerNorm, the 7-column position-feature gradient, the ascent / projection step of an adversarial perturbation, and the
+enters its LayerNorm, the 7-column position-feature gradient, the ascent / projection step of an adversarial perturbation (csrc/adv.hip), and the
 host-side refusals.
 
 The perturbation is restated for the oracle as a word table of B * T rows, word[ids[b, t]] + delta[b, t], with

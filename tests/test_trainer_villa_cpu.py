@@ -58,3 +58,18 @@ def test_adv_delta_step_refuses_an_unknown_norm_before_it_touches_the_library():
     from meme_challenge_amd.trainer import adv_delta_step
     with pytest.raises(ValueError, match='norm_type'):
         adv_delta_step(None, None, 0.1, 1.0, norm_type='l1')
+
+
+def test_adv_rounds_of_every_accepted_algorithm_and_modality():
+    from meme_challenge_amd.trainer import ADV_ALGOS, ADV_MODALITIES, adv_config, adv_rounds
+    one = {'both': (('txt', 'img'),), 'txt': (('txt',),), 'img': (('img',),)}
+    want = {(algo, m): r for algo in ('freelb', 'villa') for m, r in one.items()}
+    want[('villa', 'each')] = (('txt',), ('img',))
+    accepted = {}
+    for algo in ADV_ALGOS:
+        for m in ADV_MODALITIES:
+            try:
+                accepted[(algo, m)] = adv_rounds(adv_config({'adv_steps': 2, 'adv_algo': algo, 'adv_modality': m}))
+            except ValueError:
+                assert (algo, m) == ('freelb', 'each')
+    assert accepted == want
