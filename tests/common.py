@@ -19,6 +19,17 @@ BASE = dict(attention_probs_dropout_prob=0.1, hidden_act='gelu',
 LARGE = dict(BASE, hidden_size=1024, intermediate_size=4096,
              num_attention_heads=16, num_hidden_layers=24)
 
+# the smallest model at which the heuristics pick the split-K and stream-K forms (tests/test_step_det_gpu.py), with B = 16,
+# 64 tokens, 32 regions
+MID = dict(vocab_size=997, hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=1024, hidden_act='gelu',
+           hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, max_position_embeddings=64, type_vocab_size=2,
+           initializer_range=0.02)
+MID_IMG_DIM = 2048
+
+# the resident pretraining dataset of tests/test_device_pretrain_gpu.py: N samples of T tokens, batches of PRETRAIN_BATCH
+PRETRAIN_T, PRETRAIN_IMG_DIM, PRETRAIN_N, PRETRAIN_BATCH = 16, 64, 24, 5
+PRETRAIN_CFG = dict(TINY, vocab_size=28996, max_position_embeddings=64, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+
 
 def sd_from_npz(z, prefix='sd/'):
     return {k[len(prefix):]: torch.from_numpy(z[k]) for k in z.files
@@ -57,3 +68,57 @@ def simple_tokenizer(texts, max_length=12):
         lens.append(len(toks))
     return {'input_ids': ids, 'length': torch.tensor(lens), 'attention_mask': (ids != 0).long(),
             'token_type_ids': torch.zeros_like(ids)}
+
+
+def trainer_config(optname, **kw):
+    # beta1 = 0.8: the momentum of sgd; adamax must NOT take it (torch's default 0.9, utils/optim_utils.py:36-37)
+    c = dict(optimizer=optname, lr=1e-3, beta1=0.8, beta2=0.95, weight_decay=1e-2, gradient_accumulation=1, max_grad_norm=0.05,
+             pos_wt=1.8, loss_func='bce_logits', scheduler='warmup_cosine', warmup_steps=2, max_epoch=2)
+    c.update(kw)
+    return c
+
+
+def build_meme_uniter(cfg, img_dim, precision, seed=0, train=True):
+    """a MemeUniter of `cfg` on the GPU, initialised from `seed`, dropout seed (5, 0)"""
+    from meme_challenge_amd.model import UniterConfig, UniterModel
+    from meme_challenge_amd.meme_uniter import MemeUniter
+    c = UniterConfig.from_dict(cfg)
+    torch.manual_seed(seed)
+    m = MemeUniter(UniterModel(c, img_dim=img_dim), c.hidden_size, 1).cuda()
+    m = m.train() if train else m.eval()
+    m.uniter_model.precision = precision
+    m.uniter_model.set_dropout_seed(5, 0)
+    return m
+
+
+def pretrain_dataset(tmp_path_factory):
+    """the device-resident synthetic dataset the pretraining tests share (a module-scoped fixture calls this)"""
+    import os
+    from functools import partial
+    from meme_challenge_amd.data import (DeviceFeaturePool, DeviceMemeDataset, HashTokenizer, MemeDataset, write_synthetic_dataset)
+    d = str(tmp_path_factory.mktemp('devpre'))
+    write_synthetic_dataset(d, n=PRETRAIN_N, num_bb=(3, 11), img_dim=PRETRAIN_IMG_DIM, seed=2, splits=('train',), text_words=(1, 9))
+    tok = partial(HashTokenizer(max_length=PRETRAIN_T), max_length=PRETRAIN_T)
+    ds = MemeDataset(os.path.join(d, 'train.jsonl'), os.path.join(d, 'img_feats'), text_padding=tok, return_ids=True, ragged_regions=True)
+    return DeviceMemeDataset(ds, DeviceFeaturePool('cuda'))
+
+
+def pretrain_model(train=False):
+    from meme_challenge_amd.model import UniterConfig
+    from meme_challenge_amd.pretrain import UniterForPretraining
+    torch.manual_seed(0)
+    m = UniterForPretraining(UniterConfig.from_dict(PRETRAIN_CFG), img_dim=PRETRAIN_IMG_DIM, img_label_dim=12).cuda()
+    return m.train() if train else m.eval()
+
+
+def pretrain_loader(dds, seed=3, **kw):
+    from meme_challenge_amd.data import DevicePretrainLoader
+    return DevicePretrainLoader(dds, PRETRAIN_BATCH, seed=seed, **kw)
+
+
+def take(loader, steps):
+    out = []
+    for task, batch in loader:
+        out.append((task, batch))
+        if len(out) == steps:
+            return out

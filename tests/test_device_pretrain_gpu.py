@@ -1,49 +1,18 @@
 """data.DevicePretrainLoader end to end: MLM / MRFR / ITM batches drawn on the device from a resident dataset feed
 UniterForPretraining; `masked_positions` replaces the model's own nonzero without changing a bit of the loss."""
-import os
-from functools import partial
-
 import numpy as np
 import pytest
 import torch
 
-from common import TINY
+from common import (PRETRAIN_BATCH as BATCH, PRETRAIN_N as N, pretrain_dataset, pretrain_loader as _loader,
+                    pretrain_model as _model, take as _take)
 
 pytestmark = pytest.mark.gpu
-
-T, IMG_DIM, N, BATCH = 16, 64, 24, 5
-CFG = dict(TINY, vocab_size=28996, max_position_embeddings=64, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
 
 
 @pytest.fixture(scope='module')
 def dds(tmp_path_factory):
-    from meme_challenge_amd.data import (DeviceFeaturePool, DeviceMemeDataset, HashTokenizer, MemeDataset, write_synthetic_dataset)
-    d = str(tmp_path_factory.mktemp('devpre'))
-    write_synthetic_dataset(d, n=N, num_bb=(3, 11), img_dim=IMG_DIM, seed=2, splits=('train',), text_words=(1, 9))
-    tok = partial(HashTokenizer(max_length=T), max_length=T)
-    ds = MemeDataset(os.path.join(d, 'train.jsonl'), os.path.join(d, 'img_feats'), text_padding=tok, return_ids=True, ragged_regions=True)
-    return DeviceMemeDataset(ds, DeviceFeaturePool('cuda'))
-
-
-def _model(train=False):
-    from meme_challenge_amd.model import UniterConfig
-    from meme_challenge_amd.pretrain import UniterForPretraining
-    torch.manual_seed(0)
-    m = UniterForPretraining(UniterConfig.from_dict(CFG), img_dim=IMG_DIM, img_label_dim=12).cuda()
-    return m.train() if train else m.eval()
-
-
-def _loader(dds, **kw):
-    from meme_challenge_amd.data import DevicePretrainLoader
-    return DevicePretrainLoader(dds, BATCH, seed=3, **kw)
-
-
-def _take(loader, steps):
-    out = []
-    for task, batch in loader:
-        out.append((task, batch))
-        if len(out) == steps:
-            return out
+    return pretrain_dataset(tmp_path_factory)
 
 
 def test_text_class_indexes_the_distinct_texts(dds):

@@ -8,14 +8,10 @@ fixed seed, side and auxiliary streams on."""
 import pytest
 import torch
 
-from common import TINY, TINY_IMG_DIM, model_kwargs
+from common import MID as CFG, MID_IMG_DIM as IMG_DIM, TINY, TINY_IMG_DIM, model_kwargs
 
 pytestmark = pytest.mark.gpu
 
-CFG = dict(vocab_size=997, hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=1024, hidden_act='gelu',
-           hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, max_position_embeddings=64, type_vocab_size=2,
-           initializer_range=0.02)
-IMG_DIM = 2048
 B, T, R = 16, 64, 32
 PRECISIONS = ['fp32', 'fp32x3', 'bf16']
 DET_ALL = 15

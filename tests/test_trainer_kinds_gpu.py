@@ -13,19 +13,11 @@ import torch
 
 import optim_kinds_ref as K
 import optim_ref as R
-from common import TINY, TINY_IMG_DIM
+from common import TINY, TINY_IMG_DIM, trainer_config as _config
 
 pytestmark = pytest.mark.gpu
 
 OPTS = ('adamax', 'sgd')
-
-
-def _config(optname, **kw):
-    # beta1 = 0.8: the momentum of sgd; adamax must NOT take it (torch's default 0.9, utils/optim_utils.py:36-37)
-    c = dict(optimizer=optname, lr=1e-3, beta1=0.8, beta2=0.95, weight_decay=1e-2, gradient_accumulation=1, max_grad_norm=0.05,
-             pos_wt=1.8, loss_func='bce_logits', scheduler='warmup_cosine', warmup_steps=2, max_epoch=2)
-    c.update(kw)
-    return c
 
 
 def _model(precision, train=True, seed=0):
