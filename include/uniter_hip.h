@@ -1235,6 +1235,49 @@ int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const int64_t* sel
                                   int64_t* targets /* [B] */, int64_t* masked_positions /* [B*T or B*R, 2] */,
                                   int32_t* n_masked /* device [1] */, void* stream);
 
+/* Ensemble weight search (utils/ensemble.py:35-112, :180-272): the AUROC pair counts of C weight vectors against one fixed
+ * prediction matrix, in ONE launch (csrc/ensemble.hip).  meme_challenge_amd/ensemble_search.py is the caller.
+ *
+ * THE SCORING CONTRACT
+ *
+ * Inputs
+ *  - A plane x[M][N] of doubles.  It holds either the probabilities, or their logits
+ *    log(clip(p,1e-8,1)) - log(clip(1-p,1e-8,1)).
+ *  - The Python wrapper computes the logits with numpy.  The kernel takes no log or exp.  This way no transcendental differs
+ *    between host and device.
+ *  - An optional plane present[M][N] of 0.0 / 1.0.  NULL means all present.  The wrapper has already set missing entries of x
+ *    to 0.5, or to their logit 0.
+ *  - The wrapper permutes the columns so that the first n_pos columns are the positive samples.
+ *  - Weights w[C][M] of doubles.
+ *
+ * Per candidate c and sample i.  All arithmetic is IEEE double, in this order:
+ *  1. num = 0; ws = 0.
+ *  2. For m = 0..M-1: num = num + (w[c][m]*x[m][i])*present[m][i] and ws = ws + w[c][m]*present[m][i].
+ *  3. s_i = num / min(max(ws,1e-4),1e5).
+ *  4. s_i = 0.5 where ws == 0.
+ * This is create_ensemble_prediction without its final sigmoid.
+ *
+ * Output
+ *  counts[c] = 2 * #{(p,n): s_p > s_n} + #{(p,n): s_p == s_n} over positive p and negative n, as int64.  The score is
+ *  counts[c] / (2 * n_pos * (N - n_pos)).  With only one class present, counts[c] = 0, the score is 0.0 as in metrics.aucroc,
+ *  and nothing divides by zero.
+ *
+ * The sigmoid is left out on purpose.  The statistic is rank-based, so a correctly ordered sigmoid can only merge neighbours
+ * within rounding: on 6-decimal probabilities (what the CSV exports hold) counts / denominator equalled
+ * aucroc(create_ensemble_prediction(..)) bit for bit on every candidate compared.
+ *
+ * One workgroup per candidate mixes the N scores once into LDS and counts the pairs there; one plain store of the int64 per
+ * candidate.  No atomics, no workspace, no dependence on the launch geometry: the result is deterministic, and every element of
+ * counts is written.
+ * UNITER_E_ARG: x, w or counts NULL, a pointer that is not 8-byte aligned, n_pos outside [0, N].
+ * UNITER_E_SHAPE (never clamped): N < 1 or N > 16384 (128 KB of doubles inside the 160 KB of LDS), M < 1 or M > 64, C < 1.
+ * A refusal sets the message and launches nothing. */
+#define UNITER_ENSEMBLE_MAX_N 16384
+#define UNITER_ENSEMBLE_MAX_M 64
+int uniter_ensemble_auc_counts(const double* x /* [M,N] */, const double* present /* [M,N] or NULL */,
+                               const double* w /* [C,M] */, int64_t* counts /* [C] */, int M, int N, int n_pos, int C,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

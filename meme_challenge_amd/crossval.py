@@ -189,5 +189,6 @@ def train_crossval(trainer_class, config, data_loader_funcs, num_folds=0, dev_si
         dev_files = sorted(glob(pattern + '_%s_preds.csv' % dev_names[0]))
         test_files = [sorted(glob(pattern + '_%s_preds.csv' % n)) for n in names if n != dev_names[0]]
     if dev_files:
-        find_ensemble(dev_files=dev_files, test_files=[t for t in test_files if t])
+        find_ensemble(dev_files=dev_files, test_files=[t for t in test_files if t],
+                      backend=config.get('ensemble_backend', 'host'), ea=bool(config.get('ensemble_ea', False)))
     return val_metrics

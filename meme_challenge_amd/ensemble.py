@@ -5,9 +5,14 @@ Prediction files are the trainer's CSV exports (`id,proba,label[,gt]`, train_tem
 weights -- on probabilities and on logits -- that maximise AUROC on the dev predictions
 (utils/ensemble.py:35-112, brute force :180-203), picks the accuracy-optimal threshold and writes
 `<model>_<set>_ensemble.csv` next to the inputs.  The reference adds an evolutionary search when the
-`deap` package is installed (:63-71, :206-284); like the reference without that package, this
-module stops at the brute-force result.
+`deap` package is installed (:63-71, :206-284); by default, like the reference without that package, this
+module stops at the brute-force result.  `find_ensemble(..., backend='hip', ea=True)` scores the candidates
+in batches on the GPU and runs that evolutionary search too (ensemble_search.py, csrc/ensemble.hip).
+
+    python -m meme_challenge_amd.ensemble --regex_dev 'ckpt/uniter_fold_*_dev_seen_preds.csv' \\
+        --regex_test 'ckpt/uniter_fold_*_test_seen_preds.csv' [--backend hip] [--ea]
 """
+import argparse
 import csv
 import logging
 import os
@@ -80,10 +85,9 @@ def create_ensemble_prediction(predictions, weights, on_logits=False):
     return out
 
 
-def brute_force_finder(eval_func, num_weights, weight_range, max_weights=1e5):
-    """Best (weights, on_logits) over the grid weight_range^num_weights, capped at max_weights tuples (a seeded
-    shuffle of the grid, or seeded random draws when the grid itself is too large; utils/ensemble.py:180-203).
-    The first maximum wins."""
+def weight_tuples(num_weights, weight_range, max_weights=1e5):
+    """The candidates of the brute-force search: the grid weight_range^num_weights, capped at max_weights tuples by a seeded
+    shuffle of the grid, or seeded random draws when the grid itself is too large (utils/ensemble.py:180-192)."""
     max_weights = int(max_weights)
     if np.log(len(weight_range)) * num_weights < np.log(2e7):
         tuples = list(product(weight_range, repeat=num_weights))
@@ -95,6 +99,12 @@ def brute_force_finder(eval_func, num_weights, weight_range, max_weights=1e5):
         np.random.seed(42)
         idx = np.random.randint(0, len(weight_range), size=(max_weights, num_weights))
         tuples = [[weight_range[idx[m, n]] for n in range(num_weights)] for m in range(max_weights)]
+    return tuples
+
+
+def brute_force_finder(eval_func, num_weights, weight_range, max_weights=1e5):
+    """Best (weights, on_logits) over `weight_tuples` (utils/ensemble.py:180-203).  The first maximum wins."""
+    tuples = weight_tuples(num_weights, weight_range, max_weights)
     best_score, best_config = -1, None
     for weights in tuples:
         for on_logits in (True, False):
@@ -112,8 +122,17 @@ def _names(dev_file):
     return base.rsplit('_', 5)[0], '_'.join(dev_file.rsplit('_', 3)[-3:-1])
 
 
-def find_ensemble(dev_files, test_files, weight_range=(0.0, 0.5, 1.0, 2.0), max_weights=10000):
-    """utils/ensemble.py:35-112.  Returns {'score', 'config', 'threshold', 'files'} (the reference returns None)."""
+def find_ensemble(dev_files, test_files, weight_range=(0.0, 0.5, 1.0, 2.0), max_weights=10000, backend='host', ea=False,
+                  ea_kwargs=None):
+    """utils/ensemble.py:35-112.  Returns {'score', 'config', 'threshold', 'files'} (the reference returns None).
+
+    With the defaults the search is `brute_force_finder` on the host, one candidate at a time.  backend='hip', or ea=True with either
+    backend, scores the candidates in batches through `ensemble_search.EnsembleScorer` ('hip': csrc/ensemble.hip); ea=True adds the
+    evolutionary search (`ensemble_search.ea_ensemble_finder`, keywords from ea_kwargs), whose result replaces the brute-force one
+    only if it is strictly greater (utils/ensemble.py:68).  The score returned and logged is metrics.aucroc of the winner's
+    prediction on every path."""
+    if backend not in ('host', 'hip'):
+        raise ValueError("backend must be 'host' or 'hip'; got %r" % (backend,))
     dev_preds = align_ids([load_csv(f) for f in dev_files])
     dev_gt = dev_preds[0]['gt']
     dev_scores = [aucroc(d['orig']['proba'], d['orig']['gt']) for d in dev_preds]
@@ -130,7 +149,22 @@ def find_ensemble(dev_files, test_files, weight_range=(0.0, 0.5, 1.0, 2.0), max_
         predictions[predictions == -1] = 0.5
         return score,
 
-    best_score, best = brute_force_finder(eval_func, len(dev_preds), weight_range, max_weights)
+    if backend == 'host' and not ea:
+        best_score, best = brute_force_finder(eval_func, len(dev_preds), weight_range, max_weights)
+    else:
+        from .ensemble_search import EnsembleScorer, brute_force_finder_batched, ea_ensemble_finder
+        scorer = EnsembleScorer(predictions, dev_gt, backend=backend)
+        best_score, best = brute_force_finder_batched(scorer, len(dev_preds), weight_range, max_weights)
+        predictions[predictions == -1] = 0.5      # what eval_func has done to them by now: the winner is exported from these
+        if ea:
+            logger.info('Starting EA to find optimal weights...')
+            # (the reference's EA runs after the brute force, on the predictions it has filled: no mask)
+            ea_score, ea_best = ea_ensemble_finder(scorer, len(dev_preds), dev_scores, **dict(ea_kwargs or {}, masked=False, trace=False))
+            if ea_score > best_score:
+                logger.info('Found better config with EA: [%s], on_logits=%s'
+                            % (', '.join('%4.3f' % w for w in ea_best['weights']), ea_best['on_logits']))
+                best_score, best = ea_score, ea_best
+        best_score = float(aucroc(create_ensemble_prediction(predictions, best['weights'], best['on_logits']), dev_gt))
     proba = create_ensemble_prediction(predictions, best['weights'], best['on_logits'])
     threshold = find_optimal_threshold(proba, dev_gt)
     written = []
@@ -156,3 +190,24 @@ def find_ensemble(dev_files, test_files, weight_range=(0.0, 0.5, 1.0, 2.0), max_
         written.append(os.path.join(output_dir, test_model + '_' + test_name + '_ensemble.csv'))
         export_csv(d, written[-1])
     return {'score': best_score, 'config': best, 'threshold': threshold, 'files': written}
+
+
+def main(argv=None):
+    """The reference's command line (utils/ensemble.py:275-285), plus --backend and --ea."""
+    from glob import glob
+    parser = argparse.ArgumentParser(description='Weighted ensemble of per-fold prediction files')
+    parser.add_argument('--regex_dev', type=str, required=True, help='Glob pattern of the dev csv files')
+    parser.add_argument('--regex_test', type=str, nargs='+', default=[], help='Glob patterns of the test csv files')
+    parser.add_argument('--backend', choices=('host', 'hip'), default='host', help='where the candidates are scored')
+    parser.add_argument('--ea', action='store_true', help='run the evolutionary search after the brute force')
+    args = parser.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format='%(message)s')
+    dev_files = sorted(glob(args.regex_dev))
+    if not dev_files:
+        parser.error('no file matches --regex_dev %s' % args.regex_dev)
+    test_files = [sorted(glob(t)) for t in args.regex_test]
+    return find_ensemble(dev_files, [t for t in test_files if t], max_weights=int(1e4), backend=args.backend, ea=args.ea)
+
+
+if __name__ == '__main__':
+    main()

@@ -39,6 +39,37 @@ def aucroc(probs, labels):
     return float((ranks[y == 1].sum() - n1 * (n1 + 1) / 2.0) / (n0 * n1))
 
 
+def aucroc_device(probs, labels):
+    """`aucroc` of fp32 / fp64 probabilities and 0 / 1 labels that are on the GPU already, without bringing them to the host: the
+    pair-count kernel of the ensemble search (uniter_ensemble_auc_counts, include/uniter_hip.h) with one model of weight 1.
+    The partition is torch ops and needs no count on the host: the plane is [the probabilities, NaN where the label is not 1 |
+    the probabilities, NaN where it is not 0], scored with n_pos = N of 2 N columns -- a NaN compares false both ways, so a
+    padding column is in no pair.  One host read of one int64 (the count and the number of positives packed).  At most 8192
+    samples; labels and the range of the probabilities are not checked (a check would be a host read of its own).  `aucroc`
+    stays what every caller in this package uses; this one is for callers that keep an epoch's probabilities on the device."""
+    from . import _lib
+    _lib.require_gpu_tensor(probs, name='probs')
+    _lib.require_gpu_tensor(labels, name='labels')
+    if probs.dtype not in (torch.float32, torch.float64):
+        raise _lib.UniterHipError('probs must be fp32 or fp64; got %s' % probs.dtype)
+    p, y = probs.reshape(-1).to(torch.float64), labels.reshape(-1)
+    n = p.numel()
+    if y.numel() != n or n < 1 or 2 * n > 16384:
+        raise ValueError('aucroc_device takes 1 .. 8192 probabilities and as many labels; got %d and %d' % (n, y.numel()))
+    nan = torch.full_like(p, float('nan'))
+    plane = torch.cat([torch.where(y == 1, p, nan), torch.where(y == 0, p, nan)]).contiguous()
+    weight = torch.ones(1, dtype=torch.float64, device=p.device)
+    count = torch.empty(1, dtype=torch.int64, device=p.device)
+    _lib.check(_lib.lib().uniter_ensemble_auc_counts(_lib.ptr(plane), None, _lib.ptr(weight), _lib.ptr(count), 1, 2 * n, n, 1,
+                                                     _lib.cur_stream()), 'uniter_ensemble_auc_counts')
+    packed = int(count[0] * 16384 + (y == 1).sum())           # count <= 2 * 8192^2 = 2^27, positives < 2^14
+    count, n1 = packed >> 14, packed & 16383
+    if n1 == 0 or n1 == n:
+        LOGGER.warning("ROC AUC calculation got only one label. Score not defined here, setting it to 0.")
+        return 0.0
+    return count / float(2 * n1 * (n - n1))
+
+
 def standard_metrics_binary(probs, labels, threshold=0.5, add_aucroc=True, add_optimal_acc=False, **kwargs):
     p, y = _np(probs).astype(np.float64), _np(labels).astype(np.int64)
     assert np.all((p <= 1.0) & (p >= 0.0)), "Probabilities must be between 0 and 1, but are as follows: " + str(p)

@@ -540,7 +540,11 @@ class TrainerTemplate(object):
              ('adv_algo', str, 'freelb'), ('adv_kl_weight', float, 0.0), ('adv_norm_type', str, 'l2'),
              # additive: evaluate and checkpoint an exponential moving average of the weights, kept by the fused step (0 = off);
              # add optimizer_state_dict to the checkpoint (utils/save.py:60-61)
-             ('ema_decay', float, 0.0), ('save_optimizer_state', None, False))
+             ('ema_decay', float, 0.0), ('save_optimizer_state', None, False),
+             # additive: the folds' ensemble (crossval.train_crossval -> ensemble.find_ensemble): where the weight search scores its
+             # candidates, and the evolutionary search after the brute force
+             ('ensemble_backend', str, 'host'), ('ensemble_ea', None, False))
+    CHOICES = {'ensemble_backend': ('host', 'hip')}
 
     @classmethod
     def add_default_argparse(cls, parser, defaults=dict()):
@@ -548,7 +552,7 @@ class TrainerTemplate(object):
             if kind is None:
                 parser.add_argument('--' + name, action='store_true')
             else:
-                parser.add_argument('--' + name, type=kind, default=defaults.get(name, default))
+                parser.add_argument('--' + name, type=kind, default=defaults.get(name, default), choices=cls.CHOICES.get(name))
 
     @staticmethod
     def preprocess_args(config, require_data_path=True):
