@@ -1235,6 +1235,54 @@ int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const int64_t* sel
                                   int64_t* targets /* [B] */, int64_t* masked_positions /* [B*T or B*R, 2] */,
                                   int32_t* n_masked /* device [1] */, void* stream);
 
+/* Masked region classification batches (MRC and MRC-kl, model/pretrain.py:205-233) from the same resident dataset, in ONE
+ * launch on `stream` with no host synchronisation, allocation or workspace.  A new function: uniter_collate_pretrain_batch keeps
+ * refusing task id 3, and uniter_dataset_t keeps its layout -- the soft labels are arguments.
+ *
+ * soft [pool_rows, ld_soft] holds the detector's class distribution of every pool row: row i of it belongs to the region of row
+ * i of ds->feat, columns [0, C) are the distribution (column 0 the background), columns [C, ld_soft) belong to the row and may
+ * hold anything.  C is arbitrary (the detector's is 1601).  Rows are read as 16-byte items when soft is 16-byte aligned and
+ * ld_soft % 4 == 0 (data.DeviceFeaturePool stores C rounded up to 4), else float by float; soft must be 4-byte aligned.
+ *
+ * Dense outputs (img_feat, img_pos_feat, input_ids, position_ids, token_type_ids, attn_mask, gather_index, labels, ids,
+ * img_masks, img_mask_tgt): UNITER_TASK_MRFR's of uniter_collate_pretrain_batch with txt_sel == NULL -- the img_feat rows of
+ * selected regions are zero, img_mask_tgt[b, tl + r] is set, .. -- drawn on UNITER_STREAM_MRC in place of UNITER_STREAM_MRFR,
+ * the forced region at c0 = 0xFFFFFFFF included.  A sample's MRC mask therefore differs from its MRFR mask at the same
+ * (seed, draw); 'mrc' and 'mrc-kl' share the stream.
+ *
+ * Compacted outputs.  masked_positions, *n_masked, their order and their capacity of B * R rows are MRFR's.  For the i-th
+ * selected entry, region r of sample s = sel[b]:
+ *   label_targets[i, 0:C] = soft[row_start[s] + r, 0:C]   dense [B*R, C] (leading dimension C), bit for bit;
+ *   label_ids[i] = 1 + (index of the first maximum of that row's columns 1 .. C-1)
+ *                = what uniter_row_argmax(label_targets, .., c0 = 1) returns for row i (NaN never wins; 1 without a winner).
+ * A selected region whose pool row lies outside [0, pool_rows) gives a zero row (and the class 1).  Rows at and beyond
+ * *n_masked are not written.  Either of label_targets and label_ids may be NULL and is then not produced (MRC needs the
+ * classes only and spares the C-wide rows; MRC-kl needs the rows only), but not both.  There is no feat_targets: a selected
+ * region's features are not read at all.
+ *
+ * One wave per selected row walks the row ONCE: every load of a stretch of 2048 columns (C = 1601: the whole row) is issued
+ * before its first store, each lane keeps a (value, column) pair and the wave reduces it by shuffles, ties to the smaller
+ * column -- no second pass over memory for the classes.  Destination rows lie C floats apart and are written float by float.
+ * Every dense output element, and every element of the first *n_masked rows of the compacted ones, has exactly one writer;
+ * plain vector stores only, no atomics; nothing outside the extents is touched.  Clamping of sel and row_cnt: as
+ * uniter_collate_batch.
+ *
+ * R == 0 is legal: the arrays of B * R rows have no elements and may be NULL, and *n_masked = 0 is written.
+ * UNITER_E_ARG: everything uniter_collate_batch answers so, NULL cfg, cfg.prob outside [0, 1] (NaN too), NULL soft with
+ * pool_rows > 0, soft or label_targets not 4-byte aligned, NULL n_masked or img_mask_tgt, and with R > 0 label_targets and
+ * label_ids both NULL, NULL masked_positions or NULL img_masks;  UNITER_E_SHAPE: C < 2, ld_soft < C, and
+ * uniter_collate_batch's.  A refusal sets the message (which names collate_mrc_batch) and launches nothing. */
+#define UNITER_STREAM_MRC         0xFFFF0004u   /* c2 of a region's draw for MRC / MRC-kl (and of the forced one) */
+int uniter_collate_mrc_batch(const uniter_dataset_t* ds, const float* soft /* device [pool_rows, ld_soft] */, int C, int ld_soft,
+                             const int64_t* sel /* device [B] */, const uniter_mask_cfg_t* cfg, int B, int R, int L_out, int flags,
+                             float* img_feat /* [B,R,D] */, float* img_pos_feat /* [B,R,7] */,
+                             int64_t* input_ids /* [B,T] */, int64_t* position_ids /* [B,T] */,
+                             int64_t* token_type_ids /* [B,T] or NULL */, float* attn_mask /* [B,L_out] */,
+                             int64_t* gather_index /* [B,L_out] */, int64_t* labels /* [B] */, int64_t* ids /* [B] */,
+                             int64_t* img_masks /* [B,R] */, unsigned char* img_mask_tgt /* [B,L_out] bool */,
+                             float* label_targets /* [B*R,C] or NULL */, int64_t* label_ids /* [B*R] or NULL */,
+                             int64_t* masked_positions /* [B*R, 2] */, int32_t* n_masked /* device [1] */, void* stream);
+
 /* Ensemble weight search (utils/ensemble.py:35-112, :180-272): the AUROC pair counts of C weight vectors against one fixed
  * prediction matrix, in ONE launch (csrc/ensemble.hip).  meme_challenge_amd/ensemble_search.py is the caller.
  *

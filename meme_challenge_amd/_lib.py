@@ -191,6 +191,8 @@ _SIGS = {
     'uniter_collate_batch': (_I, [_P, _P, _I, _I, _I, _I] + [_P] * 10),
     # the same with the MLM / MRFR masks and ITM targets of a pretraining batch: (ds, sel, txt_sel, task, cfg, B, R, L_out, flags, 16 outputs, stream)
     'uniter_collate_pretrain_batch': (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I] + [_P] * 17),
+    # the MRC / MRC-kl batch with soft labels: (ds, soft, C, ld_soft, sel, cfg, B, R, L_out, flags, 15 outputs, stream)
+    'uniter_collate_mrc_batch': (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _I] + [_P] * 16),
     # ensemble weight search: AUROC pair counts of C weight vectors (csrc/ensemble.hip): (x, present, w, counts, M, N, n_pos, C, stream)
     'uniter_ensemble_auc_counts': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_pooler_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

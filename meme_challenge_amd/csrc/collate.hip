@@ -144,6 +144,8 @@ extern "C" int uniter_collate_batch(const uniter_dataset_t* ds, const int64_t* s
 //   MRFR  a wave moving region row (b, r) draws its own sample's n <= R regions (lanes over regions); only when the row is selected
 //         does it count the samples in front (one sample per lane, serial over its regions).  The workgroup of sample b writes the
 //         dense img_masks / img_mask_tgt; the last one counts every sample (one per thread) for n_masked.
+//   MRC   MRFR on its own stream.  A selected region keeps no copy of its features, so the wave of its first piece has no loads
+//         of its own: it moves the region's soft-label row instead and finds the row's class on the way (soft_row).
 namespace {
 
 struct PretrainArgs {
@@ -161,6 +163,11 @@ struct PretrainArgs {
   int64_t* targets;
   int64_t* masked_positions;
   int32_t* n_masked;
+  // uniter_collate_mrc_batch only (collate_pretrain_kernel<true>): the soft-label rows beside ds.feat and their two outputs
+  const float* soft;
+  int C, ld_soft, soft4;                 // soft4: rows of `soft` start 16-byte aligned (base aligned, ld_soft % 4 == 0)
+  float* label_targets;
+  int64_t* label_ids;
 };
 
 __device__ __forceinline__ long long text_sample_of(const PretrainArgs& a, int b) {
@@ -189,22 +196,125 @@ __device__ __forceinline__ int mlm_count_wave(const PretrainArgs& a, long long t
   return cnt > 0 ? cnt : 1;              // T >= 2: position 1 exists
 }
 
-__device__ __forceinline__ bool mrfr_drawn(const PretrainArgs& a, long long s, int r) {
-  return hit(a, philox4x32_10((uint32_t)r, (uint32_t)s, UNITER_STREAM_MRFR, a.draw, a.k0, a.k1).x);
+// The region masks of MRFR and of MRC are the same rule on two streams; MRC selects the stream of uniter_collate_mrc_batch.
+template <bool MRC>
+__device__ __forceinline__ bool region_drawn(const PretrainArgs& a, long long s, int r) {
+  constexpr uint32_t stream = MRC ? UNITER_STREAM_MRC : UNITER_STREAM_MRFR;
+  return hit(a, philox4x32_10((uint32_t)r, (uint32_t)s, stream, a.draw, a.k0, a.k1).x);
 }
 // the region taken when none of the n > 0 regions of sample s was drawn
-__device__ __forceinline__ int mrfr_forced(const PretrainArgs& a, long long s, int n) {
-  const u32x4 w = philox4x32_10(0xFFFFFFFFu, (uint32_t)s, UNITER_STREAM_MRFR, a.draw, a.k0, a.k1);
+template <bool MRC>
+__device__ __forceinline__ int region_forced(const PretrainArgs& a, long long s, int n) {
+  constexpr uint32_t stream = MRC ? UNITER_STREAM_MRC : UNITER_STREAM_MRFR;
+  const u32x4 w = philox4x32_10(0xFFFFFFFFu, (uint32_t)s, stream, a.draw, a.k0, a.k1);
   return (int)(((unsigned long long)w.x * (unsigned long long)n) >> 32);
 }
 // selected regions of sample s, by ONE thread
-__device__ __forceinline__ int mrfr_count_serial(const PretrainArgs& a, long long s) {
+template <bool MRC>
+__device__ __forceinline__ int region_count_serial(const PretrainArgs& a, long long s) {
   const int n = regions_of(a.c, s);
   int cnt = 0;
-  for (int r = 0; r < n; ++r) cnt += mrfr_drawn(a, s, r) ? 1 : 0;
+  for (int r = 0; r < n; ++r) cnt += region_drawn<MRC>(a, s, r) ? 1 : 0;
   return (cnt == 0 && n > 0) ? 1 : cnt;
 }
+// Region r < n of sample s = sel[b], by the whole wave: is it selected, and if so which row of the compacted outputs
+// (masked_positions, feat_targets | label_targets, label_ids) is its own?  Uniform over the wave.
+template <bool MRC>
+__device__ __forceinline__ bool region_slot(const PretrainArgs& a, long long s, int n, int b, int r, int lane, long long& dest) {
+  int before = 0, total = 0;
+  bool mine = false;
+  for (int base = 0; base < n; base += 64) {
+    const int rr = base + lane;
+    const unsigned long long bal = __ballot(rr < n && region_drawn<MRC>(a, s, rr));
+    total += __popcll(bal);
+    if (r >= base + 64) before += __popcll(bal);
+    else if (r >= base) {
+      before += __popcll(bal & ((1ull << (r - base)) - 1ull));
+      mine = (bal >> (r - base)) & 1ull;
+    }
+  }
+  bool masked;
+  if (total == 0) { masked = r == region_forced<MRC>(a, s, n); before = 0; }
+  else masked = mine;
+  if (masked) {
+    int front = 0;
+    for (int bp = lane; bp < b; bp += 64) front += region_count_serial<MRC>(a, sample_of(a.c, bp));
+    for (int o = 32; o > 0; o >>= 1) front += __shfl_xor(front, o, 64);
+    dest = (long long)front + before;                  // < B * R: every sample contributes at most its n <= R
+  }
+  return masked;
+}
 
+// MRC: one wave moves the soft-label row of a selected region to row `dest` of label_targets and finds its class for label_ids
+// in the same walk (the first maximum of columns 1 .. C-1, as heads.hip's row_argmax_kernel with c0 = 1: NaN never wins, a row
+// without a winner gives 1).  The row is walked in chunks of 2048 columns -- C = 1601 is one chunk -- and a chunk's loads are all
+// issued before its first store.  Source rows are read as 16-byte items when they start aligned (a.soft4; the columns between C
+// and ld_soft belong to the row and are read but neither stored nor compared), else as single floats, consecutive lanes taking
+// consecutive items either way.  Destination rows lie C floats apart, so in general only 4-byte aligned: single-float stores.
+// src == nullptr (a pool row outside the pool): a zero row.
+__device__ __forceinline__ void soft_row(const PretrainArgs& a, const float* src, long long dest, int lane) {
+  const int C = a.C;
+  float* dst = a.label_targets ? a.label_targets + (size_t)dest * C : nullptr;
+  float best = -__builtin_huge_valf();
+  int at = 0x7fffffff;
+  if (src == nullptr) {
+    if (dst)
+      for (int col = lane; col < C; col += 64) dst[col] = 0.f;
+    best = 0.f; at = 1;                                // every column equal: the first one
+  } else if (a.soft4) {
+    const f32x4* sp = reinterpret_cast<const f32x4*>(src);
+    const int n4 = (C + 3) >> 2;                       // <= ld_soft / 4
+    for (int base = 0; base < n4; base += 512) {
+      f32x4 v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int q = base + lane + 64 * k;
+        v[k] = q < n4 ? sp[q] : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int col = 4 * (base + lane + 64 * k);
+        const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (col + j < C) {
+            if (dst) dst[col + j] = e[j];
+            if (col + j >= 1 && e[j] > best) { best = e[j]; at = col + j; }      // ascending columns per lane: its first maximum
+          }
+        }
+      }
+    }
+  } else {
+    for (int base = 0; base < C; base += 1024) {
+      float v[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int col = base + lane + 64 * k;
+        v[k] = col < C ? src[col] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int col = base + lane + 64 * k;
+        if (col < C) {
+          if (dst) dst[col] = v[k];
+          if (col >= 1 && v[k] > best) { best = v[k]; at = col; }
+        }
+      }
+    }
+  }
+  if (a.label_ids) {
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oa = __shfl_xor(at, o, 64);
+      if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+    }
+    if (lane == 0) a.label_ids[dest] = at == 0x7fffffff ? 1 : at;
+  }
+}
+
+// MRC = false: uniter_collate_pretrain_batch;  MRC = true: uniter_collate_mrc_batch, whose dense outputs are MRFR's on its own
+// stream (a.task is UNITER_TASK_MRFR) and whose selected rows carry soft labels instead of feat_targets.
+template <bool MRC>
 __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArgs a) {
   __shared__ int sh[4];
   const CollateArgs& c = a.c;
@@ -221,42 +331,26 @@ __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArg
     const bool real = r < n && src_row >= 0 && src_row < c.ds.pool_rows;
     // (everything up to `dest` is uniform over the wave)
     bool masked = false;
-    long long dest = 0;                                // row of feat_targets / masked_positions
-    if (a.task == UNITER_TASK_MRFR && r < n) {
-      int before = 0, total = 0;
-      bool mine = false;
-      for (int base = 0; base < n; base += 64) {
-        const int rr = base + lane;
-        const unsigned long long bal = __ballot(rr < n && mrfr_drawn(a, s, rr));
-        total += __popcll(bal);
-        if (r >= base + 64) before += __popcll(bal);
-        else if (r >= base) {
-          before += __popcll(bal & ((1ull << (r - base)) - 1ull));
-          mine = (bal >> (r - base)) & 1ull;
-        }
-      }
-      if (total == 0) { masked = r == mrfr_forced(a, s, n); before = 0; }
-      else masked = mine;
-      if (masked) {
-        int front = 0;
-        for (int bp = lane; bp < b; bp += 64) front += mrfr_count_serial(a, sample_of(c, bp));
-        for (int o = 32; o > 0; o >>= 1) front += __shfl_xor(front, o, 64);
-        dest = (long long)front + before;              // < B * R: every sample contributes at most its n <= R
-      }
-    }
+    long long dest = 0;                                // row of feat_targets | label_targets, label_ids and masked_positions
+    if (a.task == UNITER_TASK_MRFR && r < n) masked = region_slot<MRC>(a, s, n, b, r, lane, dest);
     f32x4* dp = reinterpret_cast<f32x4*>(c.img_feat) + (size_t)row * c.D4;
     const int c0 = piece * PIECE4 + lane;
     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = zero;
-    if (real) {
+    if (real && !(MRC && masked)) {                    // (MRC keeps no copy of a selected region's features)
       const f32x4* sp = reinterpret_cast<const f32x4*>(c.ds.feat) + (size_t)src_row * c.D4;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (c0 + 64 * k < c.D4) v[k] = sp[c0 + 64 * k];
     }
-    if (masked) {
+    if (MRC && masked) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c0 + 64 * k < c.D4) dp[c0 + 64 * k] = zero;
+      if (piece == 0) soft_row(a, real ? a.soft + (size_t)src_row * a.ld_soft : nullptr, dest, lane);
+    } else if (masked) {
       f32x4* tp = reinterpret_cast<f32x4*>(a.feat_targets) + (size_t)dest * c.D4;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -351,18 +445,18 @@ __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArg
     int any = 0;
     for (int base = 0; base < n; base += 256) {
       const int r = base + (int)threadIdx.x;
-      any |= __syncthreads_or(r < n && mrfr_drawn(a, s, r));
+      any |= __syncthreads_or(r < n && region_drawn<MRC>(a, s, r));
     }
-    const int forced = (any || n == 0) ? -1 : mrfr_forced(a, s, n);
+    const int forced = (any || n == 0) ? -1 : region_forced<MRC>(a, s, n);
     for (int r = threadIdx.x; r < c.R; r += 256)
-      a.img_masks[(size_t)b * c.R + r] = (r < n && (forced >= 0 ? r == forced : mrfr_drawn(a, s, r))) ? 1 : 0;
+      a.img_masks[(size_t)b * c.R + r] = (r < n && (forced >= 0 ? r == forced : region_drawn<MRC>(a, s, r))) ? 1 : 0;
     for (int j = threadIdx.x; j < c.L_out; j += 256) {
       const long long r = j - tl;
-      a.img_mask_tgt[(size_t)b * c.L_out + j] = (r >= 0 && r < n && (forced >= 0 ? r == forced : mrfr_drawn(a, s, (int)r))) ? 1 : 0;
+      a.img_mask_tgt[(size_t)b * c.L_out + j] = (r >= 0 && r < n && (forced >= 0 ? r == forced : region_drawn<MRC>(a, s, (int)r))) ? 1 : 0;
     }
     if (b == c.B - 1) {
       int cnt = 0;
-      for (int bp = threadIdx.x; bp < c.B; bp += 256) cnt += mrfr_count_serial(a, sample_of(c, bp));
+      for (int bp = threadIdx.x; bp < c.B; bp += 256) cnt += region_count_serial<MRC>(a, sample_of(c, bp));
       for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
       if (lane == 0) sh[wave] = cnt;
       __syncthreads();
@@ -441,7 +535,66 @@ extern "C" int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const i
   a.txt_sel = txt_sel; a.task = task;
   a.txt_labels = txt_labels; a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.feat_targets = feat_targets;
   a.targets = targets; a.masked_positions = masked_positions; a.n_masked = n_masked;
-  hipLaunchKernelGGL(collate_pretrain_kernel, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  a.soft = nullptr; a.C = a.ld_soft = a.soft4 = 0; a.label_targets = nullptr; a.label_ids = nullptr;
+  hipLaunchKernelGGL(collate_pretrain_kernel<false>, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+// ---- masked region classification: MRFR's batch on its own stream, soft labels and their classes in place of feat_targets ------
+extern "C" int uniter_collate_mrc_batch(const uniter_dataset_t* ds, const float* soft, int C, int ld_soft, const int64_t* sel,
+                                        const uniter_mask_cfg_t* cfg, int B, int R, int L_out, int flags, float* img_feat,
+                                        float* img_pos_feat, int64_t* input_ids, int64_t* position_ids, int64_t* token_type_ids,
+                                        float* attn_mask, int64_t* gather_index, int64_t* labels, int64_t* ids, int64_t* img_masks,
+                                        unsigned char* img_mask_tgt, float* label_targets, int64_t* label_ids,
+                                        int64_t* masked_positions, int32_t* n_masked, void* stream) {
+  UCHECK_ARG(ds && sel, "collate_mrc_batch: null dataset or selection");
+  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids,
+             "collate_mrc_batch: null pointer in the dataset");
+  UCHECK_ARG(input_ids && position_ids && attn_mask && gather_index && labels && ids, "collate_mrc_batch: null output pointer");
+  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "collate_mrc_batch: dataset of %lld samples, %lld pool rows", (long long)ds->N,
+             (long long)ds->pool_rows);
+  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0, "collate_mrc_batch: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)",
+               B, ds->T, L_out, R);
+  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "collate_mrc_batch: L_out = %d exceeds T + R = %d + %d", L_out, ds->T, R);
+  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "collate_mrc_batch: D = %d must be a positive multiple of 4 (rows move as 16-byte items)", ds->D);
+  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "collate_mrc_batch: null feat / pos with %lld pool rows", (long long)ds->pool_rows);
+  UCHECK_ARG((img_feat && img_pos_feat) || R == 0, "collate_mrc_batch: null img_feat / img_pos_feat with R = %d", R);
+  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "collate_mrc_batch: feat is not 16-byte aligned");
+  UCHECK_ARG(((uintptr_t)img_feat & 15) == 0, "collate_mrc_batch: img_feat is not 16-byte aligned");
+  UCHECK_ARG(cfg, "collate_mrc_batch: null mask configuration");
+  UCHECK_ARG(cfg->prob >= 0.0f && cfg->prob <= 1.0f, "collate_mrc_batch: prob = %g is outside [0, 1]", (double)cfg->prob);
+  UCHECK_ARG(soft || ds->pool_rows == 0, "collate_mrc_batch: null soft labels with %lld pool rows", (long long)ds->pool_rows);
+  UCHECK_SHAPE(C >= 2 && ld_soft >= C, "collate_mrc_batch: C = %d, ld_soft = %d (C >= 2: a background and a class; ld_soft >= C)", C, ld_soft);
+  UCHECK_ARG(((uintptr_t)soft & 3) == 0 && ((uintptr_t)label_targets & 3) == 0, "collate_mrc_batch: soft / label_targets is not 4-byte aligned");
+  // (R == 0: both have no elements, and an empty tensor's pointer is null)
+  UCHECK_ARG(label_targets || label_ids || R == 0, "collate_mrc_batch: label_targets and label_ids are both null with R = %d", R);
+  UCHECK_ARG(n_masked && img_mask_tgt && ((masked_positions && img_masks) || R == 0),
+             "collate_mrc_batch: null masked_positions / n_masked / img_masks / img_mask_tgt with R = %d", R);
+  PretrainArgs a;
+  a.k0 = (uint32_t)(cfg->seed & 0xffffffffu); a.k1 = (uint32_t)(cfg->seed >> 32); a.draw = cfg->draw;
+  const double t = (double)cfg->prob * 4294967296.0;         // make_drop's floor and clamp (philox.h)
+  a.always = cfg->prob >= 1.0f;
+  a.thresh = t >= 4294967295.0 ? 0xffffffffu : (t <= 0.0 ? 0u : (uint32_t)t);
+  a.cls = a.sep = a.pad = a.mask_token = a.vocab_lo = 0; a.vocab_span = 1;
+  CollateArgs& c = a.c;
+  c.ds = *ds;
+  if (!token_type_ids || !ds->token_type_ids) token_type_ids = nullptr;
+  c.sel = sel; c.B = B; c.R = R; c.L_out = L_out; c.ragged = flags & 1;
+  c.D4 = ds->D / 4;
+  c.pieces = (c.D4 + PIECE4 - 1) / PIECE4;
+  c.region_items = (long long)B * R * c.pieces;
+  const long long region_blocks = (c.region_items + 3) / 4;
+  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "collate_mrc_batch: %lld region items exceed one launch", c.region_items);
+  c.region_blocks = (unsigned)region_blocks;
+  c.img_feat = img_feat; c.img_pos_feat = img_pos_feat; c.input_ids = input_ids; c.position_ids = position_ids;
+  c.token_type_ids = token_type_ids; c.attn_mask = attn_mask; c.gather_index = gather_index; c.labels = labels; c.ids = ids;
+  a.txt_sel = nullptr; a.task = UNITER_TASK_MRFR;            // the dense outputs are MRFR's, on UNITER_STREAM_MRC
+  a.txt_labels = nullptr; a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.feat_targets = nullptr;
+  a.targets = nullptr; a.masked_positions = masked_positions; a.n_masked = n_masked;
+  a.soft = soft; a.C = C; a.ld_soft = ld_soft; a.soft4 = ((uintptr_t)soft & 15) == 0 && ld_soft % 4 == 0;
+  a.label_targets = label_targets; a.label_ids = label_ids;
+  hipLaunchKernelGGL(collate_pretrain_kernel<true>, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
 }

@@ -40,6 +40,19 @@ def load_img_feature(feature_dir, img_id, normalize=True):
     return feat.float(), pos, info['objects'], conf
 
 
+def load_soft_labels(feature_dir, img_id):
+    """-> the detector's class distribution of every region, `cls_prob` of `<id>_info.npy`, fp32 [nbb, C] (column 0 is the
+    background): the `label_targets` of masked region classification, which load_img_feature reduces to one confidence."""
+    path = os.path.join(feature_dir, '%s_info.npy' % expand_id(img_id))
+    info = np.load(path, allow_pickle=True).item()
+    if 'cls_prob' not in info:
+        raise ValueError('%s has no cls_prob: soft labels need the detector\'s class distribution per region' % path)
+    soft = np.asarray(info['cls_prob'], dtype=np.float32)
+    if soft.ndim != 2:
+        raise ValueError('%s: cls_prob must be [nbb, C]; got %s' % (path, soft.shape))
+    return torch.from_numpy(np.ascontiguousarray(soft))
+
+
 # ---- packed feature shard (SURVEY 8(f) N2) -------------------------------------------------------
 # At >1000 samples/s per GPU the per-sample `<id>.npy` + pickled `<id>_info.npy` pair (two opens, one
 # unpickle, 295 KB) is the input bottleneck.  A shard is the same data laid out for streaming: one
@@ -207,13 +220,18 @@ class DevicePrefetcher(object):
 class MemeDataset(data.Dataset):
     def __init__(self, filepath, feature_dir=None, text_padding=None, return_ids=False, compact_batch=True,
                  confidence_threshold=0.0, preload_images=False, text_only=False, debug=False,
-                 feature_shard=None, ragged_regions=False, **unused):
-        """`ragged_regions=False` reproduces the reference's collate exactly: it measures the region count of every
+                 feature_shard=None, ragged_regions=False, soft_labels=False, **unused):
+        """`soft_labels=True` adds 'img_soft_label' [kept, C] to every sample: the detector's class distribution of the regions
+        the sample keeps (load_soft_labels), for masked region classification.  Feature shards carry no cls_prob and are refused.
+        `ragged_regions=False` reproduces the reference's collate exactly: it measures the region count of every
         sample on the already zero-padded stack (data/meme_dataset.py:161,191), so every sample of a batch carries the
         batch's largest region count and the zero rows are attended like real regions (pinned by
         tests/golden/data_pipeline.npz).  True masks each sample at its own region count instead (what
         utils/utils.py:111-125 describes; fewer valid positions for token packing)."""
         self.ragged_regions = ragged_regions
+        self.soft_labels = bool(soft_labels) and not text_only
+        if self.soft_labels and feature_shard:
+            raise ValueError('soft_labels=True needs the per-image feature files: the feature shard %s carries no cls_prob' % feature_shard)
         assert os.path.isfile(filepath), "Dataset file cannot be found: \"%s\"." % filepath
         assert filepath.endswith(".jsonl"), "The filepath requires a JSON list file (\".jsonl\")."
         self.filepath, self.feature_dir = filepath, feature_dir
@@ -240,13 +258,15 @@ class MemeDataset(data.Dataset):
         self._cache = None
         if preload_images and not text_only:
             self._cache = [load_img_feature(feature_dir, i) for i in self.data.ids.tolist()]
+            if self.soft_labels:
+                self._soft_cache = [load_soft_labels(feature_dir, i) for i in self.data.ids.tolist()]
 
     def __len__(self):
         return len(self.data.ids)
 
     def __getitem__(self, idx):
         data_id, label = self.data.ids[idx], self.data.labels[idx]
-        feat = pos = None
+        feat = pos = soft = None
         if not self.text_only:
             if self._cache is not None:
                 feat, pos, _, conf = self._cache[idx]
@@ -257,8 +277,16 @@ class MemeDataset(data.Dataset):
             if self.confidence_threshold > 0.0:
                 keep = torch.from_numpy(np.asarray(conf) > self.confidence_threshold)
                 feat, pos = feat[keep], pos[keep]
-        return {'img_feat': feat, 'img_pos_feat': pos, 'text': self.data.text[idx], 'label': label,
-                'data_id': data_id}
+            if self.soft_labels:
+                soft = self._soft_cache[idx] if self._cache is not None else load_soft_labels(self.feature_dir, data_id.item())
+                if soft.shape[0] != conf.shape[0]:
+                    raise ValueError('image %d: cls_prob has %d rows for %d regions' % (data_id.item(), soft.shape[0], conf.shape[0]))
+                if self.confidence_threshold > 0.0:
+                    soft = soft[keep]
+        sample = {'img_feat': feat, 'img_pos_feat': pos, 'text': self.data.text[idx], 'label': label, 'data_id': data_id}
+        if self.soft_labels:
+            sample['img_soft_label'] = soft
+        return sample
 
     def get_collate_fn(self):
         def collate_fn(samples):
@@ -352,11 +380,15 @@ def hash_str(s):
     return h
 
 
-def write_synthetic_dataset(root, n=64, num_bb=(10, 36), img_dim=2048, seed=0, splits=('train', 'dev_seen'), text_words=(3, 8)):
+def write_synthetic_dataset(root, n=64, num_bb=(10, 36), img_dim=2048, seed=0, splits=('train', 'dev_seen'), text_words=(3, 8),
+                            label_dim=None):
     """Create a dataset in the reference's ON-DISK FORMAT (jsonl + per-image .npy feature files) with
     a learnable signal: label 1 memes have a shifted feature mean and contain a marker word.  text_words / num_bb: (min, max)
-    words per caption and regions per image (BASELINE configs[1] shapes: text_words=(126, 126), num_bb=(36, 36))."""
+    words per caption and regions per image (BASELINE configs[1] shapes: text_words=(126, 126), num_bb=(36, 36)).  label_dim: every
+    info dict also gets `cls_prob` [nbb, label_dim], a softmax of normals (strictly positive, rows summing to 1 up to fp32 rounding), from a
+    generator of its own: every other field is bit-identical to the call without it."""
     rng = np.random.default_rng(seed)
+    soft_rng = np.random.default_rng([seed, 1]) if label_dim is not None else None
     feat_dir = os.path.join(root, 'img_feats')
     os.makedirs(feat_dir, exist_ok=True)
     words = ['cat', 'dog', 'meme', 'funny', 'sky', 'tree', 'car', 'look', 'when', 'you', 'me', 'nobody']
@@ -373,6 +405,10 @@ def write_synthetic_dataset(root, n=64, num_bb=(10, 36), img_dim=2048, seed=0, s
                 info = {'bbox': np.concatenate([x1, y1, x1 + bw, y1 + bh], 1).astype(np.float32),
                         'image_width': W, 'image_height': H,
                         'objects': rng.integers(0, 1600, nbb), 'objects_conf': rng.random(nbb).astype(np.float32)}
+                if soft_rng is not None:
+                    z = soft_rng.standard_normal((nbb, int(label_dim)))
+                    e = np.exp(z - z.max(axis=1, keepdims=True))
+                    info['cls_prob'] = (e / e.sum(axis=1, keepdims=True)).astype(np.float32)
                 np.save(os.path.join(feat_dir, expand_id(idx) + '.npy'), feat)
                 np.save(os.path.join(feat_dir, expand_id(idx) + '_info.npy'), info, allow_pickle=True)
                 text = ' '.join(rng.choice(words, int(rng.integers(text_words[0], text_words[1] + 1)))) + (' hateful' if label else ' nice')
@@ -392,20 +428,31 @@ _GB = float(1 << 30)
 class DeviceFeaturePool(object):
     """The process-wide store of region rows on `device`: feat [rows, D] and pos [rows, 7], fp32, growing.  A sample is
     keyed by (feature source, image id, confidence threshold), so datasets that share images -- the fold files of a
-    cross-validation run -- upload every image once."""
+    cross-validation run -- upload every image once.
+
+    soft_labels=True keeps a third buffer beside them, soft [rows, ld_soft]: row i holds the detector's class distribution
+    ('img_soft_label', C = label_dim columns) of the region of row i of feat.  ld_soft is C rounded up to a multiple of 4, so
+    that with torch's 512-byte aligned allocations every row starts 16-byte aligned and uniter_collate_mrc_batch reads it as
+    16-byte items (C = 1601: 1604 floats, 0.2 % more memory); the columns [C, ld_soft) are zero.  At 8500 images x 36 regions
+    x 1601 classes that is 1.96 GB, counted by resident_bytes and the max_gb budget."""
 
     CHUNK_BYTES = 256 << 20          # host rows gathered before one upload (and one budget check)
 
-    def __init__(self, device, max_gb=32.0):
+    def __init__(self, device, max_gb=32.0, soft_labels=False):
         self.device = torch.device(device)
         self.max_bytes = int(float(max_gb) * _GB)
-        self.feat = self.pos = None          # [capacity, D] / [capacity, 7]; rows [0, self.rows) are in use
+        self.soft_labels = bool(soft_labels)
+        self.feat = self.pos = self.soft = None        # [capacity, D] / [capacity, 7] / [capacity, ld_soft]; rows [0, self.rows) are in use
         self.rows, self.dim = 0, None
+        self.label_dim = self.ld_soft = None # C and the leading dimension of soft, from the first image
         self._where = {}                     # key -> (row_start, row_cnt)
 
     @property
     def resident_bytes(self):
-        return 0 if self.dim is None else self.rows * (self.dim + 7) * 4
+        return 0 if self.dim is None else self.rows * self._row_floats() * 4
+
+    def _row_floats(self):
+        return self.dim + 7 + ((self.ld_soft or 0) if self.soft_labels else 0)
 
     @staticmethod
     def source_of(dataset):
@@ -419,15 +466,18 @@ class DeviceFeaturePool(object):
         new_cap = max(rows, cap + cap // 2)
         feat = torch.empty((new_cap, self.dim), dtype=torch.float32, device=self.device)
         pos = torch.empty((new_cap, 7), dtype=torch.float32, device=self.device)
+        soft = torch.empty((new_cap, self.ld_soft), dtype=torch.float32, device=self.device) if self.soft_labels else None
         if self.rows:
             feat[:self.rows].copy_(self.feat[:self.rows])
             pos[:self.rows].copy_(self.pos[:self.rows])
-        self.feat, self.pos = feat, pos      # (the old buffers go back to torch's allocator, in stream order)
+            if soft is not None:
+                soft[:self.rows].copy_(self.soft[:self.rows])
+        self.feat, self.pos, self.soft = feat, pos, soft      # (the old buffers go back to torch's allocator, in stream order)
 
-    def _upload(self, feats, poss, pending):
+    def _upload(self, feats, poss, softs, pending):
         """append the host rows to the device buffers; the budget is checked before anything is allocated"""
         n = sum(int(f.shape[0]) for f in feats)
-        need = (self.rows + n) * (self.dim + 7) * 4
+        need = (self.rows + n) * self._row_floats() * 4
         if need > self.max_bytes:
             raise ValueError('device dataset: %d bytes of region features needed, %d allowed (--device_dataset_max_gb %.3g)'
                              % (need, self.max_bytes, self.max_bytes / _GB))
@@ -435,16 +485,23 @@ class DeviceFeaturePool(object):
         if n:
             self.feat[self.rows:self.rows + n].copy_(torch.cat(feats))
             self.pos[self.rows:self.rows + n].copy_(torch.cat(poss))
+            if self.soft_labels:
+                self.soft[self.rows:self.rows + n, :self.label_dim].copy_(torch.cat(softs))
+                self.soft[self.rows:self.rows + n, self.label_dim:].zero_()
         self.rows += n
         self._where.update(pending)          # resident from here on
 
     def add(self, dataset):
         """Make every sample of `dataset` resident (each not-yet-resident one is read ONCE, through dataset[idx]: the host path's
-        feature directory, shard and confidence threshold) -> (row_start int64 [N], row_cnt int32 [N]) numpy arrays."""
+        feature directory, shard and confidence threshold) -> (row_start int64 [N], row_cnt int32 [N]) numpy arrays.  A pool with
+        soft labels takes 'img_soft_label' [regions, C] of one common C from every sample of every dataset."""
         src, thr = self.source_of(dataset), float(dataset.confidence_threshold)
         ids = dataset.data.ids.tolist()
+        if self.soft_labels and ids and not getattr(dataset, 'soft_labels', False):
+            raise ValueError('device dataset: the pool keeps soft labels, but dataset %s (image %d first) gives no img_soft_label: '
+                             'build it with soft_labels=True' % (getattr(dataset, 'name', '?'), int(ids[0])))
         row_start, row_cnt = np.zeros(len(ids), dtype=np.int64), np.zeros(len(ids), dtype=np.int32)
-        feats, poss, pending, held, at = [], [], {}, 0, self.rows
+        feats, poss, softs, pending, held, at = [], [], [], {}, 0, self.rows
         for idx, img in enumerate(ids):
             key = (src, int(img), thr)
             if key not in self._where and key not in pending:
@@ -455,16 +512,32 @@ class DeviceFeaturePool(object):
                 if int(f.shape[1]) != self.dim or tuple(p.shape) != (int(f.shape[0]), 7):
                     raise ValueError('device dataset: image %d has features %s / %s, the pool holds rows of %d'
                                      % (int(img), tuple(f.shape), tuple(p.shape), self.dim))
+                if self.soft_labels:
+                    q = s.get('img_soft_label')
+                    if q is None or q.dim() != 2 or int(q.shape[0]) != int(f.shape[0]):
+                        raise ValueError('device dataset: image %d has soft labels %s for %d regions'
+                                         % (int(img), None if q is None else tuple(q.shape), int(f.shape[0])))
+                    if self.label_dim is None:
+                        if int(q.shape[1]) < 2:
+                            raise ValueError('device dataset: image %d has soft labels of %d classes; a background and a class are the least'
+                                             % (int(img), int(q.shape[1])))
+                        self.label_dim = int(q.shape[1])
+                        self.ld_soft = (self.label_dim + 3) // 4 * 4
+                    if int(q.shape[1]) != self.label_dim:
+                        raise ValueError('device dataset: image %d has soft labels of %d classes, the pool holds rows of %d'
+                                         % (int(img), int(q.shape[1]), self.label_dim))
+                    softs.append(q.float().contiguous())
+                    held += q.numel() * 4
                 pending[key] = (at, int(f.shape[0]))
                 at += int(f.shape[0])
                 feats.append(f); poss.append(p)
                 held += f.numel() * 4
                 if held >= self.CHUNK_BYTES:
-                    self._upload(feats, poss, pending)
-                    feats, poss, pending, held = [], [], {}, 0
+                    self._upload(feats, poss, softs, pending)
+                    feats, poss, softs, pending, held = [], [], [], {}, 0
             row_start[idx], row_cnt[idx] = self._where[key] if key in self._where else pending[key]
         if self.dim is not None:
-            self._upload(feats, poss, pending)
+            self._upload(feats, poss, softs, pending)
         return row_start, row_cnt
 
 
@@ -484,6 +557,7 @@ class DeviceMemeDataset(object):
         self.name, self.return_ids, self.data = dataset.name, dataset.return_ids, dataset.data
         self.ragged_regions = bool(dataset.ragged_regions)
         row_start, self.row_cnt = pool.add(dataset)               # raises before any allocation when over budget
+        self.label_dim = pool.label_dim if getattr(pool, 'soft_labels', False) else None      # C of the resident soft labels
         ids, tts, lens = [], [], []
         for a in range(0, len(dataset), self.TEXT_CHUNK):
             texts = dataset.text_padding(dataset.data.text[a:a + self.TEXT_CHUNK])
@@ -737,6 +811,81 @@ def collate_pretrain_batch(task, sel, txt_sel, feat, pos, row_start, row_cnt, in
     return out
 
 
+# Masked region classification (data/pretrain_mrc.py; model/pretrain.py:205-233) needs what the three tasks above do not: the
+# detector's class distribution of every region, resident beside the features (DeviceFeaturePool(soft_labels=True)).  Both tasks
+# draw their region masks from one stream of their own; 'mrc' takes the classes, 'mrc-kl' the distributions.
+MRC_TASKS = ('mrc', 'mrc-kl')
+
+
+def collate_mrc_batch(sel, feat, pos, soft, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids, R, L_out, label_dim,
+                      hard=True, soft_out=True, ragged_regions=False, seed=0, draw=0, prob=0.15, out=None):
+    """uniter_collate_mrc_batch (include/uniter_hip.h) on the current stream: the MRC / MRC-kl batch of the samples `sel`.  `soft`
+    [rows, ld_soft >= label_dim] holds the soft labels of the rows of `feat`.  -> dict with the reference collate's keys
+    (`attn_masks`, `img_masks`, `img_mask_tgt`, `label_targets`), `labels` / `ids` / `token_type_ids` as collate_batch gives them,
+    and the compaction at full capacity: `masked_positions` [B*R, 2], `n_masked` (int32 [1], on the device; the first n_masked rows
+    are defined), `label_targets` [B*R, label_dim] (soft_out) and `label_ids` [B*R] (hard: 1 + the first maximum of a row's columns
+    1 .., what pretrain._hard_region_labels finds).  At least one of hard and soft_out.  `out`: the same dict of preallocated
+    outputs to write into (tests)."""
+    import ctypes as C
+    from . import _lib
+    if not (hard or soft_out):
+        raise ValueError('collate_mrc_batch: neither label_ids (hard) nor label_targets (soft_out) asked for')
+    i64, i32, f32 = torch.int64, torch.int32, torch.float32
+    for name, t, dt in (('sel', sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('soft', soft, f32), ('row_start', row_start, i64),
+                        ('row_cnt', row_cnt, i32), ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64),
+                        ('txt_len', txt_len, i32), ('labels', labels, i64), ('ids', ids, i64)):
+        if t is None and name != 'token_type_ids':
+            raise _lib.UniterHipError('collate_mrc_batch: %s is missing' % name)
+        _lib.require_gpu_tensor(t, dt, name)
+    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
+    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
+        raise _lib.UniterHipError('collate_mrc_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s'
+                                  % (tuple(feat.shape), tuple(pos.shape)))
+    Cn = int(label_dim)
+    if soft.dim() != 2 or soft.shape[0] != feat.shape[0] or Cn < 2 or int(soft.shape[1]) < Cn:
+        raise _lib.UniterHipError('collate_mrc_batch: soft [%d rows, ld_soft >= label_dim = %d >= 2] expected; got %s'
+                                  % (int(feat.shape[0]), Cn, tuple(soft.shape)))
+    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
+                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()):
+        if tuple(t.shape) != shape:
+            raise _lib.UniterHipError('collate_mrc_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
+    R, L_out = max(int(R), 0), max(int(L_out), 0)
+    dev = sel.device
+    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
+              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
+              'ids': ((B,), i64), 'img_masks': ((B, R), i64), 'img_mask_tgt': ((B, L_out), torch.bool),
+              'masked_positions': ((B * R, 2), i64), 'n_masked': ((1,), i32)}
+    if soft_out:
+        shapes['label_targets'] = ((B * R, Cn), f32)
+    if hard:
+        shapes['label_ids'] = ((B * R,), i64)
+    if out is None:
+        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
+               for k, (s, dt) in shapes.items()}
+    else:
+        for k, (s, dt) in shapes.items():
+            t = out.get(k)
+            if t is None and k == 'token_type_ids':
+                continue
+            if t is None or tuple(t.shape) != s:
+                raise _lib.UniterHipError('collate_mrc_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
+            _lib.require_gpu_tensor(t, dt, 'output ' + k)
+    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
+                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
+                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+    cfg = _lib.UniterMaskCfgC(int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(prob), 0, 0, 0, 0, 0, 0)
+    for t in (sel, feat, pos, soft, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
+        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
+    o = lambda k: None if (k not in shapes or out.get(k) is None) else C.c_void_p(out[k].data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().uniter_collate_mrc_batch(
+            C.byref(ds), C.c_void_p(soft.data_ptr()), Cn, int(soft.shape[1]), C.c_void_p(sel.data_ptr()), C.byref(cfg), B, R, L_out,
+            1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'), o('input_ids'), o('position_ids'), o('token_type_ids'),
+            o('attn_masks'), o('gather_index'), o('labels'), o('ids'), o('img_masks'), o('img_mask_tgt'), o('label_targets'),
+            o('label_ids'), o('masked_positions'), o('n_masked'), _lib.cur_stream()), 'uniter_collate_mrc_batch')
+    return out
+
+
 class DevicePretrainLoader(object):
     """MetaLoader over a DeviceMemeDataset: an indefinite iterator of (task, batch).  Every `accum_steps` steps the task is drawn
     from the ratio pool (`tasks`: (name, ratio) pairs) by a generator seeded from `seed`.  Every task walks its own epochs: its
@@ -747,7 +896,11 @@ class DevicePretrainLoader(object):
     the collate launch queued behind the previous step's tail -- and yields `masked_positions[:n]` / `feat_targets[:n]` as views
     (UniterForPretraining uses masked_positions in place of its own nonzero).  Batches carry the reference collates' keys
     (`attn_masks`; `txt_labels` | `img_masks`, `img_mask_tgt`, `feat_targets` | `targets`), `labels`, `ids`, `token_type_ids` and
-    the host list `seq_lens`.  len() is the sum of the tasks' batches per epoch."""
+    the host list `seq_lens`.  len() is the sum of the tasks' batches per epoch.
+
+    A dataset with resident soft labels (`label_dim` is not None) also serves 'mrc' and 'mrc-kl': one uniter_collate_mrc_batch
+    launch, the same one read of n_masked, then views [:n] of `masked_positions` and of `label_ids` ('mrc': the classes alone, no
+    label_dim-wide row is written) or `label_targets` ('mrc-kl': the distributions alone)."""
 
     def __init__(self, device_dataset, batch_size, tasks=(('mlm', 1), ('mrfr', 1), ('itm', 1)), seed=0, mask_prob=0.15, replace_prob=0.5,
                  accum_steps=1, samplers=None, cls_token=101, sep_token=102, pad_token=0, mask_token=103, vocab_range=(1000, 28996)):
@@ -756,9 +909,13 @@ class DevicePretrainLoader(object):
         tasks = [(str(n), int(r)) for n, r in tasks]
         if not tasks:
             raise ValueError('DevicePretrainLoader: no task given')
+        served = PRETRAIN_TASKS + (MRC_TASKS if getattr(device_dataset, 'label_dim', None) is not None else ())
         for name, ratio in tasks:
-            if name not in PRETRAIN_TASKS:
-                raise ValueError('DevicePretrainLoader: unknown task %r (one of %s)' % (name, ', '.join(PRETRAIN_TASKS)))
+            if name not in served:
+                raise ValueError('DevicePretrainLoader: unknown task %r (this dataset serves %s%s)'
+                                 % (name, ', '.join(served), '' if len(served) > len(PRETRAIN_TASKS) else
+                                    '; %s need resident soft labels: MemeDataset and DeviceFeaturePool with soft_labels=True'
+                                    % ' and '.join(MRC_TASKS)))
             if ratio < 1:
                 raise ValueError('DevicePretrainLoader: task %s has ratio %d; ratios are positive integers' % (name, ratio))
         if len({n for n, _ in tasks}) != len(tasks):
@@ -786,8 +943,10 @@ class DevicePretrainLoader(object):
 
     @staticmethod
     def task_rng(seed, task):
-        """the generator behind a task's default orders and ITM pairings"""
-        return np.random.default_rng([int(seed), PRETRAIN_TASKS.index(task)])
+        """the generator behind a task's default orders and ITM pairings: [seed, 0 .. 2] for the three tasks of PRETRAIN_TASKS,
+        [seed, 3] and [seed, 4] for 'mrc' and 'mrc-kl' (the task choice is seeded [seed, 3] as well, and stays so: the sequences of
+        the three older tasks must not move; the two generators are separate objects)"""
+        return np.random.default_rng([int(seed), (PRETRAIN_TASKS + MRC_TASKS).index(task)])
 
     def _epoch_len(self, task):
         s = self.samplers.get(task)
@@ -821,6 +980,19 @@ class DevicePretrainLoader(object):
         self._dev_orders[task] = dev = torch.from_numpy(np.stack([order, txt_order])).to(d.pool.device)
         for a, b, R, L_out, seq_lens in plan:
             pool = d.pool
+            if task in MRC_TASKS:
+                hard = task == 'mrc'
+                batch = collate_mrc_batch(dev[0, a:b], pool.feat[:pool.rows], pool.pos[:pool.rows], pool.soft[:pool.rows], d.d_row_start,
+                                          d.d_row_cnt, d.d_input_ids, d.d_token_type_ids, d.d_txt_len, d.d_labels, d.d_ids, R, L_out,
+                                          d.label_dim, hard=hard, soft_out=not hard, ragged_regions=d.ragged_regions, seed=self.seed,
+                                          draw=draw, prob=self.mask_prob)
+                n = batch['n_masked'] = int(batch['n_masked'].item())          # the step's one host synchronisation
+                batch['masked_positions'] = batch['masked_positions'][:n]
+                key = 'label_ids' if hard else 'label_targets'
+                batch[key] = batch[key][:n]
+                batch['seq_lens'] = seq_lens
+                yield batch
+                continue
             batch = collate_pretrain_batch(task, dev[0, a:b], dev[1, a:b] if task == 'itm' else None, pool.feat[:pool.rows],
                                            pool.pos[:pool.rows], d.d_row_start, d.d_row_cnt, d.d_input_ids, d.d_token_type_ids,
                                            d.d_txt_len, d.d_labels, d.d_ids, R, L_out, ragged_regions=d.ragged_regions, seed=self.seed,

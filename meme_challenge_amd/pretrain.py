@@ -432,7 +432,7 @@ class UniterForPretraining(UniterPreTrainedModel):
             return self.forward_itm(*common, batch['targets'], batch['ot_inputs'], compute_loss)
         elif task.startswith('mrc'):
             return self.forward_mrc(*common, batch['img_masks'], batch['img_mask_tgt'], batch['label_targets'], task,
-                                    compute_loss, masked_positions=batch['masked_positions'])
+                                    compute_loss, masked_positions=batch['masked_positions'], label_ids=batch['label_ids'])
         raise ValueError('invalid task')
 
     @staticmethod
@@ -493,10 +493,14 @@ class UniterForPretraining(UniterPreTrainedModel):
         return _MseFn.apply(pred, feat_targets)
 
     def forward_mrc(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
-                    img_masks, img_mask_tgt, label_targets, task, compute_loss=True, masked_positions=None):
+                    img_masks, img_mask_tgt, label_targets, task, compute_loss=True, masked_positions=None, label_ids=None):
         """model/pretrain.py:205-233: region classification on the masked regions; 'mrc' trains against the most
-        likely non-background detector class, 'mrc-kl' against the detector's soft labels."""
+        likely non-background detector class, 'mrc-kl' against the detector's soft labels.  `label_ids` (int64 [n], task
+        'mrc'): those classes already found by whoever built the batch (uniter_collate_mrc_batch) -- no argmax launch here,
+        and label_targets may be None."""
         self._sync_head_precision()
+        if label_ids is not None and (label_ids.dim() != 1 or label_ids.dtype != torch.int64):
+            raise ValueError('label_ids must be int64 [n]; got %s %s' % (label_ids.dtype, tuple(label_ids.shape)))
         nz = self._given_positions(masked_positions) if masked_positions is not None else self._mask_positions(img_mask_tgt)
         seq = self.uniter(input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
                           output_all_encoded_layers=False, img_masks=img_masks, seq_lens=getattr(self, '_seq_lens', None))
@@ -507,7 +511,7 @@ class UniterForPretraining(UniterPreTrainedModel):
         if 'kl' in task:
             return _KlDivFn.apply(scores, label_targets)
         # ignore_index=0 (:231) never fires: the targets are 1 + an argmax over the non-background classes
-        return _CrossEntropyFn.apply(scores, _hard_region_labels(label_targets))
+        return _CrossEntropyFn.apply(scores, label_ids if label_ids is not None else _hard_region_labels(label_targets))
 
     def forward_itm(self, input_ids, position_ids, img_feat, img_pos_feat, attention_mask, gather_index,
                     targets, ot_inputs=None, compute_loss=True):

@@ -1,0 +1,246 @@
+"""uniter_collate_mrc_batch (csrc/collate.hip), the C entry point itself, against the numpy restatement tests/mrc_collate_ref.py,
+bit for bit (the kernel copies values, does integer arithmetic, compares floats and draws from the Philox stream the header
+specifies).  Every output lies inside a larger buffer, pre-filled with a sentinel byte between two guard bands: afterwards no
+sentinel is left in a dense extent or in the first n_masked rows of a compacted one, the rows at and beyond n_masked still hold
+the sentinel, and every guard byte is unchanged.  The cases are those of tests/mrc_cases.py (tests/test_mrc_collate_cpu.py checks
+what they contain)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from meme_challenge_amd import _lib
+from meme_challenge_amd.data import collate_mrc_batch
+from mrc_cases import ARRAY_KEYS, BATCHES, CFG, CRAFTED, D, MAIN, T, crafted_rows, leading_dimensions, shape_of, synth
+from mrc_collate_ref import mrc_collate_ref
+
+pytestmark = pytest.mark.gpu
+
+GUARD, GUARD_BYTE, SENTINEL_BYTE = 256, 0x5A, 0xCD      # GUARD % 16 == 0: img_feat stays 16-byte aligned
+COMMON = ('img_feat', 'img_pos_feat', 'input_ids', 'position_ids', 'token_type_ids', 'attn_masks', 'gather_index', 'labels', 'ids')
+DENSE = COMMON + ('img_masks', 'img_mask_tgt')
+COMPACT = ('label_targets', 'label_ids', 'masked_positions')
+ALL_OUT = DENSE + COMPACT + ('n_masked',)               # the C function's order
+E_ARG, E_SHAPE = -1, -2
+
+
+def to_device(a):
+    return {k: (None if v is None else torch.from_numpy(v).cuda()) for k, v in a.items()}
+
+
+class Guarded(object):
+    """an output tensor inside a larger byte buffer: [guard | extent, filled with `fill` | guard]"""
+
+    def __init__(self, shape, dtype, fill=SENTINEL_BYTE):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        self.nbytes, self.fill = n, fill
+        self.buf = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device='cuda')
+        self.buf[GUARD:GUARD + n] = fill
+        self.t = self.buf[GUARD:GUARD + n].view(dtype).view(shape)
+
+    def check_guards(self, what):
+        b = self.buf.cpu()
+        assert bool((b[:GUARD] == GUARD_BYTE).all()) and bool((b[GUARD + self.nbytes:] == GUARD_BYTE).all()), '%s: a guard byte changed' % what
+
+    def untouched(self, first_byte=0):
+        return bool((self.buf[GUARD + first_byte:GUARD + self.nbytes] == self.fill).all())
+
+
+def guarded_outputs(B, R, Cn, L_out, fill=SENTINEL_BYTE):
+    i64, f32 = torch.int64, torch.float32
+    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
+              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
+              'ids': ((B,), i64), 'img_masks': ((B, R), i64), 'img_mask_tgt': ((B, L_out), torch.bool),
+              'label_targets': ((B * R, Cn), f32), 'label_ids': ((B * R,), i64), 'masked_positions': ((B * R, 2), i64),
+              'n_masked': ((1,), torch.int32)}
+    return {k: Guarded(s, dt, fill) for k, (s, dt) in shapes.items()}
+
+
+def sentinel_of(dtype):
+    return torch.full((1,), SENTINEL_BYTE, dtype=torch.uint8).repeat(8).view(dtype)[0]
+
+
+def raw_call(d, sel, outs, B, R, L_out, Cn, ld_soft, flags=0, drop=(), ds_null=False, sel_null=False, cfg_null=False, soft_null=False,
+             D_=None, T_=None, feat_ptr=None, prob=0.15, seed=CFG['seed'], draw=CFG['draw']):
+    """the C call itself; drop: 'ds.<field>' / 'out.<name>' pointers passed as NULL"""
+    p = lambda t: None if t is None else t.data_ptr()
+    f = {k: (None if 'ds.' + k in drop else p(d[k])) for k in ARRAY_KEYS}
+    if feat_ptr is not None:
+        f['feat'] = feat_ptr
+    ds = _lib.UniterDatasetC(f['feat'], f['pos'], f['row_start'], f['row_cnt'], f['input_ids'], f['token_type_ids'], f['txt_len'],
+                             f['labels'], f['ids'], d['row_start'].shape[0], d['feat'].shape[0], D if D_ is None else D_,
+                             T if T_ is None else T_)
+    mc = _lib.UniterMaskCfgC(seed, draw, prob, 0, 0, 0, 0, 0, 0)
+    o = [None if 'out.' + k in drop else C.c_void_p(outs[k].t.data_ptr()) for k in ALL_OUT]
+    return _lib.lib().uniter_collate_mrc_batch(None if ds_null else C.byref(ds), None if soft_null else C.c_void_p(f['soft']), Cn, ld_soft,
+                                               None if sel_null else C.c_void_p(sel.data_ptr()), None if cfg_null else C.byref(mc),
+                                               B, R, L_out, flags, *o, _lib.cur_stream())
+
+
+def run_and_check(a, d, sel, Cn, ld_soft, ragged, prob, what, drop=(), fill=SENTINEL_BYTE):
+    R, L_out = shape_of(a, sel, ragged)
+    cfg = dict(CFG, prob=prob)
+    want = mrc_collate_ref(sel, *[a[k] for k in ('feat', 'pos', 'soft')], Cn, *[a[k] for k in ARRAY_KEYS[3:]], R=R, L_out=L_out,
+                           ragged=ragged, cfg=cfg)
+    g = guarded_outputs(len(sel), R, Cn, L_out, fill)
+    dsel = torch.tensor(sel, dtype=torch.int64, device='cuda')
+    rc = raw_call(d, dsel, g, len(sel), R, L_out, Cn, ld_soft, flags=1 if ragged else 0, drop=drop, prob=prob)
+    assert rc == 0, '%s: rc %d: %s' % (what, rc, _lib.lib().uniter_last_error())
+    torch.cuda.synchronize()
+    for k, v in g.items():
+        v.check_guards(k + ': ' + what)
+    for k in DENSE:
+        t = g[k].t.cpu()
+        if t.dtype == torch.bool:
+            assert bool((t.view(torch.uint8) <= 1).all()), '%s: %s holds bytes other than 0 / 1' % (k, what)
+        elif fill == SENTINEL_BYTE:
+            assert not bool((t == sentinel_of(t.dtype)).any()), '%s: a sentinel is left inside the extent: %s' % (k, what)
+        assert torch.equal(t, torch.from_numpy(want[k])), '%s: %s' % (k, what)
+    n = int(g['n_masked'].t.item())
+    assert n == want['n_masked'], what
+    for k in COMPACT:
+        if 'out.' + k in drop:
+            assert g[k].untouched(), '%s was passed as NULL and written: %s' % (k, what)
+            continue
+        t = g[k].t[:n].cpu()
+        # (bytes, not values: a NaN of the pad columns would compare unequal to itself and hide nothing, but say so anyway)
+        assert torch.equal(t.contiguous().view(torch.uint8), torch.from_numpy(want[k]).contiguous().view(torch.uint8)), '%s: %s' % (k, what)
+        row_bytes = g[k].nbytes // max(g[k].t.shape[0], 1)
+        assert g[k].untouched(first_byte=n * row_bytes), '%s: a row at or beyond n_masked was written: %s' % (k, what)
+    mp = g['masked_positions'].t[:n].cpu()
+    key = mp[:, 0] * (T + R + 1) + mp[:, 1]
+    assert bool((key[1:] > key[:-1]).all()), 'masked_positions is not strictly increasing: ' + what
+    return want, g, n
+
+
+@pytest.mark.parametrize('ld_kind', ['C', 'aligned', 'odd'])
+@pytest.mark.parametrize('Cn', [5, 12, 1601])
+def test_mrc_batches_equal_the_restatement(Cn, ld_kind):
+    """C = 5 and 12: less than a wave's lanes, one and three 16-byte items; 1601 is the detector's (401 items: seven per lane, the last
+    one cut; 1601 floats: two stretches of the float-by-float walk).  ld_soft == C reads float by float unless C % 4 == 0; the
+    'aligned' one reads 16-byte items; the 'odd' one float by float with rows that start at every alignment.  Batches: B = 5 with
+    R = 11 and ragged counts 3 .. 11 in both region modes, B = 1, R = 0, a sample without regions among others, samples sharing pool
+    rows, and rows outside the pool (zero rows); each with prob 0 (every sample takes its forced region), 0.15 and 1."""
+    ld_soft = leading_dimensions(Cn)[ld_kind]
+    a = synth(Cn, ld_soft, seed=Cn)
+    d = to_device(a)
+    selected = 0
+    for name, sel in BATCHES.items():
+        for ragged in ((True, False) if name == 'main' else (True,)):
+            for prob in (0.0, 0.15, 1.0):
+                what = '%s: sel %s C %d ld_soft %d ragged %s prob %g' % (name, sel, Cn, ld_soft, ragged, prob)
+                want, g, n = run_and_check(a, d, sel, Cn, ld_soft, ragged, prob, what)
+                if prob == 0.0:
+                    assert n == sum(1 for s in sel if a['row_cnt'][s] > 0), what
+                if name == 'no regions at all':
+                    assert n == 0 and shape_of(a, sel, ragged)[0] == 0, what
+                if name == 'outside the pool' and prob == 1.0:
+                    assert (want['label_targets'] == 0).all(axis=1).sum() == 2 * 4, what
+                selected += n if prob == 0.15 else 0
+    assert selected > 0
+
+
+@pytest.mark.parametrize('ld_kind', ['C', 'aligned'])
+@pytest.mark.parametrize('Cn', [5, 1601])
+def test_label_ids_at_the_edges_and_against_row_argmax(Cn, ld_kind):
+    """prob = 1 selects every region, the five crafted rows of sample CRAFTED among them: a tie between two maxima, an all-equal row,
+    the maximum in column 0, the maximum in column C-1, a tie inside one lane.  label_ids equals numpy's and equals
+    uniter_row_argmax run on the kernel's own label_targets; with either output NULL the other one is the same bytes."""
+    ld_soft = leading_dimensions(Cn)[ld_kind]
+    a = synth(Cn, ld_soft, seed=Cn)
+    d = to_device(a)
+    what = 'C %d ld_soft %d' % (Cn, ld_soft)
+    want, g, n = run_and_check(a, d, MAIN, Cn, ld_soft, True, 1.0, what)
+    assert n == int(a['row_cnt'][MAIN].sum())
+    first = int(a['row_cnt'][MAIN[:MAIN.index(CRAFTED)]].sum())
+    ids = g['label_ids'].t[:n].cpu()
+    assert ids[first:first + 5].tolist() == crafted_rows(Cn)[1], what
+    assert torch.equal(ids, 1 + torch.from_numpy(want['label_targets'][:, 1:]).argmax(dim=1)), what
+    lt = g['label_targets'].t[:n].contiguous()
+    again = torch.empty(n, dtype=torch.int64, device='cuda')
+    _lib.check(_lib.lib().uniter_row_argmax(C.c_void_p(lt.data_ptr()), n, Cn, Cn, 1, C.c_void_p(again.data_ptr()), _lib.cur_stream()),
+               'uniter_row_argmax')
+    assert torch.equal(again.cpu(), ids), what
+    for prob in (0.15, 1.0):
+        _, full, n = run_and_check(a, d, MAIN, Cn, ld_soft, True, prob, what)
+        for gone, kept in (('label_targets', 'label_ids'), ('label_ids', 'label_targets')):
+            _, part, m = run_and_check(a, d, MAIN, Cn, ld_soft, True, prob, what + ' without ' + gone, drop=('out.' + gone,))
+            assert m == n and torch.equal(part[kept].buf, full[kept].buf), what
+
+
+def test_the_result_does_not_depend_on_what_the_outputs_held():
+    """the fills of tests/poison.py as the outputs' earlier contents, through the C call and through data.collate_mrc_batch's own
+    allocations: the same bytes in every defined element"""
+    from poison import Poison
+    Cn = 1601
+    ld_soft = leading_dimensions(Cn)['aligned']
+    a = synth(Cn, ld_soft, seed=Cn)
+    d = to_device(a)
+    R, L_out = shape_of(a, MAIN, True)
+    for fill in (0x00, 0xFF):
+        run_and_check(a, d, MAIN, Cn, ld_soft, True, 0.15, 'outputs pre-filled with %#x' % fill, fill=fill)
+    dsel = torch.tensor(MAIN, dtype=torch.int64, device='cuda')
+    results = []
+    for fill in ('zeros', 'ones', 'unit'):
+        with Poison(fill) as p:
+            out = collate_mrc_batch(dsel, *[d[k] for k in ARRAY_KEYS], R=R, L_out=L_out, label_dim=Cn, ragged_regions=True,
+                                    prob=0.15, **CFG)
+            torch.cuda.synchronize()
+            n = int(out['n_masked'].item())
+            results.append({k: (v[:n] if k in COMPACT else v).clone() for k, v in out.items()})
+        assert sum(p.sites.values()) == len(ALL_OUT) and all(s.startswith('data.py:') for s in p.sites), p.report()
+    want = mrc_collate_ref(MAIN, *[a[k] for k in ('feat', 'pos', 'soft')], Cn, *[a[k] for k in ARRAY_KEYS[3:]], R=R, L_out=L_out, ragged=True,
+                           cfg=dict(CFG, prob=0.15))
+    for r in results:
+        for k, v in r.items():
+            w = torch.from_numpy(np.asarray(want[k])).reshape(v.shape)
+            assert torch.equal(v.cpu().to(w.dtype), w), k
+
+
+def test_refusals_return_their_codes_and_write_nothing():
+    Cn, ld_soft, B = 12, 12, 3
+    a = synth(Cn, ld_soft)
+    d = to_device(a)
+    sel = torch.tensor([0, 1, 2], device='cuda')
+    R, L_out = shape_of(a, [0, 1, 2], False)
+    outs = guarded_outputs(B, R, Cn, L_out)
+    cases = [('a NULL dataset', E_ARG, dict(ds_null=True)), ('a NULL selection', E_ARG, dict(sel_null=True))]
+    cases += [('dataset pointer %s NULL' % k, E_ARG, dict(drop=('ds.' + k,))) for k in ARRAY_KEYS if k not in ('token_type_ids', 'soft')]
+    cases += [('output %s NULL' % k, E_ARG, dict(drop=('out.' + k,))) for k in COMMON if k != 'token_type_ids']
+    cases += [('D % 4 != 0', E_SHAPE, dict(D_=6)), ('a misaligned feat', E_ARG, dict(feat_ptr=d['feat'].data_ptr() + 4)),
+              ('B = 0', E_SHAPE, dict(B=0)), ('B < 0', E_SHAPE, dict(B=-1)), ('T = 0', E_SHAPE, dict(T_=0)),
+              ('L_out = 0', E_SHAPE, dict(L_out=0)), ('L_out > T + R', E_SHAPE, dict(L_out=T + R + 1)), ('R < 0', E_SHAPE, dict(R=-1)),
+              ('a NULL configuration', E_ARG, dict(cfg_null=True)), ('prob < 0', E_ARG, dict(prob=-0.01)), ('prob > 1', E_ARG, dict(prob=1.5)),
+              ('prob NaN', E_ARG, dict(prob=float('nan'))), ('NULL soft labels', E_ARG, dict(soft_null=True)),
+              ('C = 1', E_SHAPE, dict(Cn=1)), ('C = 0', E_SHAPE, dict(Cn=0)), ('ld_soft < C', E_SHAPE, dict(ld_soft=Cn - 1)),
+              ('both label outputs NULL', E_ARG, dict(drop=('out.label_targets', 'out.label_ids'))),
+              ('masked_positions NULL', E_ARG, dict(drop=('out.masked_positions',))), ('n_masked NULL', E_ARG, dict(drop=('out.n_masked',))),
+              ('img_masks NULL', E_ARG, dict(drop=('out.img_masks',))), ('img_mask_tgt NULL', E_ARG, dict(drop=('out.img_mask_tgt',)))]
+    lib = _lib.lib()
+    for what, code, kw in cases:
+        rc = raw_call(d, sel, outs, **dict(dict(B=B, R=R, L_out=L_out, Cn=Cn, ld_soft=ld_soft), **kw))
+        assert rc == code, '%s: rc %d' % (what, rc)
+        assert b'collate_mrc_batch' in lib.uniter_last_error(), what
+    torch.cuda.synchronize()
+    for k, g in outs.items():
+        assert g.untouched(), '%s was written by a refused call' % k
+        g.check_guards(k)
+    # the old entry point keeps refusing the task id the new tasks might have taken
+    arrays = [d[k] for k in ARRAY_KEYS]
+    with pytest.raises(_lib.UniterHipError, match='must live on the GPU'):
+        collate_mrc_batch(sel.cpu(), *arrays, R=R, L_out=L_out, label_dim=Cn)
+    with pytest.raises(_lib.UniterHipError, match='soft'):
+        collate_mrc_batch(sel, *arrays, R=R, L_out=L_out, label_dim=Cn + 1)
+    with pytest.raises(ValueError, match='neither'):
+        collate_mrc_batch(sel, *arrays, R=R, L_out=L_out, label_dim=Cn, hard=False, soft_out=False)
+    with pytest.raises(_lib.UniterHipError, match='outside'):
+        collate_mrc_batch(sel, *arrays, R=R, L_out=L_out, label_dim=Cn, prob=1.25)
+    torch.cuda.synchronize()
+    assert all(g.untouched() for g in outs.values())
+    # and the valid call on the same buffers goes through
+    assert raw_call(d, sel, outs, B, R, L_out, Cn, ld_soft) == 0
+    torch.cuda.synchronize()
+    assert not any(outs[k].untouched() for k in ALL_OUT)
+    for k, g in outs.items():
+        g.check_guards(k)
