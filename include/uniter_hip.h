@@ -709,6 +709,37 @@ int uniter_bce_logits(const float* logits, const int64_t* labels, float pos_weig
  * dlogits [B] may each be NULL and are then not touched.  Refused: a NULL input, B <= 0, a NaN kl_weight. */
 int uniter_bce_kl_logits(const float* logits, const float* clean_logits, const int64_t* labels, float pos_weight,
                          float kl_weight, float* terms, float* probs, float* dlogits, float grad_scale, int B, void* stream);
+/* BCE plus a pairwise AUROC surrogate over (current batch) x (current batch U a bank of recent scores), the gradient with respect
+ * to the current logits, and the push of the batch's scores into the bank (a ring buffer in device memory): one launch, no host
+ * read (csrc/head.hip).
+ * Sets.   Batch positives S+ are the rows with labels[b] == 1, batch negatives S- those with labels[b] == 0; a row with any other
+ *         label takes part in BCE only.  The bank's valid slots are the `fill` most recently pushed ones, read BEFORE this call's
+ *         push; K+ are the valid slots whose stored label is 1, K- those whose stored label is 0.  The score s of a batch row is
+ *         its logit, that of a bank slot the stored value.
+ * Pairs.  P = S+ x S-  U  S+ x K-  U  K+ x S-,  n = |P|.  Bank-bank pairs carry no gradient and are not in P.
+ * Surrogate.  kind 0, logistic: l(d) = softplus(-d), evaluated as max(-d, 0) + log1p(exp(-|d|)); l'(d) = -sigmoid(-d).
+ *         kind 1, squared hinge: l(d) = max(0, margin - d)^2; l'(d) = -2 max(0, margin - d); exactly 0 at d = margin.
+ * Values. auc = (1 / n) sum over (i, j) in P of l(s_i - s_j); with n = 0, auc = 0 and the term contributes no gradient.
+ *         terms = {bce + auc_weight * auc, bce, auc},  *n_pairs = n,  probs = sigmoid(logits),
+ *         dlogits[b] = grad_scale * (bce'_b / B + auc_weight * g_b), bce'_b = uniter_bce_logits' per-element term, z_b = logits[b],
+ *           g_b = (1 / n) sum over j in S- U K- of l'(z_b - s_j)        for b in S+
+ *           g_b = -(1 / n) sum over i in S+ U K+ of l'(s_i - z_b)       for b in S-
+ *           g_b = 0                                                      for any other row.
+ *         Bank scores are constants: no gradient flows into them.
+ * Push (push != 0), after every read of the bank in this launch has completed: slot (head + r) mod N receives
+ *         (logits[r], (int32)labels[r]) for r = 0 .. B - 1; then head = (head + B) mod N and fill = min(fill + B, N).
+ *         bank_state = {head, fill}.  With push == 0 the three bank arrays come back bit-identical.
+ * No bank: bank_scores == NULL or N == 0.  Then K+ = K- = {}, nothing is pushed, and bank_labels and bank_state may be NULL.
+ * terms [3], n_pairs, probs [B] and dlogits [B] may each be NULL and are then not touched.
+ * With auc_weight == 0, terms[0], terms[1], probs and dlogits are uniter_bce_logits' bits; a push still happens if asked.
+ * One workgroup, a fixed summation order: two launches on the same inputs give the same bits.
+ * Refused (UNITER_E_ARG, nothing launched): NULL logits or labels; B <= 0 or B > 4096; a bank with N < B or N > 8192; a bank with
+ * NULL bank_labels or bank_state; auc_weight negative or NaN; kind outside {0, 1}; a NaN margin.  A head or fill on the device
+ * that lies outside [0, N) / [0, N] is clamped, for memory safety only (as gather indices are, below). */
+int uniter_bce_auc_logits(const float* logits, const int64_t* labels, float pos_weight, float auc_weight, int kind, float margin,
+                          float* bank_scores /*[N]*/, int32_t* bank_labels /*[N]*/, int32_t* bank_state /*{head, fill}*/, int N,
+                          int push, float* terms /*[3]*/, int32_t* n_pairs, float* probs, float* dlogits, float grad_scale, int B,
+                          void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Pretraining heads (BASELINE config 5: UniterForPretraining.forward_{mlm,mrfr,itm},

@@ -178,6 +178,9 @@ _SIGS = {
     'uniter_bce_kl_logits': (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I, _P]),
     'uniter_adv_delta_step_linf': (_I, [_P, _P, _I, _I, _F, _F, _P, _P]),
     'uniter_adv_delta_linf_ws_bytes': (_SZ, [_I, _I]),
+    # BCE + the pairwise AUROC surrogate against a bank of recent scores, and the bank's push (csrc/head.hip):
+    # (logits, labels, pos_weight, auc_weight, kind, margin, bank_scores, bank_labels, bank_state, N, push, terms, n_pairs, probs, dlogits, grad_scale, B, stream)
+    'uniter_bce_auc_logits': (_I, [_P, _P, _F, _F, _I, _F, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P]),
     # the attention probabilities as an output, and rollout on them (csrc/attn_probs.hip)
     'uniter_attn_probs': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_attn_rollout': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),

@@ -185,6 +185,16 @@ __global__ __launch_bounds__(256) void linear_small_bwd_kernel(const float* __re
   }
 }
 
+// One element of the BCE sum, the arithmetic every logits loss below shares (the library is built without contraction, so one
+// expression is one sequence of roundings wherever it is inlined): its term of the sum, sigmoid(x), and d term / dx
+struct BceElem { float term, sg, dterm; };
+__device__ __forceinline__ BceElem bce_elem(float x, float y, float pw) {
+  const float lw = 1.0f + (pw - 1.0f) * y;
+  const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);     // softplus(-x)
+  const float sg = 1.0f / (1.0f + expf(-x));
+  return {(1.0f - y) * x + lw * sp, sg, (1.0f - y) - lw * (1.0f - sg)};
+}
+
 // The logits loss, single workgroup: loss = mean_b [ (1-y) x + (1 + (pw-1) y) softplus(-x) ], and with KL the symmetric divergence to
 // the clean prediction on top (a perturbed pass of VILLA).  One body for both kernels; without KL none of the KL arithmetic exists,
 // and the BCE statements are the same ones in the same order either way, so with klw = 0 the total, the probabilities and the
@@ -203,11 +213,9 @@ __device__ __forceinline__ void bce_logits_body(const float* __restrict__ logits
     const float x = logits[b];
     float c = 0.f;
     if constexpr (KL) c = clean[b];
-    const float y = (float)labels[b];
-    const float lw = 1.0f + (pw - 1.0f) * y;
-    const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);     // softplus(-x)
-    acc += (1.0f - y) * x + lw * sp;
-    const float sg = 1.0f / (1.0f + expf(-x));
+    const BceElem el = bce_elem(x, (float)labels[b], pw);
+    acc += el.term;
+    const float sg = el.sg;
     if constexpr (KL) {
       const float sc = 1.0f / (1.0f + expf(-c));
       kacc += (sc - sg) * (c - x);
@@ -216,11 +224,11 @@ __device__ __forceinline__ void bce_logits_body(const float* __restrict__ logits
         const float e = expf(-fabsf(x));
         const float qq = e / ((1.0f + e) * (1.0f + e));               // q (1 - q)
         const float kg = (sg - sc) + qq * (x - c);
-        dlogits[b] = (((1.0f - y) - lw * (1.0f - sg)) + klw * kg) * (gscale / (float)B);
+        dlogits[b] = (el.dterm + klw * kg) * (gscale / (float)B);
       }
     } else {
       if (probs) probs[b] = sg;
-      if (dlogits) dlogits[b] = ((1.0f - y) - lw * (1.0f - sg)) * (gscale / (float)B);
+      if (dlogits) dlogits[b] = el.dterm * (gscale / (float)B);
     }
   }
   acc = wave_sum(acc);
@@ -256,6 +264,154 @@ __global__ __launch_bounds__(256) void bce_kl_logits_kernel(const float* __restr
                                                             float* __restrict__ terms, float* __restrict__ probs,
                                                             float* __restrict__ dlogits, float gscale, int B) {
   bce_logits_body<true>(logits, clean, labels, pw, klw, terms, probs, dlogits, gscale, B);
+}
+
+// ---- BCE + a pairwise AUROC surrogate over (batch) x (batch U bank of recent scores), and the bank's push: one launch ----------
+// (contract: include/uniter_hip.h, uniter_bce_auc_logits).  One workgroup, in three stretches:
+//   1. thread per element: the BCE element (bce_elem: uniter_bce_logits' statements in its order, so its bits), and the scores
+//      and classes (1 positive, 0 negative, 2 takes no part) of the batch rows and of every bank slot into LDS -- a slot outside
+//      the `fill` most recent ones is class 2 whatever it holds;
+//   2. behind the barrier every read of the bank is done: the push (slots are distinct, N >= B) and the two state words;
+//   3. wave per batch row (rows strided over the 4 waves), the row's opposite class strided over the 64 lanes.  A positive row
+//      sums loss and slope over every negative (batch and bank); a negative row the slope over every positive and the loss over
+//      the BANK's positives only -- its pairs with batch positives were counted from their side.  wave_sum's butterfly, the
+//      serial sum over a wave's rows and the four waves' partial sums in index order: a fixed order.
+// The surrogate's value and slope at d = s_positive - s_negative:
+template <int KIND>
+__device__ __forceinline__ void auc_pair(float d, float margin, float& l, float& dl) {
+  if constexpr (KIND == 0) {            // softplus(-d), -sigmoid(-d): e <= 1 in both branches, nothing cancels
+    const float e = expf(-fabsf(d));
+    l = fmaxf(-d, 0.f) + log1pf(e);
+    dl = -((d >= 0.f ? e : 1.0f) / (1.0f + e));
+  } else {                              // max(0, margin - d)^2, exactly 0 (and flat) from d = margin on
+    const float h = fmaxf(margin - d, 0.f);
+    l = h * h;
+    dl = -2.0f * h;
+  }
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+constexpr int AUC_MAX_B = 4096, AUC_MAX_N = 8192;       // (B + N) * 5 bytes of LDS: 60 KB at the limits
+
+template <int KIND>
+__global__ __launch_bounds__(256) void bce_auc_logits_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                             float pw, float aw, float margin, float* bank_scores,
+                                                             int32_t* bank_labels, int32_t* bank_state, int N, int push,
+                                                             float* __restrict__ terms, int32_t* __restrict__ n_pairs,
+                                                             float* __restrict__ probs, float* __restrict__ dlogits, float gscale,
+                                                             int B) {
+  extern __shared__ float auc_lds[];
+  __shared__ float red[4][2];
+  __shared__ int cnt[4][4];
+  const int M = B + N;
+  float* sc = auc_lds;                                                   // [M] scores: the batch rows, then the bank's slots
+  unsigned char* cls = reinterpret_cast<unsigned char*>(auc_lds + M);    // [M] classes
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool grad_pairs = dlogits != nullptr && aw != 0.f;               // else stretch 1 writes dlogits, as uniter_bce_logits does
+  int head = 0, fill = 0;
+  if (N > 0) {                                                           // (clamped for memory safety only)
+    head = min(max(bank_state[0], 0), N - 1);
+    fill = min(max(bank_state[1], 0), N);
+  }
+  float acc = 0.f;
+  int nsp = 0, nsn = 0, nkp = 0, nkn = 0;
+  for (int b = tid; b < B; b += 256) {
+    const float x = logits[b];
+    const int64_t lab = labels[b];
+    const BceElem el = bce_elem(x, (float)lab, pw);
+    acc += el.term;
+    if (probs) probs[b] = el.sg;
+    if (dlogits && !grad_pairs) dlogits[b] = el.dterm * (gscale / (float)B);
+    const int c = lab == 1 ? 1 : (lab == 0 ? 0 : 2);
+    sc[b] = x;
+    cls[b] = (unsigned char)c;
+    nsp += c == 1;
+    nsn += c == 0;
+  }
+  for (int s = tid; s < N; s += 256) {
+    int age = head - 1 - s;                                              // 0: the slot pushed last
+    if (age < 0) age += N;
+    const int32_t bl = bank_labels[s];
+    const int c = age < fill ? (bl == 1 ? 1 : (bl == 0 ? 0 : 2)) : 2;
+    sc[B + s] = bank_scores[s];
+    cls[B + s] = (unsigned char)c;
+    nkp += c == 1;
+    nkn += c == 0;
+  }
+  acc = wave_sum(acc);
+  nsp = wave_sum_int(nsp), nsn = wave_sum_int(nsn), nkp = wave_sum_int(nkp), nkn = wave_sum_int(nkn);
+  if (lane == 0) {
+    red[wv][0] = acc;
+    cnt[wv][0] = nsp, cnt[wv][1] = nsn, cnt[wv][2] = nkp, cnt[wv][3] = nkn;
+  }
+  __syncthreads();
+  if (push && N > 0) {
+    for (int r = tid; r < B; r += 256) {
+      int s = head + r;
+      if (s >= N) s -= N;
+      bank_scores[s] = sc[r];
+      bank_labels[s] = (int32_t)labels[r];
+    }
+    if (tid == 0) {
+      int h = head + B;
+      if (h >= N) h -= N;
+      bank_state[0] = h;
+      bank_state[1] = min(fill + B, N);
+    }
+  }
+  nsp = cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0];
+  nsn = cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
+  nkp = cnt[0][2] + cnt[1][2] + cnt[2][2] + cnt[3][2];
+  nkn = cnt[0][3] + cnt[1][3] + cnt[2][3] + cnt[3][3];
+  const int n = nsp * (nsn + nkn) + nkp * nsn;                           // below AUC_MAX_B * (AUC_MAX_B + AUC_MAX_N) = 5.0e7
+  const float inv_n = n > 0 ? 1.0f / (float)n : 0.f;
+  float wl = 0.f;
+  if (terms != nullptr || grad_pairs) {
+    for (int b = wv; b < B; b += 4) {                                    // (b, c, z are wave-uniform: wave_sum sees every lane)
+      const int c = cls[b];
+      const float z = sc[b];
+      float la = 0.f, ga = 0.f, l, dl;
+      if (n > 0 && c == 1) {
+        for (int j = lane; j < M; j += 64)
+          if (cls[j] == 0) {
+            auc_pair<KIND>(z - sc[j], margin, l, dl);
+            la += l;
+            ga += dl;
+          }
+      } else if (n > 0 && c == 0) {
+        for (int j = lane; j < M; j += 64)
+          if (cls[j] == 1) {
+            auc_pair<KIND>(sc[j] - z, margin, l, dl);
+            ga -= dl;
+            if (j >= B) la += l;
+          }
+      }
+      la = wave_sum(la);
+      ga = wave_sum(ga);
+      wl += la;
+      if (grad_pairs && lane == 0) {
+        const BceElem el = bce_elem(z, (float)labels[b], pw);
+        dlogits[b] = el.dterm * (gscale / (float)B) + (gscale * aw) * (ga * inv_n);
+      }
+    }
+  }
+  if (lane == 0) red[wv][1] = wl;
+  __syncthreads();
+  if (tid == 0) {
+    if (terms) {
+      const float bce = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (float)B;
+      const float auc = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) * inv_n;
+      terms[0] = aw != 0.f ? bce + aw * auc : bce;
+      terms[1] = bce;
+      terms[2] = auc;
+    }
+    if (n_pairs) *n_pairs = n;
+  }
 }
 
 
@@ -555,6 +711,29 @@ extern "C" int uniter_bce_kl_logits(const float* logits, const float* clean_logi
   UCHECK_ARG(kl_weight == kl_weight, "bce_kl_logits: kl_weight is NaN");
   hipLaunchKernelGGL(bce_kl_logits_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, clean_logits, labels, pos_weight,
                      kl_weight, terms, probs, dlogits, grad_scale, B);
+  UCHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int uniter_bce_auc_logits(const float* logits, const int64_t* labels, float pos_weight, float auc_weight, int kind,
+                                     float margin, float* bank_scores, int32_t* bank_labels, int32_t* bank_state, int N, int push,
+                                     float* terms, int32_t* n_pairs, float* probs, float* dlogits, float grad_scale, int B,
+                                     void* stream) {
+  UCHECK_ARG(logits && labels, "bce_auc_logits: null logits or labels");
+  UCHECK_ARG(B > 0 && B <= AUC_MAX_B, "bce_auc_logits: B must lie in [1, %d] (got %d)", AUC_MAX_B, B);
+  const bool bank = bank_scores != nullptr && N != 0;
+  if (bank) {
+    UCHECK_ARG(N >= B && N <= AUC_MAX_N, "bce_auc_logits: the bank's capacity must lie in [B, %d] (got N = %d, B = %d)", AUC_MAX_N, N, B);
+    UCHECK_ARG(bank_labels && bank_state, "bce_auc_logits: a bank needs bank_labels and bank_state");
+  }
+  UCHECK_ARG(auc_weight >= 0.f, "bce_auc_logits: auc_weight is negative or NaN");
+  UCHECK_ARG(kind == 0 || kind == 1, "bce_auc_logits: kind must be 0 (logistic) or 1 (squared hinge), got %d", kind);
+  UCHECK_ARG(margin == margin, "bce_auc_logits: margin is NaN");
+  const int Nk = bank ? N : 0;
+  const size_t lds = (size_t)(B + Nk) * 5;
+  auto kernel = kind == 0 ? bce_auc_logits_kernel<0> : bce_auc_logits_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(256), align_up(lds, 16), (hipStream_t)stream, logits, labels, pos_weight, auc_weight, margin,
+                     bank_scores, bank_labels, bank_state, Nk, push, terms, n_pairs, probs, dlogits, grad_scale, B);
   UCHECK_LAUNCH();
   return 0;
 }

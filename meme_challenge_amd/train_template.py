@@ -39,7 +39,8 @@ import torch.distributed as dist
 
 from . import dp
 from .metrics import standard_metrics, find_optimal_threshold
-from .trainer import TrainStep, adv_config, bce_with_logits_loss, get_optimizer, get_scheduler, sync_step
+from .trainer import (TrainStep, adv_config, auc_config, bce_auc_with_logits_loss, bce_with_logits_loss, get_optimizer, get_scheduler,
+                      new_score_bank, sync_step)
 from .utils import set_seed
 
 LOGGER = logging.getLogger('TrainerLogger')
@@ -208,8 +209,12 @@ class TrainerTemplate(object):
             raise ValueError('invalid loss_func %r' % loss_func)
         adv_config(self.config)          # --adv_*: an unknown adv_modality fails here, before anything is built
         self._adv_step = None
+        self.auc = auc_config(self.config)     # --auc_*: likewise
         self.init_model()
         self.model.to(self.device)
+        # auc_weight > 0 with auc_bank > 0: the bank of recent training scores the loss launch reads and pushes into, on this
+        # rank's device (data parallel: every rank its own, no exchange), kept across epochs and never written to a checkpoint
+        self.auc_bank = new_score_bank(self.auc, self.device)
         self.model_saver = ModelSaver(self.model_file)
         if self.config.get('parallel_computing') and _distributed() and dist.get_world_size() > 1:
             dp.broadcast_parameters(self.model)
@@ -255,7 +260,13 @@ class TrainerTemplate(object):
         """Step semantics of train_template.py:95-126.  The modulo test is on the per-epoch iteration
         index, so iteration 0 of every epoch steps with a single micro-batch that is still averaged
         over `gradient_accumulation` (kept: it is what the reference trains with)."""
-        loss, probs = self._loss_and_probs(preds, batch_label)
+        if grad_step and self.auc.weight > 0:
+            # the training step's loss carries the pairwise AUROC term and pushes the batch's scores into the bank; evaluation
+            # passes (grad_step False) keep the plain loss and leave the bank alone, so 'loss' compares between runs
+            loss, probs = bce_auc_with_logits_loss(preds.squeeze(1), batch_label, self.config['pos_wt'], self.auc.weight, bank=self.auc_bank,
+                                                   surrogate=self.auc.surrogate, margin=self.auc.margin, push=True, return_probs=True)
+        else:
+            loss, probs = self._loss_and_probs(preds, batch_label)
         if grad_step:
             accum = self.config['gradient_accumulation']
             stepping = self.iters % accum == 0
@@ -272,7 +283,8 @@ class TrainerTemplate(object):
         (trainer.TrainStep runs the passes and takes the step when the accumulation modulo says so); the epoch log gets the
         first, least perturbed pass (VILLA: the clean one)."""
         if self._adv_step is None:
-            self._adv_step = TrainStep(self.model, self.optimizer, self.scheduler, self.config, grad_sync=self.grad_sync)
+            self._adv_step = TrainStep(self.model, self.optimizer, self.scheduler, self.config, grad_sync=self.grad_sync,
+                                       auc_bank=self.auc_bank)
         self._adv_step.optimizer, self._adv_step.scheduler = self.optimizer, self.scheduler
         loss = self._adv_step.train_iter(batch, iters=self.iters)
         self.log.add(self._adv_step.last_probs, batch['labels'], loss, ids=self._ids)
@@ -487,6 +499,8 @@ class TrainerTemplate(object):
         if _is_main():
             print("\nBeginning training at:  {} \n".format(datetime.datetime.now()))
         self.model.to(self.device)
+        if self.auc_bank is not None:
+            self.auc_bank.reset()           # a run starts from an empty bank and keeps it across its epochs
         for self.epoch in range(self.start_epoch, self.config['max_epoch'] + 1):
             self._train_epoch()
             self._after_epoch()
@@ -543,7 +557,11 @@ class TrainerTemplate(object):
              ('ema_decay', float, 0.0), ('save_optimizer_state', None, False),
              # additive: the folds' ensemble (crossval.train_crossval -> ensemble.find_ensemble): where the weight search scores its
              # candidates, and the evolutionary search after the brute force
-             ('ensemble_backend', str, 'host'), ('ensemble_ea', None, False))
+             ('ensemble_backend', str, 'host'), ('ensemble_ea', None, False),
+             # additive: a pairwise AUROC surrogate beside BCE in the training step's loss launch (trainer.auc_config): its weight
+             # (0 = off), the capacity of the device-resident bank of recent scores its pairs reach into (0 = the batch alone, else at
+             # least batch_size), 'logistic' or 'hinge2' (squared hinge), and the hinge's margin
+             ('auc_weight', float, 0.0), ('auc_bank', int, 0), ('auc_surrogate', str, 'logistic'), ('auc_margin', float, 1.0))
     CHOICES = {'ensemble_backend': ('host', 'hip')}
 
     @classmethod

@@ -85,13 +85,81 @@ class _LogitsLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dextra):
-        (dlog,) = ctx.saved_tensors
-        if dloss is None:
-            return (None,) * 6
-        unit = _UNIT.get(dlog.device)
-        if unit is not None and dloss.data_ptr() == unit.data_ptr():
-            return (dlog.view(ctx.shape),) + (None,) * 5     # loss.backward(unit_gradient(..)): d loss = 1, nothing to multiply
-        return ((dlog * dloss).view(ctx.shape),) + (None,) * 5
+        return (_saved_dlogits(ctx, dloss),) + (None,) * 5
+
+
+def _saved_dlogits(ctx, dloss):
+    """The backward of a loss whose forward launch left d loss / d logits in ctx: that tensor, times dloss unless it is
+    unit_gradient's"""
+    (dlog,) = ctx.saved_tensors
+    if dloss is None:
+        return None
+    unit = _UNIT.get(dlog.device)
+    if unit is not None and dloss.data_ptr() == unit.data_ptr():
+        return dlog.view(ctx.shape)                # loss.backward(unit_gradient(..)): d loss = 1, nothing to multiply
+    return (dlog * dloss).view(ctx.shape)
+
+
+AUC_SURROGATES = ('logistic', 'hinge2')            # `kind` 0, 1 of uniter_bce_auc_logits
+AUC_MAX_BANK = 8192
+
+
+class ScoreBank(object):
+    """The ring buffer of recent (score, label) pairs that uniter_bce_auc_logits reads and pushes into, in device memory:
+    `scores` float32 [capacity], `labels` int32 [capacity], `state` int32 {head, fill} -- head the slot the next push starts
+    at, fill the number of valid slots (the most recently pushed ones).  Nothing here reads the device but contents()."""
+
+    def __init__(self, capacity, device):
+        capacity = int(capacity)
+        if not 1 <= capacity <= AUC_MAX_BANK:
+            raise ValueError('ScoreBank capacity must lie in [1, %d], got %d' % (AUC_MAX_BANK, capacity))
+        self.capacity = capacity
+        self.scores = torch.zeros(capacity, dtype=torch.float32, device=device)
+        self.labels = torch.zeros(capacity, dtype=torch.int32, device=device)
+        self.state = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def reset(self):
+        """forget every score: head = fill = 0 (one fill launch, no host read)"""
+        self.state.zero_()
+
+    def contents(self):
+        """(scores, labels) of the valid slots, oldest first, as host tensors.  Reads on the host: for tests and tools only"""
+        head, fill = self.state.tolist()
+        idx = (torch.arange(fill) + (head - fill)) % self.capacity
+        return self.scores.cpu()[idx], self.labels.cpu()[idx]
+
+
+class _AucLogitsLossFn(torch.autograd.Function):
+    """uniter_bce_auc_logits after _LogitsLossFn's pattern: one launch forward (which also pushes into the bank), none
+    backward -> (the view terms[0], terms [total, bce, auc], probs, n_pairs); only the first is differentiable."""
+    @staticmethod
+    def forward(ctx, logits, labels, pos_weight, auc_weight, bank, kind, margin, grad_scale, push):
+        _lib.require_gpu_tensor(logits, torch.float32, 'logits')
+        x = logits.reshape(-1).contiguous()
+        y = labels.reshape(-1).to(torch.int64).contiguous()
+        B = x.numel()
+        if B != y.numel():
+            raise ValueError('logits/labels size mismatch')
+        if bank is not None and bank.scores.device != x.device:
+            raise UniterHipError('the score bank lives on %s, the logits on %s' % (bank.scores.device, x.device))
+        dlog = torch.empty(B, dtype=torch.float32, device=x.device)
+        terms = torch.empty(3, dtype=torch.float32, device=x.device)
+        probs = torch.empty(B, dtype=torch.float32, device=x.device)
+        n_pairs = torch.empty((), dtype=torch.int32, device=x.device)
+        bs, bl, bst, N = (ptr(bank.scores), ptr(bank.labels), ptr(bank.state), bank.capacity) if bank is not None else (None, None, None, 0)
+        check(_lib.lib().uniter_bce_auc_logits(ptr(x), ptr(y), float(pos_weight), float(auc_weight), int(kind), float(margin), bs, bl, bst,
+                                               N, int(bool(push)), ptr(terms), ptr(n_pairs), ptr(probs), ptr(dlog), float(grad_scale), B,
+                                               _lib.cur_stream()), 'uniter_bce_auc_logits')
+        loss = terms[0]                            # (a view: the total needs no launch of its own)
+        ctx.save_for_backward(dlog)
+        ctx.shape = logits.shape
+        ctx.mark_non_differentiable(terms, probs, n_pairs)
+        ctx.set_materialize_grads(False)
+        return loss, terms, probs, n_pairs
+
+    @staticmethod
+    def backward(ctx, dloss, *_dextras):
+        return (_saved_dlogits(ctx, dloss),) + (None,) * 8
 
 
 _UNIT = {}
@@ -124,6 +192,22 @@ def bce_kl_with_logits_loss(logits, clean_logits, labels, pos_weight, kl_weight,
         raise ValueError('bce_kl_with_logits_loss needs the clean logits')
     loss, terms = _LogitsLossFn.apply(logits, clean_logits, labels, pos_weight, kl_weight, grad_scale)
     return (loss, terms) if return_terms else loss
+
+
+def bce_auc_with_logits_loss(logits, labels, pos_weight, auc_weight, bank=None, surrogate='logistic', margin=1.0, grad_scale=1.0,
+                             push=True, return_terms=False, return_probs=False):
+    """bce_with_logits_loss(logits, labels, pos_weight) + auc_weight * a pairwise AUROC surrogate, one launch
+    (uniter_bce_auc_logits): the mean of l(s_positive - s_negative) over the pairs of the batch's rows with each other and with
+    the `bank`'s recent scores (a ScoreBank, or None: the batch alone), l = softplus(-d) ('logistic') or max(0, margin - d)^2
+    ('hinge2').  The bank's scores are constants; with push (and a bank) the launch then pushes the batch's logits and labels
+    into it.  The gradient handed back is grad_scale times the loss's; the value is not scaled.  return_terms: also the device
+    tensor [total, bce, auc]; return_probs: also sigmoid(logits), behind it."""
+    if surrogate not in AUC_SURROGATES:
+        raise ValueError('surrogate must be one of %s, got %r' % (', '.join(repr(s) for s in AUC_SURROGATES), surrogate))
+    loss, terms, probs, _ = _AucLogitsLossFn.apply(logits, labels, pos_weight, auc_weight, bank, AUC_SURROGATES.index(surrogate), margin,
+                                                   grad_scale, push)
+    out = (loss,) + ((terms,) if return_terms else ()) + ((probs,) if return_probs else ())
+    return out if len(out) > 1 else loss
 
 
 # --------------------------------------------------------------------------- #
@@ -1180,6 +1264,35 @@ def adv_config(config):
     return adv
 
 
+AucConfig = namedtuple('AucConfig', 'weight bank surrogate margin')
+
+
+def auc_config(config):
+    """The pairwise AUROC term's settings of a trainer config (auc_weight = 0, the default, switches it off): auc_weight (its
+    weight beside BCE), auc_bank (capacity of the bank of recent scores, 0: the batch alone), auc_surrogate ('logistic' |
+    'hinge2'), auc_margin (the squared hinge's margin)."""
+    auc = AucConfig(float(config.get('auc_weight', 0.0) or 0.0), int(config.get('auc_bank', 0) or 0),
+                    config.get('auc_surrogate', 'logistic') or 'logistic', float(config.get('auc_margin', 1.0)))
+    if not auc.weight >= 0:
+        raise ValueError('auc_weight must not be negative, got %r' % auc.weight)
+    if auc.surrogate not in AUC_SURROGATES:
+        raise ValueError("auc_surrogate must be one of %s, got %r" % (', '.join(repr(s) for s in AUC_SURROGATES), auc.surrogate))
+    if auc.margin != auc.margin:
+        raise ValueError('auc_margin is NaN')
+    if auc.bank < 0 or auc.bank > AUC_MAX_BANK:
+        raise ValueError('auc_bank must lie in [0, %d], got %d' % (AUC_MAX_BANK, auc.bank))
+    if auc.bank and auc.bank < int(config.get('batch_size', 0) or 0):
+        raise ValueError('auc_bank = %d holds less than one batch (batch_size = %d)' % (auc.bank, config['batch_size']))
+    if auc.weight > 0 and config.get('loss_func', 'bce_logits') != 'bce_logits':
+        raise ValueError("auc_weight > 0 needs loss_func='bce_logits': the term is part of that loss's launch")
+    return auc
+
+
+def new_score_bank(auc, device):
+    """The ScoreBank the AucConfig `auc` asks for, or None: the term is off, or it takes its pairs from the batch alone"""
+    return ScoreBank(auc.bank, device) if auc.weight > 0 and auc.bank > 0 else None
+
+
 def adv_rounds(adv):
     """The rounds of an adversarial micro-batch under the AdvConfig `adv`, each the tuple of the modalities it perturbs together:
     one round, or with adv_modality = 'each' a text round and then an image round"""
@@ -1224,16 +1337,27 @@ class TrainStep(object):
     perturbation of its own; ``adv_norm_type`` chooses the L2 or the L-infinity ball.  The logged loss and probabilities are
     the clean pass's; `last_adv_terms` holds [total, bce, kl] of the last perturbed pass.
 
+    With ``auc_weight`` > 0 (`auc_config`) the loss of the training passes is `bce_auc_with_logits_loss`: BCE plus the pairwise
+    AUROC surrogate against the batch and a `ScoreBank` of ``auc_bank`` recent scores, which the same launch pushes into -- the
+    plain step, VILLA's clean pass, and FreeLB's K passes (the first of them pushes).  VILLA's perturbed passes keep their BCE +
+    KL loss, and `eval_iter` the plain BCE: it never touches the bank.  `last_auc_terms` holds [total, bce, auc].
+
     Quirk kept on purpose: the modulo test is on the per-epoch iteration index
     starting at 0, so iteration 0 steps immediately with a single micro-batch whose
     gradient is still divided by ``gradient_accumulation``.
     """
 
-    def __init__(self, model, optimizer, scheduler, config, grad_sync=None):
+    def __init__(self, model, optimizer, scheduler, config, grad_sync=None, auc_bank=None):
         self.model, self.optimizer, self.scheduler, self.config = model, optimizer, scheduler, config
         self.grad_sync = grad_sync          # DP: object with .finish() called before the optimizer step
+        self.auc = auc_config(config)       # (before the loss_func check: auc_weight > 0 with another loss is a ValueError)
         if config.get('loss_func', 'bce_logits') != 'bce_logits':
             raise UniterHipError("only loss_func='bce_logits' is built on the HIP path")
+        # auc_weight > 0: the training passes' loss is bce_auc_with_logits_loss (_train_loss); the bank of recent scores is the
+        # caller's (TrainerTemplate keeps one across epochs) or this step's own.  Each rank of a data-parallel run has its own
+        self.auc_bank = auc_bank if (auc_bank is not None or self.auc.weight <= 0) else \
+            new_score_bank(self.auc, next(model.parameters()).device)
+        self.last_auc_terms = None          # the device tensor [total, bce, auc] of the last training pass that carried the term
         enc = getattr(model, 'uniter_model', None)
         if grad_sync is None and enc is not None and isinstance(optimizer, FusedAdam) and (config.get('max_grad_norm') or 0) > 0:
             optimizer.attach_norm_hooks(enc)        # the clip norm is reduced bucket by bucket during the backward pass
@@ -1273,10 +1397,24 @@ class TrainStep(object):
             adv_delta_step(delta, delta, 0.0, self.adv.max_norm, self.adv.norm_type)
         return delta
 
-    def _clean_pass(self, batch):
-        """forward + the plain loss -> (logits, loss, probs); the caller runs backward (or none: eval_iter)"""
+    def _train_loss(self, logits, labels, push=True):
+        """The loss of a training pass on unperturbed or FreeLB-perturbed logits -> (loss, probs): today's launch, or with
+        auc_weight > 0 the one that adds the pairwise AUROC term and, with `push`, pushes the logits into the bank"""
+        if self.auc.weight <= 0:
+            return bce_with_logits_loss(logits, labels, self.config['pos_wt'], return_probs=True)
+        loss, self.last_auc_terms, probs = bce_auc_with_logits_loss(
+            logits, labels, self.config['pos_wt'], self.auc.weight, bank=self.auc_bank, surrogate=self.auc.surrogate,
+            margin=self.auc.margin, push=push, return_terms=True, return_probs=True)
+        return loss, probs
+
+    def _clean_pass(self, batch, train=False):
+        """forward + the loss -> (logits, loss, probs); the caller runs backward (or none: eval_iter, whose loss is the plain BCE
+        whatever the training passes add to it, and which never touches the bank)"""
         preds = self.model(**self.forward_kwargs(batch))
-        loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], self.config['pos_wt'], return_probs=True)
+        if train:
+            loss, probs = self._train_loss(preds.squeeze(1), batch['labels'])
+        else:
+            loss, probs = bce_with_logits_loss(preds.squeeze(1), batch['labels'], self.config['pos_wt'], return_probs=True)
         return preds, loss, probs
 
     def _adv_deltas(self, batch, which, delta0):
@@ -1320,14 +1458,19 @@ class TrainStep(object):
         cfg, adv = self.config, self.adv
         K, villa, labels, pos_wt = adv.steps, adv.algo == 'villa', batch['labels'], cfg['pos_wt']
         if villa:
-            preds, loss, probs = self._clean_pass(batch)
+            preds, loss, probs = self._clean_pass(batch, train=True)
             loss.backward(unit_gradient(loss.device))
             result = loss.detach(), probs
             clean = preds.detach().squeeze(1)       # (no copy: every forward pass returns logits in a tensor of its own)
             # the 1 / K of the round's average sits in the loss launch: the optimizer step's grad_scale stays the plain one
             loss_fn = lambda z: bce_kl_with_logits_loss(z, clean, labels, pos_wt, adv.kl_weight, grad_scale=1.0 / K, return_terms=True)
         else:
-            loss_fn = lambda z: bce_with_logits_loss(z, labels, pos_wt, return_probs=True)
+            # (auc_weight > 0: a sample enters the bank once per micro-batch -- the first, least perturbed pass pushes, the others do not)
+            seen = []
+
+            def loss_fn(z):
+                seen.append(1)
+                return self._train_loss(z, labels, push=len(seen) == 1)
         final = {}
         for which in adv_rounds(adv):
             deltas = self._adv_deltas(batch, which, delta0 or {})
@@ -1370,7 +1513,7 @@ class TrainStep(object):
             self.last_loss, self.last_probs = self._train_iter_adv(batch, stepping, adv_delta0)
             self.iters += 1
             return self.last_loss
-        _, loss, probs = self._clean_pass(batch)
+        _, loss, probs = self._clean_pass(batch, train=True)
         if self.grad_sync is not None:
             self.grad_sync.prepare(will_step=stepping, token_ids=batch['input_ids'])
         loss.backward(unit_gradient(loss.device))
