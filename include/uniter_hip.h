@@ -685,7 +685,9 @@ int uniter_linear_small_bwd(const float* dy, const float* x, const float* W,
 /* Pooler + classifier as ONE launch each way (model/layer.py:179-185 followed by model/meme_uniter.py:19-21): results equal
  * uniter_pooler_fwd + uniter_linear_small_fwd, and uniter_linear_small_bwd + uniter_pooler_bwd.  `ticket`:
  * UNITER_POOL_HEAD_TICKET_WORDS zero-initialised unsigneds in device memory, left zero by every launch (the workgroups count
- * themselves there; the last one to finish computes the logits).  Hidden sizes up to 4096.  The backward ACCUMULATES
+ * themselves there; the last one to finish computes the logits).  Both entry points refuse (UNITER_E_ARG, before any launch) a hidden
+ * size above 4096 and a pooled tensor of B * H * 4 >= 0x7ffffff0 bytes (the forward addresses it through a 32-bit buffer descriptor
+ * whose out-of-range offset is that value); the backward requires C <= H as uniter_linear_small_bwd does.  The backward ACCUMULATES
  * into dWp, dbp, dWl, dbl; dhidden (optional) gets row 0 of every sample (assigned, or added with beta_dhidden != 0). */
 #define UNITER_POOL_HEAD_TICKET_WORDS (17 * 64)
 int uniter_pool_head_fwd(const float* hidden, const float* Wp, const float* bp, const float* Wl, const float* bl,

@@ -536,6 +536,9 @@ __global__ __launch_bounds__(256) void pool_head_fwd_kernel(const float* __restr
 //   dpooled[b][n] = sum_c dlogits[b][c] Wl[c][n],  dpre[b][n] = dpooled[b][n] (1 - pooled[b][n]^2)
 constexpr int PHB_WAVES = 16;
 constexpr int PHB_MAX_H = 4096;     // (the X role keeps one sample's row of H gradients in LDS)
+// the forward's descriptor over `pooled` takes its size as an int, and the offset 0x7ffffff0 it hands a column beyond H must lie
+// outside it: both launchers refuse a pooled tensor of that many bytes or more
+constexpr size_t PH_MAX_POOLED_BYTES = 0x7ffffff0u;
 __device__ __forceinline__ float phb_dpre(const float* __restrict__ dlogits, const float* __restrict__ Wl,
                                           const float* __restrict__ pooled, int b, int n, int H, int Cn) {
   float s = 0.f;
@@ -740,11 +743,14 @@ extern "C" int uniter_bce_auc_logits(const float* logits, const int64_t* labels,
 
 // Pooler + classifier, one launch: pooled = tanh(hidden[:, 0] Wp^T + bp) (model/layer.py:179-185), logits = pooled Wl^T + bl
 // (model/meme_uniter.py:19-21).  `ticket`: UNITER_POOL_HEAD_TICKET_WORDS zero-initialised unsigneds the launch leaves zero again (its last
-// workgroup computes the logits).  Results equal uniter_pooler_fwd followed by uniter_linear_small_fwd.
+// workgroup computes the logits).  Results equal uniter_pooler_fwd followed by uniter_linear_small_fwd.  H <= 4096 and
+// B * H * 4 < 0x7ffffff0, as the backward launch.
 extern "C" int uniter_pool_head_fwd(const float* hidden, const float* Wp, const float* bp, const float* Wl, const float* bl,
                                     float* pooled, float* logits, unsigned* ticket, int B, int L, int H, int Cn, void* stream) {
   UCHECK_ARG(hidden && Wp && bp && Wl && bl && pooled && logits && ticket && B > 0 && L > 0 && H > 0 && Cn > 0,
              "pool_head_fwd: bad argument");
+  UCHECK_ARG(H <= PHB_MAX_H, "pool_head_fwd: hidden size up to %d (got %d)", PHB_MAX_H, H);
+  UCHECK_ARG((size_t)B * H * 4 < PH_MAX_POOLED_BYTES, "pool_head_fwd: B * H * 4 must stay below 0x7ffffff0 (got B = %d, H = %d)", B, H);
   hipLaunchKernelGGL(pool_head_fwd_kernel, dim3((H + 3) / 4, (B + 3) / 4), dim3(256), 0, (hipStream_t)stream, hidden, Wp, bp, Wl,
                      bl, pooled, logits, ticket, B, L, H, Cn);
   UCHECK_LAUNCH();
@@ -759,6 +765,7 @@ extern "C" int uniter_pool_head_bwd(const float* dlogits, const float* pooled, c
                                     int H, int Cn, int beta_dhidden, void* stream) {
   UCHECK_ARG(dlogits && pooled && hidden && Wp && Wl && dWp && dbp && dWl && dbl && B > 0 && L > 0 && H > 0 && Cn > 0 && Cn <= H &&
                  H <= PHB_MAX_H, "pool_head_bwd: bad argument (hidden size up to 4096)");
+  UCHECK_ARG((size_t)B * H * 4 < PH_MAX_POOLED_BYTES, "pool_head_bwd: B * H * 4 must stay below 0x7ffffff0 (got B = %d, H = %d)", B, H);
   const int nW = (H + 3) / 4;
   const int nX = dhidden ? ((H + 63) / 64) * B : 0;
   const int nL = (H + 64 * PHB_WAVES - 1) / (64 * PHB_WAVES);
