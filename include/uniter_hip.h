@@ -1061,6 +1061,15 @@ int uniter_model_set_input_grads(uniter_model_t* m, const float* txt_delta, floa
  * The handle forgets the setting when that uniter_model_forward returns, with or without an error.  out = NULL, or never called:
  * exactly the launches without it. */
 int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t layer_stride_elems, int head_mean);
+/* "Head rows only", a request for the NEXT forward pass and its backward pass, held like uniter_model_set_input_grads: the caller
+ * reads row 0 of every sample of the last layer's output and nothing else, and the gradient it hands to the backward pass is zero
+ * in every other row (a pooled head: uniter_pool_head_fwd / _bwd).  The last layer then runs everything behind its attention kernel
+ * -- attention output, both dropout + residual + LayerNorm passes, the feed-forward pair, their input gradients and the reduction of
+ * three of its four weight gradients -- on B rows instead of B * L; dropout draws what the full pass draws for those rows.
+ * hidden_out then holds the B result rows and EXACT ZEROS in every other row.  The request is honoured only in the fp32x3 mode on a
+ * padded (not packed) batch with all_layers = 0; everywhere else it is ignored and the pass runs launch for launch as without it.
+ * The next forward pass forgets it.  on = 0, or never called: no request. */
+int uniter_model_set_head_rows(uniter_model_t* m, int on);
 /* Every layer's gradient-weighted attention out of the backward pass of the NEXT forward pass, a setting on the handle held like
  * uniter_model_set_input_grads: the forward pass takes it over, uniter_model_backward_layer(l) calls uniter_attn_grad on the main
  * stream between the product that writes the context's gradient and the attention backward launch (qkv bf16 exactly when the bf16

@@ -185,6 +185,8 @@ _SIGS = {
     'uniter_attn_probs': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'uniter_attn_rollout': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     'uniter_model_set_attn_probs': (_I, [_P, _P, _SZ, _I]),
+    # the last layer's work behind its attention kernel on the rows a pooled head reads (csrc/model.cpp)
+    'uniter_model_set_head_rows': (_I, [_P, _I]),
     # gradient-weighted attention, relevance and head sums (csrc/attn_grad.hip)
     'uniter_attn_grad_ws_bytes': (_SZ, [_I, _I, _I]),
     'uniter_attn_grad': (_I, [_P, _I, _P, _P, _P, _I, _SZ, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),

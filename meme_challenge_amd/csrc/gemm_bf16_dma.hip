@@ -656,7 +656,7 @@ int gemm_bf16v2_wgrad_group(int cfg, const WgradGroupCall& c, const LaunchOpts& 
   static const char* const who = "wgrad_group";
   UCHECK_RC(wgrad_group_check(who, c));
   if (cfg == 7) return gemm_b1p_wgrad_group(c, lo);      // 128 x 256 tiles, persistent
-  UCHECK_ARG(!c.sk_ws, "%s: no launch of the bf16 family takes a workspace", who);
+  UCHECK_ARG(!c.sk_ws && !c.Kp, "%s: no launch of the bf16 family takes a workspace or per-product reduction lengths", who);
   GGroupD G;
   memset(&G.x, 0, sizeof(G.x));
   UCHECK_RC(wgrad_group_walk(who, c, G.start, [&](int p) { return wgrad_bf16_product_in_range(c, p); },

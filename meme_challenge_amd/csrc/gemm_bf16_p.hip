@@ -574,7 +574,7 @@ int gemm_b1p_wgrad_group_slots(int n, const int* Mo, const int* No, int max_wgs,
 // lo: the stamp slot and the reserve; the launch runs at the default wave priority whatever lo.prio says
 int gemm_b1p_wgrad_group(const WgradGroupCall& c, const LaunchOpts& lo) {
   static const char* const who = "wgrad_bf16p_group";
-  UCHECK_ARG(!c.sk_ws, "%s: no launch of the bf16 family takes a workspace", who);
+  UCHECK_ARG(!c.sk_ws && !c.Kp, "%s: no launch of the bf16 family takes a workspace or per-product reduction lengths", who);
   P1Group G;
   memset(&G.x, 0, sizeof(G.x));
   UCHECK_RC(wgrad_group_walk(who, c, G.start, [&](int p) { return wgrad_bf16_product_in_range(c, p); },

@@ -782,7 +782,7 @@ int choose_cfg(int M, int N) {
 // UNITER_E_SHAPE for shapes the grouped kernel does not take (the caller then launches the products one by one)
 int gemm_f32_wgrad_group(const WgradGroupCall& c, const LaunchOpts& lo) {
   static const char* const who = "wgrad_group_f32";
-  UCHECK_ARG(!c.riders && !c.max_wgs && !c.sk_ws, "%s: the fp32 launch takes no riders, no grid cap and no workspace", who);
+  UCHECK_ARG(!c.riders && !c.max_wgs && !c.sk_ws && !c.Kp, "%s: the fp32 launch takes no riders, no grid cap, no workspace and one reduction length", who);
   GemmGroup G = {};
   const int K = c.K;
   UCHECK_RC(wgrad_group_walk(who, c, G.start,

@@ -85,9 +85,11 @@ int gemm_bf16v2_wgrad_pieces(int M, int N, int K);
 
 // Up to four weight gradients dW_p[Mo_p, No_p] (+)= A_p^T B_p of one reduction length K as ONE launch (A_p [K][Mo_p], B_p [K][No_p] in
 // the family's operand format, dW_p fp32 with leading dimension No_p).  max_wgs: grid cap, 0 = the family's; riders: side work of
-// the launch (include/uniter_hip.h), not on the fp32 kernel; sk_ws: the balanced walk's workspace (x3).
+// the launch (include/uniter_hip.h), not on the fp32 kernel; sk_ws: the balanced walk's workspace (x3).  Kp (x3, without sk_ws): a
+// reduction length per product -- rows Kp[p] of A_p and B_p, the tiles, grid and riders' slots of the launch unchanged.
 struct WgradGroupCall {
   int n = 0, K = 0;
+  const int* Kp = nullptr;           // optional: product p's own reduction length Kp[p] > 0 in place of K (x3 only)
   const int *Mo = nullptr, *No = nullptr;
   const void *const *A = nullptr, *const *B = nullptr;
   float* const* dW = nullptr;
@@ -108,6 +110,7 @@ int gemm_bf16v2_wgrad_group_balanced_wgs(int n, const int* Mo, const int* No, in
 
 static inline int wgrad_group_check(const char* who, const WgradGroupCall& c) {
   UCHECK_ARG(c.n >= 1 && c.n <= 4 && c.K > 0 && c.Mo && c.No && c.A && c.B && c.dW, "%s: bad argument", who);
+  for (int p = 0; c.Kp && p < c.n; ++p) UCHECK_ARG(c.Kp[p] > 0, "%s: product %d: reduction length %d", who, p, c.Kp[p]);
   return 0;
 }
 // The walk over the products of a grouped launch, written once: product p < n is checked (UNITER_E_ARG: a null or empty product;
@@ -123,7 +126,7 @@ int wgrad_group_walk(const char* who, const WgradGroupCall& c, int* start, InRan
     if (p >= c.n) { pad(p); continue; }
     UCHECK_ARG(c.Mo[p] > 0 && c.No[p] > 0 && c.A[p] && c.B[p] && c.dW[p], "%s: bad product %d", who, p);
     UCHECK_SHAPE(in_range(p), "%s: product %d (%d x %d, K = %d) outside the grouped kernel's range (M, N multiples of 8 -- fp32: 4 --, "
-                 "16-byte aligned buffers, 31-bit offsets)", who, p, c.Mo[p], c.No[p], c.K);
+                 "16-byte aligned buffers, 31-bit offsets)", who, p, c.Mo[p], c.No[p], c.Kp ? c.Kp[p] : c.K);
     total += fill(p);
   }
   for (int p = c.n; p <= 4; ++p) start[p] = total;

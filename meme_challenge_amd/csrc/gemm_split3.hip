@@ -1516,11 +1516,14 @@ int gemm_x3_wgrad_group(int cfg, const WgradGroupCall& c, const LaunchOpts& lo) 
   S3Group G;
   memset(&G.x, 0, sizeof(G.x));
   G.sk_part = nullptr; G.sk_flag = nullptr; G.sk_units = G.sk_nk = 0;
-  const int K = c.K, overwrite = c.overwrite, max_wgs = c.max_wgs;
+  const int overwrite = c.overwrite, max_wgs = c.max_wgs;
+  // product p's reduction length: its own (WgradGroupCall::Kp) or the launch's.  The balanced walk deals k-tiles of ONE length
+  UCHECK_ARG(!c.Kp || !c.sk_ws, "%s: per-product reduction lengths do not go with the balanced walk's workspace", who);
+  auto Kof = [&](int p) { return c.Kp ? c.Kp[p] : c.K; };
   UCHECK_RC(wgrad_group_walk(who, c, G.start,
-    [&](int p) { return wgrad_product_aligned8(c, p) && x3_fits(K, 3 * c.Mo[p], c.Mo[p], c.Mo[p]) && x3_fits(K, 3 * c.No[p], c.No[p], c.No[p]); },
+    [&](int p) { return wgrad_product_aligned8(c, p) && x3_fits(Kof(p), 3 * c.Mo[p], c.Mo[p], c.Mo[p]) && x3_fits(Kof(p), 3 * c.No[p], c.No[p], c.No[p]); },
     [&](int p) {
-      const int Mo = c.Mo[p], No = c.No[p];
+      const int Mo = c.Mo[p], No = c.No[p], K = Kof(p);
       float* const dW = c.dW[p];
       S3Args& g = G.p[p];
       g = {Mo, No, K, c.A[p], 3 * Mo, Mo, c.B[p], 3 * No, No, dW, No, /*c_split_stride*/ 0, /*Cx*/ nullptr, 0, 0, /*bias*/ nullptr,
@@ -1534,7 +1537,7 @@ int gemm_x3_wgrad_group(int cfg, const WgradGroupCall& c, const LaunchOpts& lo) 
   hipStream_t st = (hipStream_t)c.stream;
   void* const sk_ws = c.sk_ws;
   // the balanced walk (128 x 256 tiles, a workspace given): 216 tiles for UNITER-base on 256 CUs -- 82 k-tiles per workgroup become 70
-  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (K + 31) / 32, max_wgs, lo.cu_reserve, sk_ws, c.sk_ws_bytes) : 0;
+  const int sk_grid = cfg == 4 ? x3_sk_grid(total, (c.K + 31) / 32, max_wgs, lo.cu_reserve, sk_ws, c.sk_ws_bytes) : 0;
   if (uniter_x3_riders_t* riders = c.riders) {
     // riders ride on the v_mfma_f32_16x16x32_bf16 geometries: 4 compute waves of 64 x 64 (cfg 3) or the 128 x 256 tile's 8 (cfg 4)
     UCHECK_ARG(cfg == 3 || cfg == 4, "wgrad_x3_group: riders need cfg 3 or 4");

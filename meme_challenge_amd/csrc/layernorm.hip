@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                                                      float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, int M, int H,
                                                      DropCfg drop, unsigned short* __restrict__ y_b16,
-                                                     int nslab, size_t slab_stride, int pieces) {
+                                                     int nslab, size_t slab_stride, int pieces, int drop_row_step) {
   LN_SETPRIO();
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] += r[k];
   }
-  if (drop.active) row_dropout<NV>(v, drop, (uint64_t)row * H4, H4, lane);
+  if (drop.active) row_dropout<NV>(v, drop, (uint64_t)row * (uint64_t)drop_row_step * H4, H4, lane);
   if (res) {
     f32x4 r[NV];
     row_load<NV>(r, res + (size_t)row * H, H4, lane);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64 * LNB_WAVES) void ln_bwd_kernel(const float* __r
                                                      float* __restrict__ part, int M, int H,
                                                      DropCfg drop, int want_dbias,
                                                      unsigned short* __restrict__ dx_b16, int nslab,
-                                                     size_t slab_stride, int pieces) {
+                                                     size_t slab_stride, int pieces, int drop_row_step) {
   __shared__ __attribute__((aligned(16))) float red[LNB_WAVES * NV * 256];
   LN_SETPRIO();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(64 * LNB_WAVES) void ln_bwd_kernel(const float* __r
     const float mu = mean[row], rs = rstd[row];
     row_ln_bwd<NV>(d, xh, g, mu, rs, dg, db, H, H4, lane);      // d <- dz, accumulates dg/db
     if (dz) row_store<NV>(d, dz + (size_t)row * H, H4, lane);
-    if (drop.active) row_dropout<NV>(d, drop, (uint64_t)row * H4, H4, lane);
+    if (drop.active) row_dropout<NV>(d, drop, (uint64_t)row * (uint64_t)drop_row_step * H4, H4, lane);
     if (dx && (dx != dz || drop.active)) row_store<NV>(d, dx + (size_t)row * H, H4, lane);
     if (dx_b16) {
       if (pieces == 3) row_store_x3<NV>(d, dx_b16 + (size_t)row * 3 * H, H, H4, lane);
@@ -479,6 +479,7 @@ static int ln_check(const char* who, const LnCall& c, bool required) {
   UCHECK_ARG(required, "%s: null pointer", who);
   UCHECK_ARG(c.nslab >= 1 && (c.nslab == 1 || c.slab_stride >= (size_t)c.M * c.H), "%s: bad slab count / stride", who);
   UCHECK_SHAPE(c.H % 4 == 0 && c.H >= 4, "%s: H must be a multiple of 4", who);
+  UCHECK_ARG(c.drop_row_step >= 1, "%s: bad dropout row step %d", who, c.drop_row_step);
   return 0;
 }
 static int ln_nv(int H) { return (H / 4 + 63) / 64; }
@@ -490,7 +491,7 @@ int ln_fwd_run(const LnCall& c) {
   if (c.M <= 0) return 0;
   hipStream_t st = (hipStream_t)c.stream;
   LN_DISPATCH_T(ln_nv(c.H), LN_FWD_K, dim3((c.M + 3) / 4), 256, c.x, c.res, c.gamma, c.beta, c.z, c.out, c.mean, c.rstd, c.M, c.H,
-                make_drop(c.drop), (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces);
+                make_drop(c.drop), (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces, c.drop_row_step);
   UCHECK_LAUNCH();
   return 0;
 }
@@ -507,7 +508,7 @@ int ln_bwd_rows_run(const LnCall& c) {
   hipStream_t st = (hipStream_t)c.stream;
   const int nv = ln_nv(c.H), nblk = ln_bwd_blocks(c.M);
 #define LNB_ARGS c.x, c.z, c.mean, c.rstd, c.gamma, c.dz, c.out, (float*)c.ws, c.M, c.H, make_drop(c.drop), c.want_dbias != 0, \
-                 (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces
+                 (unsigned short*)c.copy, c.nslab, c.slab_stride, c.pieces, c.drop_row_step
   if (lnb_waves() == 8) { LN_DISPATCH_T(nv, LN_BWD_K8, dim3(nblk), 512, LNB_ARGS); }
   else { LN_DISPATCH_T(nv, LN_BWD_K4, dim3(nblk), 256, LNB_ARGS); }
 #undef LNB_ARGS

@@ -108,6 +108,18 @@ struct Plan {
   // launches, one for the weight-gradient stream's (they run at the same time); their flag words are cleared by every forward pass
   void *sk_main, *sk_side;
   size_t sk_bytes;
+  // "head rows only" (uniter_model_set_head_rows), precision 3 on a padded batch: the last layer's stretch behind its attention kernel
+  // on the B rows b * L alone.  hr: that stretch's buffers, B rows each with natural leading dimensions (hr.ctx / hr.ctxb: those rows of
+  // the context, hr.dctx / hr.dz1: of the gradients the attention backward and the QKV input gradient read full-size, zero elsewhere);
+  // hr_x / hr_dy: those rows of the layer's input and of the caller's gradient
+  bool head_rows = false;     // this plan's forward pass ran that way: its backward pass does too
+  // k-pieces of that stretch's N = hidden products by reduction length (hidden: attention output; intermediate: FFN-down forward, FFN-up
+  // input gradient).  B rows are one row of tiles -- six workgroups at N = 768 -- so a product's time is its k-loop's: 1.1 us per
+  // k-tile, 108 us at K = 3072 in one piece (measured); pieces of at least two k-tiles, eight at most, spread it over the chip and
+  // the row pass behind sums the slabs (B rows each: nothing beside the k-loop they shorten)
+  int hr_ns_h = 1, hr_ns_i = 1;
+  LayerBufs hr;
+  float *hr_x = nullptr, *hr_dy = nullptr;
   size_t total;
 };
 
@@ -162,6 +174,7 @@ struct uniter_model {
   // uniter_model_set_attn_probs: where the next forward pass leaves every layer's attention probabilities (out == nullptr: nowhere)
   struct AttnProbs { float* out = nullptr; size_t stride = 0; int head_mean = 0; };
   AttnProbs ap_next;
+  bool head_rows_next = false;   // uniter_model_set_head_rows: the next forward pass's (Plan::head_rows is what that pass made of it)
   // uniter_model_set_attn_grads: where the backward pass of the next forward pass leaves every layer's gradient-weighted attention
   // (out == nullptr: nowhere)
   struct AttnGrads { float* out = nullptr; size_t stride = 0; int reduce = 0; float* head_sums = nullptr; void* ws = nullptr; size_t ws_bytes = 0; };
@@ -280,6 +293,26 @@ void make_plan(const uniter_model* m, Plan& pl, void* ws, int B, int T, int R, i
   pl.sk_bytes = gemm_x3_sk_ws_bytes();
   pl.sk_main = (x3 && (sw.x3_balanced & 2)) ? cv.raw(pl.sk_bytes) : nullptr;
   pl.sk_side = (x3 && save && (sw.x3_balanced & 1)) ? cv.raw(pl.sk_bytes) : nullptr;
+  pl.head_rows = false;
+  pl.hr = LayerBufs(); pl.hr_x = pl.hr_dy = nullptr;
+  if (x3 && !pl.packed) {      // (wherever a forward pass may honour uniter_model_set_head_rows: B rows of everything behind the attention kernel)
+    const size_t Bc = (size_t)B;
+    LayerBufs& h = pl.hr;
+    auto pieces_for = [](int K) { const int n = K / 32 / 2; return n < 1 ? 1 : (n > 8 ? 8 : n); };
+    pl.hr_ns_h = pieces_for(H); pl.hr_ns_i = pieces_for(I);
+    const size_t s_h = (size_t)pl.hr_ns_h, s_i = (size_t)pl.hr_ns_i;
+    h.ctx = cv.f(Bc * H); h.ctxb = cv.h(pc * Bc * H); pl.hr_x = cv.f(Bc * H); h.t1 = cv.f(s_h * Bc * H);
+    h.z1 = save ? cv.f(Bc * H) : nullptr; h.mean1 = cv.f(Bc); h.rstd1 = cv.f(Bc); h.y1 = cv.f(Bc * H); h.y1b = cv.h(pc * Bc * H);
+    h.u = save ? cv.f(Bc * I) : nullptr; h.hact = cv.f(Bc * I); h.hactb = cv.h(pc * Bc * I); h.t2 = cv.f(s_i * Bc * H);
+    h.z2 = save ? cv.f(Bc * H) : nullptr; h.mean2 = cv.f(Bc); h.rstd2 = cv.f(Bc); h.y2 = cv.f(Bc * H);
+    if (save) {
+      pl.hr_dy = cv.f(Bc * H); h.dz2 = cv.f(Bc * H); h.g2b = cv.h(pc * Bc * H); h.dub = cv.h(pc * Bc * I); h.dy1 = cv.f(s_i * Bc * H);
+      h.dz1 = cv.f(Bc * H); h.g1b = cv.h(pc * Bc * H); h.dctx = cv.f(Bc * H);
+      h.du_csum = cv.f((size_t)((Bc + 31) / 32) * I);
+      h.ln_ws1 = cv.raw(uniter_ln_bwd_ws_bytes(B, H));
+      h.ln_ws2 = cv.raw(uniter_ln_bwd_ws_bytes(B, H));
+    }
+  }
   if (save) {
     pl.hid_stride = align_up(uniter_hidden_keep_bits_bytes(M * H), 256);
     pl.hid_keepb = (unsigned char*)cv.raw(pl.hid_stride * 2 * nl);
@@ -449,7 +482,9 @@ struct WgradGroup {
   bool colpart = false;   // ... and dU's column sums (that bias gradient) start as column partials of the product that writes dU
   int cfg = 0, max_wgs = 0, slots = 0;
 };
-WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l, int cu_reserve) {
+// own_k: the launch's products have reduction lengths of their own (a last layer on its head rows): no balanced walk, whose runs of
+// k-tiles want one length
+WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l, int cu_reserve, bool own_k = false) {
   const Switches& sw = uniter_switches();
   const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size;
   const int Mo[4] = {I, H, 3 * H, H}, No[4] = {H, I, H, H};
@@ -462,7 +497,7 @@ WgradGroup wgrad_group(const uniter_model* m, const Plan& pl, int l, int cu_rese
     // UNITER_WGRAD_X3_WGS = n forces a grid for every layer (0 = one workgroup per CU); unset, layer 0 takes the smallest grid that
     // needs no more rounds (switches.h) and every other layer one workgroup per CU
     g.max_wgs = sw.wgrad_x3_wgs >= 0 ? sw.wgrad_x3_wgs : (l == 0 ? gemm_x3_wgrad_group_balanced_wgs(0, 4, Mo, No, cu_reserve) : 0);
-    if (g.riders) g.slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, g.max_wgs, pl.M, pl.sk_side ? pl.sk_bytes : 0, cu_reserve);
+    if (g.riders) g.slots = gemm_x3_wgrad_group_slots(0, 4, Mo, No, g.max_wgs, pl.M, (pl.sk_side && !own_k) ? pl.sk_bytes : 0, cu_reserve);
     return g;
   }
   // precision 2: riders only on UNITER_B16_RIDERS=1 -- except with the launch on the persistent 128 x 256-tile kernel (UNITER_B16_PERSIST
@@ -514,31 +549,36 @@ static const unsigned char* hid_keep_bits(const Plan& pl, int l, int second) {
 // Dropout + residual + LayerNorm behind layer l's attention output (second = 0) or FFN output (second = 1): t is `pieces` k-piece slabs
 // of the product in front [M][H] each (one slab: stride 0, as uniter_ln_fwd_b16 passes it); y.b takes the operand copy of the result where the plan has one.  mean / rstd are kept
 // only by a pass that saves for a backward pass.
+// rows > 0: a pass over that many compacted rows, row r standing for row r * row_step of the plan's M (its dropout draw; head rows only)
 int ln_fwd(uniter_model* m, hipStream_t st, int l, int second, const float* t, int pieces, const float* resid, float* z,
-           Act y, float* mean, float* rstd, float ph) {
+           Act y, float* mean, float* rstd, float ph, int rows = 0, int row_step = 1) {
   const Plan& pl = m->plan;
   const bool save = pl.mode != 0;
+  const int M = rows > 0 ? rows : pl.M;
   const int g = second ? L_LN2_G : L_LN1_G;      // (its bias follows it)
   const int H = m->cfg.hidden_size;
   ProfScope ps(m, UNITER_K_LN, st);
   LnCall c;
-  c.x = t; c.nslab = pieces; c.slab_stride = pieces > 1 ? (size_t)pl.M * H : 0; c.res = resid; c.gamma = m->LP(l, g); c.beta = m->LP(l, g + 1);
-  c.z = z; c.out = y.f; c.copy = y.b; c.pieces = pl.prec == PREC_X3 ? 3 : 1; c.M = pl.M; c.H = H; c.stream = st;
+  c.x = t; c.nslab = pieces; c.slab_stride = pieces > 1 ? (size_t)M * H : 0; c.res = resid; c.gamma = m->LP(l, g); c.beta = m->LP(l, g + 1);
+  c.z = z; c.out = y.f; c.copy = y.b; c.pieces = pl.prec == PREC_X3 ? 3 : 1; c.M = M; c.H = H; c.stream = st;
+  c.drop_row_step = row_step;
   if (save) { c.mean = mean; c.rstd = rstd; }
   c.drop = {ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), hid_keep_bits(pl, l, second)};
   return ln_fwd_run(c);
 }
 // its backward row pass: dy is `pieces` slabs [M][H]; g takes the dropped gradient (fp32 and / or operand copy), ws the column partials
 int ln_bwd(uniter_model* m, hipStream_t st, int l, int second, const float* dy, int pieces, const float* z, const float* mean,
-           const float* rstd, float* dz, Act g, void* ws, float ph) {
+           const float* rstd, float* dz, Act g, void* ws, float ph, int rows = 0, int row_step = 1) {
   const Plan& pl = m->plan;
   const int H = m->cfg.hidden_size;
+  const int M = rows > 0 ? rows : pl.M;
   ProfScope ps(m, UNITER_K_LN_BWD, st);
   LnCall c;
-  c.x = dy; c.nslab = pieces; c.slab_stride = (size_t)pl.M * H; c.gamma = m->LP(l, second ? L_LN2_G : L_LN1_G);
+  c.x = dy; c.nslab = pieces; c.slab_stride = (size_t)M * H; c.gamma = m->LP(l, second ? L_LN2_G : L_LN1_G);
   c.z = const_cast<float*>(z); c.mean = const_cast<float*>(mean); c.rstd = const_cast<float*>(rstd);      // (read only)
   c.dz = dz; c.out = g.f; c.copy = g.b; c.pieces = pl.prec == PREC_X3 ? 3 : 1; c.want_dbias = 1;
-  c.M = pl.M; c.H = H; c.ws = ws; c.ws_bytes = pl.ln_ws_bytes; c.stream = st;
+  c.M = M; c.H = H; c.ws = ws; c.ws_bytes = rows > 0 ? uniter_ln_bwd_ws_bytes(M, H) : pl.ln_ws_bytes; c.stream = st;
+  c.drop_row_step = row_step;
   c.drop = {ph, m->seed, m->offset, second ? SITE_FFN_OUT(l) : SITE_ATTN_OUT(l), hid_keep_bits(pl, l, second)};      // (the forward pass's flags)
   return ln_bwd_rows_run(c);
 }
@@ -566,7 +606,8 @@ static ImgEmbedCall img_embed_call(const uniter_model* m, const uniter_batch_t& 
 // The four weight gradients of a layer in PREC_BF16 / PREC_X3, dW[p] [Mo[p], No[p]] += A[p]^T B[p] over the plan's M rows, in the grouped
 // launch's order {W1, W2, QKV, attention output}.  Product 0 must be dW1 = dU^T y1: its A operand's column sums are intermediate.dense's
 // bias gradient
-struct WgradProducts { int Mo[4], No[4]; const void *A[4], *B[4]; float* dW[4]; };
+// K[p]: product p's reduction length -- the plan's M, or B for the products of a last layer that ran on its head rows
+struct WgradProducts { int Mo[4], No[4]; const void *A[4], *B[4]; float* dW[4]; int K[4]; };
 // product p alone in PREC_BF16 (both operands k-major): split-K slabs + one reduce pass where that beats stream-K atomics into the
 // gradient buffer (gemm_bf16.hip)
 int wgrad_b16(uniter_model* m, const Plan& pl, hipStream_t st, const WgradProducts& t, int p) {
@@ -595,28 +636,70 @@ int wgrad_launch(uniter_model* m, int l, hipStream_t sd, const WgradProducts& t,
                  uniter_x3_riders_t* riders, bool colsum_after) {
   const Plan& pl = m->plan;
   const bool x3 = pl.prec == PREC_X3;
-  int Mo[4], No[4];
+  int Mo[4], No[4], Kp[4];
   const void *A[4], *B[4];
   float* dW[4];
-  for (int i = 0; i < n; ++i) { Mo[i] = t.Mo[idx[i]]; No[i] = t.No[idx[i]]; A[i] = t.A[idx[i]]; B[i] = t.B[idx[i]]; dW[i] = t.dW[idx[i]]; }
+  bool own_k = false;      // some product's reduction length is not the plan's M
+  for (int i = 0; i < n; ++i) {
+    Mo[i] = t.Mo[idx[i]]; No[i] = t.No[idx[i]]; A[i] = t.A[idx[i]]; B[i] = t.B[idx[i]]; dW[i] = t.dW[idx[i]]; Kp[i] = t.K[idx[i]];
+    own_k = own_k || Kp[i] != pl.M;
+  }
   WgradGroupCall c;
-  c.n = n; c.Mo = Mo; c.No = No; c.K = pl.M; c.A = A; c.B = B; c.dW = dW; c.overwrite = m->wg_overwrite ? 1 : 0; c.max_wgs = max_wgs;
+  c.n = n; c.Mo = Mo; c.No = No; c.K = pl.M; c.Kp = own_k ? Kp : nullptr; c.A = A; c.B = B; c.dW = dW; c.overwrite = m->wg_overwrite ? 1 : 0; c.max_wgs = max_wgs;
   c.riders = riders; c.stream = sd;
   {
     ProfScope ps(m, UNITER_K_GEMM_WGRAD, sd);
     const LaunchOpts lo = {ps.stamp, 0, m->launch_reserve};
     if (x3) {
-      c.sk_ws = pl.sk_side; c.sk_ws_bytes = pl.sk_side ? pl.sk_bytes : 0;
+      c.sk_ws = own_k ? nullptr : pl.sk_side; c.sk_ws_bytes = c.sk_ws ? pl.sk_bytes : 0;
       UCHECK_RC(gemm_x3_wgrad_group(cfg, c, lo));
     } else UCHECK_RC(gemm_bf16v2_wgrad_group(cfg, c, lo));
   }
   if (!colsum_after) return 0;
+  const int rows = t.K[0];      // dU's rows (B behind a last layer on its head rows, whose dU column-partial buffer is the compact one)
   if (pl.det) {      // in a fixed order; the block partials go to the layer's dU column-partial buffer, which nothing else uses without riders
-    const LayerBufs& lb = pl.layers[l];
-    return (x3 ? uniter_colsum_x3_add_det : uniter_colsum_bf16_add_det)(t.A[0], pl.M, t.Mo[0], t.Mo[0], m->LG(l, L_B1), lb.du_csum,
-                                                                       du_csum_bytes(pl.M, t.Mo[0]), sd);
+    const LayerBufs& lb = rows != pl.M ? pl.hr : pl.layers[l];
+    return (x3 ? uniter_colsum_x3_add_det : uniter_colsum_bf16_add_det)(t.A[0], rows, t.Mo[0], t.Mo[0], m->LG(l, L_B1), lb.du_csum,
+                                                                       du_csum_bytes(rows, t.Mo[0]), sd);
   }
-  return (x3 ? uniter_colsum_x3_add : uniter_colsum_bf16_add)(t.A[0], pl.M, t.Mo[0], t.Mo[0], m->LG(l, L_B1), sd);      // intermediate.dense bias gradient
+  return (x3 ? uniter_colsum_x3_add : uniter_colsum_bf16_add)(t.A[0], rows, t.Mo[0], t.Mo[0], m->LG(l, L_B1), sd);      // intermediate.dense bias gradient
+}
+
+// Head rows only: rows b * L of a [B * L][cols] matrix into a compact [B][cols] one (gather), or back into their places (scatter);
+// row_bytes = one row's bytes
+int head_rows_gather(void* dst, const void* src, int B, int L, size_t row_bytes, hipStream_t st) {
+  UCHECK_HIP(hipMemcpy2DAsync(dst, row_bytes, src, (size_t)L * row_bytes, row_bytes, (size_t)B, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+int head_rows_scatter(void* dst, const void* src, int B, int L, size_t row_bytes, hipStream_t st) {
+  UCHECK_HIP(hipMemcpy2DAsync(dst, (size_t)L * row_bytes, src, row_bytes, row_bytes, (size_t)B, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+// The last layer's forward pass behind its attention kernel on the head rows (Plan::head_rows): the products with M = B and k-pieces
+// of their own (Plan::hr_ns_h / hr_ns_i; the plan's other slab counts were picked for M = B * L), the row passes drawing row b * L's dropout, the B result rows into a
+// zero-filled hidden_out.  x: the layer's input.
+int head_rows_forward(uniter_model* m, hipStream_t st, int l, Act x, float* hidden_out, float ph) {
+  Plan& pl = m->plan;
+  const int H = m->cfg.hidden_size, I = m->cfg.intermediate_size, B = pl.B, L = pl.L;
+  const LayerBufs& lb = pl.layers[l];
+  LayerBufs& h = pl.hr;
+  const bool save = pl.mode != 0;
+  const size_t rowb = (size_t)H * sizeof(float);
+  UCHECK_RC(head_rows_gather(h.ctx, lb.ctx, B, L, rowb, st));
+  UCHECK_RC(head_rows_gather(pl.hr_x, x.f, B, L, rowb, st));
+  const Act ctx = {h.ctx, h.ctxb}, y1 = {h.y1, h.y1b}, hact = {h.hact, h.hactb};
+  UCHECK_RC(operand_copy(pl, ctx, B, H, st));
+  UCHECK_RC(linear(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, B, H, H, l, L_OW, ctx, Act{h.t1, nullptr}, pl.hr_ns_h, UNITER_EPI_BIAS, m->LP(l, L_OB), nullptr,
+                   nullptr));
+  UCHECK_RC(ln_fwd(m, st, l, 0, h.t1, pl.hr_ns_h, pl.hr_x, h.z1, y1, h.mean1, h.rstd1, ph, B, L));
+  float* gelu_aux = save ? h.u : h.hact;      // (as in the full pass: a pass that saves nothing parks gelu'(u) in the unused fp32 buffer)
+  UCHECK_RC(linear(m, UNITER_K_GEMM_FFN_UP_FWD, st, 0, B, I, H, l, L_W1, y1, hact, 1, UNITER_EPI_BIAS_GELU_D, m->LP(l, L_B1), nullptr, gelu_aux));
+  UCHECK_RC(linear(m, UNITER_K_GEMM_FFN_DOWN_FWD, st, 0, B, H, I, l, L_W2, hact, Act{h.t2, nullptr}, pl.hr_ns_i, UNITER_EPI_BIAS, m->LP(l, L_B2), nullptr,
+                   nullptr));
+  UCHECK_RC(ln_fwd(m, st, l, 1, h.t2, pl.hr_ns_i, h.y1, h.z2, Act{h.y2, nullptr}, h.mean2, h.rstd2, ph, B, L));
+  // every other row of the output: exact zeros (a caller's hook never sees uninitialised rows)
+  UCHECK_HIP(hipMemsetAsync(hidden_out, 0, (size_t)B * L * rowb, st));
+  return head_rows_scatter(hidden_out, h.y2, B, L, rowb, st);
 }
 
 int validate_batch(const uniter_model* m, const uniter_batch_t* b) {
@@ -755,7 +838,8 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
                                     int all_layers, int train, uint64_t seed, uint32_t offset, void* ws,
                                     size_t ws_bytes, void* stream) {
   uniter_model::AttnProbs ap;      // uniter_model_set_attn_probs: this pass's, forgotten whatever becomes of the pass
-  if (m) { ap = m->ap_next; m->ap_next = uniter_model::AttnProbs(); }
+  bool head_rows_req = false;      // uniter_model_set_head_rows: this pass's, likewise
+  if (m) { ap = m->ap_next; m->ap_next = uniter_model::AttnProbs(); head_rows_req = m->head_rows_next; m->head_rows_next = false; }
   UCHECK_ARG(m && hidden_out && ws, "model_forward: null pointer");
   m->launch_reserve = 0;      // (no collective of this step is in flight during its forward pass: the reserve is the backward pass's)
   UCHECK_ARG(train >= 0 && train <= 2, "model_forward: train must be 0, 1 or 2");
@@ -862,6 +946,12 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     pl.hid_on = true;
   }
 
+  // Head rows only (uniter_model_set_head_rows): honoured where the plan carved the compact buffers (precision 3, padded batch) and the
+  // pass has one output layer.  The schedule switches that are bit-neutral on the full path stay so here: keep flags of the hidden
+  // dropout drawn ahead are addressed by the original row's group index (LnCall::drop_row_step), an attention-gradient capture reads
+  // the zero-filled full-size gradient of the context, and the balanced walk's workspaces go to the products that can use them
+  pl.head_rows = head_rows_req && pl.prec == PREC_X3 && !packed && pl.hr.ctx && !all_layers;
+
   // parameters still being written by an optimizer step on another stream (uniter_model_set_ready_events)
   // ready = [embeddings, layer 0 .. nl-1] or, with one more event, [embeddings WITHOUT the word table, layers.., word table]:
   // the image branch (region projection, 3 LayerNorms) then runs while the optimizer still streams the 89-MB word table
@@ -949,6 +1039,10 @@ extern "C" int uniter_model_forward(uniter_model_t* m, const uniter_batch_t* b, 
     if (ap.out)
       UCHECK_RC(uniter_attn_probs(lb.qkv, attn_b16 ? 1 : 0, mask, cu_seqlens, ap.out + (size_t)l * ap.stride, B, L, nh, ap.head_mean, st));
     // the context's operand copy: operand of the projection below and of its weight gradient
+    if (pl.head_rows && l == nl - 1) {      // the rest of the last layer on the rows the caller reads
+      UCHECK_RC(head_rows_forward(m, st, l, x, hidden_out, ph));
+      break;
+    }
     const Act ctx = {lb.ctx, lb.ctxb}, y1 = {lb.y1, lb.y1b}, hact = {lb.hact, lb.hactb};
     if (ctx_copy) UCHECK_RC(operand_copy(pl, ctx, M, H, st));
     UCHECK_RC(linear(m, UNITER_K_GEMM_ATTN_OUT_FWD, st, 0, M, H, H, l, L_OW, ctx, Act{lb.t1, nullptr}, pl.ns_kh, UNITER_EPI_BIAS,
@@ -1024,7 +1118,15 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
       dh = pl.dpk;
     }
   }
-  if (l == nl - 1) {
+  // the last layer of a plan that ran on its head rows (Plan::head_rows): the stretch in front of the attention backward on pl.hr's
+  // B rows -- pb, Mp rows, row r standing for row r * row_step; every other layer: the layer's own buffers, M rows
+  const bool hr = pl.head_rows && l == nl - 1;
+  LayerBufs& pb = hr ? pl.hr : lb;
+  const int Mp = hr ? B : M, row_step = hr ? L : 1;
+  if (hr) {
+    UCHECK_RC(head_rows_gather(pl.hr_dy, dh, B, L, (size_t)H * sizeof(float), st));
+    dy = pl.hr_dy;
+  } else if (l == nl - 1) {
     dy = dh;
   } else if (m->all_layers) {
     UCHECK_RC(launch_add_f32(pl.dsum, pl.layers[l + 1].dx, dh, MH, st));
@@ -1035,13 +1137,13 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // the dropped gradient in fp32: the operand of the fp32 GEMMs; the bf16-resident GEMMs read its bf16 copy only, so
   // the fp32 store (8 MB per pass) is skipped there
   const bool copies = pl.copies();
-  const Act g2 = {ph > 0.f ? (copies ? nullptr : lb.g2) : lb.dz2, lb.g2b};
-  const Act g1 = {ph > 0.f ? (copies ? nullptr : lb.g1) : lb.dz1, lb.g1b};
+  const Act g2 = {ph > 0.f ? (copies ? nullptr : pb.g2) : pb.dz2, pb.g2b};
+  const Act g1 = {ph > 0.f ? (copies ? nullptr : pb.g1) : pb.dz1, pb.g1b};
   // precision 2: the next layer's dx may be split-K slabs (summed here); never for the last layer (dy is the caller's
   // gradient), with all_layers (dy is dsum) or in layer 0 (the embedding backward reads a plain dx)
   const int ns_dy = (l == nl - 1 || m->all_layers) ? 1 : pl.ns_k3h;
   const int ns_dx = (l == 0 || m->all_layers) ? 1 : pl.ns_k3h;
-  UCHECK_RC(ln_bwd(m, st, l, 1, dy, ns_dy, lb.z2, lb.mean2, lb.rstd2, lb.dz2, g2, lb.ln_ws2, ph));
+  UCHECK_RC(ln_bwd(m, st, l, 1, dy, ns_dy, pb.z2, pb.mean2, pb.rstd2, pb.dz2, g2, pb.ln_ws2, ph, hr ? Mp : 0, row_step));
   // FFN down dgrad (+ GELU'), FFN up dgrad (+ residual grad)
   // the GEMM's epilogue also emits per-32-row column sums of du (= partial bias gradients of
   // intermediate.dense): saves a 32 MB re-read of du
@@ -1052,22 +1154,24 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // query|key|value bias gradient before its sum over the batch): no 24 MB re-read of dqkv
   const bool fused_qb = pl.attn_bwd != ATTN_F32;
   // precision 3 with the x3 attention backward: the attention-output input gradient leaves as k-pieces (the kernel sums them)
-  const int ns_dctx = (pl.attn_bwd == ATTN_X3 && sw.dctx_split) ? pl.ns_kh_b : 1;
+  // (head rows: one slab -- it is placed into the zero-filled full-size buffer the attention backward reads)
+  const int ns_dctx = hr ? 1 : (pl.attn_bwd == ATTN_X3 && sw.dctx_split) ? pl.ns_kh_b : 1;
+  const int ns_dy1 = hr ? pl.hr_ns_i : pl.ns_ki_b;
   const int epi_du = pl.gelu_d ? UNITER_EPI_MUL : UNITER_EPI_DGELU;
   // what rides on the layer's grouped weight-gradient launch (precisions 2 and 3), and that launch's geometry
-  const WgradGroup wg = copies ? wgrad_group(m, pl, l, m->launch_reserve) : WgradGroup();
+  const WgradGroup wg = copies ? wgrad_group(m, pl, l, m->launch_reserve, hr && Mp != M) : WgradGroup();
   // dU = (g2 . W2) * gelu'(u): with operand copies it exists only as one (operand of the next product and of intermediate.dense's weight
   // gradient).  Its column sums (that layer's bias gradient) start here as column partials: per 32 rows in the fp32 kernels; with operand
   // copies only when riders of the 128 x 256 weight-gradient geometry finish them (one row of partial sums per 64 rows of dU)
-  const Act du = {lb.du, lb.dub}, dqkv = {lb.dqkv, lb.dqkvb};
-  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, I, H, l, L_W2, g2, du, 1, epi_du, nullptr, lb.u, nullptr,
-                   (copies ? wg.colpart : fuse_db1) ? lb.du_csum : nullptr));
-  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, I, l, L_W1, du, Act{lb.dy1, nullptr}, pl.ns_ki_b, UNITER_EPI_ADD, nullptr, lb.dz2,
+  const Act du = {pb.du, pb.dub}, dqkv = {lb.dqkv, lb.dqkvb};
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, Mp, I, H, l, L_W2, g2, du, 1, epi_du, nullptr, pb.u, nullptr,
+                   (copies ? wg.colpart : fuse_db1) ? pb.du_csum : nullptr));
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, Mp, H, I, l, L_W1, du, Act{pb.dy1, nullptr}, ns_dy1, UNITER_EPI_ADD, nullptr, pb.dz2,
                    nullptr));
-  UCHECK_RC(ln_bwd(m, st, l, 0, lb.dy1, pl.ns_ki_b, lb.z1, lb.mean1, lb.rstd1, lb.dz1, g1, lb.ln_ws1, ph));
-  // the layer's weight gradients in precisions 2 and 3 (WgradProducts)
-  const WgradProducts wp = {{I, H, 3 * H, H}, {H, I, H, H}, {lb.dub, lb.g2b, lb.dqkvb, lb.g1b}, {lb.y1b, lb.hactb, x.b, lb.ctxb},
-                            {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)}};
+  UCHECK_RC(ln_bwd(m, st, l, 0, pb.dy1, ns_dy1, pb.z1, pb.mean1, pb.rstd1, pb.dz1, g1, pb.ln_ws1, ph, hr ? Mp : 0, row_step));
+  // the layer's weight gradients in precisions 2 and 3 (WgradProducts): the query|key|value one always reduces over the plan's M rows
+  const WgradProducts wp = {{I, H, 3 * H, H}, {H, I, H, H}, {pb.dub, pb.g2b, lb.dqkvb, pb.g1b}, {pb.y1b, pb.hactb, x.b, pb.ctxb},
+                            {m->LG(l, L_W1), m->LG(l, L_W2), m->LG(l, L_QW), m->LG(l, L_OW)}, {Mp, Mp, M, Mp}};
   const int wp_all[4] = {0, 1, 2, 3}, wp_early[3] = {0, 1, 3}, wp_late[1] = {2};
   const bool wg_early = pl.prec == PREC_BF16 && pl.wg_group >= 2 && sd != st;
   if (wg_early) {
@@ -1078,8 +1182,17 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
     UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_early, 3, 1, 0, nullptr, true));
   }
   // (two k-pieces when the x3 attention backward follows: it sums the slabs while it reads them -- 126 tiles do not fill the chip)
-  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, M, H, H, l, L_OW, g1, Act{lb.dctx, nullptr}, ns_dctx, UNITER_EPI_NONE, nullptr, nullptr,
+  UCHECK_RC(linear(m, UNITER_K_GEMM_DGRAD, st, 1, Mp, H, H, l, L_OW, g1, Act{pb.dctx, nullptr}, ns_dctx, UNITER_EPI_NONE, nullptr, nullptr,
                    nullptr));
+  if (hr) {
+    // what the attention backward and the QKV input gradient read over all M rows -- the context's gradient and the residual branch's
+    // gradient lb.dz1 -- is zero outside the head rows: zero-fill, then the B rows into their places
+    const size_t rowb = (size_t)H * sizeof(float);
+    UCHECK_HIP(hipMemsetAsync(lb.dctx, 0, MH * sizeof(float), st));
+    UCHECK_RC(head_rows_scatter(lb.dctx, pb.dctx, B, L, rowb, st));
+    UCHECK_HIP(hipMemsetAsync(lb.dz1, 0, MH * sizeof(float), st));
+    UCHECK_RC(head_rows_scatter(lb.dz1, pb.dz1, B, L, rowb, st));
+  }
   // the gradient-weighted attention as an output (uniter_model_set_attn_grads): here, because only between the product that wrote
   // dctx and the attention backward that consumes it do this layer's qkv and dctx both hold what the pass computed
   if (m->ag.out) {
@@ -1124,10 +1237,10 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
   // LayerNorm / dense-bias gradients: the column reductions of the two row passes above, the attention backward's
   // per-sample query|key|value bias partials and (fp32 mode) the dU column partials -- ONE launch for all of them
   if (!wg.riders) {
-    const int lnp = ln_bwd_partial_rows(M);
-    const float* parts[4] = {(const float*)lb.ln_ws2, (const float*)lb.ln_ws1, fused_qb ? lb.qb_part : nullptr,
-                             (!copies && fuse_db1) ? lb.du_csum : nullptr};
-    const int nparts[4] = {lnp, lnp, B, (M + 31) / 32};
+    const int lnp = ln_bwd_partial_rows(Mp);
+    const float* parts[4] = {(const float*)pb.ln_ws2, (const float*)pb.ln_ws1, fused_qb ? lb.qb_part : nullptr,
+                             (!copies && fuse_db1) ? pb.du_csum : nullptr};
+    const int nparts[4] = {lnp, lnp, B, (Mp + 31) / 32};
     const size_t strides[4] = {(size_t)3 * H, (size_t)3 * H, (size_t)3 * H, (size_t)I};
     float* const outs[4][3] = {{m->LG(l, L_LN2_G), m->LG(l, L_LN2_B), m->LG(l, L_B2)},
                                {m->LG(l, L_LN1_G), m->LG(l, L_LN1_B), m->LG(l, L_OB)},
@@ -1150,8 +1263,13 @@ extern "C" int uniter_model_backward_layer(uniter_model_t* m, int l) {
         UCHECK_ARG((size_t)wg.slots <= m->norm_stride, "backward_layer: %d clip-norm slots per layer, room for %zu (uniter_model_set_norm_partials)",
                    wg.slots, m->norm_stride);
         riders.ssq = m->norm_parts + (size_t)l * m->norm_stride;
+        // (a launch that left the balanced walk fills fewer slots than the layer's launch on the walk would: the rest read as zero)
+        const int walk = (hr && pl.sk_side) ? wgrad_group(m, pl, l, m->launch_reserve).slots : wg.slots;
+        if (walk > wg.slots && (size_t)walk <= m->norm_stride) UCHECK_HIP(hipMemsetAsync(riders.ssq + wg.slots, 0, (size_t)(walk - wg.slots) * sizeof(double), sd));
       }
-      fill_layer_riders(riders, m, l, lb, M, B, H, fused_qb, wg.colpart);
+      LayerBufs rb = pb;      // (the row passes' and dU's column partials: Mp rows' worth; the attention backward's bias partials: the layer's own)
+      rb.qb_part = lb.qb_part;
+      fill_layer_riders(riders, m, l, rb, Mp, B, H, fused_qb, wg.colpart);
     }
     UCHECK_RC(wgrad_launch(m, l, sd, wp, wp_all, 4, wg.cfg, wg.max_wgs, wg.riders ? &riders : nullptr, !wg.riders));
   } else if (pl.prec == PREC_BF16) {
@@ -1287,6 +1405,7 @@ extern "C" int uniter_model_backward_end(uniter_model_t* m) {
   m->wg_overwrite = false;       // one backward pass: the next one accumulates again
   m->ig = uniter_model::InputGrads();      // ... and the input gradients were this pass's (uniter_model_set_input_grads)
   m->ag = uniter_model::AttnGrads();       // ... and so was the attention-gradient capture (uniter_model_set_attn_grads)
+  // (Plan::head_rows stays: it says which of the plan's buffers the forward pass wrote, until the next forward pass remakes the plan)
   return 0;
 }
 
@@ -1341,6 +1460,12 @@ extern "C" int uniter_model_set_attn_probs(uniter_model_t* m, float* out, size_t
   UCHECK_ARG(m, "set_attn_probs: null model");
   UCHECK_ARG(((uintptr_t)out & 3) == 0, "set_attn_probs: out must be 4-byte aligned");
   m->ap_next.out = out; m->ap_next.stride = out ? layer_stride_elems : 0; m->ap_next.head_mean = head_mean ? 1 : 0;
+  return 0;
+}
+
+extern "C" int uniter_model_set_head_rows(uniter_model_t* m, int on) {
+  UCHECK_ARG(m, "set_head_rows: null model");
+  m->head_rows_next = on != 0;
   return 0;
 }
 

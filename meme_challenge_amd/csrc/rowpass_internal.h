@@ -40,6 +40,7 @@ struct LnCall {
   int want_dbias = 0;
   int M = 0, H = 0;
   DropSite drop;
+  int drop_row_step = 1;             // row r draws the dropout of row r * drop_row_step of the site (a pass over every step-th row, compacted)
   void* ws = nullptr;
   size_t ws_bytes = 0;
   void* stream = nullptr;

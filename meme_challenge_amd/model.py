@@ -706,6 +706,10 @@ class _UniterFn(torch.autograd.Function):
             # UniterModel.output_attentions: a setting for THIS forward pass alone (the handle forgets it when the pass returns)
             check(lib.uniter_model_set_attn_probs(model._handle, ptr(attn), attn[0].numel(), int(attn.dim() == 4)),
                   'uniter_model_set_attn_probs')
+        if model.__dict__.pop('_head_rows_next', False):
+            # MemeUniter: the caller reads row 0 of every sample and nothing else, a request for THIS forward pass and its backward pass
+            # (the library honours it where it can -- fp32x3, padded batch -- and ignores it elsewhere)
+            check(lib.uniter_model_set_head_rows(model._handle, 1), 'uniter_model_set_head_rows')
         ctx.attn_grads = ag = model.__dict__.pop('_attn_grads_next', None)
         if ag is not None:
             # UniterModel.output_attention_grads: a setting for THIS forward pass and its backward pass (maps, head sums, workspace)
@@ -1266,6 +1270,7 @@ class UniterModel(UniterPreTrainedModel):
         finally:
             self.__dict__.pop('_attn_next', None)
             self.__dict__.pop('_attn_grads_next', None)
+            self.__dict__.pop('_head_rows_next', None)
         self.last_attentions = attn
         if output_all_encoded_layers:
             return [hidden[i] for i in range(self.config.num_hidden_layers)]
