@@ -45,45 +45,62 @@ __device__ __forceinline__ int regions_of(const CollateArgs& a, long long s) {
   return n < 0 ? 0 : (n > a.R ? a.R : n);
 }
 
-__global__ __launch_bounds__(256) void collate_batch_kernel(const CollateArgs a) {
-  const int lane = threadIdx.x & 63;
-  if (blockIdx.x < a.region_blocks) {
-    const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (item >= a.region_items) return;
-    const long long row = item / a.pieces;             // b * R + r
-    const int piece = (int)(item - row * a.pieces);
-    const int b = (int)(row / a.R), r = (int)(row - (long long)b * a.R);
-    const long long s = sample_of(a, b);
-    const long long src_row = a.ds.row_start[s] + r;
-    // a pool row outside the pool reads as padding (never dereferenced)
-    const bool real = r < regions_of(a, s) && src_row >= 0 && src_row < a.ds.pool_rows;
-    f32x4* dp = reinterpret_cast<f32x4*>(a.img_feat) + (size_t)row * a.D4;
-    const int c0 = piece * PIECE4 + lane;
-    f32x4 v[4];
+// ---- the pieces every collate kernel is built from ---------------------------------------------------------------------------
+// A region item decoded: output row b * R + r, the 4-KB piece of it, the dataset sample s with its n regions and the pool row.
+struct RegionItem {
+  long long row, s, src_row;
+  int piece, b, r, n;
+  bool real;                           // a pool row outside the pool reads as padding (never dereferenced)
+};
+// the item of this wave (four per workgroup); false beyond the last one.  Uniform over the wave.
+__device__ __forceinline__ bool region_item(const CollateArgs& a, RegionItem& it) {
+  const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= a.region_items) return false;
+  it.row = item / a.pieces;
+  it.piece = (int)(item - it.row * a.pieces);
+  it.b = (int)(it.row / a.R);
+  it.r = (int)(it.row - (long long)it.b * a.R);
+  it.s = sample_of(a, it.b);
+  it.src_row = a.ds.row_start[it.s] + it.r;
+  it.n = regions_of(a, it.s);
+  it.real = it.r < it.n && it.src_row >= 0 && it.src_row < a.ds.pool_rows;
+  return true;
+}
+// the lane's four float4 of the item: the pool row's when `take`, else zeros; all four loads are issued before anything is stored
+__device__ __forceinline__ void piece_load(const CollateArgs& a, const RegionItem& it, bool take, int lane, f32x4 (&v)[4]) {
+  const int c0 = it.piece * PIECE4 + lane;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (real) {
-      const f32x4* sp = reinterpret_cast<const f32x4*>(a.ds.feat) + (size_t)src_row * a.D4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + 64 * k < a.D4) v[k] = sp[c0 + 64 * k];
-    }
+  for (int k = 0; k < 4; ++k) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (take) {
+    const f32x4* sp = reinterpret_cast<const f32x4*>(a.ds.feat) + (size_t)it.src_row * a.D4;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (c0 + 64 * k < a.D4) dp[c0 + 64 * k] = v[k];
-    if (piece == 0 && lane < 7)
-      a.img_pos_feat[(size_t)row * 7 + lane] = real ? a.ds.pos[(size_t)src_row * 7 + lane] : 0.f;
-    return;
+      if (c0 + 64 * k < a.D4) v[k] = sp[c0 + 64 * k];
   }
-  const int b = (int)(blockIdx.x - a.region_blocks);
-  const long long s = sample_of(a, b);
+}
+// ... to the item's piece of row `row` of `base` (rows of D floats: img_feat, feat_targets)
+__device__ __forceinline__ void piece_store(const CollateArgs& a, const RegionItem& it, int lane, float* base, long long row,
+                                            const f32x4 (&v)[4]) {
+  f32x4* dp = reinterpret_cast<f32x4*>(base) + (size_t)row * a.D4;
+  const int c0 = it.piece * PIECE4 + lane;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (c0 + 64 * k < a.D4) dp[c0 + 64 * k] = v[k];
+}
+// the row's 7 box features, by the wave of its first piece
+__device__ __forceinline__ void box_row(const CollateArgs& a, const RegionItem& it, int lane) {
+  if (it.piece == 0 && lane < 7)
+    a.img_pos_feat[(size_t)it.row * 7 + lane] = it.real ? a.ds.pos[(size_t)it.src_row * 7 + lane] : 0.f;
+}
+// What the workgroup of sample b writes in every entry: position_ids, token_type_ids, attn_mask, gather_index, the label and the
+// id of sample s, for the text of sample ts (tl tokens) and il image positions.  copy_text: input_ids as well (the text unchanged).
+__device__ __forceinline__ void sample_frame(const CollateArgs& a, int b, long long s, long long ts, long long tl, long long il,
+                                             bool copy_text) {
   const int T = a.ds.T;
-  const long long tl = a.ds.txt_len[s];
-  const long long il = a.ragged ? regions_of(a, s) : a.R;
   for (int t = threadIdx.x; t < T; t += 256) {
-    a.input_ids[(size_t)b * T + t] = a.ds.input_ids[(size_t)s * T + t];
+    if (copy_text) a.input_ids[(size_t)b * T + t] = a.ds.input_ids[(size_t)ts * T + t];
     a.position_ids[(size_t)b * T + t] = t;
-    if (a.token_type_ids) a.token_type_ids[(size_t)b * T + t] = a.ds.token_type_ids[(size_t)s * T + t];
+    if (a.token_type_ids) a.token_type_ids[(size_t)b * T + t] = a.ds.token_type_ids[(size_t)ts * T + t];
   }
   for (int j = threadIdx.x; j < a.L_out; j += 256) {
     a.attn_mask[(size_t)b * a.L_out + j] = j < tl + il ? 1.0f : 0.0f;
@@ -95,39 +112,70 @@ __global__ __launch_bounds__(256) void collate_batch_kernel(const CollateArgs a)
   }
 }
 
+__global__ __launch_bounds__(256) void collate_batch_kernel(const CollateArgs a) {
+  const int lane = threadIdx.x & 63;
+  if (blockIdx.x < a.region_blocks) {
+    RegionItem it;
+    if (!region_item(a, it)) return;
+    f32x4 v[4];
+    piece_load(a, it, it.real, lane, v);
+    piece_store(a, it, lane, a.img_feat, it.row, v);
+    box_row(a, it, lane);
+    return;
+  }
+  const int b = (int)(blockIdx.x - a.region_blocks);
+  const long long s = sample_of(a, b);
+  sample_frame(a, b, s, s, a.ds.txt_len[s], a.ragged ? regions_of(a, s) : a.R, true);
+}
+
+// ---- the host side every entry shares ----------------------------------------------------------------------------------------
+// The checks of the dataset, the shapes and the nine common outputs (already in c), under the entry's name.
+int check_common(const char* who, const uniter_dataset_t* ds, const CollateArgs& c) {
+  const int B = c.B, R = c.R, L_out = c.L_out;
+  UCHECK_ARG(ds && c.sel, "%s: null dataset or selection", who);
+  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids, "%s: null pointer in the dataset", who);
+  UCHECK_ARG(c.input_ids && c.position_ids && c.attn_mask && c.gather_index && c.labels && c.ids, "%s: null output pointer", who);
+  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "%s: dataset of %lld samples, %lld pool rows", who, (long long)ds->N, (long long)ds->pool_rows);
+  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0, "%s: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)", who, B, ds->T,
+               L_out, R);
+  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "%s: L_out = %d exceeds T + R = %d + %d", who, L_out, ds->T, R);
+  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "%s: D = %d must be a positive multiple of 4 (rows move as 16-byte items)", who, ds->D);
+  // an empty pool (every sample's confidence filter left nothing) has no rows to point at; R == 0 has no region output
+  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "%s: null feat / pos with %lld pool rows", who, (long long)ds->pool_rows);
+  UCHECK_ARG((c.img_feat && c.img_pos_feat) || R == 0, "%s: null img_feat / img_pos_feat with R = %d", who, R);
+  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "%s: feat is not 16-byte aligned", who);
+  UCHECK_ARG(((uintptr_t)c.img_feat & 15) == 0, "%s: img_feat is not 16-byte aligned", who);
+  return 0;
+}
+
+// c from the arguments every entry has, checked (check_common, then the size of the launch); the grid is region_blocks + B
+int fill_args(const char* who, CollateArgs& c, const uniter_dataset_t* ds, const int64_t* sel, int B, int R, int L_out, int flags,
+              float* img_feat, float* img_pos_feat, int64_t* input_ids, int64_t* position_ids, int64_t* token_type_ids, float* attn_mask,
+              int64_t* gather_index, int64_t* labels, int64_t* ids) {
+  c.sel = sel; c.B = B; c.R = R; c.L_out = L_out; c.ragged = flags & 1;
+  c.img_feat = img_feat; c.img_pos_feat = img_pos_feat; c.input_ids = input_ids; c.position_ids = position_ids;
+  c.token_type_ids = token_type_ids; c.attn_mask = attn_mask; c.gather_index = gather_index; c.labels = labels; c.ids = ids;
+  UCHECK_RC(check_common(who, ds, c));
+  c.ds = *ds;
+  if (!ds->token_type_ids) c.token_type_ids = nullptr;
+  c.D4 = ds->D / 4;
+  c.pieces = (c.D4 + PIECE4 - 1) / PIECE4;
+  c.region_items = (long long)B * R * c.pieces;
+  const long long region_blocks = (c.region_items + 3) / 4;
+  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "%s: %lld region items exceed one launch", who, c.region_items);
+  c.region_blocks = (unsigned)region_blocks;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int uniter_collate_batch(const uniter_dataset_t* ds, const int64_t* sel, int B, int R, int L_out, int flags,
                                     float* img_feat, float* img_pos_feat, int64_t* input_ids, int64_t* position_ids,
                                     int64_t* token_type_ids, float* attn_mask, int64_t* gather_index, int64_t* labels,
                                     int64_t* ids, void* stream) {
-  UCHECK_ARG(ds && sel, "collate_batch: null dataset or selection");
-  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids,
-             "collate_batch: null pointer in the dataset");
-  UCHECK_ARG(input_ids && position_ids && attn_mask && gather_index && labels && ids, "collate_batch: null output pointer");
-  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "collate_batch: dataset of %lld samples, %lld pool rows", (long long)ds->N,
-             (long long)ds->pool_rows);
-  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0, "collate_batch: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)", B,
-               ds->T, L_out, R);
-  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "collate_batch: L_out = %d exceeds T + R = %d + %d", L_out, ds->T, R);
-  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "collate_batch: D = %d must be a positive multiple of 4 (rows move as 16-byte items)", ds->D);
-  // an empty pool (every sample's confidence filter left nothing) has no rows to point at; R == 0 has no region output
-  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "collate_batch: null feat / pos with %lld pool rows", (long long)ds->pool_rows);
-  UCHECK_ARG((img_feat && img_pos_feat) || R == 0, "collate_batch: null img_feat / img_pos_feat with R = %d", R);
-  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "collate_batch: feat is not 16-byte aligned");
-  UCHECK_ARG(((uintptr_t)img_feat & 15) == 0, "collate_batch: img_feat is not 16-byte aligned");
   CollateArgs a;
-  a.ds = *ds;
-  if (!token_type_ids || !ds->token_type_ids) token_type_ids = nullptr;
-  a.sel = sel; a.B = B; a.R = R; a.L_out = L_out; a.ragged = flags & 1;
-  a.D4 = ds->D / 4;
-  a.pieces = (a.D4 + PIECE4 - 1) / PIECE4;
-  a.region_items = (long long)B * R * a.pieces;
-  const long long region_blocks = (a.region_items + 3) / 4;
-  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "collate_batch: %lld region items exceed one launch", a.region_items);
-  a.region_blocks = (unsigned)region_blocks;
-  a.img_feat = img_feat; a.img_pos_feat = img_pos_feat; a.input_ids = input_ids; a.position_ids = position_ids;
-  a.token_type_ids = token_type_ids; a.attn_mask = attn_mask; a.gather_index = gather_index; a.labels = labels; a.ids = ids;
+  UCHECK_RC(fill_args("collate_batch", a, ds, sel, B, R, L_out, flags, img_feat, img_pos_feat, input_ids, position_ids, token_type_ids,
+                      attn_mask, gather_index, labels, ids));
   hipLaunchKernelGGL(collate_batch_kernel, dim3(a.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
@@ -320,51 +368,26 @@ __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArg
   const CollateArgs& c = a.c;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x < c.region_blocks) {
-    const long long item = (long long)blockIdx.x * 4 + wave;
-    if (item >= c.region_items) return;
-    const long long row = item / c.pieces;             // b * R + r
-    const int piece = (int)(item - row * c.pieces);
-    const int b = (int)(row / c.R), r = (int)(row - (long long)b * c.R);
-    const long long s = sample_of(c, b);
-    const int n = regions_of(c, s);
-    const long long src_row = c.ds.row_start[s] + r;
-    const bool real = r < n && src_row >= 0 && src_row < c.ds.pool_rows;
+    RegionItem it;
+    if (!region_item(c, it)) return;
     // (everything up to `dest` is uniform over the wave)
     bool masked = false;
     long long dest = 0;                                // row of feat_targets | label_targets, label_ids and masked_positions
-    if (a.task == UNITER_TASK_MRFR && r < n) masked = region_slot<MRC>(a, s, n, b, r, lane, dest);
-    f32x4* dp = reinterpret_cast<f32x4*>(c.img_feat) + (size_t)row * c.D4;
-    const int c0 = piece * PIECE4 + lane;
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (a.task == UNITER_TASK_MRFR && it.r < it.n) masked = region_slot<MRC>(a, it.s, it.n, it.b, it.r, lane, dest);
     f32x4 v[4];
+    piece_load(c, it, it.real && !(MRC && masked), lane, v);      // (MRC keeps no copy of a selected region's features)
+    // a selected region leaves zeros in img_feat: MRFR moves its features to feat_targets, MRC its soft labels to label_targets
+    if (masked) {
+      if (!MRC) piece_store(c, it, lane, a.feat_targets, dest, v);
+      else if (it.piece == 0) soft_row(a, it.real ? a.soft + (size_t)it.src_row * a.ld_soft : nullptr, dest, lane);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = zero;
-    if (real && !(MRC && masked)) {                    // (MRC keeps no copy of a selected region's features)
-      const f32x4* sp = reinterpret_cast<const f32x4*>(c.ds.feat) + (size_t)src_row * c.D4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + 64 * k < c.D4) v[k] = sp[c0 + 64 * k];
+      for (int k = 0; k < 4; ++k) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (MRC && masked) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + 64 * k < c.D4) dp[c0 + 64 * k] = zero;
-      if (piece == 0) soft_row(a, real ? a.soft + (size_t)src_row * a.ld_soft : nullptr, dest, lane);
-    } else if (masked) {
-      f32x4* tp = reinterpret_cast<f32x4*>(a.feat_targets) + (size_t)dest * c.D4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + 64 * k < c.D4) { tp[c0 + 64 * k] = v[k]; dp[c0 + 64 * k] = zero; }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c0 + 64 * k < c.D4) dp[c0 + 64 * k] = v[k];
-    }
-    if (piece == 0 && lane < 7)
-      c.img_pos_feat[(size_t)row * 7 + lane] = real ? c.ds.pos[(size_t)src_row * 7 + lane] : 0.f;
-    if (piece == 0 && masked && lane == 0) {
-      a.masked_positions[2 * dest] = b;
-      a.masked_positions[2 * dest + 1] = (long long)c.ds.txt_len[text_sample_of(a, b)] + r;
+    piece_store(c, it, lane, c.img_feat, it.row, v);
+    box_row(c, it, lane);
+    if (it.piece == 0 && masked && lane == 0) {
+      a.masked_positions[2 * dest] = it.b;
+      a.masked_positions[2 * dest + 1] = (long long)c.ds.txt_len[text_sample_of(a, it.b)] + it.r;
     }
     return;
   }
@@ -425,22 +448,9 @@ __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArg
       run += chunk;
     }
     if (b == c.B - 1 && threadIdx.x == 0) *a.n_masked = front + run;
-  } else {
-    for (int t = threadIdx.x; t < T; t += 256) c.input_ids[(size_t)b * T + t] = src[t];
   }
-  for (int t = threadIdx.x; t < T; t += 256) {
-    c.position_ids[(size_t)b * T + t] = t;
-    if (c.token_type_ids) c.token_type_ids[(size_t)b * T + t] = c.ds.token_type_ids[(size_t)ts * T + t];
-  }
-  for (int j = threadIdx.x; j < c.L_out; j += 256) {
-    c.attn_mask[(size_t)b * c.L_out + j] = j < tl + il ? 1.0f : 0.0f;
-    c.gather_index[(size_t)b * c.L_out + j] = (tl <= j && j < tl + il) ? j - tl + T : j;
-  }
-  if (threadIdx.x == 0) {
-    c.labels[b] = c.ds.labels[s];
-    c.ids[b] = c.ds.ids[s];
-    if (a.task == UNITER_TASK_ITM) a.targets[b] = ts == s ? 1 : 0;
-  }
+  sample_frame(c, b, s, ts, tl, il, a.task != UNITER_TASK_MLM);
+  if (a.task == UNITER_TASK_ITM && threadIdx.x == 0) a.targets[b] = ts == s ? 1 : 0;
   if (a.task == UNITER_TASK_MRFR) {
     int any = 0;
     for (int base = 0; base < n; base += 256) {
@@ -465,6 +475,17 @@ __global__ __launch_bounds__(256) void collate_pretrain_kernel(const PretrainArg
   }
 }
 
+// the draw fields of a from a checked mask configuration: the Philox key and counter word, prob as a threshold on a 32-bit word
+int mask_draw(const char* who, PretrainArgs& a, const uniter_mask_cfg_t* cfg) {
+  UCHECK_ARG(cfg, "%s: null mask configuration", who);
+  UCHECK_ARG(cfg->prob >= 0.0f && cfg->prob <= 1.0f, "%s: prob = %g is outside [0, 1]", who, (double)cfg->prob);
+  a.k0 = (uint32_t)(cfg->seed & 0xffffffffu); a.k1 = (uint32_t)(cfg->seed >> 32); a.draw = cfg->draw;
+  const double t = (double)cfg->prob * 4294967296.0;         // make_drop's floor and clamp (philox.h)
+  a.always = cfg->prob >= 1.0f;
+  a.thresh = t >= 4294967295.0 ? 0xffffffffu : (t <= 0.0 ? 0u : (uint32_t)t);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const int64_t* sel, const int64_t* txt_sel, int task,
@@ -475,35 +496,14 @@ extern "C" int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const i
                                              int64_t* targets, int64_t* masked_positions, int32_t* n_masked, void* stream) {
   UCHECK_ARG(task == UNITER_TASK_MLM || task == UNITER_TASK_MRFR || task == UNITER_TASK_ITM,
              "collate_pretrain_batch: unknown task %d", task);
-  UCHECK_ARG(ds && sel, "collate_pretrain_batch: null dataset or selection");
-  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids,
-             "collate_pretrain_batch: null pointer in the dataset");
-  UCHECK_ARG(input_ids && position_ids && attn_mask && gather_index && labels && ids, "collate_pretrain_batch: null output pointer");
-  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "collate_pretrain_batch: dataset of %lld samples, %lld pool rows", (long long)ds->N,
-             (long long)ds->pool_rows);
-  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0,
-               "collate_pretrain_batch: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)", B, ds->T, L_out, R);
-  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "collate_pretrain_batch: L_out = %d exceeds T + R = %d + %d", L_out, ds->T, R);
-  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "collate_pretrain_batch: D = %d must be a positive multiple of 4 (rows move as 16-byte items)",
-               ds->D);
-  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "collate_pretrain_batch: null feat / pos with %lld pool rows",
-             (long long)ds->pool_rows);
-  UCHECK_ARG((img_feat && img_pos_feat) || R == 0, "collate_pretrain_batch: null img_feat / img_pos_feat with R = %d", R);
-  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "collate_pretrain_batch: feat is not 16-byte aligned");
-  UCHECK_ARG(((uintptr_t)img_feat & 15) == 0, "collate_pretrain_batch: img_feat is not 16-byte aligned");
-  PretrainArgs a;
-  a.k0 = a.k1 = a.draw = a.thresh = 0; a.always = 0;
-  a.cls = a.sep = a.pad = a.mask_token = a.vocab_lo = 0; a.vocab_span = 1;
+  PretrainArgs a = {};                                       // (what a task does not use stays null / 0)
+  UCHECK_RC(fill_args("collate_pretrain_batch", a.c, ds, sel, B, R, L_out, flags, img_feat, img_pos_feat, input_ids, position_ids,
+                      token_type_ids, attn_mask, gather_index, labels, ids));
   if (task != UNITER_TASK_ITM) {
-    UCHECK_ARG(cfg, "collate_pretrain_batch: null mask configuration");
-    UCHECK_ARG(cfg->prob >= 0.0f && cfg->prob <= 1.0f, "collate_pretrain_batch: prob = %g is outside [0, 1]", (double)cfg->prob);
+    UCHECK_RC(mask_draw("collate_pretrain_batch", a, cfg));
     // (MRFR with R == 0: no region can be selected, masked_positions has no rows)
     UCHECK_ARG((masked_positions || (task == UNITER_TASK_MRFR && R == 0)) && n_masked,
                "collate_pretrain_batch: null masked_positions / n_masked");
-    a.k0 = (uint32_t)(cfg->seed & 0xffffffffu); a.k1 = (uint32_t)(cfg->seed >> 32); a.draw = cfg->draw;
-    const double t = (double)cfg->prob * 4294967296.0;       // make_drop's floor and clamp (philox.h)
-    a.always = cfg->prob >= 1.0f;
-    a.thresh = t >= 4294967295.0 ? 0xffffffffu : (t <= 0.0 ? 0u : (uint32_t)t);
   }
   if (task == UNITER_TASK_MLM) {
     UCHECK_ARG(txt_labels, "collate_pretrain_batch: null txt_labels");
@@ -520,23 +520,10 @@ extern "C" int uniter_collate_pretrain_batch(const uniter_dataset_t* ds, const i
   } else {
     UCHECK_ARG(targets, "collate_pretrain_batch: null targets");
   }
-  CollateArgs& c = a.c;
-  c.ds = *ds;
-  if (!token_type_ids || !ds->token_type_ids) token_type_ids = nullptr;
-  c.sel = sel; c.B = B; c.R = R; c.L_out = L_out; c.ragged = flags & 1;
-  c.D4 = ds->D / 4;
-  c.pieces = (c.D4 + PIECE4 - 1) / PIECE4;
-  c.region_items = (long long)B * R * c.pieces;
-  const long long region_blocks = (c.region_items + 3) / 4;
-  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "collate_pretrain_batch: %lld region items exceed one launch", c.region_items);
-  c.region_blocks = (unsigned)region_blocks;
-  c.img_feat = img_feat; c.img_pos_feat = img_pos_feat; c.input_ids = input_ids; c.position_ids = position_ids;
-  c.token_type_ids = token_type_ids; c.attn_mask = attn_mask; c.gather_index = gather_index; c.labels = labels; c.ids = ids;
   a.txt_sel = txt_sel; a.task = task;
   a.txt_labels = txt_labels; a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.feat_targets = feat_targets;
   a.targets = targets; a.masked_positions = masked_positions; a.n_masked = n_masked;
-  a.soft = nullptr; a.C = a.ld_soft = a.soft4 = 0; a.label_targets = nullptr; a.label_ids = nullptr;
-  hipLaunchKernelGGL(collate_pretrain_kernel<false>, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(collate_pretrain_kernel<false>, dim3(a.c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
 }
@@ -548,22 +535,10 @@ extern "C" int uniter_collate_mrc_batch(const uniter_dataset_t* ds, const float*
                                         float* attn_mask, int64_t* gather_index, int64_t* labels, int64_t* ids, int64_t* img_masks,
                                         unsigned char* img_mask_tgt, float* label_targets, int64_t* label_ids,
                                         int64_t* masked_positions, int32_t* n_masked, void* stream) {
-  UCHECK_ARG(ds && sel, "collate_mrc_batch: null dataset or selection");
-  UCHECK_ARG(ds->row_start && ds->row_cnt && ds->input_ids && ds->txt_len && ds->labels && ds->ids,
-             "collate_mrc_batch: null pointer in the dataset");
-  UCHECK_ARG(input_ids && position_ids && attn_mask && gather_index && labels && ids, "collate_mrc_batch: null output pointer");
-  UCHECK_ARG(ds->N > 0 && ds->pool_rows >= 0, "collate_mrc_batch: dataset of %lld samples, %lld pool rows", (long long)ds->N,
-             (long long)ds->pool_rows);
-  UCHECK_SHAPE(B > 0 && ds->T > 0 && L_out > 0 && R >= 0, "collate_mrc_batch: B = %d, T = %d, L_out = %d, R = %d (B, T, L_out > 0, R >= 0)",
-               B, ds->T, L_out, R);
-  UCHECK_SHAPE((long long)L_out <= (long long)ds->T + R, "collate_mrc_batch: L_out = %d exceeds T + R = %d + %d", L_out, ds->T, R);
-  UCHECK_SHAPE(ds->D > 0 && ds->D % 4 == 0, "collate_mrc_batch: D = %d must be a positive multiple of 4 (rows move as 16-byte items)", ds->D);
-  UCHECK_ARG((ds->feat && ds->pos) || ds->pool_rows == 0, "collate_mrc_batch: null feat / pos with %lld pool rows", (long long)ds->pool_rows);
-  UCHECK_ARG((img_feat && img_pos_feat) || R == 0, "collate_mrc_batch: null img_feat / img_pos_feat with R = %d", R);
-  UCHECK_ARG(((uintptr_t)ds->feat & 15) == 0, "collate_mrc_batch: feat is not 16-byte aligned");
-  UCHECK_ARG(((uintptr_t)img_feat & 15) == 0, "collate_mrc_batch: img_feat is not 16-byte aligned");
-  UCHECK_ARG(cfg, "collate_mrc_batch: null mask configuration");
-  UCHECK_ARG(cfg->prob >= 0.0f && cfg->prob <= 1.0f, "collate_mrc_batch: prob = %g is outside [0, 1]", (double)cfg->prob);
+  PretrainArgs a = {};
+  UCHECK_RC(fill_args("collate_mrc_batch", a.c, ds, sel, B, R, L_out, flags, img_feat, img_pos_feat, input_ids, position_ids,
+                      token_type_ids, attn_mask, gather_index, labels, ids));
+  UCHECK_RC(mask_draw("collate_mrc_batch", a, cfg));
   UCHECK_ARG(soft || ds->pool_rows == 0, "collate_mrc_batch: null soft labels with %lld pool rows", (long long)ds->pool_rows);
   UCHECK_SHAPE(C >= 2 && ld_soft >= C, "collate_mrc_batch: C = %d, ld_soft = %d (C >= 2: a background and a class; ld_soft >= C)", C, ld_soft);
   UCHECK_ARG(((uintptr_t)soft & 3) == 0 && ((uintptr_t)label_targets & 3) == 0, "collate_mrc_batch: soft / label_targets is not 4-byte aligned");
@@ -571,30 +546,11 @@ extern "C" int uniter_collate_mrc_batch(const uniter_dataset_t* ds, const float*
   UCHECK_ARG(label_targets || label_ids || R == 0, "collate_mrc_batch: label_targets and label_ids are both null with R = %d", R);
   UCHECK_ARG(n_masked && img_mask_tgt && ((masked_positions && img_masks) || R == 0),
              "collate_mrc_batch: null masked_positions / n_masked / img_masks / img_mask_tgt with R = %d", R);
-  PretrainArgs a;
-  a.k0 = (uint32_t)(cfg->seed & 0xffffffffu); a.k1 = (uint32_t)(cfg->seed >> 32); a.draw = cfg->draw;
-  const double t = (double)cfg->prob * 4294967296.0;         // make_drop's floor and clamp (philox.h)
-  a.always = cfg->prob >= 1.0f;
-  a.thresh = t >= 4294967295.0 ? 0xffffffffu : (t <= 0.0 ? 0u : (uint32_t)t);
-  a.cls = a.sep = a.pad = a.mask_token = a.vocab_lo = 0; a.vocab_span = 1;
-  CollateArgs& c = a.c;
-  c.ds = *ds;
-  if (!token_type_ids || !ds->token_type_ids) token_type_ids = nullptr;
-  c.sel = sel; c.B = B; c.R = R; c.L_out = L_out; c.ragged = flags & 1;
-  c.D4 = ds->D / 4;
-  c.pieces = (c.D4 + PIECE4 - 1) / PIECE4;
-  c.region_items = (long long)B * R * c.pieces;
-  const long long region_blocks = (c.region_items + 3) / 4;
-  UCHECK_SHAPE(region_blocks + B < 0x7fffffffLL, "collate_mrc_batch: %lld region items exceed one launch", c.region_items);
-  c.region_blocks = (unsigned)region_blocks;
-  c.img_feat = img_feat; c.img_pos_feat = img_pos_feat; c.input_ids = input_ids; c.position_ids = position_ids;
-  c.token_type_ids = token_type_ids; c.attn_mask = attn_mask; c.gather_index = gather_index; c.labels = labels; c.ids = ids;
-  a.txt_sel = nullptr; a.task = UNITER_TASK_MRFR;            // the dense outputs are MRFR's, on UNITER_STREAM_MRC
-  a.txt_labels = nullptr; a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.feat_targets = nullptr;
-  a.targets = nullptr; a.masked_positions = masked_positions; a.n_masked = n_masked;
+  a.task = UNITER_TASK_MRFR;                                 // the dense outputs are MRFR's, on UNITER_STREAM_MRC
+  a.img_masks = img_masks; a.img_mask_tgt = img_mask_tgt; a.masked_positions = masked_positions; a.n_masked = n_masked;
   a.soft = soft; a.C = C; a.ld_soft = ld_soft; a.soft4 = ((uintptr_t)soft & 15) == 0 && ld_soft % 4 == 0;
   a.label_targets = label_targets; a.label_ids = label_ids;
-  hipLaunchKernelGGL(collate_pretrain_kernel<true>, dim3(c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(collate_pretrain_kernel<true>, dim3(a.c.region_blocks + (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   UCHECK_LAUNCH();
   return 0;
 }

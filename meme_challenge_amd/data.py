@@ -8,8 +8,10 @@ of `ConfounderSampler` (:221-271).  Same file formats, same batch keys:
   input_ids, position_ids, img_feat, img_pos_feat, token_type_ids, attn_mask, gather_index,
   labels, ids.
 """
+import ctypes as C
 import json
 import os
+from itertools import chain
 from random import shuffle
 from types import SimpleNamespace
 
@@ -18,6 +20,7 @@ import torch
 import torch.utils.data as data
 from torch.nn.utils.rnn import pad_sequence
 
+from . import _lib
 from .utils import get_attention_mask, get_gather_index
 
 
@@ -122,7 +125,6 @@ class DevicePrefetcher(object):
         to `depth` batches ahead, instead of between two steps on the thread that launches the kernels: with a 4.4-ms bf16 step the
         launching thread had 2 ms of it taken away every iteration (the CLI ran at 72-80 % of the bare step's rate)."""
         self.loader, self.device = loader, torch.device(device)
-        from . import _lib
         self.stream = _lib.shared_stream(self.device, 'copy')      # one copy stream per device, whatever the number of loaders
         self.threaded = (os.environ.get('UNITER_PREFETCH_THREAD', '1') != '0') if threaded is None else bool(threaded)
         self.depth = max(1, int(depth))
@@ -592,15 +594,69 @@ def plan_batches(order, batch_size, txt_len, row_cnt, ragged_regions):
     """The host side of a DeviceLoader epoch, from the numpy length arrays alone: [(first, last, R, L_out, seq_lens)] over
     `order` in batches of batch_size (the last may be short).  R, L_out and seq_lens are what the host collate derives: the
     batch's largest region count, its longest text + image length, and the per-sample lengths as a list of ints."""
-    order = np.asarray(order, dtype=np.int64)
-    out = []
-    for a in range(0, len(order), batch_size):
-        sel = order[a:a + batch_size]
-        n, tl = row_cnt[sel].astype(np.int64), txt_len[sel].astype(np.int64)
-        R = int(n.max())
-        seq = tl + (n if ragged_regions else R)
-        out.append((a, a + len(sel), R, int(seq.max()), [int(x) for x in seq]))
-    return out
+    return plan_pretrain_batches(order, order, batch_size, txt_len, row_cnt, ragged_regions)
+
+
+def _checked_order(order, n, who):
+    """a sampler's draw as an int64 numpy array of indices into [0, n)"""
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    if order.size and (order.min() < 0 or order.max() >= n):
+        raise ValueError('%s drew an index outside [0, %d)' % (who, n))
+    return order
+
+
+# the tensors of uniter_dataset_t (include/uniter_hip.h) in its order, as every collate wrapper takes them
+_DATASET_NAMES = ('feat', 'pos', 'row_start', 'row_cnt', 'input_ids', 'token_type_ids', 'txt_len', 'labels', 'ids')
+_DATASET_DTYPES = (torch.float32, torch.float32, torch.int64, torch.int32, torch.int64, torch.int64, torch.int32, torch.int64, torch.int64)
+
+
+def _collate_setup(who, sel, txt_sel, extra, arrays, R, L_out, mask_key, more_shapes, out):
+    """What the wrappers of the three uniter_collate_* entry points (include/uniter_hip.h) share.  Inputs: `sel`, `txt_sel`, the entry's
+    own `extra` as (name, tensor, dtype) and the dataset's `arrays` (_DATASET_NAMES): each a GPU tensor of its type (token_type_ids
+    and txt_sel may be None), the dataset's of one N and T, txt_sel of sel's length.  Outputs: the nine every entry writes -- the mask
+    under `mask_key` -- and the entry's own, more_shapes(B, T, D) -> {key: (shape, dtype)} (None: none): allocated, or taken from
+    `out` and validated.  -> (uniter_dataset_t, B, out, o), o(key) the pointer of an output or None where there is none."""
+    require = _lib.require_gpu_tensor
+    for name, t, dt in chain((('sel', sel, torch.int64), ('txt_sel', txt_sel, torch.int64)), extra, zip(_DATASET_NAMES, arrays, _DATASET_DTYPES)):
+        if t is None and name not in ('token_type_ids', 'txt_sel'):
+            raise _lib.UniterHipError('%s: %s is missing' % (who, name))
+        require(t, dt, name)
+    feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids = arrays
+    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
+    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
+        raise _lib.UniterHipError('%s: feat [rows, D] / pos [rows, 7] expected; got %s / %s' % (who, tuple(feat.shape), tuple(pos.shape)))
+    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
+                           ('ids', ids, (N,)), ('token_type_ids', token_type_ids, (N, T)), ('txt_sel', txt_sel, (B,))):
+        if t is not None and t.shape != shape:            # (torch.Size is a tuple)
+            raise _lib.UniterHipError('%s: %s must be %s; got %s' % (who, name, shape, tuple(t.shape)))
+    i64, f32 = torch.int64, torch.float32
+    R, L_out = max(R, 0), max(L_out, 0)
+    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
+              'token_type_ids': ((B, T), i64), mask_key: ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
+              'ids': ((B,), i64)}
+    if more_shapes is not None:
+        shapes.update(more_shapes(B, T, D))
+    if out is None:
+        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=sel.device))
+               for k, (s, dt) in shapes.items()}
+    else:
+        for k, (s, dt) in shapes.items():
+            t = out.get(k)
+            if t is None and k == 'token_type_ids':
+                continue
+            if t is None or t.shape != s:
+                raise _lib.UniterHipError('%s: output %s must be %s; got %s' % (who, k, s, None if t is None else tuple(t.shape)))
+            require(t, dt, 'output ' + k)
+    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
+                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
+                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+    for t in chain((sel, txt_sel), [e[1] for e in extra], arrays, out.values()):
+        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
+
+    def o(k):
+        t = out.get(k)
+        return None if t is None else C.c_void_p(t.data_ptr())
+    return ds, B, out, o
 
 
 def collate_batch(sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids, R, L_out,
@@ -608,45 +664,10 @@ def collate_batch(sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids,
     """uniter_collate_batch (include/uniter_hip.h) on the current stream: the batch of the samples `sel` (int64, device) of a
     dataset given by its device tensors -> dict with the host collate's tensor keys.  `out`: the same dict of preallocated
     outputs to write into (tests); default: fresh tensors from torch's allocator."""
-    import ctypes as C
-    from . import _lib
-    i64, i32, f32 = torch.int64, torch.int32, torch.float32
-    for name, t, dt in (('sel', sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('row_start', row_start, i64), ('row_cnt', row_cnt, i32),
-                        ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64), ('txt_len', txt_len, i32),
-                        ('labels', labels, i64), ('ids', ids, i64)):
-        if t is None and name != 'token_type_ids':
-            raise _lib.UniterHipError('collate_batch: %s is missing' % name)
-        _lib.require_gpu_tensor(t, dt, name)
-    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
-    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
-        raise _lib.UniterHipError('collate_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s' % (tuple(feat.shape), tuple(pos.shape)))
-    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
-                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()):
-        if tuple(t.shape) != shape:
-            raise _lib.UniterHipError('collate_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
-    R, L_out = int(R), int(L_out)
-    dev = sel.device
-    shapes = {'img_feat': ((B, max(R, 0), D), f32), 'img_pos_feat': ((B, max(R, 0), 7), f32), 'input_ids': ((B, T), i64),
-              'position_ids': ((B, T), i64), 'token_type_ids': ((B, T), i64), 'attn_mask': ((B, max(L_out, 0)), f32),
-              'gather_index': ((B, max(L_out, 0)), i64), 'labels': ((B,), i64), 'ids': ((B,), i64)}
-    if out is None:
-        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
-               for k, (s, dt) in shapes.items()}
-    else:
-        for k, (s, dt) in shapes.items():
-            t = out.get(k)
-            if t is None and k == 'token_type_ids':
-                continue
-            if t is None or tuple(t.shape) != s:
-                raise _lib.UniterHipError('collate_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
-            _lib.require_gpu_tensor(t, dt, 'output ' + k)
-    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
-                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
-                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
-    for t in (sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
-        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
-    o = lambda k: None if out.get(k) is None else C.c_void_p(out[k].data_ptr())
-    with torch.cuda.device(dev):
+    R, L_out = int(R), int(L_out)                     # (handed to the library as they are: it refuses a negative one)
+    arrays = (feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids)
+    ds, B, out, o = _collate_setup('collate_batch', sel, None, (), arrays, R, L_out, 'attn_mask', None, out)
+    with torch.cuda.device(sel.device):
         _lib.check(_lib.lib().uniter_collate_batch(
             C.byref(ds), C.c_void_p(sel.data_ptr()), B, R, L_out, 1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'),
             o('input_ids'), o('position_ids'), o('token_type_ids'), o('attn_mask'), o('gather_index'), o('labels'), o('ids'),
@@ -674,10 +695,7 @@ class DeviceLoader(object):
     def order(self):
         """One epoch's sample order as a validated int64 numpy array (draws from the sampler)."""
         n = len(self.dataset)
-        order = np.asarray(list(self.sampler) if self.sampler is not None else range(n), dtype=np.int64).reshape(-1)
-        if order.size and (order.min() < 0 or order.max() >= n):
-            raise ValueError('DeviceLoader: the sampler drew an index outside [0, %d)' % n)
-        return order
+        return _checked_order(list(self.sampler) if self.sampler is not None else range(n), n, 'DeviceLoader: the sampler')
 
     def plan(self, order):
         d = self.dataset
@@ -750,58 +768,23 @@ def collate_pretrain_batch(task, sel, txt_sel, feat, pos, row_start, row_cnt, in
     `labels` / `ids` / `token_type_ids` as collate_batch gives them, and for mlm / mrfr the compaction at full capacity:
     `masked_positions` [B*T or B*R, 2], `n_masked` (int32 [1], on the device; the first n_masked rows are defined) and, for
     mrfr, `feat_targets` [B*R, D].  `out`: the same dict of preallocated outputs to write into (tests)."""
-    import ctypes as C
-    from . import _lib
     if task not in _lib.TASK_IDS:
         raise ValueError('collate_pretrain_batch: unknown task %r (one of %s)' % (task, ', '.join(PRETRAIN_TASKS)))
     i64, i32, f32 = torch.int64, torch.int32, torch.float32
-    for name, t, dt in (('sel', sel, i64), ('txt_sel', txt_sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('row_start', row_start, i64),
-                        ('row_cnt', row_cnt, i32), ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64),
-                        ('txt_len', txt_len, i32), ('labels', labels, i64), ('ids', ids, i64)):
-        if t is None and name not in ('token_type_ids', 'txt_sel'):
-            raise _lib.UniterHipError('collate_pretrain_batch: %s is missing' % name)
-        _lib.require_gpu_tensor(t, dt, name)
-    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
-    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
-        raise _lib.UniterHipError('collate_pretrain_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s'
-                                  % (tuple(feat.shape), tuple(pos.shape)))
-    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
-                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()) \
-            + ((('txt_sel', txt_sel, (B,)),) if txt_sel is not None else ()):
-        if tuple(t.shape) != shape:
-            raise _lib.UniterHipError('collate_pretrain_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
     R, L_out = max(int(R), 0), max(int(L_out), 0)
-    dev = sel.device
-    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
-              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
-              'ids': ((B,), i64)}
-    if task == 'mlm':
-        shapes.update(txt_labels=((B, T), i64), masked_positions=((B * T, 2), i64), n_masked=((1,), i32))
-    elif task == 'mrfr':
-        shapes.update(img_masks=((B, R), i64), img_mask_tgt=((B, L_out), torch.bool), feat_targets=((B * R, D), f32),
-                      masked_positions=((B * R, 2), i64), n_masked=((1,), i32))
-    else:
-        shapes.update(targets=((B,), i64))
-    if out is None:
-        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
-               for k, (s, dt) in shapes.items()}
-    else:
-        for k, (s, dt) in shapes.items():
-            t = out.get(k)
-            if t is None and k == 'token_type_ids':
-                continue
-            if t is None or tuple(t.shape) != s:
-                raise _lib.UniterHipError('collate_pretrain_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
-            _lib.require_gpu_tensor(t, dt, 'output ' + k)
-    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
-                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
-                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+
+    def more_shapes(B, T, D):
+        if task == 'mlm':
+            return dict(txt_labels=((B, T), i64), masked_positions=((B * T, 2), i64), n_masked=((1,), i32))
+        if task == 'mrfr':
+            return dict(img_masks=((B, R), i64), img_mask_tgt=((B, L_out), torch.bool), feat_targets=((B * R, D), f32),
+                        masked_positions=((B * R, 2), i64), n_masked=((1,), i32))
+        return dict(targets=((B,), i64))
+    arrays = (feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids)
+    ds, B, out, o = _collate_setup('collate_pretrain_batch', sel, txt_sel, (), arrays, R, L_out, 'attn_masks', more_shapes, out)
     cfg = _lib.UniterMaskCfgC(int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(prob), int(cls_token), int(sep_token),
                               int(pad_token), int(mask_token), int(vocab_range[0]), int(vocab_range[1]))
-    for t in (sel, txt_sel, feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
-        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
-    o = lambda k: None if out.get(k) is None else C.c_void_p(out[k].data_ptr())
-    with torch.cuda.device(dev):
+    with torch.cuda.device(sel.device):
         _lib.check(_lib.lib().uniter_collate_pretrain_batch(
             C.byref(ds), C.c_void_p(sel.data_ptr()), None if txt_sel is None else C.c_void_p(txt_sel.data_ptr()), _lib.TASK_IDS[task],
             C.byref(cfg), B, R, L_out, 1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'), o('input_ids'), o('position_ids'),
@@ -826,63 +809,33 @@ def collate_mrc_batch(sel, feat, pos, soft, row_start, row_cnt, input_ids, token
     are defined), `label_targets` [B*R, label_dim] (soft_out) and `label_ids` [B*R] (hard: 1 + the first maximum of a row's columns
     1 .., what pretrain._hard_region_labels finds).  At least one of hard and soft_out.  `out`: the same dict of preallocated
     outputs to write into (tests)."""
-    import ctypes as C
-    from . import _lib
     if not (hard or soft_out):
         raise ValueError('collate_mrc_batch: neither label_ids (hard) nor label_targets (soft_out) asked for')
     i64, i32, f32 = torch.int64, torch.int32, torch.float32
-    for name, t, dt in (('sel', sel, i64), ('feat', feat, f32), ('pos', pos, f32), ('soft', soft, f32), ('row_start', row_start, i64),
-                        ('row_cnt', row_cnt, i32), ('input_ids', input_ids, i64), ('token_type_ids', token_type_ids, i64),
-                        ('txt_len', txt_len, i32), ('labels', labels, i64), ('ids', ids, i64)):
-        if t is None and name != 'token_type_ids':
-            raise _lib.UniterHipError('collate_mrc_batch: %s is missing' % name)
-        _lib.require_gpu_tensor(t, dt, name)
-    N, T, B, D = int(row_start.shape[0]), int(input_ids.shape[1]), int(sel.shape[0]), int(feat.shape[1])
-    if feat.dim() != 2 or pos.dim() != 2 or pos.shape[1] != 7 or pos.shape[0] != feat.shape[0]:
-        raise _lib.UniterHipError('collate_mrc_batch: feat [rows, D] / pos [rows, 7] expected; got %s / %s'
-                                  % (tuple(feat.shape), tuple(pos.shape)))
-    Cn = int(label_dim)
-    if soft.dim() != 2 or soft.shape[0] != feat.shape[0] or Cn < 2 or int(soft.shape[1]) < Cn:
-        raise _lib.UniterHipError('collate_mrc_batch: soft [%d rows, ld_soft >= label_dim = %d >= 2] expected; got %s'
-                                  % (int(feat.shape[0]), Cn, tuple(soft.shape)))
-    for name, t, shape in (('row_cnt', row_cnt, (N,)), ('input_ids', input_ids, (N, T)), ('txt_len', txt_len, (N,)), ('labels', labels, (N,)),
-                           ('ids', ids, (N,))) + ((('token_type_ids', token_type_ids, (N, T)),) if token_type_ids is not None else ()):
-        if tuple(t.shape) != shape:
-            raise _lib.UniterHipError('collate_mrc_batch: %s must be %s; got %s' % (name, shape, tuple(t.shape)))
-    R, L_out = max(int(R), 0), max(int(L_out), 0)
-    dev = sel.device
-    shapes = {'img_feat': ((B, R, D), f32), 'img_pos_feat': ((B, R, 7), f32), 'input_ids': ((B, T), i64), 'position_ids': ((B, T), i64),
-              'token_type_ids': ((B, T), i64), 'attn_masks': ((B, L_out), f32), 'gather_index': ((B, L_out), i64), 'labels': ((B,), i64),
-              'ids': ((B,), i64), 'img_masks': ((B, R), i64), 'img_mask_tgt': ((B, L_out), torch.bool),
-              'masked_positions': ((B * R, 2), i64), 'n_masked': ((1,), i32)}
-    if soft_out:
-        shapes['label_targets'] = ((B * R, Cn), f32)
-    if hard:
-        shapes['label_ids'] = ((B * R,), i64)
-    if out is None:
-        out = {k: (None if (k == 'token_type_ids' and token_type_ids is None) else torch.empty(s, dtype=dt, device=dev))
-               for k, (s, dt) in shapes.items()}
-    else:
-        for k, (s, dt) in shapes.items():
-            t = out.get(k)
-            if t is None and k == 'token_type_ids':
-                continue
-            if t is None or tuple(t.shape) != s:
-                raise _lib.UniterHipError('collate_mrc_batch: output %s must be %s; got %s' % (k, s, None if t is None else tuple(t.shape)))
-            _lib.require_gpu_tensor(t, dt, 'output ' + k)
-    ds = _lib.UniterDatasetC(feat.data_ptr(), pos.data_ptr(), row_start.data_ptr(), row_cnt.data_ptr(), input_ids.data_ptr(),
-                             None if token_type_ids is None else token_type_ids.data_ptr(), txt_len.data_ptr(), labels.data_ptr(),
-                             ids.data_ptr(), N, int(feat.shape[0]), D, T)
+    R, L_out, Cn = max(int(R), 0), max(int(L_out), 0), int(label_dim)
+
+    def more_shapes(B, T, D):
+        if soft.dim() != 2 or soft.shape[0] != feat.shape[0] or Cn < 2 or int(soft.shape[1]) < Cn:
+            raise _lib.UniterHipError('collate_mrc_batch: soft [%d rows, ld_soft >= label_dim = %d >= 2] expected; got %s'
+                                      % (int(feat.shape[0]), Cn, tuple(soft.shape)))
+        shapes = dict(img_masks=((B, R), i64), img_mask_tgt=((B, L_out), torch.bool), masked_positions=((B * R, 2), i64),
+                      n_masked=((1,), i32))
+        if soft_out:
+            shapes['label_targets'] = ((B * R, Cn), f32)
+        if hard:
+            shapes['label_ids'] = ((B * R,), i64)
+        return shapes
+    arrays = (feat, pos, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids)
+    ds, B, out, o = _collate_setup('collate_mrc_batch', sel, None, (('soft', soft, f32),), arrays, R, L_out, 'attn_masks', more_shapes, out)
     cfg = _lib.UniterMaskCfgC(int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, float(prob), 0, 0, 0, 0, 0, 0)
-    for t in (sel, feat, pos, soft, row_start, row_cnt, input_ids, token_type_ids, txt_len, labels, ids) + tuple(out.values()):
-        assert t is None or t.is_contiguous(), 'libuniter_hip needs contiguous tensors'
-    o = lambda k: None if (k not in shapes or out.get(k) is None) else C.c_void_p(out[k].data_ptr())
-    with torch.cuda.device(dev):
+    with torch.cuda.device(sel.device):
+        # (an output that was not asked for is NULL to the library, whatever `out` holds under its key)
         _lib.check(_lib.lib().uniter_collate_mrc_batch(
             C.byref(ds), C.c_void_p(soft.data_ptr()), Cn, int(soft.shape[1]), C.c_void_p(sel.data_ptr()), C.byref(cfg), B, R, L_out,
             1 if ragged_regions else 0, o('img_feat'), o('img_pos_feat'), o('input_ids'), o('position_ids'), o('token_type_ids'),
-            o('attn_masks'), o('gather_index'), o('labels'), o('ids'), o('img_masks'), o('img_mask_tgt'), o('label_targets'),
-            o('label_ids'), o('masked_positions'), o('n_masked'), _lib.cur_stream()), 'uniter_collate_mrc_batch')
+            o('attn_masks'), o('gather_index'), o('labels'), o('ids'), o('img_masks'), o('img_mask_tgt'),
+            o('label_targets') if soft_out else None, o('label_ids') if hard else None, o('masked_positions'), o('n_masked'),
+            _lib.cur_stream()), 'uniter_collate_mrc_batch')
     return out
 
 
@@ -901,6 +854,9 @@ class DevicePretrainLoader(object):
     A dataset with resident soft labels (`label_dim` is not None) also serves 'mrc' and 'mrc-kl': one uniter_collate_mrc_batch
     launch, the same one read of n_masked, then views [:n] of `masked_positions` and of `label_ids` ('mrc': the classes alone, no
     label_dim-wide row is written) or `label_targets` ('mrc-kl': the distributions alone)."""
+
+    # per task with a compaction: what is cut to n_masked rows besides masked_positions
+    COMPACTED = {'mlm': (), 'mrfr': ('feat_targets',), 'mrc': ('label_ids',), 'mrc-kl': ('label_targets',)}
 
     def __init__(self, device_dataset, batch_size, tasks=(('mlm', 1), ('mrfr', 1), ('itm', 1)), seed=0, mask_prob=0.15, replace_prob=0.5,
                  accum_steps=1, samplers=None, cls_token=101, sep_token=102, pad_token=0, mask_token=103, vocab_range=(1000, 28996)):
@@ -959,11 +915,10 @@ class DevicePretrainLoader(object):
         """One epoch's validated sample order of `task` (draws from its sampler or its generator)."""
         n = len(self.dataset)
         s = self.samplers.get(task)
-        order = np.asarray(list(s), dtype=np.int64).reshape(-1) if s is not None else self._rngs[task].permutation(n).astype(np.int64)
+        order = _checked_order(list(s) if s is not None else self._rngs[task].permutation(n), n,
+                               'DevicePretrainLoader: the sampler of task %s' % task)
         if order.size == 0:
             raise ValueError('DevicePretrainLoader: the order of task %s is empty' % task)
-        if order.min() < 0 or order.max() >= n:
-            raise ValueError('DevicePretrainLoader: the sampler of task %s drew an index outside [0, %d)' % (task, n))
         return order
 
     def _epoch(self, task):
@@ -980,28 +935,19 @@ class DevicePretrainLoader(object):
         self._dev_orders[task] = dev = torch.from_numpy(np.stack([order, txt_order])).to(d.pool.device)
         for a, b, R, L_out, seq_lens in plan:
             pool = d.pool
+            regions = (pool.feat[:pool.rows], pool.pos[:pool.rows])
+            rest = (d.d_row_start, d.d_row_cnt, d.d_input_ids, d.d_token_type_ids, d.d_txt_len, d.d_labels, d.d_ids, R, L_out)
+            draws = dict(ragged_regions=d.ragged_regions, seed=self.seed, draw=draw, prob=self.mask_prob)
             if task in MRC_TASKS:
-                hard = task == 'mrc'
-                batch = collate_mrc_batch(dev[0, a:b], pool.feat[:pool.rows], pool.pos[:pool.rows], pool.soft[:pool.rows], d.d_row_start,
-                                          d.d_row_cnt, d.d_input_ids, d.d_token_type_ids, d.d_txt_len, d.d_labels, d.d_ids, R, L_out,
-                                          d.label_dim, hard=hard, soft_out=not hard, ragged_regions=d.ragged_regions, seed=self.seed,
-                                          draw=draw, prob=self.mask_prob)
+                batch = collate_mrc_batch(dev[0, a:b], *regions, pool.soft[:pool.rows], *rest, d.label_dim, hard=task == 'mrc',
+                                          soft_out=task != 'mrc', **draws)
+            else:
+                batch = collate_pretrain_batch(task, dev[0, a:b], dev[1, a:b] if task == 'itm' else None, *regions, *rest, **draws,
+                                               **self.tokens)
+            if task in self.COMPACTED:
                 n = batch['n_masked'] = int(batch['n_masked'].item())          # the step's one host synchronisation
-                batch['masked_positions'] = batch['masked_positions'][:n]
-                key = 'label_ids' if hard else 'label_targets'
-                batch[key] = batch[key][:n]
-                batch['seq_lens'] = seq_lens
-                yield batch
-                continue
-            batch = collate_pretrain_batch(task, dev[0, a:b], dev[1, a:b] if task == 'itm' else None, pool.feat[:pool.rows],
-                                           pool.pos[:pool.rows], d.d_row_start, d.d_row_cnt, d.d_input_ids, d.d_token_type_ids,
-                                           d.d_txt_len, d.d_labels, d.d_ids, R, L_out, ragged_regions=d.ragged_regions, seed=self.seed,
-                                           draw=draw, prob=self.mask_prob, **self.tokens)
-            if task != 'itm':
-                n = batch['n_masked'] = int(batch['n_masked'].item())          # the step's one host synchronisation
-                batch['masked_positions'] = batch['masked_positions'][:n]
-                if task == 'mrfr':
-                    batch['feat_targets'] = batch['feat_targets'][:n]
+                for k in ('masked_positions',) + self.COMPACTED[task]:
+                    batch[k] = batch[k][:n]
             batch['seq_lens'] = seq_lens
             yield batch
 

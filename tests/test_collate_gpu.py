@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 import torch
 
+from collate_guard import Guarded, sentinel_of, to_device
 from collate_ref import collate_ref
 from meme_challenge_amd import _lib
 from meme_challenge_amd.data import collate_batch
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE, SENTINEL_BYTE = 256, 0x5A, 0xCD      # GUARD % 16 == 0: img_feat stays 16-byte aligned behind its band
 OUT_KEYS = ('img_feat', 'img_pos_feat', 'input_ids', 'position_ids', 'token_type_ids', 'attn_mask', 'gather_index', 'labels', 'ids')
 ARRAY_KEYS = ('feat', 'pos', 'row_start', 'row_cnt', 'input_ids', 'token_type_ids', 'txt_len', 'labels', 'ids')
 
@@ -39,37 +39,11 @@ def synth(D, R, T, token_types, seed=0):
     return a
 
 
-def to_device(a):
-    return {k: (None if v is None else torch.from_numpy(v).cuda()) for k, v in a.items()}
-
-
-class Guarded(object):
-    """an output tensor inside a larger byte buffer: [guard | extent, filled with the sentinel | guard]"""
-
-    def __init__(self, shape, dtype):
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.nbytes = n
-        self.buf = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device='cuda')
-        self.buf[GUARD:GUARD + n] = SENTINEL_BYTE
-        self.t = self.buf[GUARD:GUARD + n].view(dtype).view(shape)
-
-    def check_guards(self, what):
-        b = self.buf.cpu()
-        assert bool((b[:GUARD] == GUARD_BYTE).all()) and bool((b[GUARD + self.nbytes:] == GUARD_BYTE).all()), '%s: a guard byte changed' % what
-
-    def untouched(self):
-        return bool((self.buf[GUARD:GUARD + self.nbytes] == SENTINEL_BYTE).all())
-
-
 def guarded_outputs(B, R, D, T, L_out, token_types):
     shapes = {'img_feat': ((B, R, D), torch.float32), 'img_pos_feat': ((B, R, 7), torch.float32), 'input_ids': ((B, T), torch.int64),
               'position_ids': ((B, T), torch.int64), 'token_type_ids': ((B, T), torch.int64), 'attn_mask': ((B, L_out), torch.float32),
               'gather_index': ((B, L_out), torch.int64), 'labels': ((B,), torch.int64), 'ids': ((B,), torch.int64)}
     return {k: Guarded(s, dt) for k, (s, dt) in shapes.items() if token_types or k != 'token_type_ids'}
-
-
-def sentinel_of(dtype):
-    return torch.full((1,), SENTINEL_BYTE, dtype=torch.uint8).repeat(8).view(dtype)[0]
 
 
 def run_and_check(a, d, sel, R, ragged):

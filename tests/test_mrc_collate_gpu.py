@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from collate_guard import SENTINEL_BYTE, Guarded, sentinel_of, to_device
 from meme_challenge_amd import _lib
 from meme_challenge_amd.data import collate_mrc_batch
 from mrc_cases import ARRAY_KEYS, BATCHES, CFG, CRAFTED, D, MAIN, T, crafted_rows, leading_dimensions, shape_of, synth
@@ -17,34 +18,11 @@ from mrc_collate_ref import mrc_collate_ref
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE, SENTINEL_BYTE = 256, 0x5A, 0xCD      # GUARD % 16 == 0: img_feat stays 16-byte aligned
 COMMON = ('img_feat', 'img_pos_feat', 'input_ids', 'position_ids', 'token_type_ids', 'attn_masks', 'gather_index', 'labels', 'ids')
 DENSE = COMMON + ('img_masks', 'img_mask_tgt')
 COMPACT = ('label_targets', 'label_ids', 'masked_positions')
 ALL_OUT = DENSE + COMPACT + ('n_masked',)               # the C function's order
 E_ARG, E_SHAPE = -1, -2
-
-
-def to_device(a):
-    return {k: (None if v is None else torch.from_numpy(v).cuda()) for k, v in a.items()}
-
-
-class Guarded(object):
-    """an output tensor inside a larger byte buffer: [guard | extent, filled with `fill` | guard]"""
-
-    def __init__(self, shape, dtype, fill=SENTINEL_BYTE):
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.nbytes, self.fill = n, fill
-        self.buf = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device='cuda')
-        self.buf[GUARD:GUARD + n] = fill
-        self.t = self.buf[GUARD:GUARD + n].view(dtype).view(shape)
-
-    def check_guards(self, what):
-        b = self.buf.cpu()
-        assert bool((b[:GUARD] == GUARD_BYTE).all()) and bool((b[GUARD + self.nbytes:] == GUARD_BYTE).all()), '%s: a guard byte changed' % what
-
-    def untouched(self, first_byte=0):
-        return bool((self.buf[GUARD + first_byte:GUARD + self.nbytes] == self.fill).all())
 
 
 def guarded_outputs(B, R, Cn, L_out, fill=SENTINEL_BYTE):
@@ -55,10 +33,6 @@ def guarded_outputs(B, R, Cn, L_out, fill=SENTINEL_BYTE):
               'label_targets': ((B * R, Cn), f32), 'label_ids': ((B * R,), i64), 'masked_positions': ((B * R, 2), i64),
               'n_masked': ((1,), torch.int32)}
     return {k: Guarded(s, dt, fill) for k, (s, dt) in shapes.items()}
-
-
-def sentinel_of(dtype):
-    return torch.full((1,), SENTINEL_BYTE, dtype=torch.uint8).repeat(8).view(dtype)[0]
 
 
 def raw_call(d, sel, outs, B, R, L_out, Cn, ld_soft, flags=0, drop=(), ds_null=False, sel_null=False, cfg_null=False, soft_null=False,

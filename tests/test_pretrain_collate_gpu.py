@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from collate_guard import Guarded, sentinel_of, to_device
 from meme_challenge_amd import _lib
 from meme_challenge_amd.data import collate_pretrain_batch
 from pretrain_collate_ref import pretrain_collate_ref
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_BYTE, SENTINEL_BYTE = 256, 0x5A, 0xCD      # GUARD % 16 == 0: img_feat / feat_targets stay 16-byte aligned
 ARRAY_KEYS = ('feat', 'pos', 'row_start', 'row_cnt', 'input_ids', 'token_type_ids', 'txt_len', 'labels', 'ids')
 COMMON = ('img_feat', 'img_pos_feat', 'input_ids', 'position_ids', 'token_type_ids', 'attn_masks', 'gather_index', 'labels', 'ids')
 DENSE = {'mlm': COMMON + ('txt_labels',), 'mrfr': COMMON + ('img_masks', 'img_mask_tgt'), 'itm': COMMON + ('targets',)}
@@ -46,28 +46,6 @@ def synth(D, R, T, token_types, seed=0):
             'labels': rng.integers(0, 2, N).astype(np.int64), 'ids': rng.integers(0, 99999, N).astype(np.int64)}
 
 
-def to_device(a):
-    return {k: (None if v is None else torch.from_numpy(v).cuda()) for k, v in a.items()}
-
-
-class Guarded(object):
-    """an output tensor inside a larger byte buffer: [guard | extent, filled with the sentinel | guard]"""
-
-    def __init__(self, shape, dtype):
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.nbytes = n
-        self.buf = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device='cuda')
-        self.buf[GUARD:GUARD + n] = SENTINEL_BYTE
-        self.t = self.buf[GUARD:GUARD + n].view(dtype).view(shape)
-
-    def check_guards(self, what):
-        b = self.buf.cpu()
-        assert bool((b[:GUARD] == GUARD_BYTE).all()) and bool((b[GUARD + self.nbytes:] == GUARD_BYTE).all()), '%s: a guard byte changed' % what
-
-    def untouched(self):
-        return bool((self.buf[GUARD:GUARD + self.nbytes] == SENTINEL_BYTE).all())
-
-
 def guarded_outputs(task, B, R, D, T, L_out, token_types, every=False):
     i64, f32 = torch.int64, torch.float32
     cap = B * T if task == 'mlm' else B * R
@@ -77,10 +55,6 @@ def guarded_outputs(task, B, R, D, T, L_out, token_types, every=False):
               'feat_targets': ((B * R, D), f32), 'targets': ((B,), i64), 'masked_positions': ((cap, 2), i64), 'n_masked': ((1,), torch.int32)}
     keys = ALL_OUT if every else DENSE[task] + COMPACT[task] + (('n_masked',) if task != 'itm' else ())
     return {k: Guarded(*shapes[k]) for k in keys if token_types or k != 'token_type_ids'}
-
-
-def sentinel_of(dtype):
-    return torch.full((1,), SENTINEL_BYTE, dtype=torch.uint8).repeat(8).view(dtype)[0]
 
 
 def launch(task, d, sel, txt_sel, R, L_out, ragged, cfg, g):
@@ -189,6 +163,67 @@ def test_a_sample_is_masked_alike_in_every_batch_and_anew_in_every_epoch():
     one, two, later = go('mrfr', [4, 7, 0, 10], 0), go('mrfr', [10, 2, 4], 0), go('mrfr', [4, 7, 0, 10], 1)
     assert torch.equal(one['img_masks'][0], two['img_masks'][2]) and torch.equal(one['img_masks'][3], two['img_masks'][0])
     assert not torch.equal(one['img_masks'], later['img_masks'])
+
+
+# ---- the entries agree on what they share -----------------------------------------------------------------------------
+def assert_agrees(task, got, plain, what):
+    """every one of the nine common outputs of `task` is the plain batch's, but for MLM's input_ids where a token was selected
+    and for the img_feat rows of a selected region (MRFR, MRC), which are zero"""
+    for k in COMMON:
+        t, p = got[k], plain['attn_mask' if k == 'attn_masks' else k]
+        if task == 'mlm' and k == 'input_ids':
+            kept = got['txt_labels'] == -1
+            assert not bool(kept.all()) and torch.equal(t[kept], p[kept]), '%s: %s' % (k, what)
+        elif task in ('mrfr', 'mrc') and k == 'img_feat':
+            m = got['img_masks'].bool()
+            assert bool(m.any()) and torch.equal(t[~m], p[~m]) and bool((t[m] == 0).all()), '%s: %s' % (k, what)
+        else:
+            assert torch.equal(t, p), '%s: %s' % (k, what)
+
+
+@pytest.mark.parametrize('ragged', [False, True])
+@pytest.mark.parametrize('data', [(4, 2), (4, 16), (260, 2), (260, 16), 'mrc_cases'])
+def test_the_entries_agree_on_what_they_share(data, ragged):
+    """Each entry is otherwise compared with its own restatement only.  (D, T) with R = 5: ITM with its own texts is the plain
+    batch and all its targets are 1; MLM and MRFR differ from it where they say they selected.  'mrc_cases': the same of
+    uniter_collate_mrc_batch on the dataset of tests/mrc_cases.py (C = 5, aligned rows; a batch with region counts 11, 3, 7, one
+    with samples without regions, one sample alone).  prob = 0.15; every output behind guard bands."""
+    from meme_challenge_amd.data import collate_batch, collate_mrc_batch
+    import mrc_cases
+    i64, f32 = torch.int64, torch.float32
+    cfg = dict(seed=(5 << 32) + 17, draw=3, prob=0.15)
+    if data == 'mrc_cases':
+        Cn = 5
+        a = mrc_cases.synth(Cn, mrc_cases.leading_dimensions(Cn)['aligned'], seed=Cn)
+        tasks, batches = ('mrc',), ([0, 1, 2], mrc_cases.BATCHES['a sample without regions'], mrc_cases.BATCHES['one'])
+    else:
+        a = synth(data[0], 5, data[1], True, seed=sum(data))
+        tasks, batches = ('itm', 'mlm', 'mrfr'), ([0, 1, 2], [0])
+    d = to_device(a)
+    T, D = a['input_ids'].shape[1], a['feat'].shape[1]
+    for sel in batches:
+        R, L_out = mrc_cases.shape_of(a, sel, ragged)
+        B, dsel = len(sel), torch.tensor(sel, dtype=i64, device='cuda')
+        pg = guarded_outputs('itm', B, R, D, T, L_out, True)
+        plain = collate_batch(dsel, *[d[k] for k in ARRAY_KEYS], R=R, L_out=L_out, ragged_regions=ragged,
+                              out={('attn_mask' if k == 'attn_masks' else k): pg[k].t for k in COMMON})
+        for task in tasks:
+            what = '%s %s sel %s ragged %s' % (task, data, sel, ragged)
+            if task == 'mrc':
+                g = guarded_outputs('mrfr', B, R, D, T, L_out, True)
+                del g['feat_targets']
+                g.update(label_targets=Guarded((B * R, Cn), f32), label_ids=Guarded((B * R,), i64))
+                got = collate_mrc_batch(dsel, *[d[k] for k in mrc_cases.ARRAY_KEYS], R=R, L_out=L_out, label_dim=Cn, ragged_regions=ragged,
+                                        out={k: v.t for k, v in g.items()}, **cfg)
+            else:
+                g = guarded_outputs(task, B, R, D, T, L_out, True)
+                got = launch(task, d, sel, None, R, L_out, ragged, cfg, g)
+            torch.cuda.synchronize()
+            for k, v in list(g.items()) + [('plain ' + k, pg[k]) for k in COMMON]:
+                v.check_guards(k + ': ' + what)
+            assert_agrees(task, got, plain, what)
+            if task == 'itm':
+                assert bool((got['targets'] == 1).all()), what
 
 
 # ---- refusals: an error code, a message, nothing launched ------------------------------------------------------------
